@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: dense stereo disparity throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--ingest resident|rank0]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--ingest resident|rank0] [--dump-outputs DIR]
 
 A "step" = one pass of the hot path (SGBM compute -> float scaling -> reprojectImageTo3D) over
 one batch of synthetic rectified pairs that is already resident in HBM.  One process per GPU:
@@ -102,6 +102,11 @@ STAGE_KERNEL = {
 # stages that one launch runs for ALL pairs of a step (batch entry); every other stage runs once per pair
 JOINT_STAGES = ("chain_dn", "chain_up")
 
+# --dump-outputs: bytes of array data it may write in all (under 64 MB with room for the .npy headers), and the seed
+# of the pixel sample it takes when the outputs are larger
+DUMP_BYTES = 60 * 10 ** 6
+DUMP_SEED = 20240611
+
 
 def sgbm_params(D, bs, mode):
     return dict(minDisparity=0, numDisparities=D, blockSize=bs, P1=8 * 3 * bs * bs, P2=32 * 3 * bs * bs, mode=mode, **NB)
@@ -147,6 +152,49 @@ def model_traffic(stage: str, V: int, R: int, HW: int, mode: int, D: int) -> int
         "wta": ((5 * V if D <= 64 else 2 * V) if two_vol else V) + 8 * HW,
         "cost_pix": V // 2 + 14 * HW, "cost_box": V // 2 + V, "cost_hsum": V + 14 * HW, "cost_vsum": 2 * V,
     }.get(stage)
+
+
+def dump_outputs(path, HW, fields, whole=None, masked=()):
+    """What the last timed step handed back, so that two builds can be compared output for output.  Every value written
+    is finite.
+
+    `fields`: name -> one tensor per pair whose first dimension is the flat pixel index y * W + x (HW of them), or the
+    position in a point list (shorter: 0 past its end).  Written as path/<name>.npy in float32, [pairs, n(, C)], at
+    the n positions listed in path/sample_pixels.npy: all HW, or -- when that would exceed DUMP_BYTES in all -- the same
+    seeded sample for every field.  `masked`: fields that may hold non-finite values (the XYZ of a pixel at infinity):
+    those are written as 0, and path/<name>_finite.npy, of the same shape, is 1 where the value was finite and 0 where
+    not.  `whole`: small tensors, written as they are in float64."""
+    import math
+
+    import numpy as np
+    import torch
+    whole = whole or {}
+    os.makedirs(path, exist_ok=True)
+    room = DUMP_BYTES - sum(8 * t.numel() for t in whole.values())
+    per_px = 8 + sum(4 * len(ts) * math.prod(ts[0].shape[1:]) * (2 if name in masked else 1)
+                     for name, ts in fields.items())       # bytes per position, index and masks included
+    if per_px * HW <= room:
+        idx = np.arange(HW)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(HW, room // per_px, replace=False))
+    np.save(os.path.join(path, "sample_pixels.npy"), idx.astype(np.float64))
+    for name, ts in fields.items():
+        out = []
+        for t in ts:
+            a = np.zeros((len(idx),) + tuple(t.shape[1:]), np.float32)
+            k = int(np.searchsorted(idx, len(t)))            # the sampled positions this tensor has
+            a[:k] = t[torch.from_numpy(idx[:k]).to(t.device)].cpu().numpy()
+            out.append(a)
+        out = np.stack(out)
+        fin = np.isfinite(out)
+        if name in masked:
+            np.save(os.path.join(path, f"{name}_finite.npy"), fin.astype(np.float32))
+            out[~fin] = 0.0
+        elif not fin.all():
+            raise RuntimeError(f"--dump-outputs: {name} holds non-finite values")
+        np.save(os.path.join(path, f"{name}.npy"), out)
+    for name, t in whole.items():
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy().astype(np.float64))
 
 
 def cpu_info():
@@ -274,7 +322,11 @@ def main():
     ap.add_argument("--debug", type=int, default=0, help="SGM_OPT_DEBUG bit mask (A/B measurements; csrc/sgm_debug.h)")
     ap.add_argument("--prepass-rows", type=int, default=0, help="rows per chunk of the boundary pre-pass (0 = automatic)")
     ap.add_argument("--sweep-rows", type=int, default=0, help="rows per band of the fused sweeps (0 = automatic)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed (rank 0's results) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- N > 1 without a launcher: become the parent of N ranks (before torch / HIP are imported)
     if "RANK" not in os.environ and "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -472,7 +524,7 @@ def main():
     t0 = time.perf_counter()
     stage_acc = []
     if args.ingest == "rank0":
-        ingest_steps(all_left, all_right, args.steps, want_compact)
+        timed_res = ingest_steps(all_left, all_right, args.steps, want_compact)
     else:
         for _ in range(args.steps):
             stage_acc.extend(run_local(d_left, d_right, d_disp, d_dispf, d_xyz))
@@ -487,6 +539,23 @@ def main():
         dt = float(t.item())
     if args.ingest == "rank0":
         stage_acc = [eng.stage_times()]     # (the last batch this rank computed)
+
+    # ---- the last timed step's results, before the legs below reuse the output buffers ----
+    if args.dump_outputs and rank == 0:
+        pix = lambda ts: [t.reshape(H * W, *t.shape[2:]) for t in ts]      # [H, W(, C)] -> [H * W(, C)]
+        if args.ingest == "resident":
+            fields = {"disparity": pix(d_disp)}
+            if with_xyz:
+                fields.update(disparity_float=pix(d_dispf), xyz=pix(d_xyz))
+            dump_outputs(args.dump_outputs, H * W, fields, masked=("xyz",))
+        elif want_compact:
+            disp, pts, cnt = timed_res[-1]      # pts: one (counts[i], 3) list of valid (finite) points per frame
+            dump_outputs(args.dump_outputs, H * W, {"disparity": pix(disp), "points": pts}, {"point_counts": cnt})
+        else:
+            last = timed_res[-1]
+            disp, xyz = last if with_xyz else (last, None)
+            dump_outputs(args.dump_outputs, H * W, {"disparity": pix(disp), **({"xyz": pix(xyz)} if with_xyz else {})},
+                         masked=("xyz",))
 
     # ---- per-stage HIP-event durations (this rank) ----
     stage_acc = [[t for t in st if t[0] != "_wall"] for st in stage_acc]
