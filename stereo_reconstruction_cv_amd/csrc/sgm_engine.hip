@@ -182,6 +182,31 @@ struct HostBuf {
     }
 };
 
+// The schedule of one compute (make_plan decides it; run_compute, ensure_plan_buffers and the batch entries follow it)
+struct Plan {
+    // cost stage
+    bool byte_cost;        // per-pixel cost as bytes + k_box_u8 (else the int16 pipeline k_hsum + k_vsum*)
+    bool pix_px;           // int16 pipeline: k_pix_px + k_hsum_px (D <= 32) in place of k_hsum
+    int GWc, RBb;          // k_box_u8: lane-group width, rows per band
+    bool vsum_ring, vsum_wide;  // int16 pipeline: k_vsum_ring (else the generic k_vsum), with 8 int16 per thread (else 4)
+    // path stage
+    bool v1;               // schedule 0: one kernel per direction
+    int GWs;               // lane-group width of the small-D kernels (64: none)
+    bool rows4;            // small-D schedule (D <= 64 outside throughput mode, D <= 32 always)
+    bool chain;            // chained sweeps (schedule 2)
+    int npass, R, nbands;
+    bool prepass_g;        // pre-pass: lane-grouped lines (k_prepass3_g), or three roles per wave (k_prepass3) in pre_nch
+    bool fused_prepass;    // chunks of pre_rows rows (pre_plain: the plain layout), or the single-direction kernel
+    bool pre_plain;
+    int pre_nch, pre_rows;
+    bool overlap, fork_early;  // MODE_HH: upward pre-pass on the auxiliary stream; forked right after the cost stage
+    // winner-take-all
+    bool fused_wta;        // inside the last path kernel (else k_wta_t)
+    int nvol;              // volumes k_wta_t adds up: 1 (S), 2 (+ the fifth path's), 3 (+ the other in-row path's), 5 (k_paths5_g)
+    bool path_w_main, path_w_lines;  // MODE_SGBM's fifth path on the main stream behind the sweeps; as the general line kernel
+    bool speckle;          // the speckle filter runs
+};
+
 struct sgm_engine {
     sgm_params params;
     int device = 0;
@@ -195,8 +220,7 @@ struct sgm_engine {
     int profile = 0;
     int schedule = 1;    // 0: one kernel per direction (v1); 1: fused 4-direction sweeps; 2: chained sweeps, no pre-pass (throughput mode)
     int chain_wgs = 0;   // schedule 2: workgroups (= bands in flight) per sweep launch; 0 = automatic
-    bool plan_chain = false;  // what PH_PRE of the last compute decided: chained sweeps? band height, bands
-    int plan_R = 0, plan_nbands = 0;
+    Plan plan{};         // what PH_PRE of the last compute decided (run_group checks it against the group's)
     int sweep_rows = 0;  // rows per band of the sweep (0 = automatic)
     int debug = 0;       // timing experiments (SweepArgs::dbg)
     int prepass_rows = 0;  // rows per chunk of the boundary pre-pass (0 = automatic, about 135, a multiple of 8)
@@ -366,6 +390,42 @@ static void stage_break(sgm_engine *e) { e->last_end_ev = -1; }
 
 #define KCHECK() HIP_TRY(hipGetLastError())
 
+// ---- template ladders --------------------------------------------------------------------------
+// f(NP, PARTIAL) as std::integral_constant for the geometry: NP 128-disparity pieces per lane, PARTIAL = the last piece is not full
+template <class F>
+static auto with_np(const Geom &g, F &&f)
+{
+    using std::integral_constant;
+    const bool partial = g.D != 128 * g.NP;
+    if (g.NP == 1) return partial ? f(integral_constant<int, 1>(), std::true_type()) : f(integral_constant<int, 1>(), std::false_type());
+    if (g.NP == 2) return partial ? f(integral_constant<int, 2>(), std::true_type()) : f(integral_constant<int, 2>(), std::false_type());
+    return partial ? f(integral_constant<int, 4>(), std::true_type()) : f(integral_constant<int, 4>(), std::false_type());
+}
+// f(GW, PARTIAL) for a lane-group width of the small-D kernels (8, 16, 32); PARTIAL = the group is not full (D = 48 in
+// groups of 32; D = 16, 32, 64 fill theirs)
+template <class F>
+static auto with_gw(int GW, int D, F &&f)
+{
+    using std::integral_constant;
+    if (GW == 8) return f(integral_constant<int, 8>(), std::false_type());
+    if (GW == 16) return f(integral_constant<int, 16>(), std::false_type());
+    return D < 64 ? f(integral_constant<int, 32>(), std::true_type()) : f(integral_constant<int, 32>(), std::false_type());
+}
+// f(R) for a window radius 1 .. 5 (the instantiations of the box kernels); nothing for any other radius
+template <class F>
+static void with_radius(int r, F &&f)
+{
+    using std::integral_constant;
+    switch (r) {
+    case 1: f(integral_constant<int, 1>()); break;
+    case 2: f(integral_constant<int, 2>()); break;
+    case 3: f(integral_constant<int, 3>()); break;
+    case 4: f(integral_constant<int, 4>()); break;
+    case 5: f(integral_constant<int, 5>()); break;
+    default: break;
+    }
+}
+
 // ---- path launch dispatch ---------------------------------------------------------------------
 template <int NP, bool PARTIAL>
 static void launch_path_np(const Geom &g, int rx, int ry, int mode, const int16_t *C, int16_t *S, int keepS,
@@ -389,17 +449,7 @@ static void launch_path_np(const Geom &g, int rx, int ry, int mode, const int16_
 static void launch_path(const Geom &g, int rx, int ry, int mode, const int16_t *C, int16_t *S, int keepS,
                         uint2 *wta, hipStream_t st, Boundary bd = Boundary{nullptr, 1, 0})
 {
-    const bool partial = g.D != 128 * g.NP;
-    if (g.NP == 1) {
-        if (partial) launch_path_np<1, true>(g, rx, ry, mode, C, S, keepS, wta, bd, st);
-        else launch_path_np<1, false>(g, rx, ry, mode, C, S, keepS, wta, bd, st);
-    } else if (g.NP == 2) {
-        if (partial) launch_path_np<2, true>(g, rx, ry, mode, C, S, keepS, wta, bd, st);
-        else launch_path_np<2, false>(g, rx, ry, mode, C, S, keepS, wta, bd, st);
-    } else {
-        if (partial) launch_path_np<4, true>(g, rx, ry, mode, C, S, keepS, wta, bd, st);
-        else launch_path_np<4, false>(g, rx, ry, mode, C, S, keepS, wta, bd, st);
-    }
+    with_np(g, [&](auto np, auto part) { launch_path_np<np, part>(g, rx, ry, mode, C, S, keepS, wta, bd, st); });
 }
 
 // ---- sweep launch dispatch --------------------------------------------------------------------
@@ -426,14 +476,9 @@ static void launch_rows_g(const Geom &g, int H, int rx, int mode, const int16_t 
 // the in-row path of a pass (rows are independent): GW < 64 packs 64/GW rows into a wave
 static void launch_rows_grouped(const Geom &g, int H, int GW, int rx, int mode, const int16_t *C, int16_t *S, int keepS, uint2 *wta, hipStream_t st)
 {
-    const bool partial = g.D != 128 * g.NP;
-    // lane groups: PARTIAL = the group is not full (D = 48 in groups of 32; D = 16, 32, 64 fill theirs)
-    if (GW == 8) launch_rows_g<8, 1, false>(g, H, rx, mode, C, S, keepS, wta, st);
-    else if (GW == 16) launch_rows_g<16, 1, false>(g, H, rx, mode, C, S, keepS, wta, st);
-    else if (GW == 32) { if (g.D < 64) launch_rows_g<32, 1, true>(g, H, rx, mode, C, S, keepS, wta, st); else launch_rows_g<32, 1, false>(g, H, rx, mode, C, S, keepS, wta, st); }
-    else if (g.NP == 1) { if (partial) launch_rows_g<64, 1, true>(g, H, rx, mode, C, S, keepS, wta, st); else launch_rows_g<64, 1, false>(g, H, rx, mode, C, S, keepS, wta, st); }
-    else if (g.NP == 2) { if (partial) launch_rows_g<64, 2, true>(g, H, rx, mode, C, S, keepS, wta, st); else launch_rows_g<64, 2, false>(g, H, rx, mode, C, S, keepS, wta, st); }
-    else { if (partial) launch_rows_g<64, 4, true>(g, H, rx, mode, C, S, keepS, wta, st); else launch_rows_g<64, 4, false>(g, H, rx, mode, C, S, keepS, wta, st); }
+    auto go = [&](auto gw, auto np, auto part) { launch_rows_g<gw, np, part>(g, H, rx, mode, C, S, keepS, wta, st); };
+    if (GW < 64) with_gw(GW, g.D, [&](auto gw, auto part) { go(gw, std::integral_constant<int, 1>(), part); });
+    else with_np(g, [&](auto np, auto part) { go(std::integral_constant<int, 64>(), np, part); });
 }
 
 template <int NP, bool PARTIAL, int MODE, bool POSW>
@@ -463,10 +508,7 @@ static int check_sweep_direction(const SweepArgs &a, int mode)
 static int launch_sweep(const Geom &g, const SweepArgs &a, int mode, int nbands, hipStream_t st)
 {
     if (int rc = check_sweep_direction(a, mode)) return rc;
-    const bool partial = g.D != 128 * g.NP;
-    if (g.NP == 1) return partial ? launch_sweep_np<1, true>(g, a, mode, nbands, st) : launch_sweep_np<1, false>(g, a, mode, nbands, st);
-    if (g.NP == 2) return partial ? launch_sweep_np<2, true>(g, a, mode, nbands, st) : launch_sweep_np<2, false>(g, a, mode, nbands, st);
-    return partial ? launch_sweep_np<4, true>(g, a, mode, nbands, st) : launch_sweep_np<4, false>(g, a, mode, nbands, st);
+    return with_np(g, [&](auto np, auto part) { return launch_sweep_np<np, part>(g, a, mode, nbands, st); });
 }
 
 // chained sweep (kernels_sweep.h: k_sweep_chain): `wgs` persistent workgroups of R compute waves + loader + publisher
@@ -487,10 +529,7 @@ static int launch_chain_np(const Geom &g, const SweepArgs &a, const ChainFrames 
 static int launch_chain(const Geom &g, const SweepArgs &a, const ChainFrames &fr, int mode, int wgs, hipStream_t st)
 {
     if (int rc = check_sweep_direction(a, mode)) return rc;
-    const bool partial = g.D != 128 * g.NP;
-    if (g.NP == 1) return partial ? launch_chain_np<1, true>(g, a, fr, mode, wgs, st) : launch_chain_np<1, false>(g, a, fr, mode, wgs, st);
-    if (g.NP == 2) return partial ? launch_chain_np<2, true>(g, a, fr, mode, wgs, st) : launch_chain_np<2, false>(g, a, fr, mode, wgs, st);
-    return partial ? launch_chain_np<4, true>(g, a, fr, mode, wgs, st) : launch_chain_np<4, false>(g, a, fr, mode, wgs, st);
+    return with_np(g, [&](auto np, auto part) { return launch_chain_np<np, part>(g, a, fr, mode, wgs, st); });
 }
 // workgroups of a chained launch over nf frames: a band trails the band above by about 2 (R - 1) + 17 lockstep steps and
 // lasts T steps, so a frame keeps about T / lag workgroups busy; more would only wait (and hold CUs)
@@ -520,18 +559,16 @@ static int sweep_rows_for(const Geom &g, int override_rows, int npass, bool chai
     return std::max(1, std::min(R, maxR));
 }
 
+// columns per workgroup of k_box_u8: 4 waves x (64 / GW groups) x 4 columns
+static int box_columns(int GW) { return 16 * (64 / GW); }
+
 // ---- the schedule of one compute, decided from the geometry and the engine's options alone ----------------
 // (run_compute follows it; the batch entries read it BEFORE anything is allocated or enqueued: whether a configuration
-// runs chained, and what a pair costs in device memory)
-struct Plan {
-    bool byte_cost;   // per-pixel cost as bytes + k_box_u8 (else the int16 pipeline k_hsum + k_vsum*)
-    int GWs;          // lane-group width of the small-D kernels (64: none)
-    bool rows4;       // small-D schedule (D <= 64 outside throughput mode, D <= 32 always)
-    bool chain;       // chained sweeps (schedule 2)
-    int npass, R, nbands;
-};
+// runs chained, and what a pair costs in device memory).  Every A/B switch of sgm_debug.h that picks a schedule is read
+// here; the sweep kernels see the mask itself (SweepArgs::dbg).
 static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
 {
+    const int dbg = e->debug;
     Plan p;
     // Byte pipeline (default): k_pix writes the per-pixel cost as uint8, k_box_u8 does the whole box
     // filter from it.  Needs a window radius 1..5 (instantiations), a cost that fits a byte, and a
@@ -539,12 +576,26 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     // disparities side by side in a wave); the per-pixel cost comes from k_pix_px (D <= 32, one thread per pixel) or
     // k_pix (D = 48, 64: half its lanes idle, still less than the int16 pipeline's 3 V more traffic).
     // debug 256: the int16 pipeline always; debug 4 (no lane groups): the int16 pipeline for D <= 64.
-    p.byte_cost = !(e->debug & 256) && (g.D > 64 || !(e->debug & 4)) && g.SW2 >= 1 && g.SW2 <= 5 && g.SH2 == g.SW2 &&
-                  2 * g.ftzero + 63 <= 255 && (int64_t)H * g.rowsz < (int64_t)0x7ff00000;
+    p.byte_cost = !(dbg & SGM_DBG_INT16_COST) && (g.D > 64 || !(dbg & SGM_DBG_NO_LANE_GROUPS)) && g.SW2 >= 1 && g.SW2 <= 5 &&
+                  g.SH2 == g.SW2 && 2 * g.ftzero + 63 <= 255 && (int64_t)H * g.rowsz < (int64_t)0x7ff00000;
+    // int16 pipeline, D <= 32: one thread per pixel (lanes spanning D would mostly idle; at D = 64 the wave-per-
+    // chunk kernel is still ahead); the byte volume borrows the S buffer, unused before the paths
+    p.pix_px = g.D <= 32 && !(dbg & SGM_DBG_NO_LANE_GROUPS) && 2 * g.ftzero + 63 <= 255;
+    p.GWc = g.D > 64 ? 64 : (g.D <= 16 ? 8 : (g.D <= 32 ? 16 : 32));  // lane-group width of k_box_u8
+    // rows per band of k_box_u8 (a band re-reads 2 * SH2 rows above it; multiples of 16: the register rings): 96, less
+    // on frames too small to fill the chip with bands that tall
+    const int cpw = box_columns(p.GWc);
+    p.RBb = 96;
+    for (int cand : {48, 32, 16})
+        if ((int64_t)((g.W1 + cpw - 1) / cpw) * ((H + p.RBb - 1) / p.RBb) * 4 < 1024) p.RBb = cand;
+    p.vsum_ring = g.SH2 >= 1 && g.SH2 <= 5;         // ring variant: each hsum row is read once
+    p.vsum_wide = !(dbg & SGM_DBG_NARROW_VSUM);    // 8 int16 per thread (debug 8: 4, for A/B timing)
+
+    p.v1 = e->schedule == 0;
     // D <= 32: rows without hand-off: band height 1, the pre-pass stores every row's
     // state; needs the 3-volume state buffer below the 4 GiB a 32-bit buffer offset reaches.
     // (At D = 64 the fused sweep is still ahead: 720p 0.35 against 0.39 ms, and 3 V of state.)
-    p.GWs = (e->debug & 4) ? 64 : group_width(g, H);
+    p.GWs = (dbg & SGM_DBG_NO_LANE_GROUPS) ? 64 : group_width(g, H);
     // Throughput mode (schedule 2) takes D = 48 .. 64 through the chained sweeps all the same (half the lanes idle, but
     // 7 V of traffic per pair instead of the 22 V of the per-row state: batches of small frames are bound by HBM --
     // 64 pairs 720p D=64: 0.38 against 0.55 ms per pair); D <= 32 keeps the small-D kernels in every mode.
@@ -554,18 +605,83 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     // Chained schedule (SGM_OPT_SCHEDULE 2, kernels_sweep.h: k_sweep_chain): no pre-pass; the bands of a sweep hand the
     // state of their last row to each other.  Only where the fused sweep runs (the small-D schedule keeps its own
     // kernels), where there is more than one band, and not with debug 2 (winner-take-all inside the second sweep).
-    p.chain = e->schedule == 2 && !p.rows4 && !((e->debug & 2) && g.mode == 1) && g.W1 > 0;
+    p.chain = e->schedule == 2 && !p.rows4 && !((dbg & SGM_DBG_WTA_IN_LAST_PATH) && g.mode == 1) && g.W1 > 0;
     p.R = p.rows4 ? 1 : sweep_rows_for(g, e->sweep_rows, p.npass, p.chain);
     if (p.chain && (H + p.R - 1) / p.R <= 1) {
         p.chain = false;
         p.R = sweep_rows_for(g, e->sweep_rows, p.npass, false);
     }
     p.nbands = (H + p.R - 1) / p.R;
+    // small-D schedule: lane-grouped pre-pass lines, state stored after every row (debug 16: the single-direction kernel)
+    p.prepass_g = p.rows4 && !(dbg & SGM_DBG_PREPASS_3_LAUNCHES);
+    // Narrow frames (fewer than ~1.5 lines per SIMD) are bound by the latency of one wave's
+    // instruction stream: there the single-direction kernel with one wave per (line, role) -- three
+    // times the waves, a third of the work each -- is faster (720p D=64: 0.26 against 0.34 ms); its
+    // three readers of C are served by L2 / the Infinity Cache at these sizes.
+    const bool narrow = g.W1 <= 1536 && e->prepass_rows == 0;  // (an explicit chunk height selects k_prepass3: tests)
+    // the three roles fused in one wave (k_prepass3); debug bit 16 selects the 3-launch variant.
+    // Row chunks of about 135 rows, one launch each, base columns grouped per XCD: two of the
+    // three reads of a C pixel hit L2 (kernels_path.h).  debug 512: one chunk, plain layout (A/B).
+    p.fused_prepass = !p.rows4 && !(dbg & SGM_DBG_PREPASS_3_LAUNCHES) && !narrow && (int64_t)g.rowsz * H < (1ll << 31);
+    p.pre_plain = (dbg & SGM_DBG_PREPASS_ONE_CHUNK) != 0;
+    p.pre_nch = p.pre_plain ? 1 : (e->prepass_rows > 0 ? (H + e->prepass_rows - 1) / e->prepass_rows : std::max(1, (H + 67) / 135));
+    // multiples of 8 rows (two prefetch blocks): a chunk then ends in straight-line code
+    p.pre_rows = e->prepass_rows > 0 ? e->prepass_rows : ((H + p.pre_nch - 1) / p.pre_nch + 7) / 8 * 8;
+    // MODE_HH: the upward pre-pass only reads C, so it runs on the auxiliary stream while the
+    // main stream does the downward pre-pass and sweep (memory-bound beside issue-bound work)
+    p.overlap = p.npass == 2 && p.nbands > 1 && !(dbg & SGM_DBG_NO_PREPASS_OVERLAP) && !p.chain;
+    // debug bit 64+128: fork right after the cost stage (both pre-passes side by side) instead
+    // of after the downward pre-pass (upward pre-pass beside the downward sweep)
+    p.fork_early = (dbg & SGM_DBG_FORK_PREPASS_EARLY) != 0;
+
+    // Winner-take-all: a separate pass over S (k_wta_t, one lane per pixel) after the second sweep
+    // of MODE_HH and after the in-row path of MODE_SGBM for D <= 128; fused into the in-row path
+    // kernel for MODE_SGBM with D > 128 (there the separate form costs a third volume of traffic:
+    // 4K D=256 2.49 ms fused against 2.56 + 0.73; D=128: 2.01 against 1.42 + 0.43, 1080p 0.79 against
+    // 0.44 + 0.10).  debug 2 forces the fused form everywhere, debug 2048 the separate one (A/B, cross-check).
+    // (The v1 schedule always fuses it into its last path kernel.)
+    p.fused_wta = p.v1 || (!(dbg & SGM_DBG_WTA_SEPARATE) && (((dbg & SGM_DBG_WTA_IN_LAST_PATH) && !p.rows4) ||
+                                                             (g.mode == 0 && ((dbg & SGM_DBG_NO_LANE_GROUPS) || g.D > 128))));
+    // MODE_SGBM with the separate winner-take-all (D <= 128): the fifth path (in-row, right to left) needs
+    // nothing but C, so it runs on the auxiliary stream from here on, as a FIRST pass into a volume of its
+    // own (2 V of traffic instead of the 3 V of "S +="), beside the pre-pass and the sweep -- which at these
+    // D are bound by instruction issue, not by HBM; k_wta_t adds the two volumes while it stages them.
+    // debug 65536: the fifth path after the sweep, accumulating into S (A/B).
+    const bool two_vol = g.mode == 0 && !p.fused_wta && g.D <= 128 && !(dbg & SGM_DBG_NO_LANE_GROUPS) &&
+                         !(dbg & SGM_DBG_FIFTH_PATH_AFTER_SWEEP);
+    // D <= 64 (small-D schedule): the OTHER in-row path (left to right) needs nothing but C either.  It used to follow
+    // the element-wise vertical kernel as "S +=" on the main stream -- a chain of W1 dependent steps on the
+    // critical path of a latency-bound frame; now it runs as a FIRST pass into a third volume on a stream of its
+    // own, beside the per-row pre-pass and k_vert3_g, and the winner-take-all adds three volumes.
+    const bool three_vol = two_vol && p.rows4 && !(dbg & SGM_DBG_IN_ROW_ON_MAIN_STREAM);
+    // ... and so do the three directions that come from the row above: the walk along their lines (the "pre-pass" of
+    // the small-D schedule) forms L_r(p, .) on its way, so each role writes it to a volume of its own and the
+    // winner-take-all adds five volumes: no per-row record (3 V written, 3 V read), no element-wise kernel behind
+    // the walk -- and all five directions are ONE launch (k_paths5_g: why, see there).  debug 8192: the record form
+    // with the in-row paths on streams of their own (A/B; MODE_HH keeps it).
+    const bool five_vol = three_vol && !(dbg & SGM_DBG_SMALL_D_RECORD);
+    p.nvol = five_vol ? 5 : three_vol ? 3 : two_vol ? 2 : 1;
+    // otherwise MODE_SGBM's fifth path follows the sweep on the main stream (S +=, or with the winner-take-all);
+    // debug 4 (no lane groups): as the general line kernel (A/B)
+    p.path_w_main = !p.v1 && g.mode == 0 && p.nvol == 1;
+    p.path_w_lines = (dbg & SGM_DBG_NO_LANE_GROUPS) != 0;
+    p.speckle = e->params.speckleRange >= 0 && e->params.speckleWindowSize > 0;  // upstream's condition for filterSpeckles
     return p;
 }
 
 // ---- the matcher on device buffers ---------------------------------------------------------
-static int ensure_buffers(sgm_engine *e, int H, int W)
+static int ensure_speckle_buffers(sgm_engine *e, size_t npx)
+{
+    int rc;
+    if ((rc = e->label.ensure(npx * 4)) || (rc = e->csize.ensure(npx * 4))) return rc;
+    return e->rlen.ensure(npx * 4);
+}
+// control words of a chained launch over nf frames: ticket + one progress word per band (zeroed before every launch)
+static size_t chain_ctl_bytes(int nf, int nbands) { return ((size_t)(1 + (size_t)nf * nbands) * 4 + 15) & ~(size_t)15; }
+
+// Every device buffer one compute of this shape needs under plan p, allocated BEFORE anything is enqueued (a pair of a
+// chained group that does not fit then costs nothing but a smaller group).  Records the shape in e->g.
+static int ensure_plan_buffers(sgm_engine *e, const Plan &p, int H, int W)
 {
     Geom g;
     int rc = normalise(&e->params, H, W, &g);
@@ -586,15 +702,36 @@ static int ensure_buffers(sgm_engine *e, int H, int W)
         // complete, and no kernel writes S before that (the sweeps, the in-row paths and k_paths5_g all read C; in a batch
         // every pair's cost stage is complete before the joint sweep launch starts).  Only the int16 pipeline needs a
         // volume of its own for the horizontal sums.  4K D=256: 13 -> 9 GB per engine (round 3 allocated V for them always).
-        if (!make_plan(e, g, H).byte_cost && (rc = e->hsum.ensure(vol))) return rc;
+        if (!p.byte_cost && (rc = e->hsum.ensure(vol))) return rc;
         if ((rc = e->cost.ensure(vol))) return rc;
         if ((rc = e->aggr.ensure(vol))) return rc;
+        DevBuf *more[] = {&e->aggr2, &e->aggr3, &e->aggr4, &e->aggr5};  // the volumes k_wta_t adds to S (Plan::nvol)
+        for (int k = 1; k < p.nvol; k++)
+            if ((rc = more[k - 1]->ensure(vol))) return rc;
     }
     if ((rc = e->wta.ensure(npx * 8))) return rc;
     if ((rc = e->disp_raw.ensure(npx * 2))) return rc;
     if ((rc = e->disp_med.ensure(npx * 2))) return rc;
     if ((rc = e->headroom.ensure(8))) return rc;
     e->g.hr = (uint32_t *)e->headroom.p;
+    if (g.W1 > 0 && !p.v1 && p.nbands > 1 && p.nvol != 5) {
+        const size_t bnd_bytes = (size_t)p.nbands * g.W1 * 3 * g.D * 2;
+        if ((rc = e->bndL.ensure(bnd_bytes))) return rc;
+        if (!p.chain) {
+            if (p.npass == 2 && (rc = e->bndL2.ensure(bnd_bytes))) return rc;
+            const size_t st_bytes = (size_t)2 * 3 * g.W1 * g.D * 2;  // ping-pong line state between pre-pass chunks
+            if ((rc = e->pstate.ensure(st_bytes))) return rc;
+            if (p.npass == 2 && (rc = e->pstate2.ensure(st_bytes))) return rc;
+        }
+    }
+    if (p.speckle && (rc = ensure_speckle_buffers(e, npx))) return rc;
+    if (p.chain) {
+        if ((rc = e->chain_ctl.ensure(chain_ctl_bytes(1, p.nbands)))) return rc;
+        if (!e->chain_err.p) {  // the sticky give-up flag (check_chain) starts out clear
+            if ((rc = e->chain_err.ensure(16))) return rc;
+            HIP_TRY(hipMemsetAsync(e->chain_err.p, 0, 16, e->stream));
+        }
+    }
     return SGM_OK;
 }
 
@@ -602,7 +739,7 @@ static int run_speckles(sgm_engine *e, int16_t *d_img, int H, int W, int newVal,
 {
     const size_t npx = (size_t)H * W;
     int rc;
-    if ((rc = e->label.ensure(npx * 4)) || (rc = e->csize.ensure(npx * 4)) || (rc = e->rlen.ensure(npx * 4))) return rc;
+    if ((rc = ensure_speckle_buffers(e, npx))) return rc;
     int *label = (int *)e->label.p, *csz = (int *)e->csize.p, *rlen = (int *)e->rlen.p;
     hipStream_t st = e->stream;
     dim3 g2((W + 255) / 256, H);
@@ -620,11 +757,471 @@ __global__ void k_fill_i16(int16_t *p, int64_t n, int16_t v)
     if (i < n) p[i] = v;
 }
 
+// ---- cost stage launches ---------------------------------------------------------------------
+constexpr int COST_XL = 128;  // columns per chunk of k_pix / k_hsum
+static int cost_chunks(const Geom &g) { return (g.W1 + COST_XL - 1) / COST_XL; }
+
+// per-pixel cost of the whole frame as bytes (px: the S buffer, ensure_plan_buffers)
+static void launch_pix(const Geom &g, const uint2 *lrec, const uint8_t *rpl, uint8_t *px, hipStream_t st)
+{
+    if (g.D <= 32) {  // one thread per pixel
+        hipLaunchKernelGGL(k_pix_px, dim3((g.W1 + 255) / 256, g.H), dim3(256), (size_t)6 * (256 + g.D), st, g, lrec, rpl, px);
+        return;
+    }
+    const int nchunks = cost_chunks(g), nj = COST_XL + 2;
+    const int lrec_b = ((nj * 8) + 15) & ~15;
+    const int seg_l = (nj + 128 * g.NP + 15) & ~15;
+    const size_t lds = (size_t)lrec_b + 6 * (size_t)seg_l;
+    dim3 grid((unsigned)((int64_t)g.H * nchunks)), block(64);
+    if (g.NP == 1) hipLaunchKernelGGL(k_pix<1>, grid, block, lds, st, g, lrec, rpl, px, COST_XL, nchunks, lrec_b, seg_l, 0);
+    else if (g.NP == 2) hipLaunchKernelGGL(k_pix<2>, grid, block, lds, st, g, lrec, rpl, px, COST_XL, nchunks, lrec_b, seg_l, 0);
+    else hipLaunchKernelGGL(k_pix<4>, grid, block, lds, st, g, lrec, rpl, px, COST_XL, nchunks, lrec_b, seg_l, 0);
+}
+
+// box filter of the byte costs -> block cost C (k_box_u8), bands of p.RBb rows
+static void launch_box(const Geom &g, const Plan &p, const uint8_t *px, int16_t *C, hipStream_t st)
+{
+    const int cpw = box_columns(p.GWc), RBb = p.RBb;
+    dim3 grid((g.W1 + cpw - 1) / cpw, (g.H + RBb - 1) / RBb), block(256);
+    with_radius(g.SW2, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        if (p.GWc == 8) hipLaunchKernelGGL((k_box_u8<R, 1, 8>), grid, block, 0, st, g, px, C, RBb);
+        else if (p.GWc == 16) hipLaunchKernelGGL((k_box_u8<R, 1, 16>), grid, block, 0, st, g, px, C, RBb);
+        else if (p.GWc == 32) hipLaunchKernelGGL((k_box_u8<R, 1, 32>), grid, block, 0, st, g, px, C, RBb);
+        else if (g.NP == 1) hipLaunchKernelGGL((k_box_u8<R, 1>), grid, block, 0, st, g, px, C, RBb);
+        else if (g.NP == 2) hipLaunchKernelGGL((k_box_u8<R, 2>), grid, block, 0, st, g, px, C, RBb);
+        else hipLaunchKernelGGL((k_box_u8<R, 4>), grid, block, 0, st, g, px, C, RBb);
+    });
+}
+
+// int16 pipeline: horizontal box sum of the pixel cost, all rows (k_hsum); RS_T = RS instantiations carry the unrolled
+// interior fast path (block sizes up to 15)
+template <int NP, int RS_T>
+static int launch_hsum_t(const Geom &g, const uint2 *lrec, const uint8_t *rpl, int16_t *HS, int RS, hipStream_t st)
+{
+    const int nchunks = cost_chunks(g);
+    const HsumLds l = hsum_lds_layout(g.NP, RS, COST_XL, g.SW2);
+    if (l.total_bytes > 48 * 1024)
+        HIP_TRY(hipFuncSetAttribute((const void *)k_hsum<NP, RS_T>, hipFuncAttributeMaxDynamicSharedMemorySize, l.total_bytes));
+    hipLaunchKernelGGL((k_hsum<NP, RS_T>), dim3((unsigned)((int64_t)g.H * nchunks)), dim3(64), l.total_bytes, st, g, lrec, rpl,
+                       HS, COST_XL, nchunks, RS, l.ring_bytes, l.lrec_bytes, l.seg_len, 0);
+    return SGM_OK;
+}
+static int launch_hsum(const Geom &g, const uint2 *lrec, const uint8_t *rpl, int16_t *HS, hipStream_t st)
+{
+    int RS = 1;  // ring of the last blockSize+1 cost vectors, rounded to a power of two
+    while (RS < 2 * g.SW2 + 2) RS <<= 1;
+    return with_np(g, [&](auto np, auto) {
+        if (RS == 4) return launch_hsum_t<np, 4>(g, lrec, rpl, HS, RS, st);
+        if (RS == 8) return launch_hsum_t<np, 8>(g, lrec, rpl, HS, RS, st);
+        if (RS == 16) return launch_hsum_t<np, 16>(g, lrec, rpl, HS, RS, st);
+        return launch_hsum_t<np, 0>(g, lrec, rpl, HS, RS, st);
+    });
+}
+
+// int16 pipeline: vertical box sum -> block cost C (k_vsum_ring in bands of 96 rows; the generic k_vsum for radii above 5)
+static void launch_vsum(const Geom &g, const Plan &p, const int16_t *hs, int16_t *C, hipStream_t st)
+{
+    const int H = g.H;
+    if (!p.vsum_ring) {
+        dim3 block(256), grid((unsigned)((g.rowsz / 8 + 255) / 256), (H + 63) / 64);
+        hipLaunchKernelGGL(k_vsum, grid, block, 0, st, hs, C, H, g.rowsz, g.SH2, 64, g.hr);
+        return;
+    }
+    const int RB = 96;  // rows per band of the vertical sum; multiple of every ring size used below
+    dim3 block(256), grid((unsigned)((g.rowsz / (p.vsum_wide ? 8 : 4) + 255) / 256), (H + RB - 1) / RB);
+    with_radius(g.SH2, [&](auto r) {
+        constexpr int SH2 = decltype(r)::value;
+        if (p.vsum_wide) hipLaunchKernelGGL((k_vsum_ring<SH2, 4>), grid, block, 0, st, hs, C, H, g.rowsz, RB, g.hr);
+        else hipLaunchKernelGGL((k_vsum_ring<SH2, 2>), grid, block, 0, st, hs, C, H, g.rowsz, RB, g.hr);
+    });
+}
+
+// ---- path stage launches ---------------------------------------------------------------------
+// one row chunk [s0, s1) (in sweep order) of the fused three-role pre-pass; chunk index c picks the
+// ping-pong halves of the line-state buffer (kernels_path.h)
+static void launch_prepass3(const sgm_engine *e, const Plan &p, int xdir, int ydir, int16_t *bl, hipStream_t on, int c, int s0, int s1)
+{
+    const Geom &g = e->g;
+    const int cpx = p.pre_plain ? 0 : (g.W1 + 7) / 8;
+    // (Padding the grid so that every SIMD holds the same number of waves, and halving the
+    // prefetch depth, were both measured: no change -- DESIGN.md 4.4.)
+    const int wpb = SGM_PREPASS_WPB;
+    dim3 grid(p.pre_plain ? (g.W1 + wpb - 1) / wpb : 8 * ((cpx + wpb - 1) / wpb)), block(64 * wpb);
+    const size_t half = (size_t)3 * g.W1 * g.D;  // int16 elements of one state buffer
+    int16_t *sbuf = (int16_t *)(ydir > 0 ? e->pstate.p : e->pstate2.p);
+    const int16_t *sin = sbuf ? sbuf + (size_t)(c & 1) * half : nullptr;
+    int16_t *sout = sbuf ? sbuf + (size_t)((c + 1) & 1) * half : nullptr;
+    const int16_t *C = (const int16_t *)e->cost.p;
+    // (prefetch blocks of 2 rows for the pass that runs beside the sweep -- 70 registers instead of 106 -- were
+    // measured in round 2: within noise; that instantiation is gone)
+    with_np(g, [&](auto np, auto part) {
+        hipLaunchKernelGGL((k_prepass3<np, part>), grid, block, 0, on, g, xdir, ydir, C, bl, p.R, s0, s1, sin, sout, cpx);
+    });
+}
+// the boundary pre-pass of one pass into bl, on stream `on`; returns the launch count.  Roles of the pre-pass:
+// 0 = predecessor one step earlier in the sweep's x order (x - xdir), 1 = same column, 2 = one step later
+static int launch_prepass(const sgm_engine *e, const Plan &p, int xdir, int ydir, int16_t *bl, hipStream_t on)
+{
+    const Geom &g = e->g;
+    const int16_t *C = (const int16_t *)e->cost.p;
+    if (p.prepass_g) {
+        // one role per wave (grid.y = 3): these frames have too few lines to fill the SIMDs with
+        // three-role waves (4K D=16: 478)
+        const int G = 64 / p.GWs;
+        dim3 grid((g.W1 + G - 1) / G, 3), block(64);
+        with_gw(p.GWs, g.D, [&](auto gw, auto part) {
+            hipLaunchKernelGGL((k_prepass3_g<gw, part>), grid, block, 0, on, g, xdir, ydir, C, bl);
+        });
+        return 1;
+    }
+    if (p.fused_prepass) {
+        int n = 0;
+        for (int c = 0; c < p.pre_nch; c++) {
+            const int s0 = c * p.pre_rows, s1 = std::min(g.H, s0 + p.pre_rows);
+            if (s0 >= s1) break;
+            launch_prepass3(e, p, xdir, ydir, bl, on, c, s0, s1);
+            n++;
+        }
+        return n;
+    }
+    // one launch of the single-direction kernel, grid.y = role
+    launch_path(g, xdir, ydir, PATH_BOUNDARY, C, (int16_t *)e->aggr.p, 0, (uint2 *)e->wta.p, on, Boundary{bl, p.R, 0});
+    return 1;
+}
+
+// D <= 64, band height 1: the three directions from the previous row are element-wise given the
+// pre-pass state of every row (k_vert3_g, one streaming pass over all pixels)
+static void launch_vert3(const Geom &g, int GW, bool first, int dir, const int16_t *C, int16_t *S, const int16_t *bq, int rmaj,
+                         hipStream_t st)
+{
+    dim3 grid((g.W1 + 255) / 256, g.H), block(256);
+    with_gw(GW, g.D, [&](auto gw, auto part) {
+        if (first) hipLaunchKernelGGL((k_vert3_g<gw, PATH_FIRST, part>), grid, block, 0, st, g, dir, dir, C, S, bq, rmaj);
+        else hipLaunchKernelGGL((k_vert3_g<gw, PATH_ACCUM, part>), grid, block, 0, st, g, dir, dir, C, S, bq, rmaj);
+    });
+}
+
+// D <= 64, MODE_SGBM: all five directions in one launch, one volume each (k_paths5_g; the one pass runs top-down)
+static void launch_paths5(const Geom &g, int GW, const int16_t *C, int16_t *const Sv[5], hipStream_t st)
+{
+    const int G = 64 / GW, nr = (g.H + G - 1) / G, nl = (g.W1 + G - 1) / G;
+    // (Measured beside it: rows and lines as two launches one after the other, in either order -- 4K D=16 0.60 /
+    // 0.59 ms against 0.57 ms, 720p D=64 0.21 / 0.22 against 0.19; occupancy capped at one or two waves per SIMD
+    // through an LDS allocation -- 0.66 against 0.65 ms, 0.23 / 0.27 against 0.20.  Neither the order nor the
+    // number of waves per SIMD matters: the stage moves 6 ... 10 V in 32-byte pieces per row and is bound by
+    // the memory side)
+    dim3 grid(2 * nr + 3 * nl), block(64);
+    with_gw(GW, g.D, [&](auto gw, auto part) {
+        hipLaunchKernelGGL((k_paths5_g<gw, part>), grid, block, 0, st, g, 1, 1, C, Sv[0], Sv[3], Sv[4], Sv[1], Sv[2], nr);
+    });
+}
+
+// ---- winner-take-all launch ------------------------------------------------------------------
+// k_wta_t over S plus NV - 1 more volumes.  LG = log2(D / 8) for the powers of two that have an instantiation (NV = 1:
+// D = 16 .. 512; 2: up to 128; 3, 5: up to 64), -1 (any D) otherwise
+template <bool POSW, int LG, int NV>
+static int launch_wta_t(const Geom &g, int16_t *const Sv[5], uint2 *wta, int64_t npix, hipStream_t st)
+{
+    const size_t lds = (size_t)64 * wta_t_stride(g.D);
+    // persistent blocks: LDS (64 padded rows) allows four waves per CU; each loops over its share
+    dim3 grid((unsigned)std::min<int64_t>((npix + 63) / 64, 4 * 256)), block(64);
+    if (lds > 48 * 1024)
+        HIP_TRY(hipFuncSetAttribute((const void *)k_wta_t<POSW, LG, NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_wta_t<POSW, LG, NV>), grid, block, lds, st, g, (const int16_t *)Sv[0], wta, npix,
+                       (const int16_t *)Sv[1], (const int16_t *)Sv[2], (const int16_t *)Sv[3], (const int16_t *)Sv[4]);
+    return SGM_OK;
+}
+template <bool POSW, int NV, int LG = 1>
+static int launch_wta_lg(int lg, const Geom &g, int16_t *const Sv[5], uint2 *wta, int64_t npix, hipStream_t st)
+{
+    if constexpr (LG > (NV == 1 ? 6 : NV == 2 ? 4 : 3)) return launch_wta_t<POSW, -1, NV>(g, Sv, wta, npix, st);
+    else if (lg == LG) return launch_wta_t<POSW, LG, NV>(g, Sv, wta, npix, st);
+    else return launch_wta_lg<POSW, NV, LG + 1>(lg, g, Sv, wta, npix, st);
+}
+static int launch_wta(const Geom &g, int nvol, int16_t *const Sv[5], uint2 *wta, hipStream_t st)
+{
+    const int64_t npix = (int64_t)g.H * g.W1;
+    int lg = -1;  // log2(D / 8) when D is a power of two
+    for (int q = 1; q <= 6; q++)
+        if (g.D == (8 << q)) lg = q;
+    auto go = [&](auto posw) {
+        constexpr bool POSW = decltype(posw)::value;
+        if (nvol == 5) return launch_wta_lg<POSW, 5>(lg, g, Sv, wta, npix, st);
+        if (nvol == 3) return launch_wta_lg<POSW, 3>(lg, g, Sv, wta, npix, st);
+        if (nvol == 2) return launch_wta_lg<POSW, 2>(lg, g, Sv, wta, npix, st);
+        return launch_wta_lg<POSW, 1>(lg, g, Sv, wta, npix, st);
+    };
+    return g.uniq < 100 ? go(std::true_type()) : go(std::false_type());
+}
+
+// ---- the stages of one compute -----------------------------------------------------------------
 // Phases of one compute.  A single pair runs them all; the batch entry with chained sweeps
 // (sgm_pipeline_batch_device) runs PH_PRE of every pair, then ONE sweep launch per pass for all pairs, then PH_POST
 // of every pair.
 enum { PH_PRE = 1 /* features, block cost, MODE_SGBM's fifth path beside the sweep */, PH_MID = 2 /* pre-pass + sweeps */,
        PH_POST = 4 /* the rest */, PH_ALL = 7 };
+
+// one stage on stream `on`: `enqueue` returns its launch count, or an SGM_ERR_* code (< 0)
+template <class F>
+static int run_stage(sgm_engine *e, const char *name, hipStream_t on, F &&enqueue)
+{
+    int rc = stage_begin(e, name, on);
+    if (rc) return rc;
+    const int n = enqueue();
+    if (n < 0) return n;
+    KCHECK();
+    return stage_end(e, n, on);
+}
+
+// the auxiliary streams and their events, created on first use
+static int ensure_aux(sgm_engine *e, bool second)
+{
+    if (!e->aux) {
+        HIP_TRY(hipStreamCreateWithFlags(&e->aux, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
+    }
+    if (second && !e->aux2) {
+        HIP_TRY(hipStreamCreateWithFlags(&e->aux2, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&e->ev_join2, hipEventDisableTiming));
+    }
+    return SGM_OK;
+}
+
+static int stage_features(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_right, int64_t stride)
+{
+    const Geom &g = e->g;
+    return run_stage(e, "features", e->stream, [&] {
+        hipLaunchKernelGGL(k_features, dim3((g.W + 255) / 256, g.H, 2), dim3(256), 0, e->stream, d_left, d_right, stride, g.H, g.W,
+                           g.ftzero, (uint2 *)e->lrec.p, (uint8_t *)e->rplanes.p);
+        return 1;
+    });
+}
+
+// per-pixel cost and box sums -> block cost C
+// (Running the cost stage and the downward pre-pass as a pipeline over row chunks on separate
+// streams was built and measured in round 2: the overlapped kernels only slow each other down --
+// cost_box 1.17 -> 2.75 ms, prepass_dn 2.05 -> 3.19 ms, frame 11.97 against 11.90 ms -- this phase
+// of the frame is bound by HBM bandwidth, not by the order of its launches.  DESIGN.md 4.4.)
+static int stage_cost(sgm_engine *e, const Plan &p)
+{
+    const Geom &g = e->g;
+    hipStream_t st = e->stream;
+    const uint2 *lrec = (const uint2 *)e->lrec.p;
+    const uint8_t *rpl = (const uint8_t *)e->rplanes.p;
+    uint8_t *px = (uint8_t *)e->aggr.p;  // (the byte costs live in the S buffer until C is complete: ensure_plan_buffers)
+    int16_t *C = (int16_t *)e->cost.p, *HS = (int16_t *)e->hsum.p;
+    int rc;
+    if (p.byte_cost) {
+        if ((rc = run_stage(e, "cost_pix", st, [&] { launch_pix(g, lrec, rpl, px, st); return 1; }))) return rc;
+        return run_stage(e, "cost_box", st, [&] { launch_box(g, p, px, C, st); return 1; });
+    }
+    rc = run_stage(e, "cost_hsum", st, [&] {
+        if (!p.pix_px) {
+            const int r = launch_hsum(g, lrec, rpl, HS, st);
+            return r ? r : 1;
+        }
+        launch_pix(g, lrec, rpl, px, st);
+        hipLaunchKernelGGL(k_hsum_px, dim3((g.W1 + 255) / 256, g.H), dim3(256), 0, st, g, (const uint8_t *)px, HS);
+        return 1;
+    });
+    if (rc) return rc;
+    return run_stage(e, "cost_vsum", st, [&] { launch_vsum(g, p, HS, C, st); return 1; });
+}
+
+// MODE_SGBM, Plan::nvol 2 and 3: the in-row paths on the auxiliary streams, from here on, each into a volume of its own
+static int fork_in_row(sgm_engine *e, const Plan &p)
+{
+    if (p.nvol != 2 && p.nvol != 3) return SGM_OK;
+    const Geom &g = e->g;
+    const int16_t *C = (const int16_t *)e->cost.p;
+    uint2 *wta = (uint2 *)e->wta.p;
+    int rc;
+    if ((rc = ensure_aux(e, p.nvol == 3))) return rc;
+    HIP_TRY(hipEventRecord(e->ev_fork, e->stream));
+    HIP_TRY(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
+    rc = run_stage(e, "path_W", e->aux, [&] {
+        launch_rows_grouped(g, g.H, p.GWs, -1, PATH_FIRST, C, (int16_t *)e->aggr2.p, 1, wta, e->aux);
+        return 1;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(e->ev_join, e->aux));
+    if (p.nvol == 3) {
+        HIP_TRY(hipStreamWaitEvent(e->aux2, e->ev_fork, 0));
+        rc = run_stage(e, "path_E", e->aux2, [&] {
+            launch_rows_grouped(g, g.H, p.GWs, +1, PATH_FIRST, C, (int16_t *)e->aggr3.p, 1, wta, e->aux2);
+            return 1;
+        });
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(e->ev_join2, e->aux2));
+    }
+    return SGM_OK;
+}
+
+// v1 schedule: one kernel per direction, vertical-ish first, horizontal last (WTA)
+static int paths_v1(sgm_engine *e)
+{
+    struct Dir { int rx, ry; const char *name; };
+    static const Dir dirs[8] = {{0, 1, "path_S"}, {1, 1, "path_SE"}, {-1, 1, "path_SW"}, {0, -1, "path_N"},
+                                {1, -1, "path_NE"}, {-1, -1, "path_NW"}, {1, 0, "path_E"}, {-1, 0, "path_W_wta"}};
+    const Geom &g = e->g;
+    for (int k = 0; k < 8; k++) {
+        if (g.mode == 0 && k >= 3 && k < 6) continue;  // (the upward directions: MODE_HH only)
+        const int mode = k == 0 ? PATH_FIRST : (k == 7 ? PATH_LAST : PATH_ACCUM);
+        int rc = run_stage(e, dirs[k].name, e->stream, [&] {
+            launch_path(g, dirs[k].rx, dirs[k].ry, mode, (const int16_t *)e->cost.p, (int16_t *)e->aggr.p, k == 7 ? e->keep_aggr : 0,
+                        (uint2 *)e->wta.p, e->stream);
+            return 1;
+        });
+        if (rc) return rc;
+    }
+    return SGM_OK;
+}
+
+// MODE_HH: the upward pre-pass on the auxiliary stream, from "now" on the main stream
+static int fork_prepass_up(sgm_engine *e, const Plan &p)
+{
+    int rc;
+    if ((rc = ensure_aux(e, false))) return rc;
+    HIP_TRY(hipEventRecord(e->ev_fork, e->stream));
+    HIP_TRY(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
+    if ((rc = run_stage(e, "prepass_up", e->aux, [&] { return launch_prepass(e, p, -1, -1, (int16_t *)e->bndL2.p, e->aux); })))
+        return rc;
+    HIP_TRY(hipEventRecord(e->ev_join, e->aux));
+    return SGM_OK;
+}
+
+// fused schedules: per pass a read-only boundary pre-pass (3 line scans) + one sweep; chained sweeps; the small-D kernels
+static int paths_fused(sgm_engine *e, const Plan &p)
+{
+    const Geom &g = e->g;
+    hipStream_t st = e->stream;
+    const int16_t *C = (const int16_t *)e->cost.p;
+    int16_t *S = (int16_t *)e->aggr.p;
+    uint2 *wta = (uint2 *)e->wta.p;
+    int rc;
+    if (p.overlap && p.fork_early && (rc = fork_prepass_up(e, p))) return rc;
+    for (int pass = 0; pass < p.npass; pass++) {
+        const int ydir = pass == 0 ? 1 : -1, xdir = ydir;
+        int16_t *bl = (int16_t *)(pass == 0 ? e->bndL.p : e->bndL2.p);
+        if (p.nbands > 1 && !(p.overlap && pass == 1) && !p.chain && p.nvol != 5) {
+            rc = run_stage(e, pass == 0 ? "prepass_dn" : "prepass_up", st, [&] { return launch_prepass(e, p, xdir, ydir, bl, st); });
+            if (rc) return rc;
+        }
+        if (p.overlap && pass == 0 && !p.fork_early && (rc = fork_prepass_up(e, p))) return rc;
+        if (p.overlap && pass == 1) {
+            HIP_TRY(hipStreamWaitEvent(st, e->ev_join, 0));
+            stage_break(e);  // (the wait is not part of the next stage)
+        }
+        // winner-take-all: fused into the last path kernel (debug 2), or -- default -- a
+        // separate pass over S with one lane per pixel (k_wta_t)
+        const bool last = pass == p.npass - 1 && g.mode == 1 && p.fused_wta && !p.rows4;
+        SweepArgs a{ydir, xdir, p.R, C, S, (const int16_t *)bl, wta, e->keep_aggr, e->debug, nullptr, nullptr, nullptr, p.nbands};
+        ChainFrames fr;
+        if (p.chain) {
+            // one record serves both passes (they follow each other on the stream)
+            fr.nf = 1;
+            fr.C[0] = C;
+            fr.S[0] = S;
+            fr.bnd[0] = (int16_t *)e->bndL.p;
+            fr.hr[0] = g.hr;
+            a.ctl = (uint32_t *)e->chain_ctl.p;
+            a.err = (uint32_t *)e->chain_err.p;
+            HIP_TRY(hipMemsetAsync(e->chain_ctl.p, 0, chain_ctl_bytes(1, p.nbands), st));
+            stage_break(e);
+        }
+        const char *name = p.nvol == 5 ? "paths5" : p.chain ? (pass == 0 ? "chain_dn" : "chain_up")
+                                                             : (pass == 0 ? "sweep_dn" : (p.fused_wta ? "sweep_up_wta" : "sweep_up"));
+        rc = run_stage(e, name, st, [&]() -> int {
+            if (p.nvol == 5) {
+                int16_t *const Sv[5] = {S, (int16_t *)e->aggr2.p, (int16_t *)e->aggr3.p, (int16_t *)e->aggr4.p, (int16_t *)e->aggr5.p};
+                launch_paths5(g, p.GWs, C, Sv, st);
+            } else if (p.rows4) {
+                // per-row state written by the grouped pre-pass: role-major; by the single-direction kernel (debug 16): band layout
+                launch_vert3(g, p.GWs, pass == 0, xdir, C, S, bl, p.prepass_g ? 1 : 0, st);
+                // only the in-row direction is a recurrence (k_rows_g, S +=) -- unless it runs on a stream of its own
+                if (p.nvol < 3) launch_rows_grouped(g, g.H, p.GWs, xdir, PATH_ACCUM, C, S, 1, wta, st);
+            } else if (p.chain) {
+                if (int r = launch_chain(g, a, fr, pass == 0 ? SWEEP_FIRST : SWEEP_ACCUM, chain_window(g, p.R, p.nbands, 1, e->chain_wgs), st)) return r;
+            } else if (int r = launch_sweep(g, a, pass == 0 ? SWEEP_FIRST : (last ? SWEEP_LAST : SWEEP_ACCUM), p.nbands, st)) {
+                return r;
+            }
+            return 1;
+        });
+        if (rc) return rc;
+    }
+    return SGM_OK;
+}
+
+// MODE_SGBM's fifth path joins S: the main stream waits for the volumes of the auxiliary streams, or the path runs here
+static int stage_join(sgm_engine *e, const Plan &p)
+{
+    if (p.nvol == 2 || p.nvol == 3) {
+        HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_join, 0));
+        if (p.nvol == 3) HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_join2, 0));
+        stage_break(e);
+        return SGM_OK;
+    }
+    if (!p.path_w_main) return SGM_OK;
+    const Geom &g = e->g;
+    return run_stage(e, p.fused_wta ? "path_W_wta" : "path_W", e->stream, [&] {
+        const int pm = p.fused_wta ? PATH_LAST : PATH_ACCUM;
+        const int16_t *C = (const int16_t *)e->cost.p;
+        int16_t *S = (int16_t *)e->aggr.p;
+        if (p.path_w_lines) launch_path(g, -1, 0, pm, C, S, e->keep_aggr, (uint2 *)e->wta.p, e->stream);
+        else launch_rows_grouped(g, g.H, p.GWs, -1, pm, C, S, e->keep_aggr, (uint2 *)e->wta.p, e->stream);
+        return 1;
+    });
+}
+
+static int stage_wta(sgm_engine *e, const Plan &p)
+{
+    if (p.fused_wta) return SGM_OK;
+    const Geom &g = e->g;
+    return run_stage(e, "wta", e->stream, [&] {
+        int16_t *const Sv[5] = {(int16_t *)e->aggr.p, p.nvol >= 2 ? (int16_t *)e->aggr2.p : nullptr,
+                                p.nvol >= 3 ? (int16_t *)e->aggr3.p : nullptr, p.nvol >= 5 ? (int16_t *)e->aggr4.p : nullptr,
+                                p.nvol >= 5 ? (int16_t *)e->aggr5.p : nullptr};
+        if (int rc = launch_wta(g, p.nvol, Sv, (uint2 *)e->wta.p, e->stream)) return rc;
+        if (e->keep_aggr) {  // the volume a caller inspects is the whole sum
+            const int64_t n8 = (int64_t)g.rowsz * g.H / 8;  // rowsz = W1 * D is a multiple of 16
+            for (int k = 1; k < 5; k++)
+                if (Sv[k]) hipLaunchKernelGGL(k_add_sat, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, e->stream, Sv[0], (const int16_t *)Sv[k], n8);
+        }
+        return 1;
+    });
+}
+
+// right view, sub-pixel, LR check
+static int stage_select(sgm_engine *e)
+{
+    const Geom &g = e->g;
+    return run_stage(e, "select_lr", e->stream, [&]() -> int {
+        const size_t lds = (size_t)g.W * 4;
+        if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k_select, dim3(g.H), dim3(256), lds, e->stream, g, (const uint2 *)e->wta.p, (int16_t *)e->disp_raw.p);
+        return 1;
+    });
+}
+
+// 3x3 median, then the speckle filter on the output
+static int stage_median_speckle(sgm_engine *e, const Plan &p, int16_t *d_disp)
+{
+    const int H = e->g.H, W = e->g.W;
+    int rc = run_stage(e, "median3", e->stream, [&] {
+        // the result goes to the median tap AND to the output buffer (the speckle filter works in place there)
+        hipLaunchKernelGGL(k_median3, dim3((W + 255) / 256, H), dim3(256), 0, e->stream, (const int16_t *)e->disp_raw.p,
+                           (int16_t *)e->disp_med.p, d_disp, H, W);
+        return 1;
+    });
+    if (rc || !p.speckle) return rc;
+    const sgm_params &q = e->params;
+    return run_stage(e, "speckle", e->stream, [&] {
+        const int r = run_speckles(e, d_disp, H, W, (q.minDisparity - 1) * 16, q.speckleWindowSize, 16 * q.speckleRange);
+        return r ? r : 4;
+    });
+}
 
 static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_right, int H, int W,
                        int64_t stride, int16_t *d_disp, int phases = PH_ALL)
@@ -633,627 +1230,41 @@ static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_ri
     if (H <= 0 || W < 2 || stride < W) return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld", H, W, (long long)stride);
     if (W > 32767 || H > 32767) return set_err(SGM_ERR_UNSUPPORTED, "image larger than 32767 in a dimension");
     HIP_TRY(hipSetDevice(e->device));
-    int rc = ensure_buffers(e, H, W);
+    Geom g0;
+    int rc = normalise(&e->params, H, W, &g0);
     if (rc) return rc;
-    const Geom &g = e->g;
-    hipStream_t st = e->stream;
+    const Plan p = make_plan(e, g0, H);
+    if (phases != PH_ALL && !p.chain) return set_err(SGM_ERR_INVALID_ARG, "phased compute needs the chained schedule");
+    if ((rc = ensure_plan_buffers(e, p, H, W))) return rc;
     const bool do_pre = (phases & PH_PRE) != 0, do_mid = (phases & PH_MID) != 0, do_post = (phases & PH_POST) != 0;
     if (do_pre) {
         e->nstages = 0;
         e->nevents = 0;
         e->last_end_ev = -1;
-        e->plan_chain = false;
+        e->plan = p;
     } else {
         stage_break(e);
     }
-    const int64_t npx = (int64_t)H * W;
-    const unsigned nb_px = (unsigned)((npx + 255) / 256);
+    if (do_pre && !e->hr_accumulate) HIP_TRY(hipMemsetAsync(e->headroom.p, 0, 8, e->stream));  // headroom record of this compute (sgm_get_headroom)
 
-    int16_t *raw = (int16_t *)e->disp_raw.p, *med = (int16_t *)e->disp_med.p;
-    if (do_pre && !e->hr_accumulate) HIP_TRY(hipMemsetAsync(e->headroom.p, 0, 8, st));  // headroom record of this compute (sgm_get_headroom)
-
-    if (g.W1 <= 0) {
+    if (e->g.W1 <= 0) {
         // no column can be matched: the whole map is invalid (upstream early-out), then median
         // and speckle act on a constant image
-        if (phases != PH_ALL) return set_err(SGM_ERR_INVALID_ARG, "phased compute on a frame without matchable columns");
-        if ((rc = stage_begin(e, "fill_invalid"))) return rc;
-        hipLaunchKernelGGL(k_fill_i16, dim3(nb_px), dim3(256), 0, st, raw, npx, (int16_t)g.invalid_scaled);
-        KCHECK();
-        if ((rc = stage_end(e, 1))) return rc;
+        const int64_t npx = (int64_t)H * W;
+        rc = run_stage(e, "fill_invalid", e->stream, [&] {
+            hipLaunchKernelGGL(k_fill_i16, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, e->stream, (int16_t *)e->disp_raw.p, npx,
+                               (int16_t)e->g.invalid_scaled);
+            return 1;
+        });
+        if (rc) return rc;
     } else {
-        const int16_t *C = (const int16_t *)e->cost.p;
-        int16_t *S = (int16_t *)e->aggr.p;
-        int16_t *HS = (int16_t *)e->hsum.p;
-        uint2 *wta = (uint2 *)e->wta.p;
-
-        // -- features
-        if (do_pre) {
-            if ((rc = stage_begin(e, "features"))) return rc;
-            dim3 grid((W + 255) / 256, H, 2), block(256);
-            hipLaunchKernelGGL(k_features, grid, block, 0, st, d_left, d_right, stride, H, W, g.ftzero, (uint2 *)e->lrec.p,
-                               (uint8_t *)e->rplanes.p);
-            KCHECK();
-            if ((rc = stage_end(e, 1))) return rc;
-        }
-
-        // -- horizontal box sum of the pixel cost
-        // -- horizontal box sum of the pixel cost (rows y0 .. y1-1), vertical box sum -> block cost
-        const int XL = 128;
-        const int nchunks = (g.W1 + XL - 1) / XL;
-        int RS = 1;  // ring of the last blockSize+1 cost vectors, rounded to a power of two
-        while (RS < 2 * g.SW2 + 2) RS <<= 1;
-        const HsumLds l = hsum_lds_layout(g.NP, RS, XL, g.SW2);
-        const uint2 *lrec = (const uint2 *)e->lrec.p;
-        const uint8_t *rpl = (const uint8_t *)e->rplanes.p;
-        auto launch_hsum = [&](int hs_y0, int hs_y1) -> int {
-            dim3 grid((unsigned)((int64_t)(hs_y1 - hs_y0) * nchunks)), block(64);
-            // RS_T = RS instantiations carry the unrolled interior fast path (block sizes up to 15)
-#define SGM_HSUM(NP_, RS_)                                                                                          \
-    do {                                                                                                            \
-        if (l.total_bytes > 48 * 1024)                                                                              \
-            HIP_TRY(hipFuncSetAttribute((const void *)k_hsum<NP_, RS_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        l.total_bytes));                                                            \
-        hipLaunchKernelGGL((k_hsum<NP_, RS_>), grid, block, l.total_bytes, st, g, lrec, rpl, HS, XL, nchunks, RS,    \
-                           l.ring_bytes, l.lrec_bytes, l.seg_len, hs_y0);                                           \
-    } while (0)
-#define SGM_HSUM_NP(NP_)                    \
-    do {                                    \
-        if (RS == 4) SGM_HSUM(NP_, 4);      \
-        else if (RS == 8) SGM_HSUM(NP_, 8); \
-        else if (RS == 16) SGM_HSUM(NP_, 16); \
-        else SGM_HSUM(NP_, 0);              \
-    } while (0)
-            if (g.NP == 1) SGM_HSUM_NP(1);
-            else if (g.NP == 2) SGM_HSUM_NP(2);
-            else SGM_HSUM_NP(4);
-#undef SGM_HSUM_NP
-#undef SGM_HSUM
-            return SGM_OK;
-        };
-        const int RB = 96;  // rows per band of the vertical sum; multiple of every ring size used below
-        const int nvb = (H + RB - 1) / RB;
-        const int16_t *hsp = (const int16_t *)HS;
-        int16_t *cp = (int16_t *)e->cost.p;
-        auto launch_vsum = [&](int nb) {
-            const bool wide = !(e->debug & 8);  // 8 int16 per thread (debug 8: 4, for A/B timing)
-            const int per_thread = wide ? 8 : 4;
-            dim3 block(256), gridr((unsigned)((g.rowsz / per_thread + 255) / 256), nb);
-#define SGM_VSUM(SH2_)                                                                                             \
-    case SH2_:                                                                                                     \
-        if (wide) hipLaunchKernelGGL((k_vsum_ring<SH2_, 4>), gridr, block, 0, st, hsp, cp, H, g.rowsz, RB, g.hr); \
-        else hipLaunchKernelGGL((k_vsum_ring<SH2_, 2>), gridr, block, 0, st, hsp, cp, H, g.rowsz, RB, g.hr); \
-        break;
-            switch (g.SH2) {  // ring variant: each hsum row is read once
-                SGM_VSUM(1)
-                SGM_VSUM(2)
-                SGM_VSUM(3)
-                SGM_VSUM(4)
-                SGM_VSUM(5)
-#undef SGM_VSUM
-            default: break;
-            }
-        };
-        const Plan plan = make_plan(e, g, H);   // (the same decisions the batch entries read before they enqueue anything)
-        const bool byte_cost = plan.byte_cost;
-        const int GWc = g.D > 64 ? 64 : (g.D <= 16 ? 8 : (g.D <= 32 ? 16 : 32));  // lane-group width of k_box_u8
-        const int cpw = 16 * (64 / GWc);  // columns per workgroup of k_box_u8: 4 waves x (64 / GW groups) x 4 columns
-        // rows per band of k_box_u8 (a band re-reads 2 * SH2 rows above it; multiples of 16: the register rings): 96, less
-        // on frames too small to fill the chip with bands that tall
-        int RBb = 96;
-        for (int cand : {48, 32, 16})
-            if ((int64_t)((g.W1 + cpw - 1) / cpw) * ((H + RBb - 1) / RBb) * 4 < 1024) RBb = cand;
-        const int nvbb = (H + RBb - 1) / RBb;
-        // per-pixel cost of rows [y_lo, y_hi) / block cost of the nb bands of RB rows, on stream `on`
-        auto launch_pix = [&](int y_lo, int y_hi, hipStream_t on) {
-            const int nj = XL + 2;
-            const int lrec_b = ((nj * 8) + 15) & ~15;
-            const int seg_l = (nj + 128 * g.NP + 15) & ~15;
-            const size_t lds = (size_t)lrec_b + 6 * (size_t)seg_l;
-            dim3 grid((unsigned)((int64_t)(y_hi - y_lo) * nchunks)), block(64);
-            uint8_t *px = (uint8_t *)e->aggr.p;   // (the byte costs live in the S buffer until C is complete: ensure_buffers)
-            if (g.D <= 32) {  // one thread per pixel (whole frame; callers pass [0, H))
-                dim3 gridp((g.W1 + 255) / 256, H), blockp(256);
-                hipLaunchKernelGGL(k_pix_px, gridp, blockp, (size_t)6 * (256 + g.D), on, g, lrec, rpl, px);
-            } else
-            if (g.NP == 1) hipLaunchKernelGGL(k_pix<1>, grid, block, lds, on, g, lrec, rpl, px, XL, nchunks, lrec_b, seg_l, y_lo);
-            else if (g.NP == 2) hipLaunchKernelGGL(k_pix<2>, grid, block, lds, on, g, lrec, rpl, px, XL, nchunks, lrec_b, seg_l, y_lo);
-            else hipLaunchKernelGGL(k_pix<4>, grid, block, lds, on, g, lrec, rpl, px, XL, nchunks, lrec_b, seg_l, y_lo);
-        };
-        auto launch_box = [&](int nb, hipStream_t on) {
-            dim3 grid((g.W1 + cpw - 1) / cpw, nb), block(256);
-            const uint8_t *px = (const uint8_t *)e->aggr.p;
-            int16_t *cp2 = (int16_t *)e->cost.p;
-#define SGM_BOX(R_)                                                                                        \
-    case R_:                                                                                               \
-        if (GWc == 8) hipLaunchKernelGGL((k_box_u8<R_, 1, 8>), grid, block, 0, on, g, px, cp2, RBb);        \
-        else if (GWc == 16) hipLaunchKernelGGL((k_box_u8<R_, 1, 16>), grid, block, 0, on, g, px, cp2, RBb); \
-        else if (GWc == 32) hipLaunchKernelGGL((k_box_u8<R_, 1, 32>), grid, block, 0, on, g, px, cp2, RBb); \
-        else if (g.NP == 1) hipLaunchKernelGGL((k_box_u8<R_, 1>), grid, block, 0, on, g, px, cp2, RBb);  \
-        else if (g.NP == 2) hipLaunchKernelGGL((k_box_u8<R_, 2>), grid, block, 0, on, g, px, cp2, RBb); \
-        else hipLaunchKernelGGL((k_box_u8<R_, 4>), grid, block, 0, on, g, px, cp2, RBb);            \
-        break;
-            switch (g.SW2) {
-                SGM_BOX(1)
-                SGM_BOX(2)
-                SGM_BOX(3)
-                SGM_BOX(4)
-                SGM_BOX(5)
-            default: break;
-            }
-#undef SGM_BOX
-        };
-        // ---- schedule parameters (make_plan)
-        const int GWs = plan.GWs;
-        const bool rows4 = plan.rows4;
-        const int npass = plan.npass;
-        const bool chain = plan.chain;
-        const int R = plan.R;
-        const int nbands = plan.nbands;
-        // Narrow frames (fewer than ~1.5 lines per SIMD) are bound by the latency of one wave's
-        // instruction stream: there the single-direction kernel with one wave per (line, role) -- three
-        // times the waves, a third of the work each -- is faster (720p D=64: 0.26 against 0.34 ms); its
-        // three readers of C are served by L2 / the Infinity Cache at these sizes.
-        const bool narrow = g.W1 <= 1536 && e->prepass_rows == 0;  // (an explicit chunk height selects k_prepass3: tests)
-        const bool fused_prepass = !rows4 && !(e->debug & 16) && !narrow && (int64_t)g.rowsz * H < (1ll << 31);
-        // (Running the cost stage and the downward pre-pass as a pipeline over row chunks on separate
-        // streams was built and measured in round 2: the overlapped kernels only slow each other down --
-        // cost_box 1.17 -> 2.75 ms, prepass_dn 2.05 -> 3.19 ms, frame 11.97 against 11.90 ms -- this phase
-        // of the frame is bound by HBM bandwidth, not by the order of its launches.  DESIGN.md 4.4.)
-        if (!do_pre) {
-            // (the cost stage belongs to PH_PRE)
-        } else if (byte_cost) {
-            if ((rc = stage_begin(e, "cost_pix"))) return rc;
-            launch_pix(0, H, st);
-            KCHECK();
-            if ((rc = stage_end(e, 1))) return rc;
-            if ((rc = stage_begin(e, "cost_box"))) return rc;
-            launch_box(nvbb, st);
-            KCHECK();
-            if ((rc = stage_end(e, 1))) return rc;
-        } else {
-        if ((rc = stage_begin(e, "cost_hsum"))) return rc;
-        if (g.D <= 32 && !(e->debug & 4) && 2 * g.ftzero + 63 <= 255) {
-            // D <= 32: one thread per pixel (lanes spanning D would mostly idle; at D = 64 the wave-per-
-            // chunk kernel is still ahead); the byte volume borrows the S buffer, unused before the paths
-            uint8_t *px = (uint8_t *)e->aggr.p;
-            dim3 grid((g.W1 + 255) / 256, H), block(256);
-            hipLaunchKernelGGL(k_pix_px, grid, block, (size_t)6 * (256 + g.D), st, g, lrec, rpl, px);
-            hipLaunchKernelGGL(k_hsum_px, grid, block, 0, st, g, (const uint8_t *)px, (int16_t *)HS);
-        } else if ((rc = launch_hsum(0, H))) {
+        if (do_pre && ((rc = stage_features(e, d_left, d_right, stride)) || (rc = stage_cost(e, p)) || (rc = fork_in_row(e, p))))
             return rc;
-        }
-        KCHECK();
-        if ((rc = stage_end(e, 1))) return rc;
-        if ((rc = stage_begin(e, "cost_vsum"))) return rc;
-        if (g.SH2 >= 1 && g.SH2 <= 5) {
-            launch_vsum(nvb);
-        } else {
-            dim3 block(256), grid((unsigned)((g.rowsz / 8 + 255) / 256), (H + 63) / 64);
-            hipLaunchKernelGGL(k_vsum, grid, block, 0, st, hsp, cp, H, g.rowsz, g.SH2, 64, g.hr);
-        }
-        KCHECK();
-        if ((rc = stage_end(e, 1))) return rc;
-        }  // int16 pipeline
-
-        if (e->schedule == 0) {
-            if (phases != PH_ALL) return set_err(SGM_ERR_INVALID_ARG, "phased compute needs the fused schedules");
-            // -- v1 schedule: one kernel per direction, vertical-ish first, horizontal last (WTA)
-            struct Dir { int rx, ry; const char *name; };
-            static const Dir down[3] = {{0, 1, "path_S"}, {1, 1, "path_SE"}, {-1, 1, "path_SW"}};
-            static const Dir upw[3] = {{0, -1, "path_N"}, {1, -1, "path_NE"}, {-1, -1, "path_NW"}};
-            bool first = true;
-            for (int k = 0; k < 3; k++) {
-                if ((rc = stage_begin(e, down[k].name))) return rc;
-                launch_path(g, down[k].rx, down[k].ry, first ? PATH_FIRST : PATH_ACCUM, C, S, 0, wta, st);
-                KCHECK();
-                first = false;
-                if ((rc = stage_end(e, 1))) return rc;
-            }
-            if (g.mode == 1) {
-                for (int k = 0; k < 3; k++) {
-                    if ((rc = stage_begin(e, upw[k].name))) return rc;
-                    launch_path(g, upw[k].rx, upw[k].ry, PATH_ACCUM, C, S, 0, wta, st);
-                    KCHECK();
-                    if ((rc = stage_end(e, 1))) return rc;
-                }
-            }
-            if ((rc = stage_begin(e, "path_E"))) return rc;
-            launch_path(g, 1, 0, PATH_ACCUM, C, S, 0, wta, st);
-            KCHECK();
-            if ((rc = stage_end(e, 1))) return rc;
-            if ((rc = stage_begin(e, "path_W_wta"))) return rc;
-            launch_path(g, -1, 0, PATH_LAST, C, S, e->keep_aggr, wta, st);
-            KCHECK();
-            if ((rc = stage_end(e, 1))) return rc;
-        } else {
-            // -- fused schedule: per pass a read-only boundary pre-pass (3 line scans) + one sweep
-            // Winner-take-all: a separate pass over S (k_wta_t, one lane per pixel) after the second sweep
-            // of MODE_HH and after the in-row path of MODE_SGBM for D <= 128; fused into the in-row path
-            // kernel for MODE_SGBM with D > 128 (there the separate form costs a third volume of traffic:
-            // 4K D=256 2.49 ms fused against 2.56 + 0.73; D=128: 2.01 against 1.42 + 0.43, 1080p 0.79 against
-            // 0.44 + 0.10).  debug 2 forces the fused form everywhere, debug 2048 the separate one (A/B, cross-check).
-            const bool fused_wta = !(e->debug & 2048) && (((e->debug & 2) != 0 && !rows4) ||
-                                                          (g.mode == 0 && ((e->debug & 4) || g.D > 128)));
-            // MODE_SGBM with the separate winner-take-all (D <= 128): the fifth path (in-row, right to left) needs
-            // nothing but C, so it runs on the auxiliary stream from here on, as a FIRST pass into a volume of its
-            // own (2 V of traffic instead of the 3 V of "S +="), beside the pre-pass and the sweep -- which at these
-            // D are bound by instruction issue, not by HBM; k_wta_t adds the two volumes while it stages them.
-            // debug 65536: the fifth path after the sweep, accumulating into S (A/B).
-            const bool two_vol = g.mode == 0 && !fused_wta && g.D <= 128 && !(e->debug & 4) && !(e->debug & 65536);
-            int16_t *S2 = nullptr;
-            if (two_vol) {
-                if ((rc = e->aggr2.ensure((size_t)g.rowsz * H * sizeof(int16_t)))) return rc;
-                S2 = (int16_t *)e->aggr2.p;
-            }
-            // D <= 64 (small-D schedule): the OTHER in-row path (left to right) needs nothing but C either.  It used to follow
-            // the element-wise vertical kernel as "S +=" on the main stream -- a chain of W1 dependent steps on the
-            // critical path of a latency-bound frame; now it runs as a FIRST pass into a third volume on a stream of its
-            // own, beside the per-row pre-pass and k_vert3_g, and the winner-take-all adds three volumes.
-            const bool three_vol = two_vol && rows4 && !(e->debug & SGM_DBG_IN_ROW_ON_MAIN_STREAM);
-            int16_t *S3 = nullptr;
-            if (three_vol) {
-                if ((rc = e->aggr3.ensure((size_t)g.rowsz * H * sizeof(int16_t)))) return rc;
-                S3 = (int16_t *)e->aggr3.p;
-            }
-            // ... and so do the three directions that come from the row above: the walk along their lines (the "pre-pass" of
-            // the small-D schedule) forms L_r(p, .) on its way, so each role writes it to a volume of its own and the
-            // winner-take-all adds five volumes: no per-row record (3 V written, 3 V read), no element-wise kernel behind
-            // the walk -- and all five directions are ONE launch (k_paths5_g: why, see there).  debug 8192: the record form
-            // with the in-row paths on streams of their own (A/B; MODE_HH keeps it).
-            const bool five_vol = three_vol && !(e->debug & SGM_DBG_SMALL_D_RECORD);
-            int16_t *S4 = nullptr, *S5 = nullptr;
-            if (five_vol) {
-                if ((rc = e->aggr4.ensure((size_t)g.rowsz * H * sizeof(int16_t)))) return rc;
-                if ((rc = e->aggr5.ensure((size_t)g.rowsz * H * sizeof(int16_t)))) return rc;
-                S4 = (int16_t *)e->aggr4.p;
-                S5 = (int16_t *)e->aggr5.p;
-            }
-            const size_t bnd_bytes = five_vol ? 0 : (size_t)nbands * g.W1 * 3 * g.D * 2;
-            if (nbands > 1 && !five_vol) {
-                if ((rc = e->bndL.ensure(bnd_bytes))) return rc;
-                if (!chain) {
-                    if (npass == 2 && (rc = e->bndL2.ensure(bnd_bytes))) return rc;
-                    const size_t st_bytes = (size_t)2 * 3 * g.W1 * g.D * 2;  // ping-pong line state between pre-pass chunks
-                    if ((rc = e->pstate.ensure(st_bytes))) return rc;
-                    if (npass == 2 && (rc = e->pstate2.ensure(st_bytes))) return rc;
-                }
-            }
-            const size_t ctl_bytes = ((size_t)(1 + nbands) * 4 + 15) & ~(size_t)15;
-            if (do_pre) {
-                e->plan_chain = chain;
-                e->plan_R = R;
-                e->plan_nbands = nbands;
-            }
-            if (phases != PH_ALL && !chain) return set_err(SGM_ERR_INVALID_ARG, "phased compute needs the chained schedule");
-            if (chain) {
-                if ((rc = e->chain_ctl.ensure(ctl_bytes))) return rc;
-                if (!e->chain_err.p) {
-                    if ((rc = e->chain_err.ensure(16))) return rc;
-                    HIP_TRY(hipMemsetAsync(e->chain_err.p, 0, 16, st));
-                }
-            }
-            // roles of the pre-pass: 0 = predecessor one step earlier in the sweep's x order
-            // (x - xdir), 1 = same column, 2 = one step later
-            // one row chunk [s0, s1) (in sweep order) of the fused three-role pre-pass; chunk index c picks the
-            // ping-pong halves of the line-state buffer (kernels_path.h)
-            auto prepass_chunk = [&](int xdir, int ydir, int16_t *bl, hipStream_t on, int c, int s0, int s1, bool plain) {
-                const bool partial = g.D != 128 * g.NP;
-                const int cpx = plain ? 0 : (g.W1 + 7) / 8;
-                // (Padding the grid so that every SIMD holds the same number of waves, and halving the
-                // prefetch depth, were both measured: no change -- DESIGN.md 4.4.)
-                const int wpb = SGM_PREPASS_WPB;
-                dim3 grid(plain ? (g.W1 + wpb - 1) / wpb : 8 * ((cpx + wpb - 1) / wpb)), block(64 * wpb);
-                const size_t half = (size_t)3 * g.W1 * g.D;  // int16 elements of one state buffer
-                int16_t *sbuf = (int16_t *)(ydir > 0 ? e->pstate.p : e->pstate2.p);
-                const int16_t *sin = sbuf ? sbuf + (size_t)(c & 1) * half : nullptr;
-                int16_t *sout = sbuf ? sbuf + (size_t)((c + 1) & 1) * half : nullptr;
-#define SGM_PRE(NP_, PART_) hipLaunchKernelGGL((k_prepass3<NP_, PART_>), grid, block, 0, on, g, xdir, ydir, C, bl, R, s0, s1, sin, sout, cpx)
-                // (prefetch blocks of 2 rows for the pass that runs beside the sweep -- 70 registers instead of 106 -- were
-                // measured in round 2: within noise; that instantiation is gone)
-                if (g.NP == 1) { if (partial) SGM_PRE(1, true); else SGM_PRE(1, false); }
-                else if (g.NP == 2) { if (partial) SGM_PRE(2, true); else SGM_PRE(2, false); }
-                else { if (partial) SGM_PRE(4, true); else SGM_PRE(4, false); }
-#undef SGM_PRE
-            };
-            // roles of the pre-pass: 0 = predecessor one step earlier in the sweep's x order
-            // (x - xdir), 1 = same column, 2 = one step later
-            auto launch_prepass = [&](int xdir, int ydir, int16_t *bl, hipStream_t on) -> int {  // returns the launch count
-                if (rows4 && !(e->debug & 16)) {  // lane-grouped lines, state stored after every row
-                    // one role per wave (grid.y = 3): these frames have too few lines to fill the SIMDs with
-                    // three-role waves (4K D=16: 478)
-                    dim3 grid((g.W1 + 64 / GWs - 1) / (64 / GWs), 3), block(64);
-                    if (GWs == 8) hipLaunchKernelGGL((k_prepass3_g<8, false>), grid, block, 0, on, g, xdir, ydir, C, bl);
-                    else if (GWs == 16) hipLaunchKernelGGL((k_prepass3_g<16, false>), grid, block, 0, on, g, xdir, ydir, C, bl);
-                    else if (g.D < 64) hipLaunchKernelGGL((k_prepass3_g<32, true>), grid, block, 0, on, g, xdir, ydir, C, bl);
-                    else hipLaunchKernelGGL((k_prepass3_g<32, false>), grid, block, 0, on, g, xdir, ydir, C, bl);
-                    return 1;
-                }
-                if (fused_prepass) {
-                    // the three roles fused in one wave (k_prepass3); debug bit 16 selects the 3-launch variant.
-                    // Row chunks of about 135 rows, one launch each, base columns grouped per XCD: two of the
-                    // three reads of a C pixel hit L2 (kernels_path.h).  debug 512: one chunk, plain layout (A/B).
-                    const bool plain = (e->debug & 512) != 0;
-                    const int nch = plain ? 1 : (e->prepass_rows > 0 ? (H + e->prepass_rows - 1) / e->prepass_rows
-                                                                          : std::max(1, (H + 67) / 135));
-                    // multiples of 8 rows (two prefetch blocks): a chunk then ends in straight-line code
-                    const int Hc = e->prepass_rows > 0 ? e->prepass_rows : ((H + nch - 1) / nch + 7) / 8 * 8;
-                    int n = 0;
-                    for (int c = 0; c < nch; c++) {
-                        const int s0 = c * Hc, s1 = std::min(H, s0 + Hc);
-                        if (s0 >= s1) break;
-                        prepass_chunk(xdir, ydir, bl, on, c, s0, s1, plain);
-                        n++;
-                    }
-                    return n;
-                }
-                // one launch of the single-direction kernel, grid.y = role
-                Boundary bd{bl, R, 0};
-                launch_path(g, xdir, ydir, PATH_BOUNDARY, C, S, 0, wta, on, bd);
-                return 1;
-            };
-            // MODE_HH: the upward pre-pass only reads C, so it runs on the auxiliary stream while the
-            // main stream does the downward pre-pass and sweep (memory-bound beside issue-bound work)
-            const bool overlap = npass == 2 && nbands > 1 && !(e->debug & 32) && !chain;
-            auto fork_prepass_up = [&]() -> int {  // aux stream: upward pre-pass, from "now" on the main stream
-                int rc2;
-                if (!e->aux) {
-                    HIP_TRY(hipStreamCreateWithFlags(&e->aux, hipStreamNonBlocking));
-                    HIP_TRY(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-                    HIP_TRY(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-                }
-                HIP_TRY(hipEventRecord(e->ev_fork, st));
-                HIP_TRY(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
-                if ((rc2 = stage_begin(e, "prepass_up", e->aux))) return rc2;
-                const int nl = launch_prepass(-1, -1, (int16_t *)e->bndL2.p, e->aux);
-                KCHECK();
-                if ((rc2 = stage_end(e, nl, e->aux))) return rc2;
-                HIP_TRY(hipEventRecord(e->ev_join, e->aux));
-                return SGM_OK;
-            };
-            // debug bit 64+128: fork right after the cost stage (both pre-passes side by side) instead
-            // of after the downward pre-pass (upward pre-pass beside the downward sweep)
-            const bool fork_early = (e->debug & 128) != 0;
-            if (two_vol && do_pre && !five_vol) {
-                if (!e->aux) {
-                    HIP_TRY(hipStreamCreateWithFlags(&e->aux, hipStreamNonBlocking));
-                    HIP_TRY(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-                    HIP_TRY(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-                }
-                HIP_TRY(hipEventRecord(e->ev_fork, st));
-                HIP_TRY(hipStreamWaitEvent(e->aux, e->ev_fork, 0));
-                if ((rc = stage_begin(e, "path_W", e->aux))) return rc;
-                launch_rows_grouped(g, H, group_width(g, H), -1, PATH_FIRST, C, S2, 1, wta, e->aux);
-                KCHECK();
-                if ((rc = stage_end(e, 1, e->aux))) return rc;
-                HIP_TRY(hipEventRecord(e->ev_join, e->aux));
-                if (three_vol) {
-                    if (!e->aux2) {
-                        HIP_TRY(hipStreamCreateWithFlags(&e->aux2, hipStreamNonBlocking));
-                        HIP_TRY(hipEventCreateWithFlags(&e->ev_join2, hipEventDisableTiming));
-                    }
-                    HIP_TRY(hipStreamWaitEvent(e->aux2, e->ev_fork, 0));
-                    if ((rc = stage_begin(e, "path_E", e->aux2))) return rc;
-                    launch_rows_grouped(g, H, GWs, +1, PATH_FIRST, C, S3, 1, wta, e->aux2);
-                    KCHECK();
-                    if ((rc = stage_end(e, 1, e->aux2))) return rc;
-                    HIP_TRY(hipEventRecord(e->ev_join2, e->aux2));
-                }
-            }
-            if (overlap && fork_early && (rc = fork_prepass_up())) return rc;
-            for (int pass = 0; pass < npass && do_mid; pass++) {
-                const int ydir = pass == 0 ? 1 : -1, xdir = ydir;
-                int16_t *bl = (int16_t *)(pass == 0 ? e->bndL.p : e->bndL2.p);
-                if (nbands > 1 && !(overlap && pass == 1) && !chain && !five_vol) {
-                    if ((rc = stage_begin(e, pass == 0 ? "prepass_dn" : "prepass_up"))) return rc;
-                    const int nl = launch_prepass(xdir, ydir, bl, st);
-                    KCHECK();
-                    if ((rc = stage_end(e, nl))) return rc;
-                }
-                if (overlap && pass == 0 && !fork_early && (rc = fork_prepass_up())) return rc;
-                if (overlap && pass == 1) {
-                    HIP_TRY(hipStreamWaitEvent(st, e->ev_join, 0));
-                    stage_break(e);  // (the wait is not part of the next stage)
-                }
-                // winner-take-all: fused into the last path kernel (debug 2), or -- default -- a
-                // separate pass over S with one lane per pixel (k_wta_t)
-                const bool last = pass == npass - 1 && g.mode == 1 && fused_wta && !rows4;
-                SweepArgs a{ydir, xdir, R, C, S, (const int16_t *)bl, wta, e->keep_aggr, e->debug, nullptr, nullptr, nullptr, nbands};
-                ChainFrames fr;
-                if (chain) {
-                    // one record serves both passes (they follow each other on the stream)
-                    fr.nf = 1;
-                    fr.C[0] = C;
-                    fr.S[0] = S;
-                    fr.bnd[0] = (int16_t *)e->bndL.p;
-                    fr.hr[0] = g.hr;
-                    a.ctl = (uint32_t *)e->chain_ctl.p;
-                    a.err = (uint32_t *)e->chain_err.p;
-                    HIP_TRY(hipMemsetAsync(e->chain_ctl.p, 0, ctl_bytes, st));
-                    stage_break(e);
-                }
-                if ((rc = stage_begin(e, five_vol ? "paths5" : chain ? (pass == 0 ? "chain_dn" : "chain_up")
-                                               : (pass == 0 ? "sweep_dn" : (fused_wta ? "sweep_up_wta" : "sweep_up"))))) return rc;
-                // per-row state written by the grouped pre-pass: role-major; by the single-direction kernel (debug 16): band layout
-                const int rmaj = (e->debug & 16) ? 0 : 1;
-                if (five_vol) {
-                    // D <= 64, MODE_SGBM: all five directions in one launch, one volume each (k_paths5_g)
-                    const int G = 64 / GWs, nr = (H + G - 1) / G, nl = (g.W1 + G - 1) / G;
-                    // (Measured beside it: rows and lines as two launches one after the other, in either order -- 4K D=16 0.60 /
-                    // 0.59 ms against 0.57 ms, 720p D=64 0.21 / 0.22 against 0.19; occupancy capped at one or two waves per SIMD
-                    // through an LDS allocation -- 0.66 against 0.65 ms, 0.23 / 0.27 against 0.20.  Neither the order nor the
-                    // number of waves per SIMD matters: the stage moves 6 ... 10 V in 32-byte pieces per row and is bound by
-                    // the memory side)
-                    dim3 grid(2 * nr + 3 * nl), block(64);
-                    if (GWs == 8) hipLaunchKernelGGL((k_paths5_g<8, false>), grid, block, 0, st, g, xdir, ydir, C, S, S4, S5, S2, S3, nr);
-                    else if (GWs == 16) hipLaunchKernelGGL((k_paths5_g<16, false>), grid, block, 0, st, g, xdir, ydir, C, S, S4, S5, S2, S3, nr);
-                    else if (g.D < 64) hipLaunchKernelGGL((k_paths5_g<32, true>), grid, block, 0, st, g, xdir, ydir, C, S, S4, S5, S2, S3, nr);
-                    else hipLaunchKernelGGL((k_paths5_g<32, false>), grid, block, 0, st, g, xdir, ydir, C, S, S4, S5, S2, S3, nr);
-                } else if (rows4) {
-                    // D <= 64, band height 1: the three directions from the previous row are element-wise given the
-                    // pre-pass state of every row (k_vert3_g, one streaming pass over all pixels); only the in-row
-                    // direction is a recurrence (k_rows_g, S +=)
-                    dim3 grid((g.W1 + 255) / 256, H), block(256);
-                    const int16_t *bq = (const int16_t *)bl;
-#define SGM_VERT(GW_, PART_)                                                                                     \
-    do {                                                                                                         \
-        if (pass == 0) hipLaunchKernelGGL((k_vert3_g<GW_, PATH_FIRST, PART_>), grid, block, 0, st, g, xdir, ydir, C, S, bq, rmaj); \
-        else hipLaunchKernelGGL((k_vert3_g<GW_, PATH_ACCUM, PART_>), grid, block, 0, st, g, xdir, ydir, C, S, bq, rmaj); \
-    } while (0)
-                    if (GWs == 8) SGM_VERT(8, false);
-                    else if (GWs == 16) SGM_VERT(16, false);
-                    else if (g.D < 64) SGM_VERT(32, true);
-                    else SGM_VERT(32, false);
-#undef SGM_VERT
-                    if (!three_vol) launch_rows_grouped(g, H, GWs, xdir, PATH_ACCUM, C, S, 1, wta, st);
-                } else if (chain) {
-                    if ((rc = launch_chain(g, a, fr, pass == 0 ? SWEEP_FIRST : SWEEP_ACCUM, chain_window(g, R, nbands, 1, e->chain_wgs), st))) return rc;
-                } else if ((rc = launch_sweep(g, a, pass == 0 ? SWEEP_FIRST : (last ? SWEEP_LAST : SWEEP_ACCUM), nbands, st))) {
-                    return rc;
-                }
-                KCHECK();
-                if ((rc = stage_end(e, 1))) return rc;
-            }
-            if (!do_post) return SGM_OK;
-            if (two_vol && !five_vol) {
-                HIP_TRY(hipStreamWaitEvent(st, e->ev_join, 0));
-                if (three_vol) HIP_TRY(hipStreamWaitEvent(st, e->ev_join2, 0));
-                stage_break(e);
-            }
-            if (g.mode == 0 && !two_vol) {
-                if ((rc = stage_begin(e, fused_wta ? "path_W_wta" : "path_W"))) return rc;
-                const int GW = (e->debug & 4) ? 64 : group_width(g, H);  // debug 4: no lane groups (A/B)
-                const int pm = fused_wta ? PATH_LAST : PATH_ACCUM;
-                if (GW == 64 && (e->debug & 4)) launch_path(g, -1, 0, pm, C, S, e->keep_aggr, wta, st);  // A/B: the general line kernel
-                else launch_rows_grouped(g, H, GW, -1, pm, C, S, e->keep_aggr, wta, st);
-                KCHECK();
-                if ((rc = stage_end(e, 1))) return rc;
-            }
-            if (!fused_wta) {
-                if ((rc = stage_begin(e, "wta"))) return rc;
-                const int64_t npix = (int64_t)H * g.W1;
-                const size_t lds = (size_t)64 * wta_t_stride(g.D);
-                // persistent blocks: LDS (64 padded rows) allows four waves per CU; each loops over its share
-                dim3 grid((unsigned)std::min<int64_t>((npix + 63) / 64, 4 * 256)), block(64);
-                int lgc = -1;  // log2(D / 8) when D is a power of two
-                for (int q = 1; q <= 6; q++)
-                    if (g.D == (8 << q)) lgc = q;
-#define SGM_WTA(POSW_, LG_)                                                                                            \
-    do {                                                                                                               \
-        if (lds > 48 * 1024)                                                                                           \
-            HIP_TRY(hipFuncSetAttribute((const void *)k_wta_t<POSW_, LG_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        (int)lds));                                                                    \
-        hipLaunchKernelGGL((k_wta_t<POSW_, LG_>), grid, block, lds, st, g, (const int16_t *)S, wta, npix,              \
-                           (const int16_t *)nullptr, (const int16_t *)nullptr, (const int16_t *)nullptr,              \
-                           (const int16_t *)nullptr);                                                                  \
-    } while (0)
-#define SGM_WTA2(POSW_, LG_)                                                                                           \
-    do {                                                                                                               \
-        if (lds > 48 * 1024)                                                                                           \
-            HIP_TRY(hipFuncSetAttribute((const void *)k_wta_t<POSW_, LG_, 2>,                                          \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                        \
-        hipLaunchKernelGGL((k_wta_t<POSW_, LG_, 2>), grid, block, lds, st, g, (const int16_t *)S, wta, npix,           \
-                           (const int16_t *)S2, (const int16_t *)nullptr, (const int16_t *)nullptr,                    \
-                           (const int16_t *)nullptr);                                                                  \
-    } while (0)
-#define SGM_WTA3(POSW_, LG_)                                                                                           \
-    do {                                                                                                               \
-        if (five_vol)                                                                                                  \
-            hipLaunchKernelGGL((k_wta_t<POSW_, LG_, 5>), grid, block, lds, st, g, (const int16_t *)S, wta, npix,       \
-                               (const int16_t *)S2, (const int16_t *)S3, (const int16_t *)S4, (const int16_t *)S5);   \
-        else                                                                                                           \
-            hipLaunchKernelGGL((k_wta_t<POSW_, LG_, 3>), grid, block, lds, st, g, (const int16_t *)S, wta, npix,       \
-                               (const int16_t *)S2, (const int16_t *)S3, (const int16_t *)nullptr,                     \
-                               (const int16_t *)nullptr);                                                              \
-    } while (0)
-#define SGM_WTA3_LG(POSW_)                      \
-    do {                                        \
-        switch (lgc) {                          \
-        case 1: SGM_WTA3(POSW_, 1); break;      \
-        case 2: SGM_WTA3(POSW_, 2); break;      \
-        case 3: SGM_WTA3(POSW_, 3); break;      \
-        default: SGM_WTA3(POSW_, -1); break;    \
-        }                                       \
-    } while (0)
-#define SGM_WTA2_LG(POSW_)                      \
-    do {                                        \
-        switch (lgc) {                          \
-        case 1: SGM_WTA2(POSW_, 1); break;      \
-        case 2: SGM_WTA2(POSW_, 2); break;      \
-        case 3: SGM_WTA2(POSW_, 3); break;      \
-        case 4: SGM_WTA2(POSW_, 4); break;      \
-        default: SGM_WTA2(POSW_, -1); break;    \
-        }                                       \
-    } while (0)
-#define SGM_WTA_LG(POSW_)                       \
-    do {                                        \
-        switch (lgc) {                          \
-        case 1: SGM_WTA(POSW_, 1); break;       \
-        case 2: SGM_WTA(POSW_, 2); break;       \
-        case 3: SGM_WTA(POSW_, 3); break;       \
-        case 4: SGM_WTA(POSW_, 4); break;       \
-        case 5: SGM_WTA(POSW_, 5); break;       \
-        case 6: SGM_WTA(POSW_, 6); break;       \
-        default: SGM_WTA(POSW_, -1); break;     \
-        }                                       \
-    } while (0)
-                if (two_vol) {
-                    if (three_vol) {
-                        if (g.uniq < 100) SGM_WTA3_LG(true);
-                        else SGM_WTA3_LG(false);
-                    } else if (g.uniq < 100) SGM_WTA2_LG(true);
-                    else SGM_WTA2_LG(false);
-                    if (e->keep_aggr) {  // the volume a caller inspects is the whole sum
-                        const int64_t n8 = (int64_t)g.rowsz * H / 8;  // rowsz = W1 * D is a multiple of 16
-                        hipLaunchKernelGGL(k_add_sat, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, S, (const int16_t *)S2, n8);
-                        if (three_vol) hipLaunchKernelGGL(k_add_sat, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, S, (const int16_t *)S3, n8);
-                        if (five_vol) {
-                            hipLaunchKernelGGL(k_add_sat, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, S, (const int16_t *)S4, n8);
-                            hipLaunchKernelGGL(k_add_sat, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, S, (const int16_t *)S5, n8);
-                        }
-                    }
-                } else if (g.uniq < 100) SGM_WTA_LG(true);
-                else SGM_WTA_LG(false);
-#undef SGM_WTA3_LG
-#undef SGM_WTA3
-#undef SGM_WTA2_LG
-#undef SGM_WTA2
-#undef SGM_WTA_LG
-#undef SGM_WTA
-                KCHECK();
-                if ((rc = stage_end(e, 1))) return rc;
-            }
-        }
-
-        // -- right view, sub-pixel, LR check
-        if ((rc = stage_begin(e, "select_lr"))) return rc;
-        {
-            const size_t lds = (size_t)W * 4;
-            if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_select, dim3(H), dim3(256), lds, st, g, (const uint2 *)wta, raw);
-            KCHECK();
-        }
-        if ((rc = stage_end(e, 1))) return rc;
+        if (do_mid && (rc = p.v1 ? paths_v1(e) : paths_fused(e, p))) return rc;
+        if (!do_post) return SGM_OK;
+        if ((rc = stage_join(e, p)) || (rc = stage_wta(e, p)) || (rc = stage_select(e))) return rc;
     }
-
-    // -- 3x3 median
-    if ((rc = stage_begin(e, "median3"))) return rc;
-    {
-        dim3 grid((W + 255) / 256, H), block(256);
-        // the result goes to the median tap AND to the output buffer (the speckle filter works in place there)
-        hipLaunchKernelGGL(k_median3, grid, block, 0, st, (const int16_t *)raw, med, d_disp, H, W);
-        KCHECK();
-    }
-    if ((rc = stage_end(e, 1))) return rc;
-
-    // -- speckle filter on the output
-    if (e->params.speckleRange >= 0 && e->params.speckleWindowSize > 0) {  // upstream's condition for filterSpeckles
-        if ((rc = stage_begin(e, "speckle"))) return rc;
-        if ((rc = run_speckles(e, d_disp, H, W, (e->params.minDisparity - 1) * 16, e->params.speckleWindowSize,
-                               16 * e->params.speckleRange)))
-            return rc;
-        if ((rc = stage_end(e, 4))) return rc;
-    }
-    return SGM_OK;
+    return stage_median_speckle(e, p, d_disp);
 }
 
 static int run_to_float(sgm_engine *e, const int16_t *d_disp, int64_t n, float *d_out)
@@ -1662,21 +1673,17 @@ int sgm_pipeline_device(sgm_engine *e, const void *d_left, const void *d_right, 
 // winner-take-all and the epilogue of every pair.  One frame's chain of bands keeps only about 50 workgroups busy; a
 // group of 6 or more fills the GPU, and no boundary pre-pass runs at all.
 
-// Everything one pair of a chained group needs on its engine, allocated BEFORE anything is enqueued (so that running out
-// of memory costs nothing but a smaller group)
-static int prepare_pair_buffers(sgm_engine *q, int H, int W, const Plan &pl)
+// an internal engine (a peer or a member of a chained group) plans as `e` does: every option that steers make_plan, and
+// none of the per-call ones
+static void inherit_options(sgm_engine *q, const sgm_engine *e)
 {
-    int rc = ensure_buffers(q, H, W);
-    if (rc) return rc;
-    const Geom &g = q->g;
-    const size_t npx = (size_t)H * W;
-    if (pl.nbands > 1 && (rc = q->bndL.ensure((size_t)pl.nbands * g.W1 * 3 * g.D * 2))) return rc;
-    if (q->params.speckleRange >= 0 && q->params.speckleWindowSize > 0 &&
-        ((rc = q->label.ensure(npx * 4)) || (rc = q->csize.ensure(npx * 4)) || (rc = q->rlen.ensure(npx * 4))))
-        return rc;
-    const bool two_vol = g.mode == 0 && g.D <= 128 && !(q->debug & (4 | 2 | 65536));   // (run_compute: the fifth path's own volume)
-    if (two_vol && (rc = q->aggr2.ensure((size_t)g.rowsz * H * sizeof(int16_t)))) return rc;
-    return SGM_OK;
+    q->schedule = e->schedule;
+    q->sweep_rows = e->sweep_rows;
+    q->debug = e->debug;
+    q->chain_wgs = e->chain_wgs;
+    q->prepass_rows = e->prepass_rows;
+    q->keep_aggr = 0;
+    q->profile = 0;
 }
 
 // The engines of a chained group for up to `want` pairs: e itself + internal engines, created, configured like e and
@@ -1688,7 +1695,7 @@ static int prepare_group(sgm_engine *e, int want, int H, int W, const Plan &pl, 
     *n_out = 0;
     if (e->group_max > 0) want = std::min(want, e->group_max);
     want = std::max(1, std::min(want, CHAIN_MAX_FRAMES));
-    if ((rc = prepare_pair_buffers(e, H, W, pl))) return rc;
+    if ((rc = ensure_plan_buffers(e, pl, H, W))) return rc;
     *n_out = 1;
     if (want > 1 && !e->ev_group) HIP_TRY(hipEventCreateWithFlags(&e->ev_group, hipEventDisableTiming));
     bool retried = false;
@@ -1700,15 +1707,10 @@ static int prepare_group(sgm_engine *e, int want, int H, int W, const Plan &pl, 
             e->group.push_back(q);
         }
         sgm_engine *q = e->group[k - 1];
-        q->keep_aggr = 0;
-        q->profile = 0;
-        q->schedule = e->schedule;
-        q->sweep_rows = e->sweep_rows;
-        q->debug = e->debug;
-        q->chain_wgs = e->chain_wgs;
+        inherit_options(q, e);
         if (!q->ev_done) HIP_TRY(hipEventCreateWithFlags(&q->ev_done, hipEventDisableTiming));
         const bool sized = q->H == H && q->W == W && q->cost.p;     // (ran this shape before: nothing to allocate)
-        rc = prepare_pair_buffers(q, H, W, pl);
+        rc = ensure_plan_buffers(q, pl, H, W);
         size_t fr = 0, tot = 0;
         // (the reserve: 4 GiB or 5 % -- every stream, event pool and first launch of a kernel costs the runtime device memory
         //  too, and "out of memory" from a kernel launch cannot be recovered from -- plus what the caller of this function
@@ -1778,13 +1780,15 @@ static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &p
         if ((rc = run_compute(eng[k], (const uint8_t *)d_left[k], (const uint8_t *)d_right[k], H, W, stride_bytes,
                               (int16_t *)d_disp_i16[k], PH_PRE)))
             return rc;
-        if (!eng[k]->plan_chain) return set_err(SGM_ERR_HIP, "internal: a pair of a chained group did not plan a chained sweep");
+        const Plan &q = eng[k]->plan;
+        if (!q.chain || q.R != pl.R || q.nbands != pl.nbands)
+            return set_err(SGM_ERR_HIP, "internal: a pair of a chained group did not plan the group's chained sweep");
         if (in_used && in_used[k]) HIP_TRY(hipEventRecord(in_used[k], eng[k]->stream));   // (behind the whole cost stage: the images are read by its first kernel only)
     }
     // ---- the sweeps of all n pairs: one launch per pass on e's stream, behind every pair's cost stage
     const Geom &g = e->g;
     const int R = pl.R, nbands = pl.nbands, npass = pl.npass;
-    const size_t ctl_bytes = ((size_t)(1 + (size_t)n * nbands) * 4 + 15) & ~(size_t)15;
+    const size_t ctl_bytes = chain_ctl_bytes(n, nbands);
     if ((rc = e->chain_ctl.ensure(ctl_bytes))) return rc;
     for (int k = 1; k < n; k++) {
         HIP_TRY(hipEventRecord(eng[k]->ev_done, eng[k]->stream));
@@ -1871,13 +1875,7 @@ int sgm_pipeline_batch_device(sgm_engine *e, int N, const void *const *d_left, c
     BatchGuard guard{e};
     e->last_group = 0;
     int cap = 1;
-    if (joint) {
-        if ((rc = prepare_group(e, N, H, W, pl, &cap))) return rc;
-        if (!e->chain_err.p) {
-            if ((rc = e->chain_err.ensure(16))) return rc;
-            HIP_TRY(hipMemsetAsync(e->chain_err.p, 0, 16, e->stream));
-        }
-    }
+    if (joint && (rc = prepare_group(e, N, H, W, pl, &cap))) return rc;
     if (!joint || cap < 2) {
         for (int i = 0; i < N; i++) {
             e->hr_accumulate = i > 0;     // (the headroom record of the call covers every pair)
@@ -1984,10 +1982,6 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
         const size_t slot_bytes = 2 * (2 * npx + npx * 2 + (xyz_out ? npx * 16 : 0));
         if ((rc = prepare_group(e, N, H, W, pl, &cap, slot_bytes))) return rc;
         if (cap >= 2) {
-            if (!e->chain_err.p) {
-                if ((rc = e->chain_err.ensure(16))) return rc;
-                HIP_TRY(hipMemsetAsync(e->chain_err.p, 0, 16, e->stream));
-            }
             if (!e->copy_in) HIP_TRY(hipStreamCreateWithFlags(&e->copy_in, hipStreamNonBlocking));
             if (!e->copy_out) HIP_TRY(hipStreamCreateWithFlags(&e->copy_out, hipStreamNonBlocking));
             const int ngroups = (N + cap - 1) / cap, per = (N + ngroups - 1) / ngroups;
@@ -2100,12 +2094,7 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
     } drain{eng, neng, saved_keep, saved_profile};
     for (int k = 0; k < neng; k++) {
         sgm_engine *q = eng[k];
-        q->keep_aggr = 0;
-        q->profile = 0;
-        q->schedule = e->schedule;
-        q->sweep_rows = e->sweep_rows;
-        q->debug = e->debug;
-        q->prepass_rows = e->prepass_rows;
+        inherit_options(q, e);
         if ((rc = q->in_left.ensure(npx)) || (rc = q->in_right.ensure(npx)) || (rc = q->disp_out.ensure(npx * 2))) return rc;
         if ((rc = q->pin_left.ensure(npx)) || (rc = q->pin_right.ensure(npx)) || (rc = q->pin_disp.ensure(npx * 2))) return rc;
         if (xyz_out && ((rc = q->f32.ensure(npx * 4)) || (rc = q->xyz.ensure(npx * 12)))) return rc;

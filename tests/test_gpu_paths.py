@@ -2,7 +2,8 @@
 window sizes 13..31 (generic k_vsum, k_hsum<NP,0>), preFilterCap > 96 (byte cost pipeline off),
 the 3-launch pre-pass fallback of frames with rowsz*H >= 2^31 (forced through debug bit 16), the
 A/B switches of csrc/sgm_debug.h, the engine's own regime record (sgm_get_headroom) at the edge of
-and outside the int16 no-overflow regime, and upstream's condition for the speckle filter."""
+and outside the int16 no-overflow regime, upstream's condition for the speckle filter, and the stage schedule (names
+and launch counts) of a matrix of configurations."""
 import numpy as np
 import pytest
 
@@ -174,3 +175,98 @@ def test_every_cost_saturated_whole_map_invalid(schedule):
     assert t["headroom_ok"] and (t["S"] == 32767).all() and (t["disp"] == -64).all()
     bad = [U.describe_mismatch(k, h[k], t[k]) for k, n in rep.items() if n]
     assert not bad, "\n".join(bad)
+
+
+# ---- the schedule, pinned: stage names and launch counts (sgm_get_stage_times) of one profiled compute per configuration
+# (H, W, D, blockSize, mode, schedule, debug, prepass_rows); "batch" runs three pairs through sgm_pipeline_batch_device
+_SCHEDULE_CASES = {
+    "v1_sgbm": (40, 300, 64, 5, 0, 0, 0, 0), "v1_hh": (40, 300, 64, 5, 1, 0, 0, 0),
+    "sgbm_d16": (40, 300, 16, 5, 0, 1, 0, 0), "sgbm_d32": (40, 300, 32, 5, 0, 1, 0, 0),
+    "sgbm_d48": (40, 300, 48, 5, 0, 1, 0, 0), "sgbm_d64": (40, 300, 64, 5, 0, 1, 0, 0),
+    "sgbm_d128": (40, 300, 128, 5, 0, 1, 0, 0), "sgbm_d256": (40, 300, 256, 5, 0, 1, 0, 0),
+    "hh_d64": (40, 300, 64, 5, 1, 1, 0, 0), "hh_d256": (40, 300, 256, 5, 1, 1, 0, 0), "hh_d16": (40, 300, 16, 5, 1, 1, 0, 0),
+    "chain_sgbm_d64": (40, 300, 64, 5, 0, 2, 0, 0), "chain_sgbm_d128": (40, 300, 128, 5, 0, 2, 0, 0),
+    "chain_sgbm_d32": (40, 300, 32, 5, 0, 2, 0, 0), "chain_hh_d256": (40, 300, 256, 5, 1, 2, 0, 0),
+    "wide_sgbm_d128": (150, 1700, 128, 5, 0, 1, 0, 0), "wide_hh_d128": (150, 1700, 128, 5, 1, 1, 0, 0),
+    "prepass_rows_hh": (150, 300, 128, 5, 1, 1, 0, 64),
+    "bs1_d16": (40, 300, 16, 1, 0, 1, 0, 0), "bs13_d64": (40, 300, 64, 13, 1, 1, 0, 0),
+    "no_columns": (20, 60, 64, 5, 0, 1, 0, 0),
+    "dbg8": (40, 300, 64, 5, 1, 1, 8 | 256, 0), "dbg16": (40, 300, 16, 5, 1, 1, 16, 0),
+    "dbg32": (40, 300, 128, 5, 1, 1, 32, 0), "dbg128": (40, 300, 128, 5, 1, 1, 128, 0),
+    "dbg4": (40, 300, 32, 5, 0, 1, 4, 0), "dbg512": (150, 1700, 128, 5, 0, 1, 512, 0),
+    "dbg65536": (40, 300, 128, 5, 0, 1, 65536, 0), "dbg2": (40, 300, 128, 5, 1, 1, 2, 0),
+    "dbg2048": (40, 300, 256, 5, 0, 1, 2048, 0), "dbg4096": (40, 300, 32, 5, 0, 1, 4096, 0),
+    "dbg8192": (40, 300, 32, 5, 0, 1, 8192, 0), "dbg256": (40, 300, 64, 5, 0, 1, 256, 0),
+    "batch": (40, 300, 128, 5, 0, 2, 0, 0),
+}
+
+
+def _stage_schedule(name):
+    """[(stage, launches), ...] of one profiled compute of the configuration `name`."""
+    from stereo_reconstruction_cv_amd import _lib
+    from stereo_reconstruction_cv_amd.stereo import Engine
+    H, W, D, bs, mode, schedule, debug, prepass_rows = _SCHEDULE_CASES[name]
+    eng = Engine(U.params(D, bs, 0, mode, speckleWindowSize=30, speckleRange=2))
+    eng.set_option(_lib.SGM_OPT_SCHEDULE, schedule)
+    eng.set_option(_lib.SGM_OPT_DEBUG, debug)
+    eng.set_option(_lib.SGM_OPT_PREPASS_ROWS, prepass_rows)
+    eng.set_option(_lib.SGM_OPT_PROFILE, 1)
+    pairs = [synth.make_pair(H, W, D, 7000 + i)[:2] for i in range(3 if name == "batch" else 1)]
+    if name == "batch":
+        import torch
+        dev = torch.device("cuda", 0)
+        dl, dr = ([torch.from_numpy(p[k]).to(dev) for p in pairs] for k in (0, 1))
+        dd = [torch.empty((H, W), dtype=torch.int16, device=dev) for _ in pairs]
+        torch.cuda.synchronize()
+        eng.pipeline_batch_device([t.data_ptr() for t in dl], [t.data_ptr() for t in dr], H, W, W, None,
+                                  [t.data_ptr() for t in dd])
+        eng.synchronize()
+    else:
+        eng.compute_host(*pairs[0])
+    return [(n, k) for n, _, k in eng.stage_times()]
+
+
+_EXPECTED_SCHEDULE = {  # stage names in order; `*k`: k launches (default 1); recorded on the engine before its refactor
+    "batch": "features cost_pix cost_box path_W chain_dn wta select_lr median3 speckle*4 _wall*0",
+    "bs13_d64": "features cost_hsum cost_vsum prepass_dn prepass_up sweep_dn sweep_up wta select_lr median3 speckle*4 _wall*0",
+    "bs1_d16": "features cost_hsum cost_vsum paths5 wta select_lr median3 speckle*4 _wall*0",
+    "chain_hh_d256": "features cost_pix cost_box chain_dn chain_up wta select_lr median3 speckle*4 _wall*0",
+    "chain_sgbm_d128": "features cost_pix cost_box path_W chain_dn wta select_lr median3 speckle*4 _wall*0",
+    "chain_sgbm_d32": "features cost_pix cost_box paths5 wta select_lr median3 speckle*4 _wall*0",
+    "chain_sgbm_d64": "features cost_pix cost_box path_W chain_dn wta select_lr median3 speckle*4 _wall*0",
+    "dbg128": "features cost_pix cost_box prepass_up prepass_dn sweep_dn sweep_up wta select_lr median3 speckle*4 _wall*0",
+    "dbg16": "features cost_pix cost_box prepass_dn prepass_up sweep_dn sweep_up wta select_lr median3 speckle*4 _wall*0",
+    "dbg2": "features cost_pix cost_box prepass_dn prepass_up sweep_dn sweep_up_wta select_lr median3 speckle*4 _wall*0",
+    "dbg2048": "features cost_pix cost_box prepass_dn sweep_dn path_W wta select_lr median3 speckle*4 _wall*0",
+    "dbg256": "features cost_hsum cost_vsum paths5 wta select_lr median3 speckle*4 _wall*0",
+    "dbg32": "features cost_pix cost_box prepass_dn sweep_dn prepass_up sweep_up wta select_lr median3 speckle*4 _wall*0",
+    "dbg4": "features cost_hsum cost_vsum prepass_dn sweep_dn path_W_wta select_lr median3 speckle*4 _wall*0",
+    "dbg4096": "features cost_pix cost_box path_W prepass_dn sweep_dn wta select_lr median3 speckle*4 _wall*0",
+    "dbg512": "features cost_pix cost_box path_W prepass_dn sweep_dn wta select_lr median3 speckle*4 _wall*0",
+    "dbg65536": "features cost_pix cost_box prepass_dn sweep_dn path_W wta select_lr median3 speckle*4 _wall*0",
+    "dbg8": "features cost_hsum cost_vsum prepass_dn prepass_up sweep_dn sweep_up wta select_lr median3 speckle*4 _wall*0",
+    "dbg8192": "features cost_pix cost_box path_W path_E prepass_dn sweep_dn wta select_lr median3 speckle*4 _wall*0",
+    "hh_d16": "features cost_pix cost_box prepass_dn prepass_up sweep_dn sweep_up wta select_lr median3 speckle*4 _wall*0",
+    "hh_d256": "features cost_pix cost_box prepass_dn prepass_up sweep_dn sweep_up wta select_lr median3 speckle*4 _wall*0",
+    "hh_d64": "features cost_pix cost_box prepass_dn prepass_up sweep_dn sweep_up wta select_lr median3 speckle*4 _wall*0",
+    "no_columns": "fill_invalid median3 speckle*4 _wall*0",
+    "prepass_rows_hh": "features cost_pix cost_box prepass_dn*3 prepass_up*3 sweep_dn sweep_up wta select_lr median3 speckle*4 _wall*0",
+    "sgbm_d128": "features cost_pix cost_box path_W prepass_dn sweep_dn wta select_lr median3 speckle*4 _wall*0",
+    "sgbm_d16": "features cost_pix cost_box paths5 wta select_lr median3 speckle*4 _wall*0",
+    "sgbm_d256": "features cost_pix cost_box prepass_dn sweep_dn path_W_wta select_lr median3 speckle*4 _wall*0",
+    "sgbm_d32": "features cost_pix cost_box paths5 wta select_lr median3 speckle*4 _wall*0",
+    "sgbm_d48": "features cost_pix cost_box paths5 wta select_lr median3 speckle*4 _wall*0",
+    "sgbm_d64": "features cost_pix cost_box paths5 wta select_lr median3 speckle*4 _wall*0",
+    "v1_hh": "features cost_pix cost_box path_S path_SE path_SW path_N path_NE path_NW path_E path_W_wta select_lr median3 speckle*4 _wall*0",
+    "v1_sgbm": "features cost_pix cost_box path_S path_SE path_SW path_E path_W_wta select_lr median3 speckle*4 _wall*0",
+    "wide_hh_d128": "features cost_pix cost_box prepass_dn prepass_up sweep_dn sweep_up wta select_lr median3 speckle*4 _wall*0",
+    "wide_sgbm_d128": "features cost_pix cost_box path_W prepass_dn sweep_dn wta select_lr median3 speckle*4 _wall*0",
+}
+
+
+@pytest.mark.parametrize("name", sorted(_SCHEDULE_CASES))
+def test_stage_schedule_is_pinned(name):
+    """The stages each configuration enqueues, in order, with their launch counts: a change of the host schedule shows
+    here even where the results stay bit-exact."""
+    want = [(t.split("*")[0], int(t.split("*")[1]) if "*" in t else 1) for t in _EXPECTED_SCHEDULE[name].split()]
+    assert _stage_schedule(name) == want
