@@ -99,6 +99,12 @@ typedef enum {
     SGM_OPT_PREPASS_ROWS = 5, /* rows per chunk (= launch) of the boundary pre-pass; 0 = automatic (about 135, a multiple of 8) */
     SGM_OPT_GROUP_MAX = 7,   /* schedule 2, batch entries: pairs per chained launch (= internal engines kept, about 9 GB each at
                               * 4K D=256); 0 = automatic: as many as device memory holds beside a reserve, up to 64; 1 = never chain */
+    SGM_OPT_CHANNELS = 8,    /* interleaved 8-bit channels per image pixel: 1 (default, CV_8UC1) or 3 (CV_8UC3, e.g. BGR); any other
+                              * value is refused with SGM_ERR_INVALID_ARG.  With 3, every image pointer of sgm_compute,
+                              * sgm_compute_device, sgm_pipeline_device, sgm_compute_batch and sgm_pipeline_batch_device is an
+                              * interleaved 3-channel image and stride_bytes is its row pitch in bytes (>= 3 * W); the batch entries'
+                              * host arrays are N tight [H][W][3] images.  The pixel cost is the sum of the three channels' costs
+                              * (OpenCV's calcPixelCostBT with cn = 3; channel order does not matter); P1 / P2 are not scaled. */
     /* 4 = SGM_OPT_DEBUG: A/B switches for measurements -- not part of this interface (csrc/sgm_debug.h) */
     SGM_OPT_RESERVED_4 = 4
 } sgm_option;

@@ -25,6 +25,7 @@
 #include "kernels_rectify.h"
 #include "kernels_sweep.h"
 #include "kernels_group.h"
+#include "kernels_color.h"
 
 using namespace sgm;
 
@@ -189,6 +190,7 @@ struct Plan {
     bool pix_px;           // int16 pipeline: k_pix_px + k_hsum_px (D <= 32) in place of k_hsum
     int GWc, RBb;          // k_box_u8: lane-group width, rows per band
     bool vsum_ring, vsum_wide;  // int16 pipeline: k_vsum_ring (else the generic k_vsum), with 8 int16 per thread (else 4)
+    int cn;                // channels of the images (SGM_OPT_CHANNELS): 3 takes k_features_c3 + k_hsum_c3 into the vertical sum
     // path stage
     bool v1;               // schedule 0: one kernel per direction
     int GWs;               // lane-group width of the small-D kernels (64: none)
@@ -224,6 +226,7 @@ struct sgm_engine {
     int sweep_rows = 0;  // rows per band of the sweep (0 = automatic)
     int debug = 0;       // timing experiments (SweepArgs::dbg)
     int prepass_rows = 0;  // rows per chunk of the boundary pre-pass (0 = automatic, about 135, a multiple of 8)
+    int cn = 1;          // SGM_OPT_CHANNELS: 1 or 3 interleaved 8-bit channels per image pixel
     // sgm_compute_batch: up to three pairs in flight = this engine + two peers (own stream and device
     // buffers), each with page-locked staging buffers for the images and the disparity map
     sgm_engine *peer = nullptr, *peer2 = nullptr;
@@ -576,11 +579,13 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     // disparities side by side in a wave); the per-pixel cost comes from k_pix_px (D <= 32, one thread per pixel) or
     // k_pix (D = 48, 64: half its lanes idle, still less than the int16 pipeline's 3 V more traffic).
     // debug 256: the int16 pipeline always; debug 4 (no lane groups): the int16 pipeline for D <= 64.
-    p.byte_cost = !(dbg & SGM_DBG_INT16_COST) && (g.D > 64 || !(dbg & SGM_DBG_NO_LANE_GROUPS)) && g.SW2 >= 1 && g.SW2 <= 5 &&
+    // Colour pairs (cn = 3) take the int16 pipeline: their per-pixel cost (up to 3 * (2 * ftzero + 63)) does not fit a byte.
+    p.cn = e->cn;
+    p.byte_cost = p.cn == 1 && !(dbg & SGM_DBG_INT16_COST) && (g.D > 64 || !(dbg & SGM_DBG_NO_LANE_GROUPS)) && g.SW2 >= 1 && g.SW2 <= 5 &&
                   g.SH2 == g.SW2 && 2 * g.ftzero + 63 <= 255 && (int64_t)H * g.rowsz < (int64_t)0x7ff00000;
     // int16 pipeline, D <= 32: one thread per pixel (lanes spanning D would mostly idle; at D = 64 the wave-per-
     // chunk kernel is still ahead); the byte volume borrows the S buffer, unused before the paths
-    p.pix_px = g.D <= 32 && !(dbg & SGM_DBG_NO_LANE_GROUPS) && 2 * g.ftzero + 63 <= 255;
+    p.pix_px = p.cn == 1 && g.D <= 32 && !(dbg & SGM_DBG_NO_LANE_GROUPS) && 2 * g.ftzero + 63 <= 255;
     p.GWc = g.D > 64 ? 64 : (g.D <= 16 ? 8 : (g.D <= 32 ? 16 : 32));  // lane-group width of k_box_u8
     // rows per band of k_box_u8 (a band re-reads 2 * SH2 rows above it; multiples of 16: the register rings): 96, less
     // on frames too small to fill the chip with bands that tall
@@ -681,6 +686,16 @@ static size_t chain_ctl_bytes(int nf, int nbands) { return ((size_t)(1 + (size_t
 
 // Every device buffer one compute of this shape needs under plan p, allocated BEFORE anything is enqueued (a pair of a
 // chained group that does not fit then costs nothing but a smaller group).  Records the shape in e->g.
+// device bytes of the buffers ensure_plan_buffers sizes (it allocated something iff this grew)
+static size_t plan_bytes_held(const sgm_engine *e)
+{
+    const DevBuf *bufs[] = {&e->lrec, &e->rplanes, &e->hsum, &e->cost, &e->aggr, &e->aggr2, &e->aggr3, &e->aggr4, &e->aggr5,
+                            &e->wta, &e->disp_raw, &e->disp_med, &e->headroom, &e->bndL, &e->bndL2, &e->pstate, &e->pstate2,
+                            &e->label, &e->csize, &e->rlen, &e->chain_ctl, &e->chain_err};
+    size_t n = 0;
+    for (const DevBuf *b : bufs) n += b->cap;
+    return n;
+}
 static int ensure_plan_buffers(sgm_engine *e, const Plan &p, int H, int W)
 {
     Geom g;
@@ -695,8 +710,9 @@ static int ensure_plan_buffers(sgm_engine *e, const Plan &p, int H, int W)
     // compiler may merge or widen them (the widest scalar load is 64 bytes).  Every load STARTS at a record of the
     // frame, so none can leave the allocation.  (Not in the guarded mode: there the buffer ends where its mapping
     // ends, and the parity cases of tests/test_gpu_guard.py show that no load goes past the last record at all.)
-    if ((rc = e->lrec.ensure(npx * 8 + (debug_alloc_mode() ? 0 : 64)))) return rc;
-    if ((rc = e->rplanes.ensure(npx * 6))) return rc;
+    // (colour pairs: three records per pixel and 18 planes, kernels_color.h)
+    if ((rc = e->lrec.ensure(npx * 8 * p.cn + (debug_alloc_mode() ? 0 : 64)))) return rc;
+    if ((rc = e->rplanes.ensure(npx * 6 * p.cn))) return rc;
     if (vol) {
         // The byte pipeline keeps its per-pixel costs (V / 2) in the S buffer: they are dead when the block cost C is
         // complete, and no kernel writes S before that (the sweeps, the in-row paths and k_paths5_g all read C; in a batch
@@ -816,6 +832,30 @@ static int launch_hsum(const Geom &g, const uint2 *lrec, const uint8_t *rpl, int
         if (RS == 8) return launch_hsum_t<np, 8>(g, lrec, rpl, HS, RS, st);
         if (RS == 16) return launch_hsum_t<np, 16>(g, lrec, rpl, HS, RS, st);
         return launch_hsum_t<np, 0>(g, lrec, rpl, HS, RS, st);
+    });
+}
+
+// colour pairs: pixel cost of the three channels + horizontal box sum, all rows (k_hsum_c3)
+template <int NP, int RS_T>
+static int launch_hsum_c3_t(const Geom &g, const uint2 *lrec, const uint8_t *rpl, int16_t *HS, int RS, hipStream_t st)
+{
+    const int nchunks = cost_chunks(g);
+    const HsumLds l = hsum_c3_lds_layout(g.NP, RS, COST_XL, g.SW2);
+    if (l.total_bytes > 48 * 1024)
+        HIP_TRY(hipFuncSetAttribute((const void *)k_hsum_c3<NP, RS_T>, hipFuncAttributeMaxDynamicSharedMemorySize, l.total_bytes));
+    hipLaunchKernelGGL((k_hsum_c3<NP, RS_T>), dim3((unsigned)((int64_t)g.H * nchunks)), dim3(64), l.total_bytes, st, g, lrec, rpl,
+                       HS, COST_XL, nchunks, RS, l.ring_bytes, l.lrec_bytes, l.seg_len);
+    return SGM_OK;
+}
+static int launch_hsum_c3(const Geom &g, const uint2 *lrec, const uint8_t *rpl, int16_t *HS, hipStream_t st)
+{
+    int RS = 1;  // ring of the last blockSize+1 cost vectors, rounded to a power of two
+    while (RS < 2 * g.SW2 + 2) RS <<= 1;
+    return with_np(g, [&](auto np, auto) {
+        if (RS == 4) return launch_hsum_c3_t<np, 4>(g, lrec, rpl, HS, RS, st);
+        if (RS == 8) return launch_hsum_c3_t<np, 8>(g, lrec, rpl, HS, RS, st);
+        if (RS == 16) return launch_hsum_c3_t<np, 16>(g, lrec, rpl, HS, RS, st);
+        return launch_hsum_c3_t<np, 0>(g, lrec, rpl, HS, RS, st);
     });
 }
 
@@ -989,9 +1029,15 @@ static int ensure_aux(sgm_engine *e, bool second)
     return SGM_OK;
 }
 
-static int stage_features(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_right, int64_t stride)
+static int stage_features(sgm_engine *e, const Plan &p, const uint8_t *d_left, const uint8_t *d_right, int64_t stride)
 {
     const Geom &g = e->g;
+    if (p.cn == 3)
+        return run_stage(e, "features_c3", e->stream, [&] {
+            hipLaunchKernelGGL(k_features_c3, dim3((g.W + 255) / 256, g.H, 2), dim3(256), 0, e->stream, d_left, d_right, stride, g.H,
+                               g.W, g.ftzero, (uint2 *)e->lrec.p, (uint8_t *)e->rplanes.p);
+            return 1;
+        });
     return run_stage(e, "features", e->stream, [&] {
         hipLaunchKernelGGL(k_features, dim3((g.W + 255) / 256, g.H, 2), dim3(256), 0, e->stream, d_left, d_right, stride, g.H, g.W,
                            g.ftzero, (uint2 *)e->lrec.p, (uint8_t *)e->rplanes.p);
@@ -1017,7 +1063,11 @@ static int stage_cost(sgm_engine *e, const Plan &p)
         if ((rc = run_stage(e, "cost_pix", st, [&] { launch_pix(g, lrec, rpl, px, st); return 1; }))) return rc;
         return run_stage(e, "cost_box", st, [&] { launch_box(g, p, px, C, st); return 1; });
     }
-    rc = run_stage(e, "cost_hsum", st, [&] {
+    rc = run_stage(e, p.cn == 3 ? "cost_hsum_c3" : "cost_hsum", st, [&] {
+        if (p.cn == 3) {
+            const int r = launch_hsum_c3(g, lrec, rpl, HS, st);
+            return r ? r : 1;
+        }
         if (!p.pix_px) {
             const int r = launch_hsum(g, lrec, rpl, HS, st);
             return r ? r : 1;
@@ -1227,7 +1277,8 @@ static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_ri
                        int64_t stride, int16_t *d_disp, int phases = PH_ALL)
 {
     if (!e || !d_left || !d_right || !d_disp) return set_err(SGM_ERR_INVALID_ARG, "null pointer");
-    if (H <= 0 || W < 2 || stride < W) return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld", H, W, (long long)stride);
+    if (H <= 0 || W < 2 || stride < (int64_t)W * e->cn)
+        return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld (channels %d)", H, W, (long long)stride, e->cn);
     if (W > 32767 || H > 32767) return set_err(SGM_ERR_UNSUPPORTED, "image larger than 32767 in a dimension");
     HIP_TRY(hipSetDevice(e->device));
     Geom g0;
@@ -1258,7 +1309,7 @@ static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_ri
         });
         if (rc) return rc;
     } else {
-        if (do_pre && ((rc = stage_features(e, d_left, d_right, stride)) || (rc = stage_cost(e, p)) || (rc = fork_in_row(e, p))))
+        if (do_pre && ((rc = stage_features(e, p, d_left, d_right, stride)) || (rc = stage_cost(e, p)) || (rc = fork_in_row(e, p))))
             return rc;
         if (do_mid && (rc = p.v1 ? paths_v1(e) : paths_fused(e, p))) return rc;
         if (!do_post) return SGM_OK;
@@ -1445,6 +1496,11 @@ int sgm_set_option(sgm_engine *e, int option, int value)
     }
     else if (option == SGM_OPT_PREPASS_ROWS) e->prepass_rows = std::max(0, value);
     else if (option == SGM_OPT_GROUP_MAX) e->group_max = std::max(0, std::min(value, CHAIN_MAX_FRAMES));
+    else if (option == SGM_OPT_CHANNELS) {
+        if (value != 1 && value != 3)
+            return set_err(SGM_ERR_INVALID_ARG, "SGM_OPT_CHANNELS %d: only 1 and 3 interleaved 8-bit channels are supported", value);
+        e->cn = value;
+    }
     else return set_err(SGM_ERR_INVALID_ARG, "unknown option %d", option);
     return SGM_OK;
 }
@@ -1682,6 +1738,7 @@ static void inherit_options(sgm_engine *q, const sgm_engine *e)
     q->debug = e->debug;
     q->chain_wgs = e->chain_wgs;
     q->prepass_rows = e->prepass_rows;
+    q->cn = e->cn;
     q->keep_aggr = 0;
     q->profile = 0;
 }
@@ -1709,8 +1766,11 @@ static int prepare_group(sgm_engine *e, int want, int H, int W, const Plan &pl, 
         sgm_engine *q = e->group[k - 1];
         inherit_options(q, e);
         if (!q->ev_done) HIP_TRY(hipEventCreateWithFlags(&q->ev_done, hipEventDisableTiming));
-        const bool sized = q->H == H && q->W == W && q->cost.p;     // (ran this shape before: nothing to allocate)
+        // (nothing allocated -- the engine's buffers already hold this plan -- needs no reserve check; a shape it ran before
+        //  may still need more: colour pairs (SGM_OPT_CHANNELS = 3) take larger feature buffers and the int16 hsum volume)
+        const size_t held = plan_bytes_held(q);
         rc = ensure_plan_buffers(q, pl, H, W);
+        const bool sized = plan_bytes_held(q) == held;
         size_t fr = 0, tot = 0;
         // (the reserve: 4 GiB or 5 % -- every stream, event pool and first launch of a kernel costs the runtime device memory
         //  too, and "out of memory" from a kernel launch cannot be recovered from -- plus what the caller of this function
@@ -1865,7 +1925,8 @@ int sgm_pipeline_batch_device(sgm_engine *e, int N, const void *const *d_left, c
     if (!e || N <= 0 || !d_left || !d_right || !d_disp_i16) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
     for (int i = 0; i < N; i++)
         if (!d_left[i] || !d_right[i] || !d_disp_i16[i]) return set_err(SGM_ERR_INVALID_ARG, "null pointer for pair %d", i);
-    if (stride_bytes < W) return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld", H, W, (long long)stride_bytes);
+    if (stride_bytes < (int64_t)W * e->cn)
+        return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld (channels %d)", H, W, (long long)stride_bytes, e->cn);
     if (d_xyz_f32 && !Q) return set_err(SGM_ERR_INVALID_ARG, "Q is null");
     HIP_TRY(hipSetDevice(e->device));
     int rc;
@@ -1911,14 +1972,16 @@ int sgm_compute(sgm_engine *e, const uint8_t *left, const uint8_t *right, int H,
                 int16_t *disp_out)
 {
     if (!e || !left || !right || !disp_out) return set_err(SGM_ERR_INVALID_ARG, "null pointer");
-    if (H <= 0 || W < 2 || stride_bytes < W) return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld", H, W, (long long)stride_bytes);
+    const int64_t rowb = (int64_t)W * e->cn;  // bytes of one image row (SGM_OPT_CHANNELS)
+    if (H <= 0 || W < 2 || stride_bytes < rowb)
+        return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld (channels %d)", H, W, (long long)stride_bytes, e->cn);
     HIP_TRY(hipSetDevice(e->device));
-    const size_t npx = (size_t)H * W;
+    const size_t npx = (size_t)H * W, ib = (size_t)H * rowb;
     int rc;
-    if ((rc = e->in_left.ensure(npx)) || (rc = e->in_right.ensure(npx)) || (rc = e->disp_out.ensure(npx * 2))) return rc;
-    HIP_TRY(hipMemcpy2DAsync(e->in_left.p, W, left, (size_t)stride_bytes, W, H, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpy2DAsync(e->in_right.p, W, right, (size_t)stride_bytes, W, H, hipMemcpyHostToDevice, e->stream));
-    if ((rc = run_compute(e, (const uint8_t *)e->in_left.p, (const uint8_t *)e->in_right.p, H, W, W, (int16_t *)e->disp_out.p))) return rc;
+    if ((rc = e->in_left.ensure(ib)) || (rc = e->in_right.ensure(ib)) || (rc = e->disp_out.ensure(npx * 2))) return rc;
+    HIP_TRY(hipMemcpy2DAsync(e->in_left.p, rowb, left, (size_t)stride_bytes, rowb, H, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpy2DAsync(e->in_right.p, rowb, right, (size_t)stride_bytes, rowb, H, hipMemcpyHostToDevice, e->stream));
+    if ((rc = run_compute(e, (const uint8_t *)e->in_left.p, (const uint8_t *)e->in_right.p, H, W, rowb, (int16_t *)e->disp_out.p))) return rc;
     HIP_TRY(hipMemcpyAsync(disp_out, e->disp_out.p, npx * 2, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return check_chain(e);
@@ -1958,7 +2021,8 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
     if (xyz_out && !Q16) return set_err(SGM_ERR_INVALID_ARG, "xyz_out requested without Q");
     if (H <= 0 || W < 2) return set_err(SGM_ERR_INVALID_ARG, "bad shape");
     HIP_TRY(hipSetDevice(e->device));
-    const size_t npx = (size_t)H * W;
+    const size_t npx = (size_t)H * W, ib = npx * e->cn;  // pixels, bytes of one image ([H][W][cn], tight rows)
+    const int64_t rowb = (int64_t)W * e->cn;
     int rc;
     Plan pl;
     bool joint = false;
@@ -1979,7 +2043,7 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
         // The XYZ images (99.5 MB each) go straight to the caller's memory: staging them would pin gigabytes.
         BatchGuard guard{e};
         int cap = 1;
-        const size_t slot_bytes = 2 * (2 * npx + npx * 2 + (xyz_out ? npx * 16 : 0));
+        const size_t slot_bytes = 2 * (2 * ib + npx * 2 + (xyz_out ? npx * 16 : 0));
         if ((rc = prepare_group(e, N, H, W, pl, &cap, slot_bytes))) return rc;
         if (cap >= 2) {
             if (!e->copy_in) HIP_TRY(hipStreamCreateWithFlags(&e->copy_in, hipStreamNonBlocking));
@@ -1990,8 +2054,8 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
             for (int k = 0; k < per; k++) {
                 sgm_engine *q = eng[k] = k == 0 ? e : e->group[k - 1];
                 for (int sl = 0; sl < (ngroups > 1 ? 2 : 1); sl++) {
-                    if ((rc = q->io[sl][0].ensure(npx)) || (rc = q->io[sl][1].ensure(npx)) || (rc = q->io[sl][2].ensure(npx * 2))) return rc;
-                    if ((rc = q->pin_io[sl][0].ensure(npx)) || (rc = q->pin_io[sl][1].ensure(npx)) || (rc = q->pin_io[sl][2].ensure(npx * 2))) return rc;
+                    if ((rc = q->io[sl][0].ensure(ib)) || (rc = q->io[sl][1].ensure(ib)) || (rc = q->io[sl][2].ensure(npx * 2))) return rc;
+                    if ((rc = q->pin_io[sl][0].ensure(ib)) || (rc = q->pin_io[sl][1].ensure(ib)) || (rc = q->pin_io[sl][2].ensure(npx * 2))) return rc;
                     if (xyz_out && ((rc = q->io[sl][3].ensure(npx * 4)) || (rc = q->io[sl][4].ensure(npx * 12)))) return rc;
                     for (hipEvent_t *ev : {&q->ev_io_in[sl], &q->ev_io_used[sl], &q->ev_io_out[sl], &q->ev_io_dl[sl]})
                         if (!*ev) HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
@@ -2009,10 +2073,10 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
                         HIP_TRY(hipEventSynchronize(q->ev_io_in[sl]));                 // the staging buffers: their last upload has left them (long ago)
                         HIP_TRY(hipStreamWaitEvent(e->copy_in, q->ev_io_used[sl], 0));  // the device images: group gi - 2 has read them
                     }
-                    host_copy(q->pin_io[sl][0].p, lefts + i * npx, npx);
-                    host_copy(q->pin_io[sl][1].p, rights + i * npx, npx);
-                    HIP_TRY(hipMemcpyAsync(q->io[sl][0].p, q->pin_io[sl][0].p, npx, hipMemcpyHostToDevice, e->copy_in));
-                    HIP_TRY(hipMemcpyAsync(q->io[sl][1].p, q->pin_io[sl][1].p, npx, hipMemcpyHostToDevice, e->copy_in));
+                    host_copy(q->pin_io[sl][0].p, lefts + i * ib, ib);
+                    host_copy(q->pin_io[sl][1].p, rights + i * ib, ib);
+                    HIP_TRY(hipMemcpyAsync(q->io[sl][0].p, q->pin_io[sl][0].p, ib, hipMemcpyHostToDevice, e->copy_in));
+                    HIP_TRY(hipMemcpyAsync(q->io[sl][1].p, q->pin_io[sl][1].p, ib, hipMemcpyHostToDevice, e->copy_in));
                     HIP_TRY(hipEventRecord(q->ev_io_in[sl], e->copy_in));
                 }
                 return SGM_OK;
@@ -2033,12 +2097,12 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
                 }
                 if (n == 1) {   // (a last group of one pair: the plain entry on e, behind its upload)
                     HIP_TRY(hipStreamWaitEvent(e->stream, evi[0], 0));
-                    int r2 = sgm_pipeline_device(e, dl[0], dr[0], H, W, W, Q16, dd[0], df[0], dx[0]);
+                    int r2 = sgm_pipeline_device(e, dl[0], dr[0], H, W, rowb, Q16, dd[0], df[0], dx[0]);
                     if (r2) return r2;
                     HIP_TRY(hipEventRecord(evu[0], e->stream));
                     HIP_TRY(hipEventRecord(evo[0], e->stream));
                 } else {
-                    int r2 = run_group(e, eng.data(), n, pl, dl.data(), dr.data(), H, W, W, Q16, dd.data(), xyz_out ? df.data() : nullptr,
+                    int r2 = run_group(e, eng.data(), n, pl, dl.data(), dr.data(), H, W, rowb, Q16, dd.data(), xyz_out ? df.data() : nullptr,
                                        xyz_out ? dx.data() : nullptr, evi.data(), evu.data(), evo.data());
                     if (r2) return r2;
                 }
@@ -2095,8 +2159,8 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
     for (int k = 0; k < neng; k++) {
         sgm_engine *q = eng[k];
         inherit_options(q, e);
-        if ((rc = q->in_left.ensure(npx)) || (rc = q->in_right.ensure(npx)) || (rc = q->disp_out.ensure(npx * 2))) return rc;
-        if ((rc = q->pin_left.ensure(npx)) || (rc = q->pin_right.ensure(npx)) || (rc = q->pin_disp.ensure(npx * 2))) return rc;
+        if ((rc = q->in_left.ensure(ib)) || (rc = q->in_right.ensure(ib)) || (rc = q->disp_out.ensure(npx * 2))) return rc;
+        if ((rc = q->pin_left.ensure(ib)) || (rc = q->pin_right.ensure(ib)) || (rc = q->pin_disp.ensure(npx * 2))) return rc;
         if (xyz_out && ((rc = q->f32.ensure(npx * 4)) || (rc = q->xyz.ensure(npx * 12)))) return rc;
         if (!q->ev_done) HIP_TRY(hipEventCreateWithFlags(&q->ev_done, hipEventDisableTiming));
     }
@@ -2111,11 +2175,11 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
     for (int i = 0; i < N; i++) {
         sgm_engine *q = eng[i % neng];
         if (i >= neng && (rc = finish(i - neng))) return rc;
-        std::memcpy(q->pin_left.p, lefts + (size_t)i * npx, npx);
-        std::memcpy(q->pin_right.p, rights + (size_t)i * npx, npx);
-        HIP_TRY(hipMemcpyAsync(q->in_left.p, q->pin_left.p, npx, hipMemcpyHostToDevice, q->stream));
-        HIP_TRY(hipMemcpyAsync(q->in_right.p, q->pin_right.p, npx, hipMemcpyHostToDevice, q->stream));
-        rc = sgm_pipeline_device(q, q->in_left.p, q->in_right.p, H, W, W, Q16, q->disp_out.p, xyz_out ? q->f32.p : nullptr,
+        std::memcpy(q->pin_left.p, lefts + (size_t)i * ib, ib);
+        std::memcpy(q->pin_right.p, rights + (size_t)i * ib, ib);
+        HIP_TRY(hipMemcpyAsync(q->in_left.p, q->pin_left.p, ib, hipMemcpyHostToDevice, q->stream));
+        HIP_TRY(hipMemcpyAsync(q->in_right.p, q->pin_right.p, ib, hipMemcpyHostToDevice, q->stream));
+        rc = sgm_pipeline_device(q, q->in_left.p, q->in_right.p, H, W, rowb, Q16, q->disp_out.p, xyz_out ? q->f32.p : nullptr,
                                  xyz_out ? q->xyz.p : nullptr);
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(q->pin_disp.p, q->disp_out.p, npx * 2, hipMemcpyDeviceToHost, q->stream));

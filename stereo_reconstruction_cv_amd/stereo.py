@@ -74,10 +74,18 @@ class Engine:
         _check(self._L.sgm_create(C.byref(p), self.device, C.c_void_p(stream or 0), C.byref(h)))
         self._h = h
         self._fin = weakref.finalize(self, self._L.sgm_destroy, h)
+        self._cn = 1                        # SGM_OPT_CHANNELS the engine is set to
 
     # -- options / introspection
     def set_option(self, opt: int, value: int) -> None:
         _check(self._L.sgm_set_option(self._h, opt, int(value)))
+        if opt == _lib.SGM_OPT_CHANNELS:
+            self._cn = int(value)
+
+    def _channels(self, cn: int) -> None:
+        """Images of the next call have cn interleaved channels (1 or 3); the option is set only when it changes."""
+        if cn != self._cn:
+            self.set_option(_lib.SGM_OPT_CHANNELS, cn)
 
     def geometry(self, W: int):
         a, b = C.c_int(), C.c_int()
@@ -122,11 +130,15 @@ class Engine:
 
     # -- host-pointer path
     def compute_host(self, left: np.ndarray, right: np.ndarray) -> np.ndarray:
-        H, W = left.shape
+        """(H, W) or (H, W, 3) uint8 pair: rows may be padded, pixels must be dense (strides[-1] == 1, and 3 for a
+        colour pixel)."""
+        H, W = left.shape[:2]
+        cn = 1 if left.ndim == 2 else left.shape[2]
         disp = np.empty((H, W), np.int16)
         if left.strides[0] != right.strides[0]:
             right = np.ascontiguousarray(right)
             left = np.ascontiguousarray(left)
+        self._channels(cn)
         _check(self._L.sgm_compute(self._h, left.ctypes.data, right.ctypes.data, H, W, left.strides[0],
                                    disp.ctypes.data))
         return disp
@@ -135,9 +147,12 @@ class Engine:
         """N pairs from / to host arrays (sgm_compute_batch).  out: optional (disps int16 [N, H, W][, xyz float32 [N, H, W, 3]])
         arrays to fill -- like the `disparity` argument of cv2's compute(); a caller that runs batch after batch saves the
         page faults of a fresh 17 MB per 4K map (about a millisecond per pair)."""
-        N, H, W = lefts.shape
+        N, H, W = lefts.shape[:3]
+        cn = 1 if lefts.ndim == 3 else lefts.shape[3]     # (N, H, W) or (N, H, W, 3)
         lefts = np.ascontiguousarray(lefts, np.uint8)
         rights = np.ascontiguousarray(rights, np.uint8)
+        if rights.shape != lefts.shape:
+            raise error("compute_batch_host: lefts and rights must have the same shape")
         disps = xyz = None
         if out is not None:
             disps, xyz = (out if isinstance(out, (tuple, list)) else (out, None))
@@ -153,6 +168,7 @@ class Engine:
             if xyz is None:
                 xyz = np.empty((N, H, W, 3), np.float32)
             qp = Q.ctypes.data
+        self._channels(cn)
         _check(self._L.sgm_compute_batch(self._h, N, lefts.ctypes.data, rights.ctypes.data, H, W, disps.ctypes.data,
                                          xyz.ctypes.data if Q is not None else None, qp))
         return (disps, xyz) if Q is not None else disps
@@ -221,19 +237,22 @@ class Engine:
         return out.astype(bool)
 
     # -- device-pointer path (raw addresses; torch only supplies the memory)
-    def compute_device(self, d_left: int, d_right: int, H: int, W: int, stride: int, d_disp: int) -> None:
+    # (cn: interleaved channels of the images, 1 or 3; stride is the row pitch in bytes)
+    def compute_device(self, d_left: int, d_right: int, H: int, W: int, stride: int, d_disp: int, cn: int = 1) -> None:
+        self._channels(cn)
         _check(self._L.sgm_compute_device(self._h, d_left, d_right, H, W, stride, d_disp))
 
     def pipeline_device(self, d_left: int, d_right: int, H: int, W: int, stride: int, Q: np.ndarray | None,
-                        d_disp: int | None, d_dispf: int | None, d_xyz: int | None) -> None:
+                        d_disp: int | None, d_dispf: int | None, d_xyz: int | None, cn: int = 1) -> None:
         qp = None
         if Q is not None:
             Q = np.ascontiguousarray(Q, np.float64)
             qp = Q.ctypes.data
+        self._channels(cn)
         _check(self._L.sgm_pipeline_device(self._h, d_left, d_right, H, W, stride, qp, d_disp, d_dispf, d_xyz))
 
     def pipeline_batch_device(self, d_lefts, d_rights, H: int, W: int, stride: int, Q: np.ndarray | None,
-                              d_disps, d_dispfs=None, d_xyzs=None) -> None:
+                              d_disps, d_dispfs=None, d_xyzs=None, cn: int = 1) -> None:
         """N resident pairs in throughput mode (sgm_pipeline_batch_device): sequences of N device addresses.
         With SGM_OPT_SCHEDULE = 2 the pairs share one chained sweep launch per pass.  Asynchronous."""
         n = len(d_lefts)
@@ -243,6 +262,7 @@ class Engine:
             Q = np.ascontiguousarray(Q, np.float64)
             qp = Q.ctypes.data
         a, b, c, d, f = arr(d_lefts), arr(d_rights), arr(d_disps), arr(d_dispfs), arr(d_xyzs)
+        self._channels(cn)
         _check(self._L.sgm_pipeline_batch_device(self._h, n, a, b, H, W, stride, qp, c, d, f))
 
     def disp_to_float_device(self, d_disp: int, n: int, d_out: int) -> None:
@@ -347,7 +367,8 @@ class StereoSGBM:
         raise AttributeError(name)
 
     def compute(self, left, right):
-        """int16 (H, W) disparity * 16, invalid = (minDisparity - 1) * 16  (main.ipynb:668)."""
+        """int16 (H, W) disparity * 16, invalid = (minDisparity - 1) * 16  (main.ipynb:668).  left / right: uint8
+        (H, W) or colour (H, W, 3) pairs of the same shape (the pixel cost sums the three channels, as cv2's)."""
         if self._p["mode"] not in (STEREO_SGBM_MODE_SGBM, STEREO_SGBM_MODE_HH):
             raise error("StereoSGBM.compute: only MODE_SGBM and MODE_HH are implemented "
                         "(the reference never selects MODE_SGBM_3WAY / MODE_HH4)")
@@ -360,14 +381,15 @@ class StereoSGBM:
                         "left.type() == right.type() && left.depth() == CV_8U")
         if left.ndim == 3 and left.shape[2] == 1:
             left, right = left[:, :, 0], right[:, :, 0]
-        if left.ndim != 2:
-            raise error("StereoSGBM.compute: only single-channel 8-bit images are supported "
-                        "(the reference reads its pairs with IMREAD_GRAYSCALE, main.ipynb:362-363)")
+        _check_channels(left.ndim, left.shape[2] if left.ndim == 3 else 1)
         if left.shape[0] == 0 or left.shape[1] == 0:
             raise error("StereoSGBM.compute: empty image")
-        if left.strides[1] != 1 or left.strides[0] < left.shape[1]:
+        # pixels must be dense (a colour pixel is 3 adjacent bytes); padded rows pass as they are
+        cn = 1 if left.ndim == 2 else 3
+        px = (1,) if cn == 1 else (3, 1)
+        if left.strides[1:] != px or left.strides[0] < cn * left.shape[1]:
             left = np.ascontiguousarray(left)
-        if right.strides[1] != 1 or right.strides[0] < right.shape[1]:
+        if right.strides[1:] != px or right.strides[0] < cn * right.shape[1]:
             right = np.ascontiguousarray(right)
         if left.shape[1] < 2:
             raise error("StereoSGBM.compute: image width < 2")
@@ -377,19 +399,30 @@ class StereoSGBM:
         import torch
         if not (_is_torch(left) and _is_torch(right)) or not left.is_cuda or not right.is_cuda:
             raise error("StereoSGBM.compute: torch inputs must both be CUDA (HIP) tensors")
-        if left.shape != right.shape or left.dtype != torch.uint8 or right.dtype != torch.uint8 or left.dim() != 2:
+        if left.shape != right.shape or left.dtype != torch.uint8 or right.dtype != torch.uint8:
             raise error("StereoSGBM.compute: (-215:Assertion failed) left.size() == right.size() && "
                         "left.type() == right.type() && left.depth() == CV_8U")
+        if left.dim() == 3 and left.shape[2] == 1:
+            left, right = left[:, :, 0], right[:, :, 0]
+        _check_channels(left.dim(), left.shape[2] if left.dim() == 3 else 1)
         left, right = left.contiguous(), right.contiguous()
-        H, W = left.shape
+        H, W = left.shape[:2]
+        cn = 1 if left.dim() == 2 else 3
         dev = left.device.index or 0
         eng = get_engine(self._p, dev)
         out = torch.empty((H, W), dtype=torch.int16, device=left.device)
         # the engine runs on its own stream: order it after torch's current stream and wait for it
         torch.cuda.current_stream(left.device).synchronize()
-        eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, W, out.data_ptr())
+        eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn)
         eng.synchronize()
         return out
+
+
+def _check_channels(ndim: int, cn: int) -> None:
+    """upstream: CV_Assert(cn == 1 || cn == 3) behind the size / type assertion -- 8-bit 1- or 3-channel pairs"""
+    if ndim not in (2, 3) or (ndim == 3 and cn != 3):
+        raise error("StereoSGBM.compute: (-215:Assertion failed) left.channels() == 1 || left.channels() == 3: "
+                    "only 8-bit single-channel (H, W) and 3-channel (H, W, 3) images are supported")
 
 
 def StereoSGBM_create(minDisparity=0, numDisparities=16, blockSize=3, P1=0, P2=0, disp12MaxDiff=0,
