@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: dense stereo disparity throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--ingest resident|rank0] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--ingest resident|rank0] [--dump-outputs DIR] [--full]
 
 A "step" = one pass of the hot path (SGBM compute -> float scaling -> reprojectImageTo3D) over
 one batch of synthetic rectified pairs that is already resident in HBM.  One process per GPU:
@@ -17,19 +17,24 @@ has 17 x 180 band tickets = 11.95 per persistent workgroup and no idle tail; twe
 MODE_HH (8 paths) + LR check + sub-pixel + median + speckle + reprojection to XYZ (the union of
 BASELINE.json configs[2] and configs[4]), in THROUGHPUT MODE: chained sweeps without a boundary
 pre-pass, all pairs of the step through sgm_pipeline_batch_device (one sweep launch per pass for the
-whole batch).  The single-pair latency of the same configuration (pre-pass schedule, one pair per
-step: workload "c3c5") rides along as `latency_mode` at N = 1.  The other configs are selectable
-with --workload and are parity-test cases (tests/test_gpu_configs.py runs every one of them at full
-size against the oracle).
+whole batch).  The other configs are selectable with --workload and are parity-test cases
+(tests/test_gpu_configs.py runs every one of them at full size against the oracle).
 
 --ingest rank0: rank 0 owns every frame; scatter of the u8 pairs, compute, gather of the int16
 disparities (and XYZ when the workload reprojects) over torch.distributed ("nccl" = RCCL over xGMI)
 run as a pipeline inside the timed region (stereo_reconstruction_cv_amd/dist.py: IngestPipeline --
 the gather of step k and the scatter of step k + 2 beside the compute of step k + 1, every transfer
-of a scatter / gather posted as one batch so that rank 0's links work at the same time).  The default
-("resident") N > 1 run times that path too, after its own timed region and over the same number of
-steps, and reports it as `ingest_rank0` (with a check that the gathered results equal the resident
-ones) -- under a watchdog and a try/except: whatever happens there, the headline line is printed.
+of a scatter / gather posted as one batch so that rank 0's links work at the same time).
+
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print
+the line.  --full adds the measurements that run after the timed region, each on its own:
+  * N = 1: `cpu_baseline` -- the CPU oracle on a sample of the frame, one core and all usable threads;
+  * N = 1: `latency_mode` -- the same configuration one pair per call (pre-pass schedule, workload "c3c5");
+  * N > 1, resident: `ingest_rank0` -- the rank-0 ingest path over the same number of steps (with a check that
+    the gathered results equal the resident ones), under a watchdog and a try/except: whatever happens there,
+    the headline line is printed.
+--no-cpu-baseline / --no-latency-mode / --no-ingest-leg drop one of them from a --full run.  --verify (the
+oracle on the full frames) is an opt-in of its own, with or without --full.
 """
 from __future__ import annotations
 
@@ -42,6 +47,7 @@ import subprocess
 import sys
 import threading
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -307,9 +313,12 @@ def main():
     ap.add_argument("--xyz", default="dense", choices=("dense", "compact"),
                     help="--ingest rank0 with a reprojecting workload: what travels back to rank 0 beside the int16 maps -- the dense "
                          "XYZ image (12 bytes per pixel) or the valid points only, compacted on the GPU (main.ipynb:726-737)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency-mode", action="store_true", help="skip the single-pair latency measurement that rides along at N = 1")
-    ap.add_argument("--no-ingest-leg", action="store_true", help="N > 1, resident: skip the timed rank-0 ingest leg after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the CPU baseline and the single-pair latency mode (N = 1) or the "
+                         "timed rank-0 ingest leg (N > 1, resident)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-latency-mode", action="store_true", help="--full: skip the single-pair latency measurement at N = 1")
+    ap.add_argument("--no-ingest-leg", action="store_true", help="--full, N > 1, resident: skip the timed rank-0 ingest leg")
     ap.add_argument("--cpu-rows", type=int, default=0, help="rows of the frame the CPU baseline runs (0 = auto)")
     ap.add_argument("--verify", action="store_true", help="also run the oracle on the full frame and compare")
     ap.add_argument("--stages", action="store_true", help="print the per-stage HIP-event table to stderr")
@@ -393,8 +402,9 @@ def main():
         seeds = [1234 + i for i in range(ppg * world)] if rank == 0 else []
     else:
         seeds = [1234 + rank * ppg + i for i in range(ppg)]
-    nuniq = min(len(seeds), 4)          # (four different images are plenty; generating one 4K pair costs the host a second)
-    uniq = [synth.make_pair(H, W, D, seed=s)[:2] for s in seeds[:nuniq]]
+    nuniq = min(len(seeds), 4)          # (four different images are plenty; generating one 4K pair costs the host seconds)
+    with ThreadPoolExecutor(max(nuniq, 1)) as ex:     # side by side: numpy releases the GIL in its array loops
+        uniq = list(ex.map(lambda s: synth.make_pair(H, W, D, seed=s)[:2], seeds[:nuniq]))
     pairs = [uniq[i % nuniq] for i in range(len(seeds))]
     d_left = [torch.from_numpy(a).to(dev) for a, _ in pairs]
     d_right = [torch.from_numpy(b).to(dev) for _, b in pairs]
@@ -685,11 +695,11 @@ def main():
         "stage_ms": {n: float(m) for n, m in zip(names, mean_ms)},
     }
 
-    # ---- N > 1, resident: the rank-0 ingest path on hardware, timed over the same number of steps ----
+    # ---- --full, N > 1, resident: the rank-0 ingest path on hardware, timed over the same number of steps ----
     # (scatter / compute / gather pipeline over RCCL; never run on real multi-GPU hardware before the driver's scaling
     #  run -- so a watchdog prints the finished headline line if it stalls and ENDS THE RUN WITH STATUS 3: a stalled
     #  GPU or RCCL leg is a failure, not a success with a note; any exception is reported in the line, not raised)
-    if world > 1 and args.ingest == "resident" and not args.no_ingest_leg:
+    if args.full and world > 1 and args.ingest == "resident" and not args.no_ingest_leg:
         state = {"done": False}
 
         def watchdog():
@@ -768,11 +778,9 @@ def main():
                 out["ingest_rank0"] = {"ok": False, "error": f"{type(ex).__name__}: {ex}"[:500]}
         state["done"] = True
 
-    # ---- CPU baseline: the oracle (a scalar port, one thread per frame like upstream), bounded
+    # ---- --full, CPU baseline: the oracle (a scalar port, one thread per frame like upstream), bounded
     # sample, rank 0 at N = 1; plus the frame-parallel rate on every usable core (one frame per core) ----
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and not mock:
-        from concurrent.futures import ThreadPoolExecutor
-
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline and not mock:
         from oracle import oracle as O  # test infrastructure; timed here only as the CPU baseline
         model, nproc, usable = cpu_info()
         rows = args.cpu_rows or min(H, max(64, int(1080 * (3840 * 256) / (W * D))))
@@ -835,8 +843,8 @@ def main():
         out["cpu_baseline"]["all_threads"] = best
         out["speedup_vs_cpu_all_threads"] = mdisp / best["value"]
 
-    # ---- the same configuration, one pair at a time in latency mode (pre-pass schedule), N = 1 only ----
-    if world == 1 and rank == 0 and not mock and not args.no_latency_mode and (ppg > 1 or schedule != 1):
+    # ---- --full: the same configuration, one pair at a time in latency mode (pre-pass schedule), N = 1 only ----
+    if args.full and world == 1 and rank == 0 and not mock and not args.no_latency_mode and (ppg > 1 or schedule != 1):
         e1 = make_engine(1)
         lat = []
         for it in range(5):

@@ -26,17 +26,26 @@ def _run(*extra, n=2):
 
 
 def test_plain_start_with_two_gpus_launches_its_own_ranks():
-    d = _run()
+    d = _run("--full")
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak"
     assert d["config"]["world_size"] == 2 and d["config"]["frames_per_rank"] == [2, 2]
     assert d["config"]["global_pairs_per_step"] == 4 and d["config"]["ingest"] == "resident"
-    # the default run also times the rank-0 ingest pipeline (scatter -> compute -> gather) after the timed region
+    # --full also times the rank-0 ingest pipeline (scatter -> compute -> gather) after the timed region
     assert d["ingest_rank0"]["ok"] is True and d["ingest_rank0"]["frames_per_step"] == 4 and d["ingest_rank0"]["pairs_per_s"] > 0
     # ... on the timed region's pairs per rank, once with dense XYZ images and once with the compacted point lists
     assert d["ingest_rank0"]["pairs_per_rank"] == d["config"]["pairs_per_gpu_per_step"]
     assert d["ingest_rank0"]["dense"]["ok"] is True and d["ingest_rank0"]["compact"]["ok"] is True
     assert d["ingest_rank0"]["compact"]["bytes_per_pair_gathered"] < d["ingest_rank0"]["dense"]["bytes_per_pair_gathered"]
     assert "BENCH_MOCK" in d["data"]
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "vs_baseline", "dtype", "roofline"):
+        assert k in d
+
+
+def test_a_plain_run_with_two_gpus_skips_the_ingest_leg():
+    """without --full the run ends after the timed region: the same headline, no rank-0 ingest leg"""
+    d = _run()
+    assert d["n_gpus"] == 2 and d["config"]["world_size"] == 2 and d["config"]["frames_per_rank"] == [2, 2]
+    assert "ingest_rank0" not in d
     for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "vs_baseline", "dtype", "roofline"):
         assert k in d
 
@@ -58,8 +67,8 @@ def test_a_stalled_ingest_leg_fails_the_run():
     env = dict(os.environ, BENCH_MOCK="1", BENCH_INGEST_TIMEOUT="0.0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "2", "--warmup", "1"],
-                       capture_output=True, text=True, env=env, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "2", "--warmup", "1",
+                        "--full"], capture_output=True, text=True, env=env, timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     if r.returncode == 0:      # (the leg finished before the watchdog's first look: nothing stalled, nothing to assert)
         assert json.loads(lines[0])["ingest_rank0"]["ok"] is True
@@ -69,7 +78,7 @@ def test_a_stalled_ingest_leg_fails_the_run():
 
 def test_throughput_mode_workload_through_the_batch_entry():
     env_n = 2
-    d = _run("--workload", "tinyt", n=env_n)
+    d = _run("--workload", "tinyt", "--full", n=env_n)
     assert d["config"]["batch_entry"] is True and d["config"]["pairs_per_gpu_per_step"] == 3
     assert d["config"]["frames_per_rank"] == [3, 3] and d["ingest_rank0"]["ok"] is True
     assert "floor_bytes" in d and "unfused_model_bytes" in d and "frac_whole_step" not in d

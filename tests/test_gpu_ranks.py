@@ -1,4 +1,4 @@
-"""Two ranks with the real engine on the one GPU of the box (needs an MI355X): `bench.py --gpus 2` started
+"""Two ranks with the real engine on the one GPU of the box (needs an MI355X): `bench.py --gpus 2 --full` started
 plainly spawns its own ranks as CHILD processes (nothing here execs; the pytest process never hands its GPU
 context to another program), BENCH_REHEARSE=1 lets both ranks share cuda:0 and rendezvous over gloo (RCCL
 refuses two ranks on one device).  What is under test is the N > 1 code path with real kernels: sharding, the
@@ -21,7 +21,7 @@ def test_two_ranks_share_the_gpu_and_the_ingest_pipeline_reproduces_the_resident
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "BENCH_MOCK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", workload, "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout

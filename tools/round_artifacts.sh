@@ -9,7 +9,7 @@ TAG=${1:-r04}
 O=$R/gpurun_out/art_$TAG
 mkdir -p $O
 cd $R
-python bench.py --stages > $O/bench_default.json 2> $O/bench_default_stages.txt || echo "default bench failed"
+python bench.py --full --stages > $O/bench_default.json 2> $O/bench_default_stages.txt || echo "default bench failed"
 for w in c3c5 c1 c1x8 c1t c2 c3 c4 c5 nb c3c5x2 c3c5x3 c3c5x6 c3c5x8 c3c5x12 c3c5x14 c3c5x16 c3c5x18 c3c5x24 c5x12 c5x17 c4t; do
     python bench.py --workload $w --stages --no-cpu-baseline --no-latency-mode > $O/bench_$w.json 2> $O/bench_${w}_stages.txt || echo "bench $w failed"
 done
@@ -19,5 +19,5 @@ for w in default c3c5 c1 c1x8 c1t c2 c3 c4 c5 nb c3c5x2 c3c5x3 c3c5x6 c3c5x8 c3c
 done
 python bench.py --verify --no-cpu-baseline > $O/bench_default_verify.json 2> /dev/null; python3 -c "import json; d=json.loads(open('$O/bench_default_verify.json').read().strip().splitlines()[-1]); print('verify', d.get('verify'))"
 python tools/host_rate.py > $O/host_rate.txt 2>&1; cat $O/host_rate.txt
-BENCH_REHEARSE=1 python bench.py --gpus 2 --workload c4 --steps 2 --warmup 1 --no-cpu-baseline > $O/rehearse_n2_c4.json 2> $O/rehearse_n2_c4.err; tail -c 600 $O/rehearse_n2_c4.json
-BENCH_REHEARSE=1 python bench.py --gpus 2 --workload c3c5x6 --steps 2 --warmup 1 --no-cpu-baseline > $O/rehearse_n2_c3c5x6.json 2> $O/rehearse_n2_c3c5x6.err; tail -c 600 $O/rehearse_n2_c3c5x6.json
+BENCH_REHEARSE=1 python bench.py --gpus 2 --workload c4 --steps 2 --warmup 1 --full --no-cpu-baseline > $O/rehearse_n2_c4.json 2> $O/rehearse_n2_c4.err; tail -c 600 $O/rehearse_n2_c4.json
+BENCH_REHEARSE=1 python bench.py --gpus 2 --workload c3c5x6 --steps 2 --warmup 1 --full --no-cpu-baseline > $O/rehearse_n2_c3c5x6.json 2> $O/rehearse_n2_c3c5x6.err; tail -c 600 $O/rehearse_n2_c3c5x6.json
