@@ -3,7 +3,8 @@
 // Upstream's calcPixelCostBT with cn = 3 (restated): every channel of the interleaved row gets the A.2
 // prefilter from its own neighbours (same channel at x-1 / x+1 of rows y-1, y, y+1) and a raw plane, the border columns
 // hold ftzero in all six planes, and the pixel cost is the sum over the six planes -- exactly the sum of the three
-// single-channel pixel costs of the channel images (at most 3 * (2 * ftzero + 63) = 567 at preFilterCap 63).  Nothing
+// single-channel pixel costs of the channel images (at most 3 * (2 * ftzero + 63) = 567 at preFilterCap 63, and
+// 3 * (255 + 63) = 954 once the byte-valued prefilter wraps).  Nothing
 // downstream of the pixel cost changes, so the colour path ends in the int16 pipeline's vertical box sum (k_vsum_ring /
 // k_vsum), which also writes the headroom record.  C is written once: the three channels are summed in registers.
 //
@@ -40,13 +41,13 @@ __global__ __launch_bounds__(256) void k_features_c3(const uint8_t *__restrict__
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const int xx = x + k - 1;
-            if (xx <= 0 || xx >= W - 1) {  // border columns hold ftzero in all six planes (A.2, A.10)
-                pf[k] = ftzero;
-                rw[k] = ftzero;
+            if (xx <= 0 || xx >= W - 1) {  // border columns hold ftzero in all six planes (A.2, A.10), as a byte
+                pf[k] = ftzero & 0xff;
+                rw[k] = ftzero & 0xff;
             } else {
                 const int a = 3 * (xx + 1) + ch, b = 3 * (xx - 1) + ch;
                 int g = 2 * ((int)row[a] - (int)row[b]) + ((int)up[a] - (int)up[b]) + ((int)dn[a] - (int)dn[b]);
-                pf[k] = min(max(g, -ftzero), ftzero) + ftzero;
+                pf[k] = (min(max(g, -ftzero), ftzero) + ftzero) & 0xff;  // a byte, as in k_features
                 rw[k] = row[3 * xx + ch];
             }
         }

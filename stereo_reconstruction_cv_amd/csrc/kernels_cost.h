@@ -50,17 +50,19 @@ __global__ __launch_bounds__(256) void k_features(const uint8_t *__restrict__ im
     const uint8_t *up = y > 0 ? row - stride : row;
     const uint8_t *dn = y < H - 1 ? row + stride : row;
 
+    // Upstream's clip table and row buffers hold bytes: from ftzero = 129 (preFilterCap >= 128) on, the prefilter value
+    // and the border value wrap mod 256 before the interval is formed (A.2), and every record byte stays a byte.
     int pf[3], rw[3];  // values at x-1, x, x+1 (only read where they exist)
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         const int xx = x + k - 1;
         if (xx <= 0 || xx >= W - 1) {  // border columns hold ftzero in BOTH channels (A.2)
-            pf[k] = ftzero;
-            rw[k] = ftzero;
+            pf[k] = ftzero & 0xff;
+            rw[k] = ftzero & 0xff;
         } else {
             int g = 2 * ((int)row[xx + 1] - (int)row[xx - 1]) + ((int)up[xx + 1] - (int)up[xx - 1]) +
                     ((int)dn[xx + 1] - (int)dn[xx - 1]);
-            pf[k] = min(max(g, -ftzero), ftzero) + ftzero;
+            pf[k] = (min(max(g, -ftzero), ftzero) + ftzero) & 0xff;
             rw[k] = row[xx];
         }
     }
@@ -294,7 +296,8 @@ __global__ __launch_bounds__(64) void k_hsum(Geom g, const uint2 *__restrict__ l
 }
 
 // ---- byte pipeline of the block cost (default for window radii 1..5) ----------------------------
-// The per-pixel Birchfield-Tomasi cost is at most 2*ftzero + 63 <= 255: stored as one BYTE per
+// The per-pixel Birchfield-Tomasi cost is at most min(2*ftzero, 255) + 63, so the engine takes this pipeline only where
+// 2*ftzero + 63 <= 255 (ftzero <= 96; the wrapped values of ftzero >= 129 can reach 255 + 63): stored as one BYTE per
 // (x, d) it is half the volume of the int16 horizontal sums that k_hsum hands to k_vsum, and the
 // box filter becomes one kernel that reads it back (k_box_u8).  HBM traffic of the cost stage:
 // 0.5 V written + ~0.55 V read + V written, against 3.1 V of k_hsum + k_vsum_ring.

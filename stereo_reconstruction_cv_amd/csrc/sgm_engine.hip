@@ -579,7 +579,9 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     // disparities side by side in a wave); the per-pixel cost comes from k_pix_px (D <= 32, one thread per pixel) or
     // k_pix (D = 48, 64: half its lanes idle, still less than the int16 pipeline's 3 V more traffic).
     // debug 256: the int16 pipeline always; debug 4 (no lane groups): the int16 pipeline for D <= 64.
-    // Colour pairs (cn = 3) take the int16 pipeline: their per-pixel cost (up to 3 * (2 * ftzero + 63)) does not fit a byte.
+    // Colour pairs (cn = 3) take the int16 pipeline: their per-pixel cost (up to 3 * (min(2 * ftzero, 255) + 63)) does not
+    // fit a byte.  A gray pixel cost is at most min(2 * ftzero, 255) + 63 (the prefilter values are bytes, k_features), so
+    // 2 * ftzero + 63 <= 255 below is the exact bound for ftzero <= 96 and keeps every larger ftzero off the byte volumes.
     p.cn = e->cn;
     p.byte_cost = p.cn == 1 && !(dbg & SGM_DBG_INT16_COST) && (g.D > 64 || !(dbg & SGM_DBG_NO_LANE_GROUPS)) && g.SW2 >= 1 && g.SW2 <= 5 &&
                   g.SH2 == g.SW2 && 2 * g.ftzero + 63 <= 255 && (int64_t)H * g.rowsz < (int64_t)0x7ff00000;

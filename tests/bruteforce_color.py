@@ -20,7 +20,6 @@ def sgbm_c3(left, right, **kw):
     assert left.ndim == 3 and left.shape[2] == 3 and left.shape == right.shape
     q = BF.normalise(**kw)
     H, W = left.shape[:2]
-    inv = (q["minD"] - 1) * 16
     pix, minX1, W1 = pixel_cost_c3(left, right, q)
     C = BF.block_cost(pix, q["r"])
     dirs = BF.DIRS8 if q["mode"] == 1 else BF.DIRS5
@@ -30,10 +29,7 @@ def sgbm_c3(left, right, **kw):
     S = np.minimum(S, BF.MAX_COST)
     raw = BF.select_disparity(S, W, minX1, q)
     med = BF.median3(raw)
-    out = med
-    if q["spw"] > 0:
-        out = BF.speckles(med, inv, q["spw"], 16 * q["spr"])
-    return dict(C=C, S=S, disp_raw=raw, disp_median=med, disp=out)
+    return dict(C=C, S=S, disp_raw=raw, disp_median=med, disp=BF.speckle_stage(med, q))
 
 
 def colour_pair(H, W, D, seed, minD=0):

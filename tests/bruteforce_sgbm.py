@@ -7,6 +7,8 @@ components through scipy's graph routine.  Its only purpose is to cross-check th
 """
 from __future__ import annotations
 
+from fractions import Fraction
+
 import numpy as np
 from scipy.sparse import coo_matrix
 from scipy.sparse.csgraph import connected_components
@@ -33,10 +35,12 @@ def _features(img, ftzero):
     up, mid, dn = P[:-2], P[1:-1], P[2:]
     grad = np.zeros_like(I)
     grad[:, 1:-1] = (2 * (mid[:, 2:] - mid[:, :-2]) + (up[:, 2:] - up[:, :-2]) + (dn[:, 2:] - dn[:, :-2]))
-    pf = np.clip(grad, -ftzero, ftzero) + ftzero
+    # the clip table and the row buffers hold bytes: at ftzero >= 129 the value and the border value wrap mod 256
+    # before the interval is formed (A.2)
+    pf = (np.clip(grad, -ftzero, ftzero) + ftzero) % 256
     raw = I.copy()
-    pf[:, [0, -1]] = ftzero
-    raw[:, [0, -1]] = ftzero
+    pf[:, [0, -1]] = ftzero % 256
+    raw[:, [0, -1]] = ftzero % 256
     out = []
     for v in (pf, raw):
         l = v.copy()
@@ -129,6 +133,8 @@ def select_disparity(S, W, minX1, q):
             s = S[y, xi]
             best = int(np.argmin(s))  # first minimum
             ms = int(s[best])
+            if ms >= MAX_COST:    # no S below MAX_COST: best stays -1, the pixel is invalid and leaves disp2 alone
+                continue
             ds = np.arange(D)
             if np.any((s * (100 - uniq) < ms * 100) & (np.abs(best - ds) > 1)):
                 continue
@@ -188,7 +194,6 @@ def sgbm(left, right, **kw):
     """Returns dict(C, S, disp_raw, disp_median, disp)."""
     q = normalise(**kw)
     H, W = left.shape
-    inv = (q["minD"] - 1) * 16
     pix, minX1, W1 = pixel_cost(left, right, q)
     C = block_cost(pix, q["r"])
     dirs = DIRS8 if q["mode"] == 1 else DIRS5
@@ -198,14 +203,28 @@ def sgbm(left, right, **kw):
     S = np.minimum(S, MAX_COST)
     raw = select_disparity(S, W, minX1, q)
     med = median3(raw)
-    out = med
-    if q["spw"] > 0:
-        out = speckles(med, inv, q["spw"], 16 * q["spr"])
-    return dict(C=C, S=S, disp_raw=raw, disp_median=med, disp=out)
+    return dict(C=C, S=S, disp_raw=raw, disp_median=med, disp=speckle_stage(med, q))
 
 
-def reproject(disp, Q, handle_missing=False):
-    """Appendix B in numpy float64 with explicit operation order."""
+def speckle_stage(med, q):
+    """A.8: the speckle filter runs only if speckleRange >= 0 and speckleWindowSize > 0."""
+    if q["spr"] >= 0 and q["spw"] > 0:
+        return speckles(med, (q["minD"] - 1) * 16, q["spw"], 16 * q["spr"])
+    return med
+
+
+def fma(a, b, c):
+    """a * b + c rounded once to double, as a fused multiply-add computes it (exact rational arithmetic)"""
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+_fma = np.vectorize(fma, otypes=[np.float64])
+
+
+def reproject(disp, Q, handle_missing=False, fused=False):
+    """Appendix B in numpy float64 with explicit operation order.  fused=True: every step s += Q[i, k] * v[k] of the
+    sums as one fused multiply-add -- what a build that contracts multiply-adds computes instead (a yardstick for the
+    tests that must tell the two apart, never the specification)."""
     H, W = disp.shape
     Q = np.asarray(Q, np.float64)
     ys, xs = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
@@ -215,7 +234,7 @@ def reproject(disp, Q, handle_missing=False):
     for i in range(4):
         s = np.zeros_like(d)
         for k in range(4):
-            s = s + Q[i, k] * vec[k]
+            s = _fma(Q[i, k], vec[k], s) if fused else s + Q[i, k] * vec[k]
         h.append(s)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         ia = 1.0 / h[3]
