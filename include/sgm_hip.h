@@ -57,13 +57,17 @@ typedef enum {
     SGM_ERR_INVALID_ARG = -1,   /* null pointer, non-positive size, unsupported parameter       */
     SGM_ERR_NO_DEVICE = -2,     /* no HIP device / device index out of range                     */
     SGM_ERR_HIP = -3,           /* a HIP runtime call failed; message has the hipError string    */
-    SGM_ERR_UNSUPPORTED = -4,   /* mode 2/3 (3WAY/HH4), numDisparities not a multiple of 16, ... */
+    SGM_ERR_UNSUPPORTED = -4,   /* mode 2 (3WAY), numDisparities not a multiple of 16, ...     */
     SGM_ERR_NOMEM = -5
 } sgm_status;
 
 /* keyword arguments of cv2.StereoSGBM_create (main.ipynb:655-666); mode: 0 = MODE_SGBM
- * (5 paths, what the notebook runs), 1 = MODE_HH (8 paths).  Zero / negative values are
- * normalised exactly as OpenCV 4.11 does. */
+ * (5 paths, what the notebook runs), 1 = MODE_HH (8 paths), 3 = MODE_HH4 = the MODE_HH pipeline
+ * over the path set {(1,0), (-1,0), (0,1), (0,-1)} (upstream's implementation is multi-threaded
+ * but, as far as it can be restated, independent of the thread count).  0, 1 and 3 are built;
+ * 2 = MODE_SGBM_3WAY is refused with SGM_ERR_UNSUPPORTED (its result depends on a stripe size
+ * upstream takes from a cache-size heuristic).  Zero / negative values are normalised exactly as
+ * OpenCV 4.11 does. */
 typedef struct {
     int32_t minDisparity;
     int32_t numDisparities;

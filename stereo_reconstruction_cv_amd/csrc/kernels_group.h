@@ -339,6 +339,22 @@ __global__ __launch_bounds__(64) void k_paths5_g(Geom g, int xdir, int ydir, con
     }
 }
 
+// The four axis-aligned directions (MODE_HH4) for D <= 64 in ONE launch, each into a volume of its own, as k_paths5_g
+// does for MODE_SGBM: workgroups [0, 2 nr) walk the rows (even: right to left -> SW, odd: left to right -> SE), the
+// rest walk the columns (role 1 of the line walk: no wrap; even: top-down -> SD, odd: bottom-up -> SU).
+template <int GW, bool PARTIAL>
+__global__ __launch_bounds__(64) void k_axis_paths4_g(Geom g, const int16_t *__restrict__ C, int16_t *__restrict__ SD,
+                                                      int16_t *__restrict__ SU, int16_t *__restrict__ SW, int16_t *__restrict__ SE, int nr)
+{
+    const int b = (int)blockIdx.x;
+    if (b < 2 * nr) {
+        rows_g_body<GW, 1, PARTIAL, PATH_FIRST, true>(g, (b & 1) ? +1 : -1, C, (b & 1) ? SE : SW, 1, nullptr, b >> 1);
+    } else {
+        const int i = b - 2 * nr;
+        lines3_g_body<GW, PARTIAL, true>(g, 1, (i & 1) ? -1 : +1, C, (i & 1) ? SU : SD, i >> 1, 1);
+    }
+}
+
 // The three directions that come from the previous row, for EVERY pixel at once (D <= 64, band height 1):
 // with the boundary pre-pass having left every row's three predecessor states in HBM, these paths need
 // no recurrence here at all -- N_r(p, d) = C(p, d) + min(Q_r(d), Q_r(d +- 1) + P1, P2) is element-wise --

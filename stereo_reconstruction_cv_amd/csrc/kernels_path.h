@@ -18,6 +18,7 @@
 // a block of steps ahead into registers.
 #pragma once
 #include "kernels_cost.h"
+#include <type_traits>
 
 namespace sgm {
 
@@ -462,6 +463,82 @@ __global__ __launch_bounds__(64) void k_path(Geom g, int rx, int ry, const int16
             compute_slow(cB, sB, s0 + PB);
         }
     }
+    if (g.hr && lane == 0) headroom_raise(g.hr + 1, hm);
+}
+
+// ------------------------------------------------------------------------------------------
+// Boundary pre-pass of the axis-only sweeps (k_axis_sweep, MODE_HH4): only the vertical path crosses rows, and a column
+// depends on no other column.  One wave per column walks the rows in sweep order (ydir) and stores the normalised state
+// of the last row of every band to the record of the band below, bnd [band][x][1][D]; it stops at the last boundary
+// (the rows of the last band are nobody's predecessor).  Reads C once, no chunks, no state between launches.
+template <int NP, bool PARTIAL>
+__global__ __launch_bounds__(64) void k_axis_prepass(Geom g, int ydir, const int16_t *__restrict__ C, int16_t *__restrict__ bnd,
+                                                     int R, int nbands)
+{
+    constexpr int PB = 8;  // rows per prefetch block (two blocks in flight)
+    const int lane = threadIdx.x;
+    const int x = blockIdx.x;
+    const int W1 = g.W1, D = g.D, H = g.H;
+    if (x >= W1) return;
+    const int nsteps = min((nbands - 1) * R, H);
+    const bool active = !PARTIAL || (2 * NP * lane < D);
+    const int lane_off = active ? 2 * NP * lane : 0;
+    const int voff = lane_off * 2;
+    const int so = x * D * 2;
+    const uint32_t P1s = splat16((uint32_t)g.P1), P2s = splat16((uint32_t)g.P2);
+    const uint32_t init = active ? 0u : SGM_SENT;
+    Pack<NP> L;
+    L.fill(init);
+    ShiftRegs sr;
+    Pack<NP> cA[PB], cB[PB];
+    uint32_t hm = 0;
+    int to_boundary = R - 1, next_band = 1;
+    auto row_of = [&](int s) { return ydir > 0 ? s : H - 1 - s; };
+    auto load_t = [&](auto full_c, Pack<NP> *cb, int s0) {
+        constexpr bool FULL = decltype(full_c)::value;
+#pragma unroll
+        for (int k = 0; k < PB; k++)
+            if (FULL || s0 + k < nsteps) buf_load<NP>(cb[k], row_rsrc(C, row_of(s0 + k), W1, D), voff, so);
+    };
+    auto compute_t = [&](auto full_c, const Pack<NP> *cb, int s0) {
+        constexpr bool FULL = decltype(full_c)::value;
+#pragma unroll
+        for (int k = 0; k < PB; k++) {
+            if (FULL || s0 + k < nsteps) {
+                Pack<NP> Ln, Lnorm;
+                uint32_t rmin;
+                path_elem<NP, PARTIAL>(cb[k], L, P1s, P2s, active, Ln, rmin, sr);
+                const uint32_t mLs = wave_min1_splat(rmin);
+                hm = max(hm, mLs & 0xffffu);
+                path_normalise_splat<NP, PARTIAL>(Ln, mLs, active, Lnorm);
+                if (to_boundary == 0) {  // last row of a band: the state the first row of the next band starts from
+                    if (active && next_band < nbands) buf_store<NP>(Lnorm, row_rsrc(bnd, next_band, W1, D), voff, so);
+                    to_boundary = R;
+                    next_band++;
+                }
+                to_boundary--;
+                L = Lnorm;
+            }
+        }
+    };
+    const std::true_type full{};
+    const std::false_type part{};
+    if (PB <= nsteps) load_t(full, cA, 0);
+    else load_t(part, cA, 0);
+    int s0 = 0;
+    for (; s0 + 3 * PB <= nsteps; s0 += 2 * PB) {
+        load_t(full, cB, s0 + PB);
+        compute_t(full, cA, s0);
+        load_t(full, cA, s0 + 2 * PB);
+        compute_t(full, cB, s0 + PB);
+    }
+    for (; s0 < nsteps; s0 += 2 * PB) {
+        load_t(part, cB, s0 + PB);
+        compute_t(part, cA, s0);
+        load_t(part, cA, s0 + 2 * PB);
+        compute_t(part, cB, s0 + PB);
+    }
+    // (the sweep raises the record for every pixel of these rows as well; this keeps the pre-pass self-contained)
     if (g.hr && lane == 0) headroom_raise(g.hr + 1, hm);
 }
 

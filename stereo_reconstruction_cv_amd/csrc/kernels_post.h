@@ -100,22 +100,23 @@ __global__ __launch_bounds__(256) void k_add_sat(int16_t *__restrict__ S, const 
 // NV: the costs are the saturating sum of NV volumes.  2: S + S2 (MODE_SGBM with D <= 128: the fifth path runs
 // beside the sweep into a volume of its own); 3: S + S2 + S3 (D <= 64: both in-row paths run beside the per-row
 // pre-pass and the element-wise vertical kernel, each into a volume of its own); 5: the five directions of MODE_SGBM each
-// in a volume of its own (D <= 64: k_lines3_g + the two in-row paths).  Every path cost is >= 0 and the
+// in a volume of its own (D <= 64: k_lines3_g + the two in-row paths); 4: the four axis-aligned directions of MODE_HH4
+// (D <= 64: k_axis_paths4_g).  Every path cost is >= 0 and the
 // sum saturates, so the order of the additions does not matter -- kernels_path.h.
 template <bool POSW, int LG, int NV = 1>
 __global__ __launch_bounds__(64) void k_wta_t(Geom g, const int16_t *__restrict__ S, uint2 *__restrict__ wta, int64_t npix,
                                               const int16_t *__restrict__ S2 = nullptr, const int16_t *__restrict__ S3 = nullptr,
                                               const int16_t *__restrict__ S4 = nullptr, const int16_t *__restrict__ S5 = nullptr)
 {
-    constexpr bool TWO = NV >= 2, THREE = NV >= 3, FIVE = NV >= 5;
-    static_assert(NV == 1 || NV == 2 || NV == 3 || NV == 5, "volumes: 1, 2, 3 or 5");
+    constexpr bool TWO = NV >= 2, THREE = NV >= 3, FOUR = NV >= 4, FIVE = NV >= 5;
+    static_assert(NV >= 1 && NV <= 5, "volumes: 1 .. 5");
     extern __shared__ __attribute__((aligned(16))) uint8_t rows[];
     const int lane = threadIdx.x, D = LG >= 0 ? (8 << LG) : g.D, W1 = g.W1;
     const int stride = wta_t_stride(D);
     const int cpr = D * 2 / 16;  // 16-byte chunks per pixel row; a lane moves cpr chunks per block
     const int64_t nblocks = (npix + 63) / 64;
     constexpr int PF = LG < 0 ? 8 : (LG >= 5 ? 32 : (1 << LG));  // chunks per lane held in registers
-    uint4 v[PF], v2[TWO ? PF : 1], v3[THREE ? PF : 1], v4[FIVE ? PF : 1], v5[FIVE ? PF : 1];
+    uint4 v[PF], v2[TWO ? PF : 1], v3[THREE ? PF : 1], v4[FOUR ? PF : 1], v5[FIVE ? PF : 1];
     // chunk c = lane + 64 k of the block's contiguous 64 * D * 2 bytes: loads with a clamped index
     // (no branch between them), committed to the padded LDS rows afterwards
     auto issue = [&](int64_t blk, int k0) {
@@ -133,6 +134,11 @@ __global__ __launch_bounds__(64) void k_wta_t(Geom g, const int16_t *__restrict_
             const uint4 *src3 = reinterpret_cast<const uint4 *>(S3 + blk * 64 * D);
 #pragma unroll
             for (int u = 0; u < PF; u++) v3[u] = src3[min(lane + 64 * (k0 + u), total - 1)];
+        }
+        if constexpr (FOUR && !FIVE) {
+            const uint4 *src4 = reinterpret_cast<const uint4 *>(S4 + blk * 64 * D);
+#pragma unroll
+            for (int u = 0; u < PF; u++) v4[u] = src4[min(lane + 64 * (k0 + u), total - 1)];
         }
         if constexpr (FIVE) {
             const uint4 *src4 = reinterpret_cast<const uint4 *>(S4 + blk * 64 * D);
@@ -156,6 +162,12 @@ __global__ __launch_bounds__(64) void k_wta_t(Geom g, const int16_t *__restrict_
             r.y = pk_adds_s(r.y, v3[u].y);
             r.z = pk_adds_s(r.z, v3[u].z);
             r.w = pk_adds_s(r.w, v3[u].w);
+        }
+        if constexpr (FOUR && !FIVE) {
+            r.x = pk_adds_s(r.x, v4[u].x);
+            r.y = pk_adds_s(r.y, v4[u].y);
+            r.z = pk_adds_s(r.z, v4[u].z);
+            r.w = pk_adds_s(r.w, v4[u].w);
         }
         if constexpr (FIVE) {
             r.x = pk_adds_s(pk_adds_s(r.x, v4[u].x), v5[u].x);

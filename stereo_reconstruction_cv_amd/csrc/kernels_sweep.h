@@ -32,7 +32,7 @@ struct SweepArgs {
     int R;           // rows per band = compute waves per workgroup
     const int16_t *C;
     int16_t *S;
-    const int16_t *bndL;  // [band][x][3 roles][D], normalised
+    const int16_t *bndL;  // [band][x][3 roles][D], normalised (axis-only sweeps: [band][x][1][D])
     uint2 *wta;
     int keepS;
     int dbg;  // timing experiments only (results become wrong): 64 = loader wave skips its HBM loads
@@ -51,7 +51,7 @@ struct ChainFrames {
     int nf;
     const int16_t *C[CHAIN_MAX_FRAMES];
     int16_t *S[CHAIN_MAX_FRAMES];
-    int16_t *bnd[CHAIN_MAX_FRAMES];   // hand-off record [band][x][3][D] of each frame
+    int16_t *bnd[CHAIN_MAX_FRAMES];   // hand-off record [band][x][3][D] of each frame ([band][x][1][D]: k_axis_chain)
     uint32_t *hr[CHAIN_MAX_FRAMES];   // headroom record of each frame
 };
 
@@ -62,10 +62,12 @@ __host__ __device__ constexpr int sweep_pps(int NP) { return NP == 4 ? 1 : (NP =
 // pixels of hand-off state kept per producer: consumers run 2 steps behind their producer
 __host__ __device__ constexpr int sweep_ring(int NP) { return 4 * sweep_pps(NP); }
 
-__host__ __device__ constexpr int sweep_slot_dwords(int NP) { return 192 * NP; }
-static inline size_t sweep_lds_bytes(int NP, int R)
+// NR = roles a row hands to the row below: 3 (the paths from x - 1, x, x + 1 of the row above), or 1 in the axis-only
+// form (MODE_HH4: only the vertical path crosses rows)
+__host__ __device__ constexpr int sweep_slot_dwords(int NP, int NR = 3) { return 64 * NR * NP; }
+static inline size_t sweep_lds_bytes(int NP, int R, int NR = 3)
 {
-    return (size_t)(R + 1) * sweep_ring(NP) * sweep_slot_dwords(NP) * 4;
+    return (size_t)(R + 1) * sweep_ring(NP) * sweep_slot_dwords(NP, NR) * 4;
 }
 
 __device__ __forceinline__ void wg_barrier()
@@ -102,14 +104,14 @@ __device__ __forceinline__ void lds_store(const Pack<NP> &p, uint32_t *dst)
 // exactly 1 + T workgroup barriers per band, T = ceil(W1 / PPS) + 2 (R - 1): barrier 0 closes the
 // prologue, barrier 1 + t closes lockstep step t.
 
-template <int NP>
+template <int NP, int NR = 3>
 __device__ __forceinline__ void sweep_write_start_state(uint32_t *ring, int slot, uint32_t init)
 {
-    constexpr int SLOT = sweep_slot_dwords(NP), ROLE = 64 * NP;
+    constexpr int SLOT = sweep_slot_dwords(NP, NR), ROLE = 64 * NP;
     Pack<NP> v;
     v.fill(init);
 #pragma unroll
-    for (int d = 0; d < 3; d++) lds_store<NP>(v, ring + slot * SLOT + d * ROLE);
+    for (int d = 0; d < NR; d++) lds_store<NP>(v, ring + slot * SLOT + d * ROLE);
 }
 
 // Chained schedule: progress word of the band above (number of pixels of its last row, in sweep order,
@@ -174,7 +176,7 @@ struct ChainWait {
 #ifndef SGM_CHAIN_HALF_BLOCKS
 #define SGM_CHAIN_HALF_BLOCKS 0
 #endif
-template <int NP, bool PARTIAL, bool CHAIN>
+template <int NP, bool PARTIAL, bool CHAIN, int NR = 3>
 __device__ __forceinline__ void sweep_loader_wave(const Geom &g, const SweepArgs &a, int band, int lane, uint32_t *lds)
 {
     // plain schedule: every byte is used once -> "nt"; chained: the record was written by another CU a
@@ -187,7 +189,7 @@ __device__ __forceinline__ void sweep_loader_wave(const Geom &g, const SweepArgs
     // buffers: bA holds the blocks that start at multiples of 2 LB, bB the others
     constexpr int OFF_A = 0, OFF_B = LB % RING;
     static_assert(2 * PPS <= LB && LB % PPS == 0 && RING % LB == 0, "prologue writes 2 * PPS pixels of block 0");
-    constexpr int SLOT = sweep_slot_dwords(NP);
+    constexpr int SLOT = sweep_slot_dwords(NP, NR);
     constexpr int ROLE = 64 * NP;  // dwords per role inside a slot
     const int R = a.R;
     const int W1 = g.W1, D = g.D;
@@ -198,13 +200,13 @@ __device__ __forceinline__ void sweep_loader_wave(const Geom &g, const SweepArgs
     uint32_t *const ring0 = lds + lane * NP;
 
     const bool has_prev = band > 0 && !(a.dbg & 64);
-    Pack<NP> bA[LB][3], bB[LB][3];
-    // this band's boundary row as a buffer resource: [x][3 roles][D] int16
-    const int row_bytes = W1 * 3 * D * 2;
+    Pack<NP> bA[LB][NR], bB[LB][NR];
+    // this band's boundary row as a buffer resource: [x][NR roles][D] int16
+    const int row_bytes = W1 * NR * D * 2;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(a.bndL + (int64_t)band * W1 * 3 * D), 0, row_bytes, 0x00020000);
+        (void *)(a.bndL + (int64_t)band * W1 * NR * D), 0, row_bytes, 0x00020000);
     const int voff = lane_off * 2;
-    const int px_bytes = 3 * D * 2;
+    const int px_bytes = NR * D * 2;
     const int pk = a.xdir > 0 ? px_bytes : -px_bytes;           // byte step per pixel of the sweep order
     const int p0 = a.xdir > 0 ? 0 : (W1 - 1) * px_bytes;
     ChainWait cw;
@@ -215,7 +217,7 @@ __device__ __forceinline__ void sweep_loader_wave(const Geom &g, const SweepArgs
     // FULL = every pixel of the block exists: no guards, so hipcc can count the loads in flight
     // (with a branch between issue and use it falls back to vmcnt(0) and the whole lockstep
     // workgroup waits for HBM latency every block)
-    auto lb_t = [&](auto full_c, Pack<NP>(*b)[3], int k0) {
+    auto lb_t = [&](auto full_c, Pack<NP>(*b)[NR], int k0) {
         constexpr bool FULL = decltype(full_c)::value;
         if (CHAIN) cw.step((uint32_t)min(k0 + LB, W1));  // (a block past the row's end waits for nothing new)
 #pragma unroll
@@ -223,16 +225,16 @@ __device__ __forceinline__ void sweep_loader_wave(const Geom &g, const SweepArgs
             if (FULL || k0 + u < W1) {
                 const int so = p0 + (k0 + u) * pk;
 #pragma unroll
-                for (int d = 0; d < 3; d++) buf_load<NP, LDAUX>(b[u][d], rsrc, voff, so + d * D * 2);
+                for (int d = 0; d < NR; d++) buf_load<NP, LDAUX>(b[u][d], rsrc, voff, so + d * D * 2);
             }
         }
     };
-    auto wb_t = [&](auto full_c, Pack<NP>(*b)[3], int off, int u, int k) {  // pixel k = u-th of its block, ring slot off + u
+    auto wb_t = [&](auto full_c, Pack<NP>(*b)[NR], int off, int u, int k) {  // pixel k = u-th of its block, ring slot off + u
         constexpr bool FULL = decltype(full_c)::value;
         if (!FULL && k > W1) return;
         uint32_t *slot = ring0 + (off + u) * SLOT;
 #pragma unroll
-        for (int d = 0; d < 3; d++) {
+        for (int d = 0; d < NR; d++) {
             Pack<NP> v;
             if (FULL || k < W1) {
                 v = b[u][d];
@@ -247,12 +249,12 @@ __device__ __forceinline__ void sweep_loader_wave(const Geom &g, const SweepArgs
     if (!has_prev) {
         // first band of the sweep: the row above is the all-zero start state everywhere
 #pragma unroll
-        for (int u = 0; u < RING; u++) sweep_write_start_state<NP>(ring0, u, init);
+        for (int u = 0; u < RING; u++) sweep_write_start_state<NP, NR>(ring0, u, init);
         wg_barrier();
         for (; t < T; t++) wg_barrier();
         return;
     }
-    sweep_write_start_state<NP>(ring0, RING - 1, init);
+    sweep_write_start_state<NP, NR>(ring0, RING - 1, init);
     const std::true_type full{};
     const std::false_type part{};
     // prologue: pixels 0 .. 2*PPS-1, then the rest of block 0
@@ -330,14 +332,16 @@ __device__ __forceinline__ void sweep_loader_wave(const Geom &g, const SweepArgs
 }
 
 // ==== compute wave: one image row ======================================================================
-template <int NP, bool PARTIAL, int MODE, bool POSW>
+// NR = 1 (axis-only form, MODE_HH4): per pixel the in-row path and role B only -- two recurrences, their minima reduced
+// together (wave_min2_splat), one role handed to the row below; same path_elem / path_normalise_splat, same lockstep.
+template <int NP, bool PARTIAL, int MODE, bool POSW, int NR = 3>
 __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArgs &a, int band, int wave, int lane, uint32_t *lds)
 {
     constexpr int LDAUX = SGM_NT_SWEEP_LOADS ? 2 : 0;  // "nt": every byte the sweep loads is used once
     constexpr int PPS = sweep_pps(NP);
     constexpr int RING = sweep_ring(NP);
     constexpr int PB = RING;
-    constexpr int SLOT = sweep_slot_dwords(NP);
+    constexpr int SLOT = sweep_slot_dwords(NP, NR);
     constexpr int ROLE = 64 * NP;
     const int R = a.R;
     const int W1 = g.W1, D = g.D, H = g.H;
@@ -356,7 +360,7 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
     // slot RING-1 (written before the prologue barrier, not reused until pixel RING-1 exists) and
     // "pixel W1" is written by each producer one step after its last real pixel.  The per-pixel
     // code therefore needs no border branches.
-    sweep_write_start_state<NP>(mine, RING - 1, init);
+    sweep_write_start_state<NP, NR>(mine, RING - 1, init);
     wg_barrier();  // prologue barrier
     if (j >= H) {  // row past the image (last band): keep the barrier count, do nothing
         for (int t = 0; t < T; t++) wg_barrier();
@@ -461,6 +465,32 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
         if (!PARTIAL || active) buf_store<NP>(Sn, Sst, vo, so);
         return Sn;
     };
+    // one pixel of the axis-only form: the in-row path and role B
+    auto pixel_axis = [&](const Pack<NP> &Cp, const Pack<NP> &Sp, const Pack<NP> &QB, int u, int vo, int so) {
+        Pack<NP> N0, NB;
+        uint32_t r0, rB;
+        path_elem<NP, PARTIAL>(Cp, L0, P1s, P2s, active, N0, r0, sr0);
+        path_elem<NP, PARTIAL>(Cp, QB, P1s, P2s, active, NB, rB, srB);
+        uint32_t ms[2];  // {m, m} of the directions 0, B
+        uint32_t rows;
+        wave_min2_splat(r0, rB, ms, rows);
+        hm = max(hm, rows);
+        Pack<NP> LB;
+        path_normalise_splat<NP, PARTIAL>(N0, ms[0], active, L0);
+        path_normalise_splat<NP, PARTIAL>(NB, ms[1], active, LB);
+        lds_store<NP>(LB, mine + u * SLOT);
+        Pack<NP> Sn;
+#pragma unroll
+        for (int i = 0; i < NP; i++) {
+            uint32_t v = pk_adds_s(N0.r[i], NB.r[i]);
+            if (READS_S) v = pk_adds_s(v, Sp.r[i]);
+            Sn.r[i] = v;
+        }
+        if (!PARTIAL || active) buf_store<NP>(Sn, Sst, vo, so);
+        return Sn;
+    };
+    (void)pixel;  // (an instantiation uses one of the two)
+    (void)pixel_axis;
 
     auto compute_block_t = [&](auto full_c, Pack<NP> *cb, Pack<NP> *sb, int k0) {  // k0 % PB == 0
         constexpr bool FULL = decltype(full_c)::value;
@@ -473,15 +503,24 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
 #pragma unroll
                 for (int p = 0; p < PPS; p++) {
                     const int u = u0 + p;
-                    lds_load<NP>(QA[p], prev + ((u + RING - 1) % RING) * SLOT + 0 * ROLE);
-                    lds_load<NP>(QB[p], prev + u * SLOT + 1 * ROLE);
-                    lds_load<NP>(QC[p], prev + ((u + 1) % RING) * SLOT + 2 * ROLE);
+                    if constexpr (NR == 1) {
+                        lds_load<NP>(QB[p], prev + u * SLOT);
+                    } else {
+                        lds_load<NP>(QA[p], prev + ((u + RING - 1) % RING) * SLOT + 0 * ROLE);
+                        lds_load<NP>(QB[p], prev + u * SLOT + 1 * ROLE);
+                        lds_load<NP>(QC[p], prev + ((u + 1) % RING) * SLOT + 2 * ROLE);
+                    }
                 }
 #pragma unroll
                 for (int p = 0; p < PPS; p++) {
                     const int u = u0 + p;
-                    if constexpr (FULL && IMM) Sn[p] = pixel(cb[u], sb[u], QA[p], QB[p], QC[p], u, voff + px_imm(u), sbase);
-                    else if (FULL || k0 + u < W1) Sn[p] = pixel(cb[u], sb[u], QA[p], QB[p], QC[p], u, voff, b0 + (k0 + u) * bk);
+                    if constexpr (NR == 1) {
+                        if constexpr (FULL && IMM) Sn[p] = pixel_axis(cb[u], sb[u], QB[p], u, voff + px_imm(u), sbase);
+                        else if (FULL || k0 + u < W1) Sn[p] = pixel_axis(cb[u], sb[u], QB[p], u, voff, b0 + (k0 + u) * bk);
+                    } else {
+                        if constexpr (FULL && IMM) Sn[p] = pixel(cb[u], sb[u], QA[p], QB[p], QC[p], u, voff + px_imm(u), sbase);
+                        else if (FULL || k0 + u < W1) Sn[p] = pixel(cb[u], sb[u], QA[p], QB[p], QC[p], u, voff, b0 + (k0 + u) * bk);
+                    }
                 }
                 if (MODE == SWEEP_LAST) {  // winner-take-all of the step's pixels, chains interleaved
                     if (FULL || k0 + u0 + PPS <= W1) {
@@ -527,7 +566,7 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
     }
     // one step after the last real pixel: the virtual pixel W1 (start state) for the row below
     if (wave < R - 1) {
-        sweep_write_start_state<NP>(mine, W1 % RING, init);
+        sweep_write_start_state<NP, NR>(mine, W1 % RING, init);
         for (int i = 0; i < 2 * (R - 1 - wave); i++) wg_barrier();
     }
 }
@@ -575,14 +614,14 @@ __global__ __launch_bounds__(SWEEP_MAX_ROWS * 64 + 64) void k_sweep(Geom g, Swee
 #endif
 constexpr int CHAIN_KD = SGM_CHAIN_KD;  // a store is taken to be complete when the stores of KD later steps have been issued *and counted*: see chain_publisher_wave
 
-template <int NP, bool PARTIAL>
+template <int NP, bool PARTIAL, int NR = 3>
 __device__ __forceinline__ void chain_publisher_wave(const Geom &g, const SweepArgs &a, int band, int lane, uint32_t *lds)
 {
     constexpr int PPS = sweep_pps(NP);
     constexpr int RING = sweep_ring(NP);
-    constexpr int SLOT = sweep_slot_dwords(NP);
+    constexpr int SLOT = sweep_slot_dwords(NP, NR);
     constexpr int ROLE = 64 * NP;
-    constexpr int STORES_PER_STEP = 3 * PPS * (NP == 4 ? 2 : 1) + 1;  // buf_store<4> = two 64-bit stores; + the progress word
+    constexpr int STORES_PER_STEP = NR * PPS * (NP == 4 ? 2 : 1) + 1;  // buf_store<4> = two 64-bit stores; + the progress word
     static_assert(CHAIN_KD * STORES_PER_STEP <= 63, "vmcnt is a 6-bit counter");
     const int R = a.R;
     const int W1 = g.W1, D = g.D;
@@ -593,11 +632,11 @@ __device__ __forceinline__ void chain_publisher_wave(const Geom &g, const SweepA
     const bool publishes = band + 1 < a.nbands;  // the last band of the sweep has nobody below it
     // ring R: written by compute wave R - 1 (its `mine`)
     const uint32_t *const last = lds + lane * NP + R * RING * SLOT;
-    const int row_bytes = W1 * 3 * D * 2;
+    const int row_bytes = W1 * NR * D * 2;
     const __amdgpu_buffer_rsrc_t rec = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(a.bndL + (int64_t)(band + 1) * W1 * 3 * D), 0, row_bytes, 0x00020000);
+        (void *)(a.bndL + (int64_t)(band + 1) * W1 * NR * D), 0, row_bytes, 0x00020000);
     const int voff = lane_off * 2;
-    const int px_bytes = 3 * D * 2;
+    const int px_bytes = NR * D * 2;
     const int pk = a.xdir > 0 ? px_bytes : -px_bytes;
     const int p0 = a.xdir > 0 ? 0 : (W1 - 1) * px_bytes;
     uint32_t *const word = a.prog + band;
@@ -616,13 +655,13 @@ __device__ __forceinline__ void chain_publisher_wave(const Geom &g, const SweepA
             for (int p = 0; p < PPS; p++) {
                 const int k = PPS * i + p;
                 const uint32_t *s = last + (k % RING) * SLOT;
-                Pack<NP> v[3];
+                Pack<NP> v[NR];
 #pragma unroll
-                for (int d = 0; d < 3; d++) lds_load<NP>(v[d], s + d * ROLE);
+                for (int d = 0; d < NR; d++) lds_load<NP>(v[d], s + d * ROLE);
                 // (a pixel past the row's end: offset past the record, the store is dropped but counted)
                 const int so = k < W1 ? p0 + k * pk : row_bytes;
 #pragma unroll
-                for (int d = 0; d < 3; d++)
+                for (int d = 0; d < NR; d++)
                     if (!PARTIAL || active) buf_store<NP, 16>(v[d], rec, voff, so + d * D * 2);
             }
         } else {
@@ -630,7 +669,7 @@ __device__ __forceinline__ void chain_publisher_wave(const Geom &g, const SweepA
             Pack<NP> z;
             z.fill(0u);
 #pragma unroll
-            for (int p = 0; p < 3 * PPS; p++)
+            for (int p = 0; p < NR * PPS; p++)
                 if (!PARTIAL || active) buf_store<NP, 16>(z, rec, voff, row_bytes);
         }
         // all stores but those of the last KD intervals (this one included) are complete
@@ -669,6 +708,49 @@ __global__ __launch_bounds__(CHAIN_MAX_ROWS * 64 + 128) void k_sweep_chain(Geom 
         if (wave == a.R) sweep_loader_wave<NP, PARTIAL, true>(g, a, band, lane, lds);
         else if (wave == a.R + 1) chain_publisher_wave<NP, PARTIAL>(g, a, band, lane, lds);
         else sweep_compute_wave<NP, PARTIAL, MODE, true>(g, a, band, wave, lane, lds);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Axis-only sweeps (MODE_HH4 = the MODE_HH pipeline over the path set {(1,0), (-1,0), (0,1), (0,-1)}): the waves of
+// k_sweep / k_sweep_chain with NR = 1.  Only the vertical path crosses rows and its predecessor is in the same column,
+// so a pixel is two recurrences instead of four, a ring slot and a pixel of the band record [band][x][1][D] hold one
+// role instead of three.  Barrier counts, lockstep distance, ChainWait and the err word are those of the 4-direction
+// kernels.  Both passes leave the winner-take-all to k_wta_t (SWEEP_FIRST, SWEEP_ACCUM only).
+template <int NP, bool PARTIAL, int MODE>
+__global__ __launch_bounds__(SWEEP_MAX_ROWS * 64 + 64) void k_axis_sweep(Geom g, SweepArgs a)
+{
+    static_assert(MODE == SWEEP_FIRST || MODE == SWEEP_ACCUM, "the axis-only sweeps have no fused winner-take-all");
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int band = blockIdx.x;
+    if (wave == a.R) sweep_loader_wave<NP, PARTIAL, false, 1>(g, a, band, lane, lds);
+    else sweep_compute_wave<NP, PARTIAL, MODE, true, 1>(g, a, band, wave, lane, lds);
+}
+
+template <int NP, bool PARTIAL, int MODE>
+__global__ __launch_bounds__(CHAIN_MAX_ROWS * 64 + 128) void k_axis_chain(Geom g, SweepArgs a, ChainFrames fr)
+{
+    static_assert(MODE == SWEEP_FIRST || MODE == SWEEP_ACCUM, "the axis-only sweeps have no fused winner-take-all");
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    uint32_t *const ticket = lds + (a.R + 1) * sweep_ring(NP) * sweep_slot_dwords(NP, 1);  // one word behind the rings
+    for (;;) {
+        if (threadIdx.x == 0) *ticket = atomicAdd(a.ctl, 1u);
+        wg_barrier();
+        const int tk = __builtin_amdgcn_readfirstlane((int)*ticket);
+        if (tk >= a.nbands * fr.nf) break;
+        const int f = tk % fr.nf, band = tk / fr.nf;
+        a.C = fr.C[f];
+        a.S = fr.S[f];
+        a.bndL = fr.bnd[f];
+        a.prog = a.ctl + 1 + f * a.nbands;
+        g.hr = fr.hr[f];
+        if (wave == a.R) sweep_loader_wave<NP, PARTIAL, true, 1>(g, a, band, lane, lds);
+        else if (wave == a.R + 1) chain_publisher_wave<NP, PARTIAL, 1>(g, a, band, lane, lds);
+        else sweep_compute_wave<NP, PARTIAL, MODE, true, 1>(g, a, band, wave, lane, lds);
     }
 }
 

@@ -127,6 +127,17 @@ __device__ __forceinline__ void wave_min4_splat(uint32_t r0, uint32_t r1, uint32
     ms[1] = __builtin_amdgcn_readlane(x, 32);
     ms[3] = __builtin_amdgcn_readlane(x, 48);
 }
+// two directions (the axis-only sweep: in-row path and vertical path).  After the half swap lanes 0-31 hold direction
+// 0 and lanes 32-63 direction 1; a row swap of that register with itself folds rows 0 / 1 and 2 / 3, so EVERY lane of
+// `rows` holds the splat of its direction (rows 0-1: direction 0, rows 2-3: direction 1).
+__device__ __forceinline__ void wave_min2_splat(uint32_t r0, uint32_t r1, uint32_t (&ms)[2], uint32_t &rows)
+{
+    const uint32_t z = fold32_pair(r0, r1);
+    const uint32_t x = row_min_eq(fold_halves(fold16_pair(z, z)));
+    rows = x;
+    ms[0] = __builtin_amdgcn_readlane(x, 0);
+    ms[1] = __builtin_amdgcn_readlane(x, 32);
+}
 __device__ __forceinline__ void wave_min3_splat(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t (&ms)[3])
 {
     // rows: direction 0, rows 0-1 of direction 2, direction 1, rows 2-3 of direction 2

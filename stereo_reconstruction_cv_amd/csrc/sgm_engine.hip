@@ -197,6 +197,8 @@ struct Plan {
     bool rows4;            // small-D schedule (D <= 64 outside throughput mode, D <= 32 always)
     bool chain;            // chained sweeps (schedule 2)
     int npass, R, nbands;
+    bool axis;             // MODE_HH4: the path set is the four axis-aligned directions -- two passes of the axis-only kernels
+    int nroles;            // roles per pixel of the band record: 3, or 1 (axis)
     bool prepass_g;        // pre-pass: lane-grouped lines (k_prepass3_g), or three roles per wave (k_prepass3) in pre_nch
     bool fused_prepass;    // chunks of pre_rows rows (pre_plain: the plain layout), or the single-direction kernel
     bool pre_plain;
@@ -204,7 +206,8 @@ struct Plan {
     bool overlap, fork_early;  // MODE_HH: upward pre-pass on the auxiliary stream; forked right after the cost stage
     // winner-take-all
     bool fused_wta;        // inside the last path kernel (else k_wta_t)
-    int nvol;              // volumes k_wta_t adds up: 1 (S), 2 (+ the fifth path's), 3 (+ the other in-row path's), 5 (k_paths5_g)
+    int nvol;              // volumes k_wta_t adds up: 1 (S), 2 (+ the fifth path's), 3 (+ the other in-row path's), 5 (k_paths5_g),
+                           // 4 (k_axis_paths4_g: MODE_HH4 in the small-D schedule)
     bool path_w_main, path_w_lines;  // MODE_SGBM's fifth path on the main stream behind the sweeps; as the general line kernel
     bool speckle;          // the speckle filter runs
 };
@@ -284,8 +287,8 @@ struct sgm_engine {
 static int normalise(const sgm_params *p, int H, int W, Geom *g)
 {
     if (p->numDisparities <= 0) return set_err(SGM_ERR_INVALID_ARG, "numDisparities must be > 0");
-    if (p->mode != 0 && p->mode != 1)
-        return set_err(SGM_ERR_UNSUPPORTED, "mode %d: only MODE_SGBM (0) and MODE_HH (1) are built; the reference never selects 3WAY/HH4", p->mode);
+    if (p->mode != 0 && p->mode != 1 && p->mode != 3)
+        return set_err(SGM_ERR_UNSUPPORTED, "mode %d: MODE_SGBM (0), MODE_HH (1) and MODE_HH4 (3) are built; MODE_SGBM_3WAY (2) is not", p->mode);
     if (p->numDisparities % 16 != 0)
         return set_err(SGM_ERR_UNSUPPORTED, "numDisparities=%d must be divisible by 16 (OpenCV's documented contract)", p->numDisparities);
     if (p->numDisparities > 512) return set_err(SGM_ERR_UNSUPPORTED, "numDisparities=%d > 512", p->numDisparities);
@@ -500,6 +503,23 @@ static int launch_sweep_np(const Geom &g, const SweepArgs &a, int mode, int nban
     if (g.uniq < 100) return launch_sweep_one<NP, PARTIAL, SWEEP_LAST, true>(g, a, nbands, st);
     return launch_sweep_one<NP, PARTIAL, SWEEP_LAST, false>(g, a, nbands, st);
 }
+// axis-only sweeps (MODE_HH4; kernels_sweep.h: k_axis_sweep, k_axis_chain): one role in the rings and in the record
+template <int NP, bool PARTIAL, int MODE>
+static int launch_axis_sweep_one(const Geom &g, const SweepArgs &a, int nbands, hipStream_t st)
+{
+    const size_t lds = sweep_lds_bytes(NP, a.R, 1);
+    HIP_TRY(hipFuncSetAttribute((const void *)k_axis_sweep<NP, PARTIAL, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_axis_sweep<NP, PARTIAL, MODE>), dim3(nbands), dim3((a.R + 1) * 64), lds, st, g, a);
+    return SGM_OK;
+}
+template <int NP, bool PARTIAL, int MODE>
+static int launch_axis_chain_one(const Geom &g, const SweepArgs &a, const ChainFrames &fr, int wgs, hipStream_t st)
+{
+    const size_t lds = sweep_lds_bytes(NP, a.R, 1) + 16;  // + the ticket word
+    HIP_TRY(hipFuncSetAttribute((const void *)k_axis_chain<NP, PARTIAL, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_axis_chain<NP, PARTIAL, MODE>), dim3(wgs), dim3((a.R + 2) * 64), lds, st, g, a, fr);
+    return SGM_OK;
+}
 // the sweep kernels take the direction of the walk from the pass (kernels_sweep.h: XD): the first pass runs top-down and left
 // to right, every other pass the other way round
 static int check_sweep_direction(const SweepArgs &a, int mode)
@@ -508,9 +528,16 @@ static int check_sweep_direction(const SweepArgs &a, int mode)
         return set_err(SGM_ERR_INVALID_ARG, "internal: sweep mode %d with direction (%d, %d)", mode, a.xdir, a.ydir);
     return SGM_OK;
 }
-static int launch_sweep(const Geom &g, const SweepArgs &a, int mode, int nbands, hipStream_t st)
+static int launch_sweep(const Geom &g, const SweepArgs &a, int mode, int nbands, hipStream_t st, bool axis = false)
 {
     if (int rc = check_sweep_direction(a, mode)) return rc;
+    if (axis) {
+        if (mode == SWEEP_LAST) return set_err(SGM_ERR_INVALID_ARG, "internal: the axis-only sweeps have no fused winner-take-all");
+        return with_np(g, [&](auto np, auto part) {
+            return mode == SWEEP_FIRST ? launch_axis_sweep_one<np, part, SWEEP_FIRST>(g, a, nbands, st)
+                                       : launch_axis_sweep_one<np, part, SWEEP_ACCUM>(g, a, nbands, st);
+        });
+    }
     return with_np(g, [&](auto np, auto part) { return launch_sweep_np<np, part>(g, a, mode, nbands, st); });
 }
 
@@ -529,9 +556,14 @@ static int launch_chain_np(const Geom &g, const SweepArgs &a, const ChainFrames 
     if (mode == SWEEP_FIRST) return launch_chain_one<NP, PARTIAL, SWEEP_FIRST>(g, a, fr, wgs, st);
     return launch_chain_one<NP, PARTIAL, SWEEP_ACCUM>(g, a, fr, wgs, st);
 }
-static int launch_chain(const Geom &g, const SweepArgs &a, const ChainFrames &fr, int mode, int wgs, hipStream_t st)
+static int launch_chain(const Geom &g, const SweepArgs &a, const ChainFrames &fr, int mode, int wgs, hipStream_t st, bool axis = false)
 {
     if (int rc = check_sweep_direction(a, mode)) return rc;
+    if (axis)
+        return with_np(g, [&](auto np, auto part) {
+            return mode == SWEEP_FIRST ? launch_axis_chain_one<np, part, SWEEP_FIRST>(g, a, fr, wgs, st)
+                                       : launch_axis_chain_one<np, part, SWEEP_ACCUM>(g, a, fr, wgs, st);
+        });
     return with_np(g, [&](auto np, auto part) { return launch_chain_np<np, part>(g, a, fr, mode, wgs, st); });
 }
 // workgroups of a chained launch over nf frames: a band trails the band above by about 2 (R - 1) + 17 lockstep steps and
@@ -608,7 +640,10 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     // 64 pairs 720p D=64: 0.38 against 0.55 ms per pair); D <= 32 keeps the small-D kernels in every mode.
     p.rows4 = p.GWs <= 32 && e->sweep_rows <= 0 && !(e->schedule == 2 && p.GWs == 32) &&
               (int64_t)H * g.rowsz * 2 * 3 < (int64_t)0xfff00000;
-    p.npass = g.mode == 1 ? 2 : 1;
+    // the path set: MODE_SGBM one pass of 5 directions, MODE_HH two passes of 4, MODE_HH4 two passes of the 2 axis-aligned ones
+    p.axis = g.mode == 3;
+    p.nroles = p.axis ? 1 : 3;
+    p.npass = g.mode == 0 ? 1 : 2;
     // Chained schedule (SGM_OPT_SCHEDULE 2, kernels_sweep.h: k_sweep_chain): no pre-pass; the bands of a sweep hand the
     // state of their last row to each other.  Only where the fused sweep runs (the small-D schedule keeps its own
     // kernels), where there is more than one band, and not with debug 2 (winner-take-all inside the second sweep).
@@ -629,7 +664,8 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     // the three roles fused in one wave (k_prepass3); debug bit 16 selects the 3-launch variant.
     // Row chunks of about 135 rows, one launch each, base columns grouped per XCD: two of the
     // three reads of a C pixel hit L2 (kernels_path.h).  debug 512: one chunk, plain layout (A/B).
-    p.fused_prepass = !p.rows4 && !(dbg & SGM_DBG_PREPASS_3_LAUNCHES) && !narrow && (int64_t)g.rowsz * H < (1ll << 31);
+    // (MODE_HH4 has one pre-pass kernel, k_axis_prepass: a column scan without chunks)
+    p.fused_prepass = !p.axis && !p.rows4 && !(dbg & SGM_DBG_PREPASS_3_LAUNCHES) && !narrow && (int64_t)g.rowsz * H < (1ll << 31);
     p.pre_plain = (dbg & SGM_DBG_PREPASS_ONE_CHUNK) != 0;
     p.pre_nch = p.pre_plain ? 1 : (e->prepass_rows > 0 ? (H + e->prepass_rows - 1) / e->prepass_rows : std::max(1, (H + 67) / 135));
     // multiples of 8 rows (two prefetch blocks): a chunk then ends in straight-line code
@@ -647,8 +683,9 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     // 4K D=256 2.49 ms fused against 2.56 + 0.73; D=128: 2.01 against 1.42 + 0.43, 1080p 0.79 against
     // 0.44 + 0.10).  debug 2 forces the fused form everywhere, debug 2048 the separate one (A/B, cross-check).
     // (The v1 schedule always fuses it into its last path kernel.)
-    p.fused_wta = p.v1 || (!(dbg & SGM_DBG_WTA_SEPARATE) && (((dbg & SGM_DBG_WTA_IN_LAST_PATH) && !p.rows4) ||
-                                                             (g.mode == 0 && ((dbg & SGM_DBG_NO_LANE_GROUPS) || g.D > 128))));
+    // MODE_HH4: always the separate pass (the axis-only sweeps have no SWEEP_LAST form).
+    p.fused_wta = p.v1 || (!p.axis && !(dbg & SGM_DBG_WTA_SEPARATE) && (((dbg & SGM_DBG_WTA_IN_LAST_PATH) && !p.rows4) ||
+                                                                        (g.mode == 0 && ((dbg & SGM_DBG_NO_LANE_GROUPS) || g.D > 128))));
     // MODE_SGBM with the separate winner-take-all (D <= 128): the fifth path (in-row, right to left) needs
     // nothing but C, so it runs on the auxiliary stream from here on, as a FIRST pass into a volume of its
     // own (2 V of traffic instead of the 3 V of "S +="), beside the pre-pass and the sweep -- which at these
@@ -668,6 +705,11 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     // with the in-row paths on streams of their own (A/B; MODE_HH keeps it).
     const bool five_vol = three_vol && !(dbg & SGM_DBG_SMALL_D_RECORD);
     p.nvol = five_vol ? 5 : three_vol ? 3 : two_vol ? 2 : 1;
+    // MODE_HH4 in the small-D schedule: all four directions in one launch, a volume each (k_axis_paths4_g), no record
+    if (p.axis && p.rows4 && !p.v1) {
+        p.nvol = 4;
+        p.overlap = false;
+    }
     // otherwise MODE_SGBM's fifth path follows the sweep on the main stream (S +=, or with the winner-take-all);
     // debug 4 (no lane groups): as the general line kernel (A/B)
     p.path_w_main = !p.v1 && g.mode == 0 && p.nvol == 1;
@@ -732,14 +774,16 @@ static int ensure_plan_buffers(sgm_engine *e, const Plan &p, int H, int W)
     if ((rc = e->disp_med.ensure(npx * 2))) return rc;
     if ((rc = e->headroom.ensure(8))) return rc;
     e->g.hr = (uint32_t *)e->headroom.p;
-    if (g.W1 > 0 && !p.v1 && p.nbands > 1 && p.nvol != 5) {
-        const size_t bnd_bytes = (size_t)p.nbands * g.W1 * 3 * g.D * 2;
+    if (g.W1 > 0 && !p.v1 && p.nbands > 1 && p.nvol < 4) {
+        const size_t bnd_bytes = (size_t)p.nbands * g.W1 * p.nroles * g.D * 2;
         if ((rc = e->bndL.ensure(bnd_bytes))) return rc;
         if (!p.chain) {
             if (p.npass == 2 && (rc = e->bndL2.ensure(bnd_bytes))) return rc;
-            const size_t st_bytes = (size_t)2 * 3 * g.W1 * g.D * 2;  // ping-pong line state between pre-pass chunks
-            if ((rc = e->pstate.ensure(st_bytes))) return rc;
-            if (p.npass == 2 && (rc = e->pstate2.ensure(st_bytes))) return rc;
+            if (!p.axis) {  // (k_axis_prepass carries no state between launches)
+                const size_t st_bytes = (size_t)2 * 3 * g.W1 * g.D * 2;  // ping-pong line state between pre-pass chunks
+                if ((rc = e->pstate.ensure(st_bytes))) return rc;
+                if (p.npass == 2 && (rc = e->pstate2.ensure(st_bytes))) return rc;
+            }
         }
     }
     if (p.speckle && (rc = ensure_speckle_buffers(e, npx))) return rc;
@@ -907,6 +951,12 @@ static int launch_prepass(const sgm_engine *e, const Plan &p, int xdir, int ydir
 {
     const Geom &g = e->g;
     const int16_t *C = (const int16_t *)e->cost.p;
+    if (p.axis) {  // the vertical path alone: one wave per column, record [band][x][1][D]
+        with_np(g, [&](auto np, auto part) {
+            hipLaunchKernelGGL((k_axis_prepass<np, part>), dim3(g.W1), dim3(64), 0, on, g, ydir, C, bl, p.R, p.nbands);
+        });
+        return 1;
+    }
     if (p.prepass_g) {
         // one role per wave (grid.y = 3): these frames have too few lines to fill the SIMDs with
         // three-role waves (4K D=16: 478)
@@ -959,9 +1009,19 @@ static void launch_paths5(const Geom &g, int GW, const int16_t *C, int16_t *cons
     });
 }
 
+// D <= 64, MODE_HH4: the four axis-aligned directions in one launch, one volume each (k_axis_paths4_g)
+static void launch_axis_paths4(const Geom &g, int GW, const int16_t *C, int16_t *const Sv[5], hipStream_t st)
+{
+    const int G = 64 / GW, nr = (g.H + G - 1) / G, nl = (g.W1 + G - 1) / G;
+    dim3 grid(2 * nr + 2 * nl), block(64);
+    with_gw(GW, g.D, [&](auto gw, auto part) {
+        hipLaunchKernelGGL((k_axis_paths4_g<gw, part>), grid, block, 0, st, g, C, Sv[0], Sv[1], Sv[2], Sv[3], nr);
+    });
+}
+
 // ---- winner-take-all launch ------------------------------------------------------------------
 // k_wta_t over S plus NV - 1 more volumes.  LG = log2(D / 8) for the powers of two that have an instantiation (NV = 1:
-// D = 16 .. 512; 2: up to 128; 3, 5: up to 64), -1 (any D) otherwise
+// D = 16 .. 512; 2: up to 128; 3, 4, 5: up to 64), -1 (any D) otherwise
 template <bool POSW, int LG, int NV>
 static int launch_wta_t(const Geom &g, int16_t *const Sv[5], uint2 *wta, int64_t npix, hipStream_t st)
 {
@@ -990,6 +1050,7 @@ static int launch_wta(const Geom &g, int nvol, int16_t *const Sv[5], uint2 *wta,
     auto go = [&](auto posw) {
         constexpr bool POSW = decltype(posw)::value;
         if (nvol == 5) return launch_wta_lg<POSW, 5>(lg, g, Sv, wta, npix, st);
+        if (nvol == 4) return launch_wta_lg<POSW, 4>(lg, g, Sv, wta, npix, st);
         if (nvol == 3) return launch_wta_lg<POSW, 3>(lg, g, Sv, wta, npix, st);
         if (nvol == 2) return launch_wta_lg<POSW, 2>(lg, g, Sv, wta, npix, st);
         return launch_wta_lg<POSW, 1>(lg, g, Sv, wta, npix, st);
@@ -1120,6 +1181,7 @@ static int paths_v1(sgm_engine *e)
     const Geom &g = e->g;
     for (int k = 0; k < 8; k++) {
         if (g.mode == 0 && k >= 3 && k < 6) continue;  // (the upward directions: MODE_HH only)
+        if (g.mode == 3 && dirs[k].rx != 0 && dirs[k].ry != 0) continue;  // (MODE_HH4: no diagonals)
         const int mode = k == 0 ? PATH_FIRST : (k == 7 ? PATH_LAST : PATH_ACCUM);
         int rc = run_stage(e, dirs[k].name, e->stream, [&] {
             launch_path(g, dirs[k].rx, dirs[k].ry, mode, (const int16_t *)e->cost.p, (int16_t *)e->aggr.p, k == 7 ? e->keep_aggr : 0,
@@ -1153,6 +1215,12 @@ static int paths_fused(sgm_engine *e, const Plan &p)
     int16_t *S = (int16_t *)e->aggr.p;
     uint2 *wta = (uint2 *)e->wta.p;
     int rc;
+    if (p.nvol == 4)
+        return run_stage(e, "paths4", st, [&] {
+            int16_t *const Sv[5] = {S, (int16_t *)e->aggr2.p, (int16_t *)e->aggr3.p, (int16_t *)e->aggr4.p, nullptr};
+            launch_axis_paths4(g, p.GWs, C, Sv, st);
+            return 1;
+        });
     if (p.overlap && p.fork_early && (rc = fork_prepass_up(e, p))) return rc;
     for (int pass = 0; pass < p.npass; pass++) {
         const int ydir = pass == 0 ? 1 : -1, xdir = ydir;
@@ -1195,8 +1263,8 @@ static int paths_fused(sgm_engine *e, const Plan &p)
                 // only the in-row direction is a recurrence (k_rows_g, S +=) -- unless it runs on a stream of its own
                 if (p.nvol < 3) launch_rows_grouped(g, g.H, p.GWs, xdir, PATH_ACCUM, C, S, 1, wta, st);
             } else if (p.chain) {
-                if (int r = launch_chain(g, a, fr, pass == 0 ? SWEEP_FIRST : SWEEP_ACCUM, chain_window(g, p.R, p.nbands, 1, e->chain_wgs), st)) return r;
-            } else if (int r = launch_sweep(g, a, pass == 0 ? SWEEP_FIRST : (last ? SWEEP_LAST : SWEEP_ACCUM), p.nbands, st)) {
+                if (int r = launch_chain(g, a, fr, pass == 0 ? SWEEP_FIRST : SWEEP_ACCUM, chain_window(g, p.R, p.nbands, 1, e->chain_wgs), st, p.axis)) return r;
+            } else if (int r = launch_sweep(g, a, pass == 0 ? SWEEP_FIRST : (last ? SWEEP_LAST : SWEEP_ACCUM), p.nbands, st, p.axis)) {
                 return r;
             }
             return 1;
@@ -1233,7 +1301,7 @@ static int stage_wta(sgm_engine *e, const Plan &p)
     const Geom &g = e->g;
     return run_stage(e, "wta", e->stream, [&] {
         int16_t *const Sv[5] = {(int16_t *)e->aggr.p, p.nvol >= 2 ? (int16_t *)e->aggr2.p : nullptr,
-                                p.nvol >= 3 ? (int16_t *)e->aggr3.p : nullptr, p.nvol >= 5 ? (int16_t *)e->aggr4.p : nullptr,
+                                p.nvol >= 3 ? (int16_t *)e->aggr3.p : nullptr, p.nvol >= 4 ? (int16_t *)e->aggr4.p : nullptr,
                                 p.nvol >= 5 ? (int16_t *)e->aggr5.p : nullptr};
         if (int rc = launch_wta(g, p.nvol, Sv, (uint2 *)e->wta.p, e->stream)) return rc;
         if (e->keep_aggr) {  // the volume a caller inspects is the whole sum
@@ -1843,7 +1911,7 @@ static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &p
                               (int16_t *)d_disp_i16[k], PH_PRE)))
             return rc;
         const Plan &q = eng[k]->plan;
-        if (!q.chain || q.R != pl.R || q.nbands != pl.nbands)
+        if (!q.chain || q.R != pl.R || q.nbands != pl.nbands || q.axis != pl.axis)
             return set_err(SGM_ERR_HIP, "internal: a pair of a chained group did not plan the group's chained sweep");
         if (in_used && in_used[k]) HIP_TRY(hipEventRecord(in_used[k], eng[k]->stream));   // (behind the whole cost stage: the images are read by its first kernel only)
     }
@@ -1872,7 +1940,7 @@ static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &p
         HIP_TRY(hipMemsetAsync(e->chain_ctl.p, 0, ctl_bytes, e->stream));
         stage_break(e);
         if ((rc = stage_begin(e, pass == 0 ? "chain_dn" : "chain_up"))) return rc;
-        if ((rc = launch_chain(g, a, fr, pass == 0 ? SWEEP_FIRST : SWEEP_ACCUM, chain_window(g, R, nbands, n, e->chain_wgs), e->stream)))
+        if ((rc = launch_chain(g, a, fr, pass == 0 ? SWEEP_FIRST : SWEEP_ACCUM, chain_window(g, R, nbands, n, e->chain_wgs), e->stream, pl.axis)))
             return rc;
         KCHECK();
         if ((rc = stage_end(e, 1))) return rc;
@@ -2423,14 +2491,14 @@ int sgm_get_stage_times(sgm_engine *e, sgm_stage_times *out)
 }
 
 // SURVEY.md 8(d):  B_alg = 2HW (L,R in) + V (1 + 3 Np) + 2HW (disp out) + 8HW (median, speckle r+w)
-//                          [+ 16 HW reproject], V = 2 H W1 D bytes, Np = 5 (mode 0) or 8 (mode 1).
+//                          [+ 16 HW reproject], V = 2 H W1 D bytes, Np = 5 (mode 0), 8 (mode 1) or 4 (mode 3).
 int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_reproject)
 {
     Geom g;
     if (!params || normalise(params, H, W, &g)) return -1;
     const int64_t HW = (int64_t)H * W;
     const int64_t V = 2 * (int64_t)H * std::max(g.W1, 0) * g.D;
-    const int Np = g.mode == 1 ? 8 : 5;
+    const int Np = g.mode == 1 ? 8 : (g.mode == 3 ? 4 : 5);
     int64_t b = 2 * HW + V * (1 + 3 * Np) + 2 * HW + 8 * HW;
     if (with_reproject) b += 16 * HW;
     return b;

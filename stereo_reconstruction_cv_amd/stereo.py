@@ -369,9 +369,9 @@ class StereoSGBM:
     def compute(self, left, right):
         """int16 (H, W) disparity * 16, invalid = (minDisparity - 1) * 16  (main.ipynb:668).  left / right: uint8
         (H, W) or colour (H, W, 3) pairs of the same shape (the pixel cost sums the three channels, as cv2's)."""
-        if self._p["mode"] not in (STEREO_SGBM_MODE_SGBM, STEREO_SGBM_MODE_HH):
-            raise error("StereoSGBM.compute: only MODE_SGBM and MODE_HH are implemented "
-                        "(the reference never selects MODE_SGBM_3WAY / MODE_HH4)")
+        if self._p["mode"] not in (STEREO_SGBM_MODE_SGBM, STEREO_SGBM_MODE_HH, STEREO_SGBM_MODE_HH4):
+            raise error("StereoSGBM.compute: MODE_SGBM, MODE_HH and MODE_HH4 are implemented; MODE_SGBM_3WAY is not "
+                        "(its result depends on a stripe size upstream derives from the cache size)")
         if _is_torch(left) or _is_torch(right):
             return self._compute_torch(left, right)
         left, right = np.asarray(left), np.asarray(right)
