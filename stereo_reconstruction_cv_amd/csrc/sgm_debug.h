@@ -9,6 +9,14 @@
 
 #define SGM_OPT_DEBUG 4 /* sgm_set_option(e, SGM_OPT_DEBUG, mask) */
 
+/* Poison switch: sgm_set_option(e, SGM_OPT_POISON, b) with b in 0..255 fills, in stream order, every device buffer that
+ * e and the engines behind it (peer, peer2, group) own with the byte b -- all but the sticky give-up flag chain_err, which
+ * is state by contract -- and ARMS the switch: from then on every buffer that any engine of the process allocates or
+ * regrows is filled with b as well.  Any other value (-1) disarms it and fills nothing.  For tests that must not depend
+ * on what a call finds in the engine's buffers (tests/test_gpu_history.py); while it is not armed the engine enqueues
+ * nothing for it, and no kernel knows about it. */
+#define SGM_OPT_POISON 9
+
 enum {
     SGM_DBG_WTA_IN_LAST_PATH = 2,        /* winner-take-all fused into the last path kernel everywhere (pre-pass schedule) */
     SGM_DBG_NO_LANE_GROUPS = 4,          /* D <= 64 through the wave-per-pixel kernels */

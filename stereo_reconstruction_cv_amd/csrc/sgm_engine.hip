@@ -71,6 +71,12 @@ static int debug_alloc_mode()
     return m;
 }
 
+// Poison switch (csrc/sgm_debug.h: SGM_OPT_POISON; test scaffolding).  -1: not armed.  0..255: armed -- every buffer that
+// DevBuf::ensure allocates or regrows is filled with this byte before anything can use it, so that growth does not bring
+// hipMalloc's friendly contents back between two poisoned calls.  One word per process, like SGM_DEBUG_ALLOC: ensure() has
+// no engine to ask, and the internal engines of the batch entries are created in the middle of a call.
+static int g_poison_byte = -1;
+
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
@@ -130,7 +136,10 @@ struct DevBuf {
         if (p) {
             if (release() != hipSuccess) return SGM_ERR_HIP;
         }
-        if (debug_alloc_mode() && bytes <= ((size_t)1 << 30)) return ensure_guarded(bytes);
+        if (debug_alloc_mode() && bytes <= ((size_t)1 << 30)) {
+            int rc = ensure_guarded(bytes);
+            return rc ? rc : poison_new();
+        }
         hipError_t e = hipMalloc(&p, bytes);
         if (e != hipSuccess) {
             p = nullptr;
@@ -138,6 +147,15 @@ struct DevBuf {
             return SGM_ERR_NOMEM;
         }
         cap = bytes;
+        return poison_new();
+    }
+    // armed poison switch only: [p, p + cap) filled and the fill complete before ensure() returns (the engine's streams are
+    // non-blocking, so nothing orders them behind the null stream but the host)
+    int poison_new()
+    {
+        if (g_poison_byte < 0) return SGM_OK;
+        if (hipMemsetAsync(p, g_poison_byte, cap, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)
+            return set_err(SGM_ERR_HIP, "SGM_OPT_POISON: filling a new buffer of %zu bytes failed", cap);
         return SGM_OK;
     }
     hipError_t release()
@@ -235,6 +253,8 @@ struct sgm_engine {
     sgm_engine *peer = nullptr, *peer2 = nullptr;
     std::vector<sgm_engine *> group;      // sgm_pipeline_batch_device: the other engines of a chained group (own streams and buffers)
     int last_group = 0;                   // engines of `group` the last batch call used (sgm_get_headroom looks at all of them)
+    int last_peers = 0;                   // peers the last sgm_compute_batch in latency mode used (likewise)
+    bool in_batch = false;                // a batch entry is running: the computes it starts on this engine keep last_group
     bool hr_accumulate = false;           // batch calls: the headroom record of this engine is NOT reset by the next compute (it then covers every pair the engine ran in the call)
     int group_max = 0;                    // SGM_OPT_GROUP_MAX: pairs per chained launch (0 = as many as fit in memory, up to CHAIN_MAX_FRAMES)
     // sgm_compute_batch, throughput mode: two groups in flight (the transfers of group g + 1 / g - 1 beside the kernels of
@@ -669,7 +689,9 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     p.pre_plain = (dbg & SGM_DBG_PREPASS_ONE_CHUNK) != 0;
     p.pre_nch = p.pre_plain ? 1 : (e->prepass_rows > 0 ? (H + e->prepass_rows - 1) / e->prepass_rows : std::max(1, (H + 67) / 135));
     // multiples of 8 rows (two prefetch blocks): a chunk then ends in straight-line code
-    p.pre_rows = e->prepass_rows > 0 ? e->prepass_rows : ((H + p.pre_nch - 1) / p.pre_nch + 7) / 8 * 8;
+    // (debug 512 is ONE chunk whatever SGM_OPT_PREPASS_ROWS says: with the chunk height taken from the option the rows
+    // below the first chunk were never walked and the bands under them started from stale boundary state)
+    p.pre_rows = e->prepass_rows > 0 && !p.pre_plain ? e->prepass_rows : ((H + p.pre_nch - 1) / p.pre_nch + 7) / 8 * 8;
     // MODE_HH: the upward pre-pass only reads C, so it runs on the auxiliary stream while the
     // main stream does the downward pre-pass and sweep (memory-bound beside issue-bound work)
     p.overlap = p.npass == 2 && p.nbands > 1 && !(dbg & SGM_DBG_NO_PREPASS_OVERLAP) && !p.chain;
@@ -1366,7 +1388,11 @@ static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_ri
     } else {
         stage_break(e);
     }
-    if (do_pre && !e->hr_accumulate) HIP_TRY(hipMemsetAsync(e->headroom.p, 0, 8, e->stream));  // headroom record of this compute (sgm_get_headroom)
+    if (do_pre && !e->hr_accumulate) {
+        HIP_TRY(hipMemsetAsync(e->headroom.p, 0, 8, e->stream));  // headroom record of this compute (sgm_get_headroom)
+        // a compute of its own forgets the internal engines of an earlier batch call: their records belong to that call
+        if (!e->in_batch) e->last_group = e->last_peers = 0;
+    }
 
     if (e->g.W1 <= 0) {
         // no column can be matched: the whole map is invalid (upstream early-out), then median
@@ -1507,6 +1533,33 @@ static void release_buffers(sgm_engine *e)
     e->g.hr = nullptr;
 }
 
+// SGM_OPT_POISON (csrc/sgm_debug.h): every byte of every device buffer the engine owns -- [p, p + cap) of each DevBuf
+// member, which is also the whole buffer under SGM_DEBUG_ALLOC=1 -- set to `byte`, in the order of the engine's stream, and
+// the same for the engines behind it (peer, peer2, group), each on its own stream.  Every stream is waited for at the end:
+// the batch entries order the engines of a group with events of their own, not with the caller's stream.
+// chain_err is the one member that is state by contract (the sticky give-up flag that check_chain reports and clears); it is
+// LEFT ALONE, neither filled nor re-cleared.  tests/test_history_walks.py checks that every DevBuf member of sgm_engine is named here.
+static int poison_buffers(sgm_engine *e, int byte)
+{
+    DevBuf *bufs[] = {&e->in_left, &e->in_right, &e->lrec, &e->rplanes, &e->hsum, &e->cost, &e->aggr, &e->aggr2, &e->aggr3, &e->aggr4,
+                      &e->aggr5, &e->wta, &e->bndL, &e->bndL2, &e->pstate, &e->pstate2, &e->disp_raw, &e->disp_med, &e->disp_out,
+                      &e->label, &e->csize, &e->rlen, &e->f32, &e->xyz, &e->mask, &e->minkey, &e->rmap1, &e->rmap2, &e->rsrc,
+                      &e->rdst, &e->ccount, &e->cpts, &e->crgb, &e->crgb_in, &e->headroom, &e->chain_ctl, &e->chain_err,
+                      &e->io[0][0], &e->io[0][1], &e->io[0][2], &e->io[0][3], &e->io[0][4],
+                      &e->io[1][0], &e->io[1][1], &e->io[1][2], &e->io[1][3], &e->io[1][4]};
+    static_assert(sizeof(e->io) == 10 * sizeof(DevBuf), "poison_buffers names every slot of io");
+    HIP_TRY(hipSetDevice(e->device));
+    for (DevBuf *b : bufs)
+        if (b != &e->chain_err && b->p && b->cap) HIP_TRY(hipMemsetAsync(b->p, byte, b->cap, e->stream));
+    int rc;
+    if (e->peer && (rc = poison_buffers(e->peer, byte))) return rc;
+    if (e->peer2 && (rc = poison_buffers(e->peer2, byte))) return rc;
+    for (sgm_engine *q : e->group)
+        if ((rc = poison_buffers(q, byte))) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SGM_OK;
+}
+
 void sgm_destroy(sgm_engine *e)
 {
     if (!e) return;
@@ -1571,6 +1624,11 @@ int sgm_set_option(sgm_engine *e, int option, int value)
             return set_err(SGM_ERR_INVALID_ARG, "SGM_OPT_CHANNELS %d: only 1 and 3 interleaved 8-bit channels are supported", value);
         e->cn = value;
     }
+    else if (option == SGM_OPT_POISON) {
+        // csrc/sgm_debug.h: 0..255 fills every buffer now and arms DevBuf::ensure; anything else disarms
+        g_poison_byte = value >= 0 && value <= 255 ? value : -1;
+        if (g_poison_byte >= 0) return poison_buffers(e, g_poison_byte);
+    }
     else return set_err(SGM_ERR_INVALID_ARG, "unknown option %d", option);
     return SGM_OK;
 }
@@ -1620,6 +1678,7 @@ int sgm_trim(sgm_engine *e)
     if (e->peer) sgm_destroy(e->peer);
     if (e->peer2) sgm_destroy(e->peer2);
     e->peer = e->peer2 = nullptr;
+    e->last_peers = 0;
     e->pin_left.release();
     e->pin_right.release();
     e->pin_disp.release();
@@ -1881,6 +1940,7 @@ struct BatchGuard {
     ~BatchGuard()
     {
         e->hr_accumulate = false;
+        e->in_batch = false;
         for (sgm_engine *q : e->group) q->hr_accumulate = false;
         if (ok) return;
         (void)hipStreamSynchronize(e->stream);
@@ -2004,6 +2064,8 @@ int sgm_pipeline_batch_device(sgm_engine *e, int N, const void *const *d_left, c
     bool joint = false;
     if ((rc = batch_plan(e, N, H, W, &pl, &joint))) return rc;
     BatchGuard guard{e};
+    e->in_batch = true;
+    e->last_peers = 0;
     e->last_group = 0;
     int cap = 1;
     if (joint && (rc = prepare_group(e, N, H, W, pl, &cap))) return rc;
@@ -2112,6 +2174,8 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
         // The host copies caller -> staging -> caller with a few threads (one thread moves about 10 GB/s; 17 4K maps are 282 MB).
         // The XYZ images (99.5 MB each) go straight to the caller's memory: staging them would pin gigabytes.
         BatchGuard guard{e};
+        e->in_batch = true;
+        e->last_peers = 0;   // (set again below if the call ends up spreading its pairs over the peers)
         int cap = 1;
         const size_t slot_bytes = 2 * (2 * ib + npx * 2 + (xyz_out ? npx * 16 : 0));
         if ((rc = prepare_group(e, N, H, W, pl, &cap, slot_bytes))) return rc;
@@ -2221,7 +2285,10 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
         ~Drain()
         {
             for (int k = 0; k < n; k++)
-                if (eng[k]) (void)hipStreamSynchronize(eng[k]->stream);
+                if (eng[k]) {
+                    (void)hipStreamSynchronize(eng[k]->stream);
+                    eng[k]->hr_accumulate = false;
+                }
             eng[0]->keep_aggr = keep;
             eng[0]->profile = prof;
         }
@@ -2249,6 +2316,7 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
         std::memcpy(q->pin_right.p, rights + (size_t)i * ib, ib);
         HIP_TRY(hipMemcpyAsync(q->in_left.p, q->pin_left.p, ib, hipMemcpyHostToDevice, q->stream));
         HIP_TRY(hipMemcpyAsync(q->in_right.p, q->pin_right.p, ib, hipMemcpyHostToDevice, q->stream));
+        q->hr_accumulate = i >= neng;   // (the headroom record of the call covers every pair: each engine keeps its pairs' maximum)
         rc = sgm_pipeline_device(q, q->in_left.p, q->in_right.p, H, W, rowb, Q16, q->disp_out.p, xyz_out ? q->f32.p : nullptr,
                                  xyz_out ? q->xyz.p : nullptr);
         if (rc) return rc;
@@ -2257,6 +2325,7 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
     }
     for (int i = std::max(0, N - neng); i < N; i++)
         if ((rc = finish(i))) return rc;
+    e->last_peers = neng - 1;   // (sgm_get_headroom: the pairs of this call ran on the peers as well)
     return SGM_OK;
 }
 
@@ -2439,10 +2508,14 @@ int sgm_get_headroom(sgm_engine *e, int *max_cost_plus_p2, int *max_delta, int *
     // keeps its record on the internal engine that ran it; e's stream ends behind all of them)
     uint32_t h[2] = {0, 0};
     HIP_TRY(hipMemcpy(h, e->headroom.p, 8, hipMemcpyDeviceToHost));
-    for (int k = 0; k < e->last_group && k < (int)e->group.size(); k++) {
+    std::vector<sgm_engine *> behind;
+    for (int k = 0; k < e->last_group && k < (int)e->group.size(); k++) behind.push_back(e->group[k]);
+    if (e->last_peers >= 1 && e->peer) behind.push_back(e->peer);      // (sgm_compute_batch in latency mode: the call has
+    if (e->last_peers >= 2 && e->peer2) behind.push_back(e->peer2);    //  drained their streams before it returned)
+    for (sgm_engine *o : behind) {
         uint32_t q[2] = {0, 0};
-        if (!e->group[k]->headroom.p) continue;
-        HIP_TRY(hipMemcpy(q, e->group[k]->headroom.p, 8, hipMemcpyDeviceToHost));
+        if (!o->headroom.p) continue;
+        HIP_TRY(hipMemcpy(q, o->headroom.p, 8, hipMemcpyDeviceToHost));
         h[0] = std::max(h[0], q[0]);
         h[1] = std::max(h[1], q[1]);
     }
