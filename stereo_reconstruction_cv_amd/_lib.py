@@ -44,6 +44,14 @@ class SgmStageTimes(C.Structure):
                 ("ms", C.c_float * SGM_MAX_STAGES), ("launches", C.c_int32 * SGM_MAX_STAGES)]
 
 
+class SgmDebugPlan(C.Structure):
+    """csrc/sgm_debug.h: sgm_debug_plan_t (test scaffolding, not part of the public interface)"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "W1", "minX1", "NP", "partial", "byte_cost", "pix_px", "GWc", "RBb", "vsum_ring", "rows4", "GWs", "chain", "R", "nbands",
+        "fused_prepass", "prepass_g", "pre_nch", "pre_rows", "overlap", "fused_wta", "nvol", "path_w_main", "speckle",
+        "chain_window")]
+
+
 class LibraryMissing(RuntimeError):
     pass
 
@@ -107,6 +115,9 @@ def load():
     L.sgm_init_undistort_rectify_map_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp]
     L.sgm_remap_linear_u8.argtypes = [vp, vp, i32, i32, i64, i32, vp, vp, i32, i32, vp]
     L.sgm_remap_linear_u8_device.argtypes = [vp, vp, i32, i32, i64, i32, vp, vp, i32, i32, vp, i64]
+    # csrc/sgm_debug.h, outside EXPORTS: the plan readout for tests
+    L.sgm_debug_plan.argtypes = [pp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(SgmDebugPlan)]
+    L.sgm_debug_plan.restype = i32
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("sgm_abi_version", "sgm_device_count"):
@@ -117,3 +128,15 @@ def load():
 
 def last_error() -> str:
     return (load().sgm_last_error() or b"").decode("utf-8", "replace")
+
+
+def debug_plan(params: dict, H: int, W: int, channels: int = 1, schedule: int = 1, sweep_rows: int = 0, prepass_rows: int = 0,
+               debug: int = 0, frames: int = 1) -> dict:
+    """The schedule one compute of an H x W frame takes with these arguments and options (csrc/sgm_debug.h: sgm_debug_plan),
+    as a dict of the fields of sgm_debug_plan_t.  Needs no GPU.  For tests: which plan a case takes is read, not assumed."""
+    out = SgmDebugPlan()
+    rc = load().sgm_debug_plan(C.byref(SgmParams(**params)), H, W, channels, schedule, sweep_rows, prepass_rows, debug, frames,
+                               C.byref(out))
+    if rc != SGM_OK:
+        raise ValueError(f"sgm_debug_plan failed ({rc}): {last_error()}")
+    return {n: getattr(out, n) for n, _ in SgmDebugPlan._fields_}

@@ -33,4 +33,23 @@ enum {
     SGM_DBG_FIFTH_PATH_AFTER_SWEEP = 65536 /* MODE_SGBM, D <= 128: the fifth path after the sweep (S +=) instead of beside it */
 };
 
+/* Plan readout: what normalise + make_plan decide for one compute of a frame of H x W pixels on an engine with these
+ * options, without an engine and without a GPU (like sgm_geometry).  For tests that must prove which schedule a case
+ * takes instead of assuming it; the fields are those of Geom and Plan in sgm_engine.hip.  chain_window: workgroups of one
+ * automatic chained sweep launch over `frames` frames (0 where the plan is not chained). */
+typedef struct {
+    int W1, minX1, NP, partial;  /* partial: the PARTIAL instantiation (with_np; with_gw where the small-D kernels run) */
+    int byte_cost, pix_px, GWc, RBb, vsum_ring;
+    int rows4, GWs, chain, R, nbands;
+    int fused_prepass, prepass_g, pre_nch, pre_rows, overlap;
+    int fused_wta, nvol, path_w_main, speckle;
+    int chain_window;
+} sgm_debug_plan_t;
+
+#ifdef __cplusplus
+extern "C"
+#endif
+int sgm_debug_plan(const sgm_params *p, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
+                   int debug, int frames, sgm_debug_plan_t *out);
+
 #endif

@@ -1489,6 +1489,52 @@ int sgm_geometry(const sgm_params *params, int W, int *minX1, int *W1)
     return SGM_OK;
 }
 
+// csrc/sgm_debug.h: the plan of one compute, read out on the host.  The options go through sgm_set_option into an engine
+// that is never handed out (it owns no stream and no buffer), then the very calls run_compute makes.
+int sgm_debug_plan(const sgm_params *params, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
+                   int debug, int frames, sgm_debug_plan_t *out)
+{
+    if (!params || !out) return set_err(SGM_ERR_INVALID_ARG, "params/out is null");
+    if (H <= 0 || W < 2 || W > 32767 || H > 32767) return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d", H, W);
+    sgm_engine e;
+    e.params = *params;
+    int rc;
+    if ((rc = sgm_set_option(&e, SGM_OPT_CHANNELS, channels)) || (rc = sgm_set_option(&e, SGM_OPT_SCHEDULE, schedule)) ||
+        (rc = sgm_set_option(&e, SGM_OPT_SWEEP_ROWS, sweep_rows)) || (rc = sgm_set_option(&e, SGM_OPT_PREPASS_ROWS, prepass_rows)) ||
+        (rc = sgm_set_option(&e, SGM_OPT_DEBUG, debug)))
+        return rc;
+    Geom g;
+    if ((rc = normalise(&e.params, H, W, &g))) return rc;
+    const Plan p = make_plan(&e, g, H);
+    const bool small_d = p.rows4 && p.GWs < 64;
+    out->W1 = g.W1;
+    out->minX1 = g.minX1;
+    out->NP = g.NP;
+    out->partial = small_d ? with_gw(p.GWs, g.D, [](auto, auto part) { return (int)decltype(part)::value; })
+                           : with_np(g, [](auto, auto part) { return (int)decltype(part)::value; });
+    out->byte_cost = p.byte_cost;
+    out->pix_px = p.pix_px;
+    out->GWc = p.GWc;
+    out->RBb = p.RBb;
+    out->vsum_ring = p.vsum_ring;
+    out->rows4 = p.rows4;
+    out->GWs = p.GWs;
+    out->chain = p.chain;
+    out->R = p.R;
+    out->nbands = p.nbands;
+    out->fused_prepass = p.fused_prepass;
+    out->prepass_g = p.prepass_g;
+    out->pre_nch = p.pre_nch;
+    out->pre_rows = p.pre_rows;
+    out->overlap = p.overlap;
+    out->fused_wta = p.fused_wta;
+    out->nvol = p.nvol;
+    out->path_w_main = p.path_w_main;
+    out->speckle = p.speckle;
+    out->chain_window = p.chain && g.W1 > 0 ? chain_window(g, p.R, p.nbands, std::max(frames, 1), 0) : 0;
+    return SGM_OK;
+}
+
 int sgm_create(const sgm_params *params, int device_id, void *stream, sgm_engine **out)
 {
     if (!params || !out) return set_err(SGM_ERR_INVALID_ARG, "params/out is null");

@@ -32,7 +32,7 @@ def run_hip_with_taps(left, right, p, schedule=1, sweep_rows=0, debug=0, prepass
     eng.set_option(_lib.SGM_OPT_KEEP_AGGR, 1)
     eng.set_option(_lib.SGM_OPT_SCHEDULE, schedule)
     eng.set_option(_lib.SGM_OPT_SWEEP_ROWS, sweep_rows)
-    H, W = left.shape
+    H, W = left.shape[:2]        # (H, W) gray or (H, W, 3) colour
     disp = eng.compute_host(left, right)
     _, W1 = eng.geometry(W)
     out = dict(disp=disp, disp_raw=eng.tap(_lib.SGM_TAP_DISP_RAW, H, W),

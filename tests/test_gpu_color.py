@@ -10,6 +10,7 @@ import pytest
 import bruteforce_color as BC
 import parity_util as U
 from oracle import oracle as O
+from oracle import volume_oracle as V
 from stereo_reconstruction_cv_amd import _lib, pipeline, synth
 from stereo_reconstruction_cv_amd import stereo as cv
 from stereo_reconstruction_cv_amd.stereo import Engine
@@ -215,6 +216,37 @@ def test_equal_channels_full_size(H, W, D, bs, mode, k1, k2):
     del Cg
     assert np.array_equal(eng.tap(_lib.SGM_TAP_DISP_RAW, H, W), t["disp_raw"])
     assert np.array_equal(got, gray), int((got != gray).sum())
+
+
+@pytest.mark.parametrize("schedule", [1, 2])
+def test_full_hd_colour_pair_against_the_volume_oracle(schedule):
+    """1920 x 1080, D = 128, bs = 5, MODE_HH on three DIFFERENT channels: every map and the headroom record against the
+    volume oracle (oracle/sgbm_volume_oracle.c, pinned by tests/test_volume_oracle.py) -- the relations above reach full
+    size only through gray images in disguise."""
+    H, W, D = 1080, 1920, 128
+    p = U.params(D, 5, 0, 1, penalty="plain", speckleWindowSize=60, speckleRange=2)
+    L3, R3 = BC.colour_pair(H, W, D, seed=1080)
+    want, t = _full_hd_colour_oracle()
+    eng = _engine(p, schedule)
+    got = eng.compute_host(L3, R3)
+    eng.check()
+    assert eng.headroom() == dict(ok=True, max_cost_plus_p2=t["max_cost_plus_p2"], max_delta=t["max_delta"])
+    assert np.array_equal(eng.tap(_lib.SGM_TAP_DISP_RAW, H, W), t["disp_raw"])
+    assert np.array_equal(eng.tap(_lib.SGM_TAP_DISP_MEDIAN, H, W), t["disp_median"])
+    assert np.array_equal(got, want), int((got != want).sum())
+
+
+_full_hd = []
+
+
+def _full_hd_colour_oracle():
+    if not _full_hd:
+        H, W, D = 1080, 1920, 128
+        p = U.params(D, 5, 0, 1, penalty="plain", speckleWindowSize=60, speckleRange=2)
+        want, t = V.sgbm_compute(*BC.colour_pair(H, W, D, seed=1080), taps="light", **p)
+        assert t["headroom_ok"] and (want >= 0).mean() > 0.5, (t["max_cost_plus_p2"], t["max_delta"], (want >= 0).mean())
+        _full_hd.append((want, t))
+    return _full_hd[0]
 
 
 # ---- 6. batches ------------------------------------------------------------------------------------------------------------

@@ -1,8 +1,9 @@
 """MODE_HH4 on the GPU (needs an MI355X): the MODE_HH pipeline over the four axis-aligned paths, through the axis-only
 kernels (k_axis_sweep, k_axis_chain, k_axis_prepass; k_axis_paths4_g for D <= 64; k_path per direction in schedule 0).
 The yardstick is the numpy restatement tests/bruteforce_hh4.py (the C oracle refuses mode 3); every comparison is
-bit-exact over the whole frame.  The full-size test compares the build with itself (the helper cannot reach 4K): it
-shows that the schedules and the batch entry agree there, not that they are right."""
+bit-exact over the whole frame.  The full-size test compares the schedules and the batch entry with each other and with the
+volume oracle (oracle/sgbm_volume_oracle.c: the C form of the restatement, pinned by tests/test_volume_oracle.py), which
+reaches 4K where the numpy helper cannot."""
 import os
 import re
 import subprocess
@@ -15,6 +16,7 @@ import bruteforce_color as BC
 import bruteforce_hh4 as HH4
 import parity_util as U
 from oracle import oracle as O
+from oracle import volume_oracle as V
 from stereo_reconstruction_cv_amd import _lib, synth
 from stereo_reconstruction_cv_amd import stereo as cv
 from stereo_reconstruction_cv_amd.stereo import Engine
@@ -192,12 +194,24 @@ def test_stereo_sgbm_surface_and_neighbouring_modes():
     assert np.array_equal(e3.compute_host(l, r), a) and np.array_equal(a, w["disp"]) and np.array_equal(b, before)
 
 
+_want_4k = []
+
+
+def volume_oracle_4k(l, r, p):
+    """map and headroom record of the 4K pair from the volume oracle (about half a minute and 8 GB on one core), kept"""
+    if not _want_4k:
+        _want_4k.append(V.sgbm_compute(l, r, taps="light", **p))
+    return _want_4k[0]
+
+
 def test_full_size_consistency():
     """2160 x 3840, D = 256, bs = 7: schedules 0, 1, 2 and a throughput-mode batch of 3 give the same map and the same
-    headroom record.  Consistency of the build with itself only -- the restatement cannot reach this size."""
+    headroom record -- and they are the volume oracle's (the numpy restatement cannot reach this size; the C form of it can)."""
     H, W, D = 2160, 3840, 256
     p = U.params(D, 7, 0, 3)
     l, r, _ = synth.make_pair(H, W, D, seed=11)
+    want, t = volume_oracle_4k(l, r, p)
+    assert t["headroom_ok"] and (want >= 0).mean() > 0.5
     maps, hrs = [], []
     for schedule in (0, 1, 2):
         eng = Engine(p)
@@ -219,6 +233,8 @@ def test_full_size_consistency():
     for i in range(3):
         assert np.array_equal(disps[i], maps[0]), i
     assert eng.headroom() == hrs[0]
+    assert hrs[0] == dict(ok=True, max_cost_plus_p2=t["max_cost_plus_p2"], max_delta=t["max_delta"]), (hrs[0], t)
+    assert np.array_equal(maps[0], want), U.describe_mismatch("disp", maps[0], want)
 
 
 def test_small_cases_with_guarded_allocations():
