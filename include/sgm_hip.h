@@ -57,7 +57,7 @@ typedef enum {
     SGM_ERR_INVALID_ARG = -1,   /* null pointer, non-positive size, unsupported parameter       */
     SGM_ERR_NO_DEVICE = -2,     /* no HIP device / device index out of range                     */
     SGM_ERR_HIP = -3,           /* a HIP runtime call failed; message has the hipError string    */
-    SGM_ERR_UNSUPPORTED = -4,   /* mode 2 (3WAY), numDisparities not a multiple of 16, ...     */
+    SGM_ERR_UNSUPPORTED = -4,   /* mode 2 (3WAY), numDisparities not a multiple of 16 or > 1024, blockSize > 31, ... */
     SGM_ERR_NOMEM = -5
 } sgm_status;
 
@@ -70,7 +70,8 @@ typedef enum {
  * OpenCV 4.11 does. */
 typedef struct {
     int32_t minDisparity;
-    int32_t numDisparities;
+    int32_t numDisparities;     /* a multiple of 16, at most 1024 (above 512: one path kernel per direction whatever
+                                 * SGM_OPT_SCHEDULE says, and batch calls run their pairs one after the other) */
     int32_t blockSize;
     int32_t P1;
     int32_t P2;

@@ -321,7 +321,9 @@ __global__ __launch_bounds__(64) void k_path(Geom g, int rx, int ry, const int16
                                              int16_t *__restrict__ S, int keepS,
                                              uint2 *__restrict__ wta, Boundary bd)
 {
-    constexpr int PB = 8;  // steps per prefetch block (two blocks in flight)
+    // steps per prefetch block (two blocks in flight).  NP = 8: four -- cA/cB/sA/sB are 4 * PB * NP registers, the same
+    // 128 as NP = 4 holds with eight, and the same bytes in flight per wave
+    constexpr int PB = NP == 8 ? 4 : 8;
     const int lane = threadIdx.x;
     const int line = blockIdx.x;
     const int W1 = g.W1, D = g.D;

@@ -3,8 +3,10 @@
 // Layout convention used by every cost-volume kernel: a volume is int16 [y][xi][d] with d
 // fastest.  One wavefront owns one pixel's D disparities: lane l holds NP packed pairs
 // (32-bit registers of two int16), pair i of lane l = disparities d = 2*(NP*l + i) + {0,1}.
-// NP = 1, 2, 4 covers D <= 128, 256, 512; lanes whose first disparity is >= D are idle
-// ("partial" waves, D % 16 == 0 makes a lane either fully valid or fully idle).
+// NP = 1, 2, 4, 8 covers D <= 128, 256, 512, 1024; lanes whose first disparity is >= D are idle
+// ("partial" waves, D % 16 == 0 makes a lane either fully valid or fully idle: a lane holds 2 NP <= 16
+// consecutive disparities).  NP = 8 exists for the per-direction path kernel and the int16 horizontal sums
+// only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -325,6 +327,8 @@ template <int NP> struct PackVec;
 template <> struct PackVec<1> { typedef uint32_t type; };
 template <> struct PackVec<2> { typedef uint2 type; };
 template <> struct PackVec<4> { typedef uint4 type; };
+struct uint4x2 { uint4 lo, hi; };
+template <> struct PackVec<8> { typedef uint4x2 type; };
 
 template <int NP> struct Pack {
     uint32_t r[NP];
@@ -375,12 +379,25 @@ __device__ __forceinline__ void buf_load(Pack<NP> &p, __amdgpu_buffer_rsrc_t rsr
         const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff_bytes, soff_bytes, AUX);
         p.r[0] = v.x;
         p.r[1] = v.y;
-    } else {
+    } else if constexpr (NP == 4) {
         const v4u32 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff_bytes, soff_bytes, AUX);
         p.r[0] = v.x;
         p.r[1] = v.y;
         p.r[2] = v.z;
         p.r[3] = v.w;
+    } else {
+        static_assert(NP == 8, "lane packings: 1, 2, 4, 8 pairs");
+        // a lane's 32 bytes as two 128-bit loads (the widest MUBUF access)
+        const v4u32 a = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff_bytes, soff_bytes, AUX);
+        const v4u32 b = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff_bytes + 16, soff_bytes, AUX);
+        p.r[0] = a.x;
+        p.r[1] = a.y;
+        p.r[2] = a.z;
+        p.r[3] = a.w;
+        p.r[4] = b.x;
+        p.r[5] = b.y;
+        p.r[6] = b.z;
+        p.r[7] = b.w;
     }
 }
 // AUX: cache policy bits of the store (2 = nt: streaming, the default; 16 = sc1: write-through, agent scope --
@@ -404,6 +421,16 @@ __device__ __forceinline__ void buf_store(const Pack<NP> &p, __amdgpu_buffer_rsr
         v.w = p.r[3];
         __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff_bytes, soff_bytes, AUX);
 #endif
+    } else if constexpr (NP == 8) {
+        // Four 64-bit stores, kept apart like the two of NP = 4 below and for the same reason.
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            v2u32 q;
+            q.x = p.r[2 * k];
+            q.y = p.r[2 * k + 1];
+            __builtin_amdgcn_raw_buffer_store_b64(q, rsrc, voff_bytes + 8 * k, soff_bytes, AUX);
+            if (k < 3) asm volatile("" ::: "memory");
+        }
     } else {
         // Two 64-bit stores, never buffer_store_dwordx4 (root cause found in round 2).
         // A MUBUF store of more than 64 bits reads its upper data registers a cycle or two after

@@ -311,7 +311,7 @@ static int normalise(const sgm_params *p, int H, int W, Geom *g)
         return set_err(SGM_ERR_UNSUPPORTED, "mode %d: MODE_SGBM (0), MODE_HH (1) and MODE_HH4 (3) are built; MODE_SGBM_3WAY (2) is not", p->mode);
     if (p->numDisparities % 16 != 0)
         return set_err(SGM_ERR_UNSUPPORTED, "numDisparities=%d must be divisible by 16 (OpenCV's documented contract)", p->numDisparities);
-    if (p->numDisparities > 512) return set_err(SGM_ERR_UNSUPPORTED, "numDisparities=%d > 512", p->numDisparities);
+    if (p->numDisparities > 1024) return set_err(SGM_ERR_UNSUPPORTED, "numDisparities=%d > 1024", p->numDisparities);
     const int dim = p->blockSize > 0 ? p->blockSize : 5;
     if (dim > 31) return set_err(SGM_ERR_UNSUPPORTED, "blockSize=%d > 31", dim);
     g->H = H;
@@ -330,7 +330,7 @@ static int normalise(const sgm_params *p, int H, int W, Geom *g)
     g->ftzero = std::max(p->preFilterCap, 15) | 1;
     g->invalid_scaled = (g->minD - 1) * 16;
     g->mode = p->mode;
-    g->NP = g->D <= 128 ? 1 : (g->D <= 256 ? 2 : 4);
+    g->NP = g->D <= 128 ? 1 : (g->D <= 256 ? 2 : (g->D <= 512 ? 4 : 8));
     g->rowsz = (int64_t)std::max(g->W1, 0) * g->D;
     g->hr = nullptr;
     return SGM_OK;
@@ -418,14 +418,26 @@ static void stage_break(sgm_engine *e) { e->last_end_ev = -1; }
 
 // ---- template ladders --------------------------------------------------------------------------
 // f(NP, PARTIAL) as std::integral_constant for the geometry: NP 128-disparity pieces per lane, PARTIAL = the last piece is not full
+// NP = 1, 2, 4 only.  D > 512 (NP = 8) never comes here: its plan (make_plan: wide_d) runs three kernels -- k_path, k_hsum,
+// k_hsum_c3 -- and those go through with_np_wide; a fourth rung HERE would instantiate every sweep, pre-pass and lane-group
+// kernel for a packing their registers and LDS do not hold.
+static bool np_partial(const Geom &g) { return g.D != 128 * g.NP; }
 template <class F>
 static auto with_np(const Geom &g, F &&f)
 {
     using std::integral_constant;
-    const bool partial = g.D != 128 * g.NP;
+    const bool partial = np_partial(g);
     if (g.NP == 1) return partial ? f(integral_constant<int, 1>(), std::true_type()) : f(integral_constant<int, 1>(), std::false_type());
     if (g.NP == 2) return partial ? f(integral_constant<int, 2>(), std::true_type()) : f(integral_constant<int, 2>(), std::false_type());
     return partial ? f(integral_constant<int, 4>(), std::true_type()) : f(integral_constant<int, 4>(), std::false_type());
+}
+// with_np plus the NP = 8 rung, for the kernels that have that instantiation
+template <class F>
+static auto with_np_wide(const Geom &g, F &&f)
+{
+    using std::integral_constant;
+    if (g.NP == 8) return np_partial(g) ? f(integral_constant<int, 8>(), std::true_type()) : f(integral_constant<int, 8>(), std::false_type());
+    return with_np(g, f);
 }
 // f(GW, PARTIAL) for a lane-group width of the small-D kernels (8, 16, 32); PARTIAL = the group is not full (D = 48 in
 // groups of 32; D = 16, 32, 64 fill theirs)
@@ -468,14 +480,14 @@ static void launch_path_np(const Geom &g, int rx, int ry, int mode, const int16_
         hipLaunchKernelGGL((k_path<NP, PARTIAL, PATH_LAST, true>), grid, block, 0, st, g, rx, ry, C, S, keepS, wta, bd);
     else if (mode == PATH_LAST)
         hipLaunchKernelGGL((k_path<NP, PARTIAL, PATH_LAST, false>), grid, block, 0, st, g, rx, ry, C, S, keepS, wta, bd);
-    else
+    else if constexpr (NP < 8)  // (the boundary role belongs to the fused sweeps' pre-pass: D <= 512)
         hipLaunchKernelGGL((k_path<NP, PARTIAL, PATH_BOUNDARY, true>), grid, block, 0, st, g, rx, ry, C, S, keepS, wta, bd);
 }
 
 static void launch_path(const Geom &g, int rx, int ry, int mode, const int16_t *C, int16_t *S, int keepS,
                         uint2 *wta, hipStream_t st, Boundary bd = Boundary{nullptr, 1, 0})
 {
-    with_np(g, [&](auto np, auto part) { launch_path_np<np, part>(g, rx, ry, mode, C, S, keepS, wta, bd, st); });
+    with_np_wide(g, [&](auto np, auto part) { launch_path_np<np, part>(g, rx, ry, mode, C, S, keepS, wta, bd, st); });
 }
 
 // ---- sweep launch dispatch --------------------------------------------------------------------
@@ -737,6 +749,18 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     p.path_w_main = !p.v1 && g.mode == 0 && p.nvol == 1;
     p.path_w_lines = (dbg & SGM_DBG_NO_LANE_GROUPS) != 0;
     p.speckle = e->params.speckleRange >= 0 && e->params.speckleWindowSize > 0;  // upstream's condition for filterSpeckles
+    // D > 512 (16 disparities per lane, NP = 8): the int16 cost pipeline and one k_path launch per
+    // direction with the winner-take-all in the last, whatever the schedule option, the band / chunk / window options
+    // and the schedule bits of SGM_OPT_DEBUG say -- no other kernel has an NP = 8 instantiation.  The batch entries
+    // then run such pairs one after the other (batch_plan: joint needs a chained plan).
+    if (g.NP == 8) {
+        p.v1 = true;
+        p.byte_cost = p.pix_px = p.rows4 = p.chain = p.prepass_g = p.fused_prepass = false;
+        p.overlap = p.fork_early = p.path_w_main = false;
+        p.GWs = 64;
+        p.fused_wta = true;
+        p.nvol = 1;
+    }
     return p;
 }
 
@@ -884,7 +908,9 @@ template <int NP, int RS_T>
 static int launch_hsum_t(const Geom &g, const uint2 *lrec, const uint8_t *rpl, int16_t *HS, int RS, hipStream_t st)
 {
     const int nchunks = cost_chunks(g);
+    // (largest: NP = 8, blockSize 31 -> RS = 32: a 64 KiB ring + 1.3 KiB of records + 7 KiB of planes, of 160 KiB)
     const HsumLds l = hsum_lds_layout(g.NP, RS, COST_XL, g.SW2);
+    if (l.total_bytes > 160 * 1024) return set_err(SGM_ERR_UNSUPPORTED, "k_hsum needs %d bytes of LDS", l.total_bytes);
     if (l.total_bytes > 48 * 1024)
         HIP_TRY(hipFuncSetAttribute((const void *)k_hsum<NP, RS_T>, hipFuncAttributeMaxDynamicSharedMemorySize, l.total_bytes));
     hipLaunchKernelGGL((k_hsum<NP, RS_T>), dim3((unsigned)((int64_t)g.H * nchunks)), dim3(64), l.total_bytes, st, g, lrec, rpl,
@@ -895,7 +921,7 @@ static int launch_hsum(const Geom &g, const uint2 *lrec, const uint8_t *rpl, int
 {
     int RS = 1;  // ring of the last blockSize+1 cost vectors, rounded to a power of two
     while (RS < 2 * g.SW2 + 2) RS <<= 1;
-    return with_np(g, [&](auto np, auto) {
+    return with_np_wide(g, [&](auto np, auto) {
         if (RS == 4) return launch_hsum_t<np, 4>(g, lrec, rpl, HS, RS, st);
         if (RS == 8) return launch_hsum_t<np, 8>(g, lrec, rpl, HS, RS, st);
         if (RS == 16) return launch_hsum_t<np, 16>(g, lrec, rpl, HS, RS, st);
@@ -908,7 +934,9 @@ template <int NP, int RS_T>
 static int launch_hsum_c3_t(const Geom &g, const uint2 *lrec, const uint8_t *rpl, int16_t *HS, int RS, hipStream_t st)
 {
     const int nchunks = cost_chunks(g);
+    // (largest: NP = 8, blockSize 31 -> RS = 32: a 64 KiB ring + 3.8 KiB of records + 20.8 KiB of planes, of 160 KiB)
     const HsumLds l = hsum_c3_lds_layout(g.NP, RS, COST_XL, g.SW2);
+    if (l.total_bytes > 160 * 1024) return set_err(SGM_ERR_UNSUPPORTED, "k_hsum_c3 needs %d bytes of LDS", l.total_bytes);
     if (l.total_bytes > 48 * 1024)
         HIP_TRY(hipFuncSetAttribute((const void *)k_hsum_c3<NP, RS_T>, hipFuncAttributeMaxDynamicSharedMemorySize, l.total_bytes));
     hipLaunchKernelGGL((k_hsum_c3<NP, RS_T>), dim3((unsigned)((int64_t)g.H * nchunks)), dim3(64), l.total_bytes, st, g, lrec, rpl,
@@ -919,7 +947,7 @@ static int launch_hsum_c3(const Geom &g, const uint2 *lrec, const uint8_t *rpl, 
 {
     int RS = 1;  // ring of the last blockSize+1 cost vectors, rounded to a power of two
     while (RS < 2 * g.SW2 + 2) RS <<= 1;
-    return with_np(g, [&](auto np, auto) {
+    return with_np_wide(g, [&](auto np, auto) {
         if (RS == 4) return launch_hsum_c3_t<np, 4>(g, lrec, rpl, HS, RS, st);
         if (RS == 8) return launch_hsum_c3_t<np, 8>(g, lrec, rpl, HS, RS, st);
         if (RS == 16) return launch_hsum_c3_t<np, 16>(g, lrec, rpl, HS, RS, st);
@@ -1511,7 +1539,7 @@ int sgm_debug_plan(const sgm_params *params, int H, int W, int channels, int sch
     out->minX1 = g.minX1;
     out->NP = g.NP;
     out->partial = small_d ? with_gw(p.GWs, g.D, [](auto, auto part) { return (int)decltype(part)::value; })
-                           : with_np(g, [](auto, auto part) { return (int)decltype(part)::value; });
+                           : (int)np_partial(g);
     out->byte_cost = p.byte_cost;
     out->pix_px = p.pix_px;
     out->GWc = p.GWc;
