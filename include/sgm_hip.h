@@ -50,7 +50,9 @@ extern "C" {
 #endif
 
 #define SGM_ABI_VERSION 4   /* 2: sgm_get_headroom, SGM_OPT_PREPASS_ROWS (round 2); 3: sgm_pipeline_batch_device, SGM_OPT_CHAIN_WGS, schedule 2;
-                             * 4: sgm_check, sgm_trim, sgm_compact_points_device_async, SGM_OPT_GROUP_MAX (round 4) */
+                             * 4: sgm_check, sgm_trim, sgm_compact_points_device_async, SGM_OPT_GROUP_MAX (round 4);
+                             * additive since, version unchanged: SGM_OPT_CHANNELS; mode 3; SGM_OPT_CONFIDENCE, SGM_TAP_CONF_RAW,
+                             * SGM_TAP_CONF, sgm_bind_confidence_device (sgm_hip_confidence.h) */
 
 typedef enum {
     SGM_OK = 0,
@@ -90,7 +92,17 @@ typedef enum {
     SGM_TAP_COST = 0,        /* int16 [H][W1][D]  block cost C (without upstream's +P2 bias)     */
     SGM_TAP_AGGR = 1,        /* int16 [H][W1][D]  aggregated cost S (needs sgm_set_option KEEP)  */
     SGM_TAP_DISP_RAW = 2,    /* int16 [H][W]      after WTA / uniqueness / sub-pixel / LR check  */
-    SGM_TAP_DISP_MEDIAN = 3  /* int16 [H][W]      after the 3x3 median                           */
+    SGM_TAP_DISP_MEDIAN = 3, /* int16 [H][W]      after the 3x3 median                           */
+    /* Match confidence (needs SGM_OPT_CONFIDENCE = 1 for that compute, else SGM_ERR_INVALID_ARG).  With S the aggregated
+     * cost of a pixel, best the first d that minimises it, minS = S[best] and far = min of S[d] over |d - best| > 1:
+     *   conf_raw = 100 if far == 0, else (far - minS) * 100 / far      (C integer division; 0 .. 100)
+     * and 0 in the columns no disparity can be matched at (outside minX1 .. minX1 + W1).  For integer u in 0 .. 100
+     * upstream's uniqueness test keeps the pixel iff conf_raw >= u: conf_raw is the largest uniquenessRatio under which the
+     * winner-take-all keeps it, whatever uniquenessRatio and disp12MaxDiff the engine was created with. */
+    SGM_TAP_CONF_RAW = 4,    /* uint8 [H][W]      the margin above                                                */
+    SGM_TAP_CONF = 5         /* uint8 [H][W]      conf_raw where the FINAL disparity (after LR check, median and speckle filter) is
+                              *                   valid, 0 where it is (minDisparity - 1) * 16.  Not held (SGM_ERR_INVALID_ARG) after a
+                              *                   compute that wrote it to a bound pointer instead (sgm_bind_confidence_device) */
 } sgm_tap;
 
 typedef enum {
@@ -110,6 +122,13 @@ typedef enum {
                               * interleaved 3-channel image and stride_bytes is its row pitch in bytes (>= 3 * W); the batch entries'
                               * host arrays are N tight [H][W][3] images.  The pixel cost is the sum of the three channels' costs
                               * (OpenCV's calcPixelCostBT with cn = 3; channel order does not matter); P1 / P2 are not scaled. */
+    SGM_OPT_CONFIDENCE = 10, /* 0 (default) or 1; any other value is refused with SGM_ERR_INVALID_ARG.  1: every compute on the engine
+                              * also produces the per-pixel match confidence (SGM_TAP_CONF_RAW, SGM_TAP_CONF; two uint8 [H][W] maps
+                              * more in device memory).  The disparity outputs do not change.  The winner-take-all then always runs as
+                              * its own pass over S; configurations that fuse it into their last path kernel by default (schedule 0,
+                              * MODE_SGBM with numDisparities > 128, numDisparities > 512) move two volumes more for it.  The internal
+                              * engines of the batch entries inherit the option.  sgm_compute_batch computes as before and returns
+                              * NO per-pair confidence: a host-batch form of the map is a follow-up.  (9: csrc/sgm_debug.h) */
     /* 4 = SGM_OPT_DEBUG: A/B switches for measurements -- not part of this interface (csrc/sgm_debug.h) */
     SGM_OPT_RESERVED_4 = 4
 } sgm_option;
@@ -238,4 +257,7 @@ int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_r
 #ifdef __cplusplus
 }
 #endif
+
+/* the one entry point added with SGM_OPT_CONFIDENCE: sgm_bind_confidence_device (a header of its own, part of this interface) */
+#include "sgm_hip_confidence.h"
 #endif

@@ -14,8 +14,10 @@ LIB_PATH = os.environ.get("SGM_HIP_LIB") or os.path.join(_HERE, "csrc", "libsgm_
 
 SGM_OK = 0
 SGM_TAP_COST, SGM_TAP_AGGR, SGM_TAP_DISP_RAW, SGM_TAP_DISP_MEDIAN = 0, 1, 2, 3
+SGM_TAP_CONF_RAW, SGM_TAP_CONF = 4, 5    # uint8 (H, W) match confidence: the uniqueness margin, and the same masked by the final map
 SGM_OPT_KEEP_AGGR, SGM_OPT_PROFILE, SGM_OPT_SCHEDULE, SGM_OPT_SWEEP_ROWS, SGM_OPT_PREPASS_ROWS, SGM_OPT_CHAIN_WGS, SGM_OPT_GROUP_MAX = 0, 1, 2, 3, 5, 6, 7
 SGM_OPT_CHANNELS = 8    # 1 (default) or 3: interleaved 8-bit channels per image pixel
+SGM_OPT_CONFIDENCE = 10  # 1: every compute also produces the confidence maps (SGM_TAP_CONF_RAW, SGM_TAP_CONF)
 SGM_OPT_DEBUG = 4    # csrc/sgm_debug.h: A/B switches for tools/ and tests/, not part of the public interface
 SGM_OPT_POISON = 9   # csrc/sgm_debug.h: fill every device buffer with a byte (0..255) and arm the same for new ones; -1 disarms (tests only)
 SGM_MAX_STAGES = 32
@@ -31,6 +33,8 @@ EXPORTS = (
     "sgm_init_undistort_rectify_map", "sgm_init_undistort_rectify_map_device",
     "sgm_remap_linear_u8", "sgm_remap_linear_u8_device",
 )
+# include/sgm_hip_confidence.h (included by sgm_hip.h): the entry point added with SGM_OPT_CONFIDENCE
+CONFIDENCE_EXPORTS = ("sgm_bind_confidence_device",)
 
 
 class SgmParams(C.Structure):
@@ -107,6 +111,7 @@ def load():
     L.sgm_valid_mask_device.argtypes = [vp, vp, vp, i64, vp]
     L.sgm_pipeline_device.argtypes = [vp, vp, vp, i32, i32, i64, vp, vp, vp, vp]
     L.sgm_pipeline_batch_device.argtypes = [vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp]
+    L.sgm_bind_confidence_device.argtypes = [vp, i32, vp]
     L.sgm_synchronize.argtypes = [vp]
     L.sgm_get_stage_times.argtypes = [vp, C.POINTER(SgmStageTimes)]
     L.sgm_algorithmic_bytes.argtypes = [pp, i32, i32, i32]
@@ -118,7 +123,7 @@ def load():
     # csrc/sgm_debug.h, outside EXPORTS: the plan readout for tests
     L.sgm_debug_plan.argtypes = [pp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(SgmDebugPlan)]
     L.sgm_debug_plan.restype = i32
-    for name in EXPORTS:
+    for name in EXPORTS + CONFIDENCE_EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("sgm_abi_version", "sgm_device_count"):
             fn.restype = i32

@@ -108,166 +108,46 @@ __global__ __launch_bounds__(64) void k_wta_t(Geom g, const int16_t *__restrict_
                                               const int16_t *__restrict__ S2 = nullptr, const int16_t *__restrict__ S3 = nullptr,
                                               const int16_t *__restrict__ S4 = nullptr, const int16_t *__restrict__ S5 = nullptr)
 {
-    constexpr bool TWO = NV >= 2, THREE = NV >= 3, FOUR = NV >= 4, FIVE = NV >= 5;
-    static_assert(NV >= 1 && NV <= 5, "volumes: 1 .. 5");
-    extern __shared__ __attribute__((aligned(16))) uint8_t rows[];
-    const int lane = threadIdx.x, D = LG >= 0 ? (8 << LG) : g.D, W1 = g.W1;
-    const int stride = wta_t_stride(D);
-    const int cpr = D * 2 / 16;  // 16-byte chunks per pixel row; a lane moves cpr chunks per block
-    const int64_t nblocks = (npix + 63) / 64;
-    constexpr int PF = LG < 0 ? 8 : (LG >= 5 ? 32 : (1 << LG));  // chunks per lane held in registers
-    uint4 v[PF], v2[TWO ? PF : 1], v3[THREE ? PF : 1], v4[FOUR ? PF : 1], v5[FIVE ? PF : 1];
-    // chunk c = lane + 64 k of the block's contiguous 64 * D * 2 bytes: loads with a clamped index
-    // (no branch between them), committed to the padded LDS rows afterwards
-    auto issue = [&](int64_t blk, int k0) {
-        const int64_t left = npix - blk * 64;  // (integer compare: min<int64_t>() goes through v_min_f64)
-        const int total = (left < 64 ? (int)left : 64) * cpr;
-        const uint4 *src = reinterpret_cast<const uint4 *>(S + blk * 64 * D);
-#pragma unroll
-        for (int u = 0; u < PF; u++) v[u] = src[min(lane + 64 * (k0 + u), total - 1)];
-        if constexpr (TWO) {
-            const uint4 *src2 = reinterpret_cast<const uint4 *>(S2 + blk * 64 * D);
-#pragma unroll
-            for (int u = 0; u < PF; u++) v2[u] = src2[min(lane + 64 * (k0 + u), total - 1)];
-        }
-        if constexpr (THREE) {
-            const uint4 *src3 = reinterpret_cast<const uint4 *>(S3 + blk * 64 * D);
-#pragma unroll
-            for (int u = 0; u < PF; u++) v3[u] = src3[min(lane + 64 * (k0 + u), total - 1)];
-        }
-        if constexpr (FOUR && !FIVE) {
-            const uint4 *src4 = reinterpret_cast<const uint4 *>(S4 + blk * 64 * D);
-#pragma unroll
-            for (int u = 0; u < PF; u++) v4[u] = src4[min(lane + 64 * (k0 + u), total - 1)];
-        }
-        if constexpr (FIVE) {
-            const uint4 *src4 = reinterpret_cast<const uint4 *>(S4 + blk * 64 * D);
-            const uint4 *src5 = reinterpret_cast<const uint4 *>(S5 + blk * 64 * D);
-#pragma unroll
-            for (int u = 0; u < PF; u++) v4[u] = src4[min(lane + 64 * (k0 + u), total - 1)];
-#pragma unroll
-            for (int u = 0; u < PF; u++) v5[u] = src5[min(lane + 64 * (k0 + u), total - 1)];
-        }
-    };
-    auto summed = [&](int u) {  // chunk u of the cost rows: S, or sat(S + S2)
-        uint4 r = v[u];
-        if constexpr (TWO) {
-            r.x = pk_adds_s(r.x, v2[u].x);
-            r.y = pk_adds_s(r.y, v2[u].y);
-            r.z = pk_adds_s(r.z, v2[u].z);
-            r.w = pk_adds_s(r.w, v2[u].w);
-        }
-        if constexpr (THREE) {
-            r.x = pk_adds_s(r.x, v3[u].x);
-            r.y = pk_adds_s(r.y, v3[u].y);
-            r.z = pk_adds_s(r.z, v3[u].z);
-            r.w = pk_adds_s(r.w, v3[u].w);
-        }
-        if constexpr (FOUR && !FIVE) {
-            r.x = pk_adds_s(r.x, v4[u].x);
-            r.y = pk_adds_s(r.y, v4[u].y);
-            r.z = pk_adds_s(r.z, v4[u].z);
-            r.w = pk_adds_s(r.w, v4[u].w);
-        }
-        if constexpr (FIVE) {
-            r.x = pk_adds_s(pk_adds_s(r.x, v4[u].x), v5[u].x);
-            r.y = pk_adds_s(pk_adds_s(r.y, v4[u].y), v5[u].y);
-            r.z = pk_adds_s(pk_adds_s(r.z, v4[u].z), v5[u].z);
-            r.w = pk_adds_s(pk_adds_s(r.w, v4[u].w), v5[u].w);
-        }
-        return r;
-    };
-    auto commit = [&](int64_t blk, int k0) {
-        const int64_t left = npix - blk * 64;
-        const int total = (left < 64 ? (int)left : 64) * cpr;
-#pragma unroll
-        for (int u = 0; u < PF; u++) {
-            const int c = lane + 64 * (k0 + u);
-            if (c < total) {
-                const int px = LG >= 0 ? c >> LG : c / cpr, w = c - px * cpr;
-                uint2 *dst = reinterpret_cast<uint2 *>(rows + px * stride + w * 16);
-                const uint4 q = summed(u);
-                dst[0] = make_uint2(q.x, q.y);
-                dst[1] = make_uint2(q.z, q.w);
-            }
-        }
-    };
-    int64_t blk = blockIdx.x;
-    if (LG >= 0 && blk < nblocks) issue(blk, 0);
-    for (; blk < nblocks; blk += gridDim.x) {
-    const int64_t p0 = blk * 64;
-    const int np = npix - p0 < 64 ? (int)(npix - p0) : 64;
-    __syncthreads();  // (one wave per block: orders the LDS traffic of consecutive blocks)
-    if (LG >= 0) {
-        commit(blk, 0);
-        if (LG == 6) {  // D = 512: the second half of the rows, not prefetched
-            issue(blk, PF);
-            commit(blk, PF);
-        }
-    } else {
-        for (int k0 = 0; k0 < cpr; k0 += PF) {  // cpr need not be a multiple of PF: clamped loads, guarded commits
-            issue(blk, k0);
-            const int total = np * cpr;
-#pragma unroll
-            for (int u = 0; u < PF; u++) {
-                const int c = lane + 64 * (k0 + u);
-                if (k0 + u < cpr && c < total) {
-                    const int px = c / cpr, w = c - px * cpr;
-                    uint2 *dst = reinterpret_cast<uint2 *>(rows + px * stride + w * 16);
-                    const uint4 q = summed(u);
-                    dst[0] = make_uint2(q.x, q.y);
-                    dst[1] = make_uint2(q.z, q.w);
-                }
-            }
-        }
+    constexpr bool CONF = false;
+    [[maybe_unused]] uint8_t *const conf = nullptr;
+#include "kernels_wta_body.h"
+}
+
+// CONF (SGM_OPT_CONFIDENCE): the lane also stores the pixel's uniqueness margin as a byte --
+//   conf_raw = 100 if far == 0, else (far - minS) * 100 / far      (C division; 0 .. 100)
+// with far the smallest S outside best-1 .. best+1, the quantity the positive-weight form already has.  For integer
+// u in 0 .. 100 upstream's test keeps a pixel iff far * (100 - u) >= minS * 100 iff conf_raw >= u, so the byte is the
+// largest uniquenessRatio under which the pixel survives.  It does not depend on uniquenessRatio; the CONF form takes the
+// engine's ratio at run time (far for a positive weight, the per-d products otherwise), one instantiation for both.
+// conf is the uint8 [H][W] map conf_raw (columns outside minX1 .. minX1 + W1 are not written: the engine clears the map first).
+// The body is the text of k_wta_t's (kernels_wta_body.h), so that k_wta_t itself compiles to what it was without the option.
+template <int LG, int NV = 1>
+__global__ __launch_bounds__(64) void k_wta_conf_t(Geom g, const int16_t *__restrict__ S, uint2 *__restrict__ wta, int64_t npix,
+                                                   const int16_t *__restrict__ S2, const int16_t *__restrict__ S3,
+                                                   const int16_t *__restrict__ S4, const int16_t *__restrict__ S5,
+                                                   uint8_t *__restrict__ conf)
+{
+    constexpr bool CONF = true, POSW = false;
+#include "kernels_wta_body.h"
+}
+
+// conf = conf_raw where the final disparity (after LR check, median and speckle filter) is valid, 0 where it is the
+// invalid value; VEC: four pixels per thread (4-byte aligned maps, 8-byte aligned disparities), the tail pixel by pixel
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_conf_final(const uint8_t *__restrict__ conf_raw, const int16_t *__restrict__ disp,
+                                                    int invalid, uint8_t *__restrict__ out, int64_t n)
+{
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * (VEC ? 4 : 1);
+    if (VEC && i + 4 <= n) {
+        const uint32_t c = *reinterpret_cast<const uint32_t *>(conf_raw + i);
+        const uint2 d = *reinterpret_cast<const uint2 *>(disp + i);
+        const int d0 = (int16_t)(d.x & 0xffffu), d1 = (int16_t)(d.x >> 16), d2 = (int16_t)(d.y & 0xffffu), d3 = (int16_t)(d.y >> 16);
+        const uint32_t m = (d0 != invalid ? 0xffu : 0u) | (d1 != invalid ? 0xff00u : 0u) | (d2 != invalid ? 0xff0000u : 0u) |
+                           (d3 != invalid ? 0xff000000u : 0u);
+        *reinterpret_cast<uint32_t *>(out + i) = c & m;
+        return;
     }
-    __syncthreads();
-    if (LG >= 0 && blk + gridDim.x < nblocks) issue(blk + gridDim.x, 0);  // next block's loads fly during this scan
-    if (lane < np) {
-    const uint8_t *row = rows + lane * stride;
-    // pass 1
-    uint32_t key = 0xffffffffu;
-#pragma unroll 64  // fully unrolled for D <= 256: constant offsets and disparity indices, many LDS reads in flight
-    for (int d0 = 0; d0 < D; d0 += 4) {
-        const uint2 v = *reinterpret_cast<const uint2 *>(row + d0 * 2);
-        const uint32_t k0 = (v.x << 16) | (uint32_t)d0, k1 = (v.x & 0xffff0000u) | (uint32_t)(d0 + 1);
-        const uint32_t k2 = (v.y << 16) | (uint32_t)(d0 + 2), k3 = (v.y & 0xffff0000u) | (uint32_t)(d0 + 3);
-        key = min(min(key, min(k0, k1)), min(k2, k3));
-    }
-    const int minS = (int)(key >> 16), best = (int)(key & 0xffffu);
-    const int wgt = 100 - g.uniq, thr = minS * 100;
-    bool reject;
-    // S[best -+ 1] for the sub-pixel step (clamped: k_select uses them only for 0 < best < D-1)
-    const int dm = max(best - 1, 0), dp = min(best + 1, D - 1);
-    uint16_t *rw = reinterpret_cast<uint16_t *>(rows + lane * stride);
-    const uint32_t nb = (uint32_t)rw[dm] | ((uint32_t)rw[dp] << 16);
-    if (POSW) {
-        // wgt > 0: one comparison against the smallest S outside best-1..best+1.  The row in LDS is
-        // this lane's alone and not needed again: overwrite those three entries with MAX_COST and
-        // take a plain packed minimum of the row.
-        rw[dm] = (uint16_t)SGM_MAX_COST;
-        rw[best] = (uint16_t)SGM_MAX_COST;
-        rw[dp] = (uint16_t)SGM_MAX_COST;
-        uint32_t far = SGM_SENT;
-#pragma unroll 64
-        for (int d0 = 0; d0 < D; d0 += 4) {
-            const uint2 v = *reinterpret_cast<const uint2 *>(row + d0 * 2);
-            far = pk_min_s(far, pk_min_s(v.x, v.y));
-        }
-        reject = (int)min(far & 0xffffu, far >> 16) * wgt < thr;
-    } else {
-        reject = false;
-        for (int d = 0; d < D; d++) {
-            const int sv = *reinterpret_cast<const uint16_t *>(row + d * 2);
-            reject |= (sv * wgt < thr) && (abs(best - d) > 1);
-        }
-    }
-    reject = reject || (minS == SGM_MAX_COST);
-    const int64_t p = p0 + lane;
-    const int y = (int)(p / W1), x = (int)(p - (int64_t)y * W1);
-    wta[(int64_t)y * g.W + g.minX1 + x] = make_uint2(reject ? 0xffffffffu : key, nb);
-    }  // lane < np
-    }  // blocks of this workgroup
+    for (int64_t j = i; j < n && j < i + (VEC ? 4 : 1); j++) out[j] = (int)disp[j] != invalid ? conf_raw[j] : (uint8_t)0;
 }
 
 __device__ __forceinline__ void cswap(int &a, int &b)

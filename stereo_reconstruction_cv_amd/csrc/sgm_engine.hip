@@ -248,6 +248,9 @@ struct sgm_engine {
     int debug = 0;       // timing experiments (SweepArgs::dbg)
     int prepass_rows = 0;  // rows per chunk of the boundary pre-pass (0 = automatic, about 135, a multiple of 8)
     int cn = 1;          // SGM_OPT_CHANNELS: 1 or 3 interleaved 8-bit channels per image pixel
+    int confidence = 0;  // SGM_OPT_CONFIDENCE: every compute also produces the uniqueness margin (conf_raw, conf)
+    int conf_last = 0;   // what the last compute on this engine left: 0 no maps, 1 conf_raw + conf, 2 conf went to a bound pointer
+    std::vector<void *> conf_bind;        // sgm_bind_confidence_device: where the next image call writes its pairs' conf
     // sgm_compute_batch: up to three pairs in flight = this engine + two peers (own stream and device
     // buffers), each with page-locked staging buffers for the images and the disparity map
     sgm_engine *peer = nullptr, *peer2 = nullptr;
@@ -285,6 +288,7 @@ struct sgm_engine {
     DevBuf bndL, bndL2;                 // band-boundary state of the sweep pre-pass (down / up)
     DevBuf pstate, pstate2;             // line state between the row chunks of the pre-pass (ping-pong, down / up)
     DevBuf disp_raw, disp_med, disp_out;  // int16 [H][W]
+    DevBuf conf_raw, conf;              // uint8 [H][W], SGM_OPT_CONFIDENCE only: the margin of the winner-take-all; masked by the final map
     DevBuf label, csize, rlen;          // int32 [H][W] each
     DevBuf f32, xyz, mask, minkey;      // host-pointer post stages
     DevBuf rmap1, rmap2, rsrc, rdst;    // host-pointer rectification stages
@@ -718,14 +722,17 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     // 0.44 + 0.10).  debug 2 forces the fused form everywhere, debug 2048 the separate one (A/B, cross-check).
     // (The v1 schedule always fuses it into its last path kernel.)
     // MODE_HH4: always the separate pass (the axis-only sweeps have no SWEEP_LAST form).
-    p.fused_wta = p.v1 || (!p.axis && !(dbg & SGM_DBG_WTA_SEPARATE) && (((dbg & SGM_DBG_WTA_IN_LAST_PATH) && !p.rows4) ||
-                                                                        (g.mode == 0 && ((dbg & SGM_DBG_NO_LANE_GROUPS) || g.D > 128))));
+    // SGM_OPT_CONFIDENCE: always the separate pass -- the confidence byte comes from k_wta_conf_t alone, so
+    // the routes that fuse by default (v1, MODE_SGBM with D > 128, D > 512) store S once more and read it back: 2 V more.
+    const bool conf = e->confidence != 0;
+    p.fused_wta = !conf && (p.v1 || (!p.axis && !(dbg & SGM_DBG_WTA_SEPARATE) && (((dbg & SGM_DBG_WTA_IN_LAST_PATH) && !p.rows4) ||
+                                                                                  (g.mode == 0 && ((dbg & SGM_DBG_NO_LANE_GROUPS) || g.D > 128)))));
     // MODE_SGBM with the separate winner-take-all (D <= 128): the fifth path (in-row, right to left) needs
     // nothing but C, so it runs on the auxiliary stream from here on, as a FIRST pass into a volume of its
     // own (2 V of traffic instead of the 3 V of "S +="), beside the pre-pass and the sweep -- which at these
     // D are bound by instruction issue, not by HBM; k_wta_t adds the two volumes while it stages them.
     // debug 65536: the fifth path after the sweep, accumulating into S (A/B).
-    const bool two_vol = g.mode == 0 && !p.fused_wta && g.D <= 128 && !(dbg & SGM_DBG_NO_LANE_GROUPS) &&
+    const bool two_vol = g.mode == 0 && !p.fused_wta && !p.v1 && g.D <= 128 && !(dbg & SGM_DBG_NO_LANE_GROUPS) &&
                          !(dbg & SGM_DBG_FIFTH_PATH_AFTER_SWEEP);
     // D <= 64 (small-D schedule): the OTHER in-row path (left to right) needs nothing but C either.  It used to follow
     // the element-wise vertical kernel as "S +=" on the main stream -- a chain of W1 dependent steps on the
@@ -758,7 +765,7 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
         p.byte_cost = p.pix_px = p.rows4 = p.chain = p.prepass_g = p.fused_prepass = false;
         p.overlap = p.fork_early = p.path_w_main = false;
         p.GWs = 64;
-        p.fused_wta = true;
+        p.fused_wta = !conf;
         p.nvol = 1;
     }
     return p;
@@ -781,7 +788,7 @@ static size_t plan_bytes_held(const sgm_engine *e)
 {
     const DevBuf *bufs[] = {&e->lrec, &e->rplanes, &e->hsum, &e->cost, &e->aggr, &e->aggr2, &e->aggr3, &e->aggr4, &e->aggr5,
                             &e->wta, &e->disp_raw, &e->disp_med, &e->headroom, &e->bndL, &e->bndL2, &e->pstate, &e->pstate2,
-                            &e->label, &e->csize, &e->rlen, &e->chain_ctl, &e->chain_err};
+                            &e->label, &e->csize, &e->rlen, &e->chain_ctl, &e->chain_err, &e->conf_raw, &e->conf};
     size_t n = 0;
     for (const DevBuf *b : bufs) n += b->cap;
     return n;
@@ -818,6 +825,7 @@ static int ensure_plan_buffers(sgm_engine *e, const Plan &p, int H, int W)
     if ((rc = e->wta.ensure(npx * 8))) return rc;
     if ((rc = e->disp_raw.ensure(npx * 2))) return rc;
     if ((rc = e->disp_med.ensure(npx * 2))) return rc;
+    if (e->confidence && ((rc = e->conf_raw.ensure(npx)) || (rc = e->conf.ensure(npx)))) return rc;
     if ((rc = e->headroom.ensure(8))) return rc;
     e->g.hr = (uint32_t *)e->headroom.p;
     if (g.W1 > 0 && !p.v1 && p.nbands > 1 && p.nvol < 4) {
@@ -1072,40 +1080,51 @@ static void launch_axis_paths4(const Geom &g, int GW, const int16_t *C, int16_t 
 // ---- winner-take-all launch ------------------------------------------------------------------
 // k_wta_t over S plus NV - 1 more volumes.  LG = log2(D / 8) for the powers of two that have an instantiation (NV = 1:
 // D = 16 .. 512; 2: up to 128; 3, 4, 5: up to 64), -1 (any D) otherwise
-template <bool POSW, int LG, int NV>
-static int launch_wta_t(const Geom &g, int16_t *const Sv[5], uint2 *wta, int64_t npix, hipStream_t st)
+// CONF: k_wta_conf_t, which also writes the confidence byte to `conf` (one instantiation for either sign of the weight)
+template <bool POSW, int LG, int NV, bool CONF>
+static int launch_wta_t(const Geom &g, int16_t *const Sv[5], uint2 *wta, uint8_t *conf, int64_t npix, hipStream_t st)
 {
     const size_t lds = (size_t)64 * wta_t_stride(g.D);
     // persistent blocks: LDS (64 padded rows) allows four waves per CU; each loops over its share
     dim3 grid((unsigned)std::min<int64_t>((npix + 63) / 64, 4 * 256)), block(64);
-    if (lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)k_wta_t<POSW, LG, NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_wta_t<POSW, LG, NV>), grid, block, lds, st, g, (const int16_t *)Sv[0], wta, npix,
-                       (const int16_t *)Sv[1], (const int16_t *)Sv[2], (const int16_t *)Sv[3], (const int16_t *)Sv[4]);
+    if constexpr (CONF) {
+        if (lds > 160 * 1024) return set_err(SGM_ERR_UNSUPPORTED, "k_wta_conf_t needs %zu bytes of LDS", lds);
+        if (lds > 48 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void *)k_wta_conf_t<LG, NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_wta_conf_t<LG, NV>), grid, block, lds, st, g, (const int16_t *)Sv[0], wta, npix, (const int16_t *)Sv[1],
+                           (const int16_t *)Sv[2], (const int16_t *)Sv[3], (const int16_t *)Sv[4], conf);
+    } else {
+        if (lds > 48 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void *)k_wta_t<POSW, LG, NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_wta_t<POSW, LG, NV>), grid, block, lds, st, g, (const int16_t *)Sv[0], wta, npix,
+                           (const int16_t *)Sv[1], (const int16_t *)Sv[2], (const int16_t *)Sv[3], (const int16_t *)Sv[4]);
+    }
     return SGM_OK;
 }
-template <bool POSW, int NV, int LG = 1>
-static int launch_wta_lg(int lg, const Geom &g, int16_t *const Sv[5], uint2 *wta, int64_t npix, hipStream_t st)
+template <bool POSW, int NV, bool CONF, int LG = 1>
+static int launch_wta_lg(int lg, const Geom &g, int16_t *const Sv[5], uint2 *wta, uint8_t *conf, int64_t npix, hipStream_t st)
 {
-    if constexpr (LG > (NV == 1 ? 6 : NV == 2 ? 4 : 3)) return launch_wta_t<POSW, -1, NV>(g, Sv, wta, npix, st);
-    else if (lg == LG) return launch_wta_t<POSW, LG, NV>(g, Sv, wta, npix, st);
-    else return launch_wta_lg<POSW, NV, LG + 1>(lg, g, Sv, wta, npix, st);
+    if constexpr (LG > (NV == 1 ? 6 : NV == 2 ? 4 : 3)) return launch_wta_t<POSW, -1, NV, CONF>(g, Sv, wta, conf, npix, st);
+    else if (lg == LG) return launch_wta_t<POSW, LG, NV, CONF>(g, Sv, wta, conf, npix, st);
+    else return launch_wta_lg<POSW, NV, CONF, LG + 1>(lg, g, Sv, wta, conf, npix, st);
 }
-static int launch_wta(const Geom &g, int nvol, int16_t *const Sv[5], uint2 *wta, hipStream_t st)
+// conf: null, or the conf_raw map of a confidence compute (already cleared)
+static int launch_wta(const Geom &g, int nvol, int16_t *const Sv[5], uint2 *wta, uint8_t *conf, hipStream_t st)
 {
     const int64_t npix = (int64_t)g.H * g.W1;
     int lg = -1;  // log2(D / 8) when D is a power of two
     for (int q = 1; q <= 6; q++)
         if (g.D == (8 << q)) lg = q;
-    auto go = [&](auto posw) {
-        constexpr bool POSW = decltype(posw)::value;
-        if (nvol == 5) return launch_wta_lg<POSW, 5>(lg, g, Sv, wta, npix, st);
-        if (nvol == 4) return launch_wta_lg<POSW, 4>(lg, g, Sv, wta, npix, st);
-        if (nvol == 3) return launch_wta_lg<POSW, 3>(lg, g, Sv, wta, npix, st);
-        if (nvol == 2) return launch_wta_lg<POSW, 2>(lg, g, Sv, wta, npix, st);
-        return launch_wta_lg<POSW, 1>(lg, g, Sv, wta, npix, st);
+    auto go = [&](auto posw, auto cf) {
+        constexpr bool POSW = decltype(posw)::value, CONF = decltype(cf)::value;
+        if (nvol == 5) return launch_wta_lg<POSW, 5, CONF>(lg, g, Sv, wta, conf, npix, st);
+        if (nvol == 4) return launch_wta_lg<POSW, 4, CONF>(lg, g, Sv, wta, conf, npix, st);
+        if (nvol == 3) return launch_wta_lg<POSW, 3, CONF>(lg, g, Sv, wta, conf, npix, st);
+        if (nvol == 2) return launch_wta_lg<POSW, 2, CONF>(lg, g, Sv, wta, conf, npix, st);
+        return launch_wta_lg<POSW, 1, CONF>(lg, g, Sv, wta, conf, npix, st);
     };
-    return g.uniq < 100 ? go(std::true_type()) : go(std::false_type());
+    if (conf) return go(std::false_type(), std::true_type());
+    return g.uniq < 100 ? go(std::true_type(), std::false_type()) : go(std::false_type(), std::false_type());
 }
 
 // ---- the stages of one compute -----------------------------------------------------------------
@@ -1223,7 +1242,7 @@ static int fork_in_row(sgm_engine *e, const Plan &p)
 }
 
 // v1 schedule: one kernel per direction, vertical-ish first, horizontal last (WTA)
-static int paths_v1(sgm_engine *e)
+static int paths_v1(sgm_engine *e, const Plan &p)
 {
     struct Dir { int rx, ry; const char *name; };
     static const Dir dirs[8] = {{0, 1, "path_S"}, {1, 1, "path_SE"}, {-1, 1, "path_SW"}, {0, -1, "path_N"},
@@ -1232,8 +1251,9 @@ static int paths_v1(sgm_engine *e)
     for (int k = 0; k < 8; k++) {
         if (g.mode == 0 && k >= 3 && k < 6) continue;  // (the upward directions: MODE_HH only)
         if (g.mode == 3 && dirs[k].rx != 0 && dirs[k].ry != 0) continue;  // (MODE_HH4: no diagonals)
-        const int mode = k == 0 ? PATH_FIRST : (k == 7 ? PATH_LAST : PATH_ACCUM);
-        int rc = run_stage(e, dirs[k].name, e->stream, [&] {
+        // (SGM_OPT_CONFIDENCE: the last direction only accumulates; k_wta_conf_t follows)
+        const int mode = k == 0 ? PATH_FIRST : (k == 7 && p.fused_wta ? PATH_LAST : PATH_ACCUM);
+        int rc = run_stage(e, k == 7 && !p.fused_wta ? "path_W" : dirs[k].name, e->stream, [&] {
             launch_path(g, dirs[k].rx, dirs[k].ry, mode, (const int16_t *)e->cost.p, (int16_t *)e->aggr.p, k == 7 ? e->keep_aggr : 0,
                         (uint2 *)e->wta.p, e->stream);
             return 1;
@@ -1349,11 +1369,12 @@ static int stage_wta(sgm_engine *e, const Plan &p)
 {
     if (p.fused_wta) return SGM_OK;
     const Geom &g = e->g;
-    return run_stage(e, "wta", e->stream, [&] {
+    uint8_t *conf = e->confidence ? (uint8_t *)e->conf_raw.p : nullptr;
+    return run_stage(e, conf ? "wta_conf" : "wta", e->stream, [&] {
         int16_t *const Sv[5] = {(int16_t *)e->aggr.p, p.nvol >= 2 ? (int16_t *)e->aggr2.p : nullptr,
                                 p.nvol >= 3 ? (int16_t *)e->aggr3.p : nullptr, p.nvol >= 4 ? (int16_t *)e->aggr4.p : nullptr,
                                 p.nvol >= 5 ? (int16_t *)e->aggr5.p : nullptr};
-        if (int rc = launch_wta(g, p.nvol, Sv, (uint2 *)e->wta.p, e->stream)) return rc;
+        if (int rc = launch_wta(g, p.nvol, Sv, (uint2 *)e->wta.p, conf, e->stream)) return rc;
         if (e->keep_aggr) {  // the volume a caller inspects is the whole sum
             const int64_t n8 = (int64_t)g.rowsz * g.H / 8;  // rowsz = W1 * D is a multiple of 16
             for (int k = 1; k < 5; k++)
@@ -1393,8 +1414,29 @@ static int stage_median_speckle(sgm_engine *e, const Plan &p, int16_t *d_disp)
     });
 }
 
+// SGM_OPT_CONFIDENCE: conf = conf_raw masked by the final map, behind the speckle filter on the pair's stream; into the
+// engine's buffer, or to the pointer bound for this pair (sgm_bind_confidence_device)
+static int stage_confidence(sgm_engine *e, const int16_t *d_disp, uint8_t *d_conf)
+{
+    const int64_t n = (int64_t)e->g.H * e->g.W;
+    uint8_t *out = d_conf ? d_conf : (uint8_t *)e->conf.p;
+    e->conf_last = d_conf ? 2 : 1;
+    return run_stage(e, "conf", e->stream, [&] {
+        const uint8_t *raw = (const uint8_t *)e->conf_raw.p;
+        const bool vec = (((uintptr_t)raw | (uintptr_t)out) & 3) == 0 && ((uintptr_t)d_disp & 7) == 0;
+        if (vec)
+            hipLaunchKernelGGL(k_conf_final<true>, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, e->stream, raw, d_disp,
+                               e->g.invalid_scaled, out, n);
+        else
+            hipLaunchKernelGGL(k_conf_final<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, raw, d_disp,
+                               e->g.invalid_scaled, out, n);
+        return 1;
+    });
+}
+
+// d_conf: SGM_OPT_CONFIDENCE only -- where this pair's final confidence map goes (null: the engine's own buffer)
 static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_right, int H, int W,
-                       int64_t stride, int16_t *d_disp, int phases = PH_ALL)
+                       int64_t stride, int16_t *d_disp, int phases = PH_ALL, uint8_t *d_conf = nullptr)
 {
     if (!e || !d_left || !d_right || !d_disp) return set_err(SGM_ERR_INVALID_ARG, "null pointer");
     if (H <= 0 || W < 2 || stride < (int64_t)W * e->cn)
@@ -1413,6 +1455,7 @@ static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_ri
         e->nevents = 0;
         e->last_end_ev = -1;
         e->plan = p;
+        e->conf_last = 0;
     } else {
         stage_break(e);
     }
@@ -1426,6 +1469,10 @@ static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_ri
         // no column can be matched: the whole map is invalid (upstream early-out), then median
         // and speckle act on a constant image
         const int64_t npx = (int64_t)H * W;
+        if (e->confidence) {
+            HIP_TRY(hipMemsetAsync(e->conf_raw.p, 0, (size_t)npx, e->stream));
+            stage_break(e);
+        }
         rc = run_stage(e, "fill_invalid", e->stream, [&] {
             hipLaunchKernelGGL(k_fill_i16, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, e->stream, (int16_t *)e->disp_raw.p, npx,
                                (int16_t)e->g.invalid_scaled);
@@ -1435,11 +1482,17 @@ static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_ri
     } else {
         if (do_pre && ((rc = stage_features(e, p, d_left, d_right, stride)) || (rc = stage_cost(e, p)) || (rc = fork_in_row(e, p))))
             return rc;
-        if (do_mid && (rc = p.v1 ? paths_v1(e) : paths_fused(e, p))) return rc;
+        if (do_mid && (rc = p.v1 ? paths_v1(e, p) : paths_fused(e, p))) return rc;
         if (!do_post) return SGM_OK;
-        if ((rc = stage_join(e, p)) || (rc = stage_wta(e, p)) || (rc = stage_select(e))) return rc;
+        if ((rc = stage_join(e, p))) return rc;
+        if (e->confidence) {  // columns no disparity can be matched at keep 0: k_wta_conf_t writes minX1 .. minX1 + W1 only
+            HIP_TRY(hipMemsetAsync(e->conf_raw.p, 0, (size_t)H * W, e->stream));
+            stage_break(e);
+        }
+        if ((rc = stage_wta(e, p)) || (rc = stage_select(e))) return rc;
     }
-    return stage_median_speckle(e, p, d_disp);
+    if ((rc = stage_median_speckle(e, p, d_disp)) || !e->confidence) return rc;
+    return stage_confidence(e, d_disp, d_conf);
 }
 
 static int run_to_float(sgm_engine *e, const int16_t *d_disp, int64_t n, float *d_out)
@@ -1600,7 +1653,7 @@ static void release_buffers(sgm_engine *e)
 {
     DevBuf *bufs[] = {&e->in_left, &e->in_right, &e->lrec, &e->rplanes, &e->hsum, &e->cost, &e->aggr, &e->aggr2, &e->rmap1, &e->rmap2, &e->rsrc, &e->rdst, &e->wta, &e->bndL, &e->bndL2, &e->pstate, &e->pstate2,
                       &e->disp_raw, &e->disp_med, &e->disp_out, &e->label, &e->csize, &e->rlen, &e->f32, &e->xyz, &e->mask,
-                      &e->minkey, &e->ccount, &e->cpts, &e->crgb, &e->crgb_in, &e->headroom, &e->chain_ctl, &e->chain_err, &e->aggr3, &e->aggr4, &e->aggr5};
+                      &e->minkey, &e->ccount, &e->cpts, &e->crgb, &e->crgb_in, &e->headroom, &e->chain_ctl, &e->chain_err, &e->aggr3, &e->aggr4, &e->aggr5, &e->conf_raw, &e->conf};
     for (DevBuf *b : bufs) (void)b->release();
     for (auto &slot : e->io)
         for (DevBuf &b : slot) (void)b.release();
@@ -1619,6 +1672,7 @@ static int poison_buffers(sgm_engine *e, int byte)
                       &e->aggr5, &e->wta, &e->bndL, &e->bndL2, &e->pstate, &e->pstate2, &e->disp_raw, &e->disp_med, &e->disp_out,
                       &e->label, &e->csize, &e->rlen, &e->f32, &e->xyz, &e->mask, &e->minkey, &e->rmap1, &e->rmap2, &e->rsrc,
                       &e->rdst, &e->ccount, &e->cpts, &e->crgb, &e->crgb_in, &e->headroom, &e->chain_ctl, &e->chain_err,
+                      &e->conf_raw, &e->conf,
                       &e->io[0][0], &e->io[0][1], &e->io[0][2], &e->io[0][3], &e->io[0][4],
                       &e->io[1][0], &e->io[1][1], &e->io[1][2], &e->io[1][3], &e->io[1][4]};
     static_assert(sizeof(e->io) == 10 * sizeof(DevBuf), "poison_buffers names every slot of io");
@@ -1698,6 +1752,11 @@ int sgm_set_option(sgm_engine *e, int option, int value)
             return set_err(SGM_ERR_INVALID_ARG, "SGM_OPT_CHANNELS %d: only 1 and 3 interleaved 8-bit channels are supported", value);
         e->cn = value;
     }
+    else if (option == SGM_OPT_CONFIDENCE) {
+        if (value != 0 && value != 1) return set_err(SGM_ERR_INVALID_ARG, "SGM_OPT_CONFIDENCE %d: 0 (off) or 1 (on)", value);
+        e->confidence = value;
+        if (!value) e->conf_bind.clear();
+    }
     else if (option == SGM_OPT_POISON) {
         // csrc/sgm_debug.h: 0..255 fills every buffer now and arms DevBuf::ensure; anything else disarms
         g_poison_byte = value >= 0 && value <= 255 ? value : -1;
@@ -1761,10 +1820,38 @@ int sgm_trim(sgm_engine *e)
     return check_chain(e);
 }
 
+// The binding of sgm_bind_confidence_device belongs to the next image call, whatever becomes of that call: taken off the
+// engine here.  *out: the n pointers (empty: none bound).
+static int take_conf_binding(sgm_engine *e, int n, std::vector<void *> *out)
+{
+    out->clear();
+    out->swap(e->conf_bind);
+    if (!out->empty() && (int)out->size() != n)
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_bind_confidence_device bound %d maps, this call has %d pair(s)", (int)out->size(), n);
+    return SGM_OK;
+}
+
+int sgm_bind_confidence_device(sgm_engine *e, int N, void *const *d_conf_u8)
+{
+    if (!e) return set_err(SGM_ERR_INVALID_ARG, "engine is null");
+    e->conf_bind.clear();
+    if (N == 0) return SGM_OK;
+    if (N < 0 || !d_conf_u8) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
+    if (!e->confidence) return set_err(SGM_ERR_INVALID_ARG, "sgm_bind_confidence_device needs SGM_OPT_CONFIDENCE=1");
+    for (int i = 0; i < N; i++)
+        if (!d_conf_u8[i]) return set_err(SGM_ERR_INVALID_ARG, "null confidence pointer for pair %d", i);
+    e->conf_bind.assign(d_conf_u8, d_conf_u8 + N);
+    return SGM_OK;
+}
+
 int sgm_compute_device(sgm_engine *e, const void *d_left, const void *d_right, int H, int W, int64_t stride_bytes,
                        void *d_disp_i16)
 {
-    return run_compute(e, (const uint8_t *)d_left, (const uint8_t *)d_right, H, W, stride_bytes, (int16_t *)d_disp_i16);
+    if (!e) return set_err(SGM_ERR_INVALID_ARG, "null pointer");
+    std::vector<void *> bound;
+    if (int rc = take_conf_binding(e, 1, &bound)) return rc;
+    return run_compute(e, (const uint8_t *)d_left, (const uint8_t *)d_right, H, W, stride_bytes, (int16_t *)d_disp_i16, PH_ALL,
+                       bound.empty() ? nullptr : (uint8_t *)bound[0]);
 }
 
 int sgm_disp_to_float_device(sgm_engine *e, const void *d_disp_i16, int64_t n, void *d_out_f32)
@@ -1909,10 +1996,10 @@ int sgm_remap_linear_u8(sgm_engine *e, const uint8_t *src, int sH, int sW, int64
     return SGM_OK;
 }
 
-int sgm_pipeline_device(sgm_engine *e, const void *d_left, const void *d_right, int H, int W, int64_t stride_bytes,
-                        const double Q[16], void *d_disp_i16, void *d_disp_f32, void *d_xyz_f32)
+// one pair through cell c13 on e; d_conf as in run_compute
+static int pipeline_one(sgm_engine *e, const void *d_left, const void *d_right, int H, int W, int64_t stride_bytes,
+                        const double Q[16], void *d_disp_i16, void *d_disp_f32, void *d_xyz_f32, uint8_t *d_conf)
 {
-    if (!e) return set_err(SGM_ERR_INVALID_ARG, "engine is null");
     const int64_t n = (int64_t)H * W;
     int rc;
     int16_t *di = (int16_t *)d_disp_i16;
@@ -1920,9 +2007,19 @@ int sgm_pipeline_device(sgm_engine *e, const void *d_left, const void *d_right, 
         if ((rc = e->disp_out.ensure((size_t)n * 2))) return rc;
         di = (int16_t *)e->disp_out.p;
     }
-    if ((rc = run_compute(e, (const uint8_t *)d_left, (const uint8_t *)d_right, H, W, stride_bytes, di))) return rc;
+    if ((rc = run_compute(e, (const uint8_t *)d_left, (const uint8_t *)d_right, H, W, stride_bytes, di, PH_ALL, d_conf))) return rc;
     // float scaling + reprojection in one launch (the float map is stored only if asked for)
     return run_float_xyz(e, di, H, W, Q, d_disp_f32, d_xyz_f32);
+}
+
+int sgm_pipeline_device(sgm_engine *e, const void *d_left, const void *d_right, int H, int W, int64_t stride_bytes,
+                        const double Q[16], void *d_disp_i16, void *d_disp_f32, void *d_xyz_f32)
+{
+    if (!e) return set_err(SGM_ERR_INVALID_ARG, "engine is null");
+    std::vector<void *> bound;
+    if (int rc = take_conf_binding(e, 1, &bound)) return rc;
+    return pipeline_one(e, d_left, d_right, H, W, stride_bytes, Q, d_disp_i16, d_disp_f32, d_xyz_f32,
+                        bound.empty() ? nullptr : (uint8_t *)bound[0]);
 }
 
 // ---- N pairs, throughput mode --------------------------------------------------------------------------------
@@ -1942,6 +2039,7 @@ static void inherit_options(sgm_engine *q, const sgm_engine *e)
     q->chain_wgs = e->chain_wgs;
     q->prepass_rows = e->prepass_rows;
     q->cn = e->cn;
+    q->confidence = e->confidence;
     q->keep_aggr = 0;
     q->profile = 0;
 }
@@ -2030,7 +2128,8 @@ struct BatchGuard {
 // behind pair k's last kernel.
 static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &pl, const void *const *d_left, const void *const *d_right,
                      int H, int W, int64_t stride_bytes, const double Q[16], void *const *d_disp_i16, void *const *d_disp_f32,
-                     void *const *d_xyz_f32, const hipEvent_t *in_ready, const hipEvent_t *in_used, const hipEvent_t *out_done)
+                     void *const *d_xyz_f32, const hipEvent_t *in_ready, const hipEvent_t *in_used, const hipEvent_t *out_done,
+                     void *const *d_conf = nullptr)
 {
     int rc;
     // cost stage of every pair on the stream of its own engine, from where `e`'s stream stands now (the caller's
@@ -2088,7 +2187,7 @@ static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &p
         // whole group's download would follow the last kernel).
         if (out_done && k >= 3 && out_done[k - 3]) HIP_TRY(hipStreamWaitEvent(eng[k]->stream, out_done[k - 3], 0));
         if ((rc = run_compute(eng[k], (const uint8_t *)d_left[k], (const uint8_t *)d_right[k], H, W, stride_bytes,
-                              (int16_t *)d_disp_i16[k], PH_POST)))
+                              (int16_t *)d_disp_i16[k], PH_POST, d_conf ? (uint8_t *)d_conf[k] : nullptr)))
             return rc;
         if ((rc = run_float_xyz(eng[k], (const int16_t *)d_disp_i16[k], H, W, Q, d_disp_f32 ? d_disp_f32[k] : nullptr,
                                 d_xyz_f32 ? d_xyz_f32[k] : nullptr)))
@@ -2126,7 +2225,12 @@ int sgm_pipeline_batch_device(sgm_engine *e, int N, const void *const *d_left, c
                               int64_t stride_bytes, const double Q[16], void *const *d_disp_i16, void *const *d_disp_f32,
                               void *const *d_xyz_f32)
 {
-    if (!e || N <= 0 || !d_left || !d_right || !d_disp_i16) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
+    if (!e) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
+    std::vector<void *> bound;
+    const int brc = take_conf_binding(e, N, &bound);   // (consumed before anything else can fail)
+    if (N <= 0 || !d_left || !d_right || !d_disp_i16) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
+    if (brc) return brc;
+    void *const *d_conf = bound.empty() ? nullptr : bound.data();
     for (int i = 0; i < N; i++)
         if (!d_left[i] || !d_right[i] || !d_disp_i16[i]) return set_err(SGM_ERR_INVALID_ARG, "null pointer for pair %d", i);
     if (stride_bytes < (int64_t)W * e->cn)
@@ -2146,8 +2250,8 @@ int sgm_pipeline_batch_device(sgm_engine *e, int N, const void *const *d_left, c
     if (!joint || cap < 2) {
         for (int i = 0; i < N; i++) {
             e->hr_accumulate = i > 0;     // (the headroom record of the call covers every pair)
-            if ((rc = sgm_pipeline_device(e, d_left[i], d_right[i], H, W, stride_bytes, Q, d_disp_i16[i],
-                                          d_disp_f32 ? d_disp_f32[i] : nullptr, d_xyz_f32 ? d_xyz_f32[i] : nullptr)))
+            if ((rc = pipeline_one(e, d_left[i], d_right[i], H, W, stride_bytes, Q, d_disp_i16[i], d_disp_f32 ? d_disp_f32[i] : nullptr,
+                                   d_xyz_f32 ? d_xyz_f32[i] : nullptr, d_conf ? (uint8_t *)d_conf[i] : nullptr)))
                 return rc;
         }
         guard.ok = true;
@@ -2161,13 +2265,14 @@ int sgm_pipeline_batch_device(sgm_engine *e, int N, const void *const *d_left, c
         const int n = std::min(N - i0, per);
         for (int k = 0; k < n; k++) eng[k]->hr_accumulate = i0 > 0;
         if (n == 1) {
-            if ((rc = sgm_pipeline_device(e, d_left[i0], d_right[i0], H, W, stride_bytes, Q, d_disp_i16[i0],
-                                          d_disp_f32 ? d_disp_f32[i0] : nullptr, d_xyz_f32 ? d_xyz_f32[i0] : nullptr)))
+            if ((rc = pipeline_one(e, d_left[i0], d_right[i0], H, W, stride_bytes, Q, d_disp_i16[i0], d_disp_f32 ? d_disp_f32[i0] : nullptr,
+                                   d_xyz_f32 ? d_xyz_f32[i0] : nullptr, d_conf ? (uint8_t *)d_conf[i0] : nullptr)))
                 return rc;
             continue;
         }
         if ((rc = run_group(e, eng.data(), n, pl, d_left + i0, d_right + i0, H, W, stride_bytes, Q, d_disp_i16 + i0,
-                            d_disp_f32 ? d_disp_f32 + i0 : nullptr, d_xyz_f32 ? d_xyz_f32 + i0 : nullptr, nullptr, nullptr, nullptr)))
+                            d_disp_f32 ? d_disp_f32 + i0 : nullptr, d_xyz_f32 ? d_xyz_f32 + i0 : nullptr, nullptr, nullptr, nullptr,
+                            d_conf ? d_conf + i0 : nullptr)))
             return rc;
     }
     guard.ok = true;
@@ -2178,6 +2283,7 @@ int sgm_compute(sgm_engine *e, const uint8_t *left, const uint8_t *right, int H,
                 int16_t *disp_out)
 {
     if (!e || !left || !right || !disp_out) return set_err(SGM_ERR_INVALID_ARG, "null pointer");
+    e->conf_bind.clear();   // (a binding is for the device entries; the host entry's map is read through the taps)
     const int64_t rowb = (int64_t)W * e->cn;  // bytes of one image row (SGM_OPT_CHANNELS)
     if (H <= 0 || W < 2 || stride_bytes < rowb)
         return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld (channels %d)", H, W, (long long)stride_bytes, e->cn);
@@ -2224,6 +2330,7 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
                       int16_t *disps_out, float *xyz_out, const double *Q16)
 {
     if (!e || !lefts || !rights || !disps_out || N <= 0) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
+    e->conf_bind.clear();   // (no per-pair confidence from this entry: sgm_hip.h)
     if (xyz_out && !Q16) return set_err(SGM_ERR_INVALID_ARG, "xyz_out requested without Q");
     if (H <= 0 || W < 2) return set_err(SGM_ERR_INVALID_ARG, "bad shape");
     HIP_TRY(hipSetDevice(e->device));
@@ -2563,6 +2670,12 @@ int sgm_get_tap(sgm_engine *e, int tap, void *host_dst, int64_t bytes)
         src = e->aggr.p; need = vol; break;
     case SGM_TAP_DISP_RAW: src = e->disp_raw.p; need = npx * 2; break;
     case SGM_TAP_DISP_MEDIAN: src = e->disp_med.p; need = npx * 2; break;
+    case SGM_TAP_CONF_RAW:
+    case SGM_TAP_CONF:
+        if (!e->conf_last) return set_err(SGM_ERR_INVALID_ARG, "tap %d needs SGM_OPT_CONFIDENCE=1 before compute", tap);
+        if (tap == SGM_TAP_CONF && e->conf_last == 2)
+            return set_err(SGM_ERR_INVALID_ARG, "SGM_TAP_CONF: the last compute wrote its map to the pointer bound with sgm_bind_confidence_device");
+        src = tap == SGM_TAP_CONF_RAW ? e->conf_raw.p : e->conf.p; need = npx; break;
     default: return set_err(SGM_ERR_INVALID_ARG, "unknown tap %d", tap);
     }
     if (bytes != need) return set_err(SGM_ERR_INVALID_ARG, "tap %d holds %lld bytes, caller passed %lld", tap, (long long)need, (long long)bytes);

@@ -1,6 +1,7 @@
 """Consumers of the XYZ image on the reference's path.
 
     valid_points(points_3D, colors, disparity_map)   main.ipynb:726-737  mask + boolean indexing
+                 [, confidence, min_confidence]        ... and confidence >= min_confidence (StereoSGBM.computeWithConfidence)
     write_point_cloud(path, points, colors)           main.ipynb:795-797  o3d.io.write_point_cloud(.ply)
 
 The compaction runs on the GPU (ordered, so the result equals numpy's `points_3D[mask]`); the
@@ -14,13 +15,26 @@ import numpy as np
 from . import stereo as _cv
 
 
-def valid_points(points_3D, colors, disparity_map):
+def mask_by_confidence(disparity_map, confidence, min_confidence):
+    """The disparity map with 0 wherever confidence < min_confidence (a copy; 0 fails the `disparity_map > 0` of the
+    notebook's mask), so that the existing compaction drops those pixels too."""
+    disp = np.asarray(disparity_map)
+    conf = np.asarray(confidence)
+    if conf.shape != disp.shape:
+        raise _cv.error("valid_points: confidence must have the shape of disparity_map")
+    return np.where(conf >= min_confidence, disp, disp.dtype.type(0))
+
+
+def valid_points(points_3D, colors, disparity_map, confidence=None, min_confidence=0):
     """Returns (valid_points float32 (N,3), valid_colors uint8 (N,3) or None) exactly like
-    `points_3D[mask]`, `colors[mask]` with mask = ~isnan(X) & ~isinf(X) & (disparity_map > 0)."""
+    `points_3D[mask]`, `colors[mask]` with mask = ~isnan(X) & ~isinf(X) & (disparity_map > 0).
+    With a confidence map (StereoSGBM.computeWithConfidence) the mask also requires confidence >= min_confidence."""
     pts = np.asarray(points_3D)
     disp = np.asarray(disparity_map)
     if pts.ndim != 3 or pts.shape[2] != 3 or pts.shape[:2] != disp.shape:
         raise _cv.error("valid_points: points_3D must be (H, W, 3) and disparity_map (H, W)")
+    if confidence is not None:
+        disp = mask_by_confidence(disp, confidence, min_confidence)
     if colors is not None:
         colors = np.asarray(colors)
         if colors.shape != pts.shape:

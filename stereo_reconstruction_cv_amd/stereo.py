@@ -123,6 +123,8 @@ class Engine:
         if which in (_lib.SGM_TAP_COST, _lib.SGM_TAP_AGGR):
             _, W1 = self.geometry(W)
             out = np.empty((H, max(W1, 0), self.params["numDisparities"]), np.int16)
+        elif which in (_lib.SGM_TAP_CONF_RAW, _lib.SGM_TAP_CONF):     # needs SGM_OPT_CONFIDENCE = 1 before the compute
+            out = np.empty((H, W), np.uint8)
         else:
             out = np.empty((H, W), np.int16)
         _check(self._L.sgm_get_tap(self._h, which, out.ctypes.data, out.nbytes))
@@ -237,22 +239,36 @@ class Engine:
         return out.astype(bool)
 
     # -- device-pointer path (raw addresses; torch only supplies the memory)
-    # (cn: interleaved channels of the images, 1 or 3; stride is the row pitch in bytes)
-    def compute_device(self, d_left: int, d_right: int, H: int, W: int, stride: int, d_disp: int, cn: int = 1) -> None:
+    def bind_confidence_device(self, ptrs) -> None:
+        """Device addresses of tight uint8 (H, W) maps for the NEXT image call on this engine (sgm_bind_confidence_device;
+        needs SGM_OPT_CONFIDENCE = 1): pair i's final confidence goes to ptrs[i].  An empty sequence clears the binding."""
+        n = len(ptrs)
+        arr = (C.c_void_p * n)(*[int(x) if x else None for x in ptrs]) if n else None
+        _check(self._L.sgm_bind_confidence_device(self._h, n, arr))
+
+    # (cn: interleaved channels of the images, 1 or 3; stride is the row pitch in bytes; d_conf / d_confs: where the
+    #  confidence maps of the call go, bind_confidence_device)
+    def compute_device(self, d_left: int, d_right: int, H: int, W: int, stride: int, d_disp: int, cn: int = 1,
+                       d_conf: int | None = None) -> None:
         self._channels(cn)
+        if d_conf is not None:
+            self.bind_confidence_device([d_conf])
         _check(self._L.sgm_compute_device(self._h, d_left, d_right, H, W, stride, d_disp))
 
     def pipeline_device(self, d_left: int, d_right: int, H: int, W: int, stride: int, Q: np.ndarray | None,
-                        d_disp: int | None, d_dispf: int | None, d_xyz: int | None, cn: int = 1) -> None:
+                        d_disp: int | None, d_dispf: int | None, d_xyz: int | None, cn: int = 1,
+                        d_conf: int | None = None) -> None:
         qp = None
         if Q is not None:
             Q = np.ascontiguousarray(Q, np.float64)
             qp = Q.ctypes.data
         self._channels(cn)
+        if d_conf is not None:
+            self.bind_confidence_device([d_conf])
         _check(self._L.sgm_pipeline_device(self._h, d_left, d_right, H, W, stride, qp, d_disp, d_dispf, d_xyz))
 
     def pipeline_batch_device(self, d_lefts, d_rights, H: int, W: int, stride: int, Q: np.ndarray | None,
-                              d_disps, d_dispfs=None, d_xyzs=None, cn: int = 1) -> None:
+                              d_disps, d_dispfs=None, d_xyzs=None, cn: int = 1, d_confs=None) -> None:
         """N resident pairs in throughput mode (sgm_pipeline_batch_device): sequences of N device addresses.
         With SGM_OPT_SCHEDULE = 2 the pairs share one chained sweep launch per pass.  Asynchronous."""
         n = len(d_lefts)
@@ -263,6 +279,8 @@ class Engine:
             qp = Q.ctypes.data
         a, b, c, d, f = arr(d_lefts), arr(d_rights), arr(d_disps), arr(d_dispfs), arr(d_xyzs)
         self._channels(cn)
+        if d_confs is not None:
+            self.bind_confidence_device(list(d_confs))
         _check(self._L.sgm_pipeline_batch_device(self._h, n, a, b, H, W, stride, qp, c, d, f))
 
     def disp_to_float_device(self, d_disp: int, n: int, d_out: int) -> None:
@@ -369,11 +387,23 @@ class StereoSGBM:
     def compute(self, left, right):
         """int16 (H, W) disparity * 16, invalid = (minDisparity - 1) * 16  (main.ipynb:668).  left / right: uint8
         (H, W) or colour (H, W, 3) pairs of the same shape (the pixel cost sums the three channels, as cv2's)."""
+        return self._compute(left, right, False)
+
+    def computeWithConfidence(self, left, right):
+        """(disp16, conf): compute()'s map and the per-pixel match confidence, uint8 (H, W) in 0 .. 100 -- the largest
+        uniquenessRatio under which the winner-take-all would still keep the pixel ((far - minS) * 100 / far over the
+        aggregated cost), 0 where the final disparity is invalid.  Same inputs and validation as compute(); numpy in,
+        numpy out; HIP tensors in, tensors out.  Lets a consumer thin the point cloud after the fact
+        (valid_points(..., confidence=conf, min_confidence=u)) instead of recomputing with another ratio.  No counterpart
+        in cv2."""
+        return self._compute(left, right, True)
+
+    def _compute(self, left, right, with_conf: bool):
         if self._p["mode"] not in (STEREO_SGBM_MODE_SGBM, STEREO_SGBM_MODE_HH, STEREO_SGBM_MODE_HH4):
             raise error("StereoSGBM.compute: MODE_SGBM, MODE_HH and MODE_HH4 are implemented; MODE_SGBM_3WAY is not "
                         "(its result depends on a stripe size upstream derives from the cache size)")
         if _is_torch(left) or _is_torch(right):
-            return self._compute_torch(left, right)
+            return self._compute_torch(left, right, with_conf)
         left, right = np.asarray(left), np.asarray(right)
         # upstream: CV_Assert(left.size() == right.size() && left.type() == right.type() && depth == CV_8U)
         if left.shape != right.shape or left.dtype != right.dtype or left.dtype != np.uint8:
@@ -393,9 +423,19 @@ class StereoSGBM:
             right = np.ascontiguousarray(right)
         if left.shape[1] < 2:
             raise error("StereoSGBM.compute: image width < 2")
-        return get_engine(self._p).compute_host(left, right)
+        eng = get_engine(self._p)
+        if not with_conf:
+            return eng.compute_host(left, right)
+        # the cached engine produces the maps for this call only: plain compute() calls do not pay for them
+        eng.set_option(_lib.SGM_OPT_CONFIDENCE, 1)
+        try:
+            disp = eng.compute_host(left, right)
+            conf = eng.tap(_lib.SGM_TAP_CONF, *disp.shape)
+        finally:
+            eng.set_option(_lib.SGM_OPT_CONFIDENCE, 0)
+        return disp, conf
 
-    def _compute_torch(self, left, right):
+    def _compute_torch(self, left, right, with_conf: bool = False):
         import torch
         if not (_is_torch(left) and _is_torch(right)) or not left.is_cuda or not right.is_cuda:
             raise error("StereoSGBM.compute: torch inputs must both be CUDA (HIP) tensors")
@@ -413,9 +453,18 @@ class StereoSGBM:
         out = torch.empty((H, W), dtype=torch.int16, device=left.device)
         # the engine runs on its own stream: order it after torch's current stream and wait for it
         torch.cuda.current_stream(left.device).synchronize()
-        eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn)
-        eng.synchronize()
-        return out
+        if not with_conf:
+            eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn)
+            eng.synchronize()
+            return out
+        conf = torch.empty((H, W), dtype=torch.uint8, device=left.device)
+        eng.set_option(_lib.SGM_OPT_CONFIDENCE, 1)
+        try:
+            eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn, d_conf=conf.data_ptr())
+            eng.synchronize()
+        finally:
+            eng.set_option(_lib.SGM_OPT_CONFIDENCE, 0)
+        return out, conf
 
 
 def _check_channels(ndim: int, cn: int) -> None:
