@@ -52,7 +52,8 @@ extern "C" {
 #define SGM_ABI_VERSION 4   /* 2: sgm_get_headroom, SGM_OPT_PREPASS_ROWS (round 2); 3: sgm_pipeline_batch_device, SGM_OPT_CHAIN_WGS, schedule 2;
                              * 4: sgm_check, sgm_trim, sgm_compact_points_device_async, SGM_OPT_GROUP_MAX (round 4);
                              * additive since, version unchanged: SGM_OPT_CHANNELS; mode 3; SGM_OPT_CONFIDENCE, SGM_TAP_CONF_RAW,
-                             * SGM_TAP_CONF, sgm_bind_confidence_device (sgm_hip_confidence.h) */
+                             * SGM_TAP_CONF, sgm_bind_confidence_device (sgm_hip_confidence.h); SGM_OPT_RIGHT_VIEW, SGM_TAP_RIGHT_RAW,
+                             * SGM_TAP_RIGHT, sgm_bind_right_device (sgm_hip_right.h) */
 
 typedef enum {
     SGM_OK = 0,
@@ -100,9 +101,21 @@ typedef enum {
      * upstream's uniqueness test keeps the pixel iff conf_raw >= u: conf_raw is the largest uniquenessRatio under which the
      * winner-take-all keeps it, whatever uniquenessRatio and disp12MaxDiff the engine was created with. */
     SGM_TAP_CONF_RAW = 4,    /* uint8 [H][W]      the margin above                                                */
-    SGM_TAP_CONF = 5         /* uint8 [H][W]      conf_raw where the FINAL disparity (after LR check, median and speckle filter) is
+    SGM_TAP_CONF = 5,        /* uint8 [H][W]      conf_raw where the FINAL disparity (after LR check, median and speckle filter) is
                               *                   valid, 0 where it is (minDisparity - 1) * 16.  Not held (SGM_ERR_INVALID_ARG) after a
                               *                   compute that wrote it to a bound pointer instead (sgm_bind_confidence_device) */
+    /* Right-view disparity (needs SGM_OPT_RIGHT_VIEW = 1 for that compute, else SGM_ERR_INVALID_ARG): the map referenced to the
+     * RIGHT image, from the same aggregated cost S as the left map.  Same scale (disparity * 16) and the same invalid value
+     * (minDisparity - 1) * 16.  Right pixel xr = minX1 - minDisparity + xr1 (xr1 in [0, W1): the matched columns of the right map)
+     * has the candidates k in [0, n), n = min(numDisparities, W1 - xr1), with the cost SR(k) = S[y][xr1 + k][k]; winner-take-all,
+     * uniqueness test and sub-pixel step as for the left map over those n candidates, then the mirror of the left map's LR
+     * check against the left winners (a right pixel at disparity d looks at left column xr + d).  This is NOT what
+     * cv2.ximgproc.createRightMatcher returns: that aggregates again on the swapped pair; here the path costs are the
+     * left view's, read along their diagonals. */
+    SGM_TAP_RIGHT_RAW = 6,   /* int16 [H][W]      after WTA / uniqueness / sub-pixel / right-to-left check                */
+    SGM_TAP_RIGHT = 7        /* int16 [H][W]      after the 3x3 median and the speckle filter (the stages of the left map).  Not held
+                              *                   (SGM_ERR_INVALID_ARG) after a compute that wrote it to a bound pointer instead
+                              *                   (sgm_bind_right_device) */
 } sgm_tap;
 
 typedef enum {
@@ -129,6 +142,14 @@ typedef enum {
                               * MODE_SGBM with numDisparities > 128, numDisparities > 512) move two volumes more for it.  The internal
                               * engines of the batch entries inherit the option.  sgm_compute_batch computes as before and returns
                               * NO per-pair confidence: a host-batch form of the map is a follow-up.  (9: csrc/sgm_debug.h) */
+    SGM_OPT_RIGHT_VIEW = 11, /* 0 (default) or 1; any other value is refused with SGM_ERR_INVALID_ARG.  1: every compute on the engine
+                              * also produces the right-view disparity map (SGM_TAP_RIGHT_RAW, SGM_TAP_RIGHT; two int16 [H][W] maps and
+                              * an 8-byte record per matched pixel more in device memory) behind the left map, from one more pass over
+                              * the aggregated cost instead of a second compute on the flipped, swapped pair.  The left outputs do not
+                              * change.  As with SGM_OPT_CONFIDENCE the winner-take-all then always runs as its own pass over S, and
+                              * the internal engines of the batch entries inherit the option; the two options may be on together
+                              * (confidence stays a left-view quantity).  sgm_compute_batch computes as before and returns NO per-pair
+                              * right-view map: a host-batch form is a follow-up. */
     /* 4 = SGM_OPT_DEBUG: A/B switches for measurements -- not part of this interface (csrc/sgm_debug.h) */
     SGM_OPT_RESERVED_4 = 4
 } sgm_option;
@@ -260,4 +281,6 @@ int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_r
 
 /* the one entry point added with SGM_OPT_CONFIDENCE: sgm_bind_confidence_device (a header of its own, part of this interface) */
 #include "sgm_hip_confidence.h"
+/* likewise for SGM_OPT_RIGHT_VIEW: sgm_bind_right_device */
+#include "sgm_hip_right.h"
 #endif

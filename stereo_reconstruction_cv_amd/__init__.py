@@ -10,6 +10,7 @@ from .stereo import (CV_32F, STEREO_SGBM_MODE_HH, STEREO_SGBM_MODE_HH4, STEREO_S
 from .pipeline import compute_disparity_map, reconstruct_3D, rectify_pair, run_disparity, valid_point_mask
 from .pointcloud import mask_by_confidence, read_point_cloud, valid_points, write_point_cloud
 from ._lib import SGM_OPT_CONFIDENCE, SGM_TAP_CONF, SGM_TAP_CONF_RAW
+from ._lib import SGM_OPT_RIGHT_VIEW, SGM_TAP_RIGHT, SGM_TAP_RIGHT_RAW
 
 __all__ = [
     "StereoSGBM_create", "StereoSGBM", "reprojectImageTo3D", "error", "Engine", "get_engine", "set_device",
@@ -17,4 +18,5 @@ __all__ = [
     "run_disparity", "valid_points", "write_point_cloud", "read_point_cloud", "STEREO_SGBM_MODE_SGBM", "STEREO_SGBM_MODE_HH", "STEREO_SGBM_MODE_SGBM_3WAY",
     "STEREO_SGBM_MODE_HH4", "CV_32F", "CV_32FC1", "INTER_LINEAR", "BORDER_CONSTANT", "initUndistortRectifyMap", "remap", "rectify_pair",
     "mask_by_confidence", "SGM_OPT_CONFIDENCE", "SGM_TAP_CONF_RAW", "SGM_TAP_CONF",
+    "SGM_OPT_RIGHT_VIEW", "SGM_TAP_RIGHT_RAW", "SGM_TAP_RIGHT",
 ]

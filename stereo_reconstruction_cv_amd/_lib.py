@@ -15,9 +15,11 @@ LIB_PATH = os.environ.get("SGM_HIP_LIB") or os.path.join(_HERE, "csrc", "libsgm_
 SGM_OK = 0
 SGM_TAP_COST, SGM_TAP_AGGR, SGM_TAP_DISP_RAW, SGM_TAP_DISP_MEDIAN = 0, 1, 2, 3
 SGM_TAP_CONF_RAW, SGM_TAP_CONF = 4, 5    # uint8 (H, W) match confidence: the uniqueness margin, and the same masked by the final map
+SGM_TAP_RIGHT_RAW, SGM_TAP_RIGHT = 6, 7  # int16 (H, W) right-view disparity: after the right-to-left check, and after median + speckle filter
 SGM_OPT_KEEP_AGGR, SGM_OPT_PROFILE, SGM_OPT_SCHEDULE, SGM_OPT_SWEEP_ROWS, SGM_OPT_PREPASS_ROWS, SGM_OPT_CHAIN_WGS, SGM_OPT_GROUP_MAX = 0, 1, 2, 3, 5, 6, 7
 SGM_OPT_CHANNELS = 8    # 1 (default) or 3: interleaved 8-bit channels per image pixel
 SGM_OPT_CONFIDENCE = 10  # 1: every compute also produces the confidence maps (SGM_TAP_CONF_RAW, SGM_TAP_CONF)
+SGM_OPT_RIGHT_VIEW = 11  # 1: every compute also produces the right-view map (SGM_TAP_RIGHT_RAW, SGM_TAP_RIGHT)
 SGM_OPT_DEBUG = 4    # csrc/sgm_debug.h: A/B switches for tools/ and tests/, not part of the public interface
 SGM_OPT_POISON = 9   # csrc/sgm_debug.h: fill every device buffer with a byte (0..255) and arm the same for new ones; -1 disarms (tests only)
 SGM_MAX_STAGES = 32
@@ -35,6 +37,8 @@ EXPORTS = (
 )
 # include/sgm_hip_confidence.h (included by sgm_hip.h): the entry point added with SGM_OPT_CONFIDENCE
 CONFIDENCE_EXPORTS = ("sgm_bind_confidence_device",)
+# include/sgm_hip_right.h (likewise): the entry point added with SGM_OPT_RIGHT_VIEW
+RIGHT_EXPORTS = ("sgm_bind_right_device",)
 
 
 class SgmParams(C.Structure):
@@ -112,6 +116,7 @@ def load():
     L.sgm_pipeline_device.argtypes = [vp, vp, vp, i32, i32, i64, vp, vp, vp, vp]
     L.sgm_pipeline_batch_device.argtypes = [vp, i32, vp, vp, i32, i32, i64, vp, vp, vp, vp]
     L.sgm_bind_confidence_device.argtypes = [vp, i32, vp]
+    L.sgm_bind_right_device.argtypes = [vp, i32, vp]
     L.sgm_synchronize.argtypes = [vp]
     L.sgm_get_stage_times.argtypes = [vp, C.POINTER(SgmStageTimes)]
     L.sgm_algorithmic_bytes.argtypes = [pp, i32, i32, i32]
@@ -123,7 +128,9 @@ def load():
     # csrc/sgm_debug.h, outside EXPORTS: the plan readout for tests
     L.sgm_debug_plan.argtypes = [pp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(SgmDebugPlan)]
     L.sgm_debug_plan.restype = i32
-    for name in EXPORTS + CONFIDENCE_EXPORTS:
+    L.sgm_debug_plan_opts.argtypes = [pp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(SgmDebugPlan)]
+    L.sgm_debug_plan_opts.restype = i32
+    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("sgm_abi_version", "sgm_device_count"):
             fn.restype = i32
@@ -136,12 +143,17 @@ def last_error() -> str:
 
 
 def debug_plan(params: dict, H: int, W: int, channels: int = 1, schedule: int = 1, sweep_rows: int = 0, prepass_rows: int = 0,
-               debug: int = 0, frames: int = 1) -> dict:
+               debug: int = 0, frames: int = 1, confidence: int = 0, right_view: int = 0) -> dict:
     """The schedule one compute of an H x W frame takes with these arguments and options (csrc/sgm_debug.h: sgm_debug_plan),
-    as a dict of the fields of sgm_debug_plan_t.  Needs no GPU.  For tests: which plan a case takes is read, not assumed."""
+    as a dict of the fields of sgm_debug_plan_t.  Needs no GPU.  For tests: which plan a case takes is read, not assumed.
+    confidence / right_view: SGM_OPT_CONFIDENCE / SGM_OPT_RIGHT_VIEW of the engine (the sibling readout sgm_debug_plan_opts)."""
     out = SgmDebugPlan()
-    rc = load().sgm_debug_plan(C.byref(SgmParams(**params)), H, W, channels, schedule, sweep_rows, prepass_rows, debug, frames,
-                               C.byref(out))
+    if confidence or right_view:
+        rc = load().sgm_debug_plan_opts(C.byref(SgmParams(**params)), H, W, channels, schedule, sweep_rows, prepass_rows, debug,
+                                        frames, confidence, right_view, C.byref(out))
+    else:
+        rc = load().sgm_debug_plan(C.byref(SgmParams(**params)), H, W, channels, schedule, sweep_rows, prepass_rows, debug, frames,
+                                   C.byref(out))
     if rc != SGM_OK:
         raise ValueError(f"sgm_debug_plan failed ({rc}): {last_error()}")
     return {n: getattr(out, n) for n, _ in SgmDebugPlan._fields_}

@@ -51,5 +51,11 @@ extern "C"
 #endif
 int sgm_debug_plan(const sgm_params *p, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
                    int debug, int frames, sgm_debug_plan_t *out);
+/* ... and with the options that change a plan but came after that signature was fixed: SGM_OPT_CONFIDENCE, SGM_OPT_RIGHT_VIEW */
+#ifdef __cplusplus
+extern "C"
+#endif
+int sgm_debug_plan_opts(const sgm_params *p, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
+                        int debug, int frames, int confidence, int right_view, sgm_debug_plan_t *out);
 
 #endif

@@ -26,6 +26,7 @@
 #include "kernels_sweep.h"
 #include "kernels_group.h"
 #include "kernels_color.h"
+#include "kernels_right.h"
 
 using namespace sgm;
 
@@ -251,6 +252,9 @@ struct sgm_engine {
     int confidence = 0;  // SGM_OPT_CONFIDENCE: every compute also produces the uniqueness margin (conf_raw, conf)
     int conf_last = 0;   // what the last compute on this engine left: 0 no maps, 1 conf_raw + conf, 2 conf went to a bound pointer
     std::vector<void *> conf_bind;        // sgm_bind_confidence_device: where the next image call writes its pairs' conf
+    int right_view = 0;  // SGM_OPT_RIGHT_VIEW: every compute also produces the right-view map (right_raw, right)
+    int right_last = 0;  // what the last compute left: 0 no maps, 1 right_raw + right, 2 right went to a bound pointer
+    std::vector<void *> right_bind;       // sgm_bind_right_device: where the next image call writes its pairs' right map
     // sgm_compute_batch: up to three pairs in flight = this engine + two peers (own stream and device
     // buffers), each with page-locked staging buffers for the images and the disparity map
     sgm_engine *peer = nullptr, *peer2 = nullptr;
@@ -289,6 +293,7 @@ struct sgm_engine {
     DevBuf pstate, pstate2;             // line state between the row chunks of the pre-pass (ping-pong, down / up)
     DevBuf disp_raw, disp_med, disp_out;  // int16 [H][W]
     DevBuf conf_raw, conf;              // uint8 [H][W], SGM_OPT_CONFIDENCE only: the margin of the winner-take-all; masked by the final map
+    DevBuf rrec, right_raw, right;      // SGM_OPT_RIGHT_VIEW only: uint2 [H][W1] record of the diagonal winner-take-all; int16 [H][W] maps
     DevBuf label, csize, rlen;          // int32 [H][W] each
     DevBuf f32, xyz, mask, minkey;      // host-pointer post stages
     DevBuf rmap1, rmap2, rsrc, rdst;    // host-pointer rectification stages
@@ -724,7 +729,8 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     // MODE_HH4: always the separate pass (the axis-only sweeps have no SWEEP_LAST form).
     // SGM_OPT_CONFIDENCE: always the separate pass -- the confidence byte comes from k_wta_conf_t alone, so
     // the routes that fuse by default (v1, MODE_SGBM with D > 128, D > 512) store S once more and read it back: 2 V more.
-    const bool conf = e->confidence != 0;
+    // SGM_OPT_RIGHT_VIEW: likewise -- the diagonal winner-take-all (k_right_wta) reads S from device memory.
+    const bool conf = e->confidence != 0 || e->right_view != 0;
     p.fused_wta = !conf && (p.v1 || (!p.axis && !(dbg & SGM_DBG_WTA_SEPARATE) && (((dbg & SGM_DBG_WTA_IN_LAST_PATH) && !p.rows4) ||
                                                                                   (g.mode == 0 && ((dbg & SGM_DBG_NO_LANE_GROUPS) || g.D > 128)))));
     // MODE_SGBM with the separate winner-take-all (D <= 128): the fifth path (in-row, right to left) needs
@@ -788,7 +794,8 @@ static size_t plan_bytes_held(const sgm_engine *e)
 {
     const DevBuf *bufs[] = {&e->lrec, &e->rplanes, &e->hsum, &e->cost, &e->aggr, &e->aggr2, &e->aggr3, &e->aggr4, &e->aggr5,
                             &e->wta, &e->disp_raw, &e->disp_med, &e->headroom, &e->bndL, &e->bndL2, &e->pstate, &e->pstate2,
-                            &e->label, &e->csize, &e->rlen, &e->chain_ctl, &e->chain_err, &e->conf_raw, &e->conf};
+                            &e->label, &e->csize, &e->rlen, &e->chain_ctl, &e->chain_err, &e->conf_raw, &e->conf,
+                            &e->rrec, &e->right_raw, &e->right};
     size_t n = 0;
     for (const DevBuf *b : bufs) n += b->cap;
     return n;
@@ -826,6 +833,10 @@ static int ensure_plan_buffers(sgm_engine *e, const Plan &p, int H, int W)
     if ((rc = e->disp_raw.ensure(npx * 2))) return rc;
     if ((rc = e->disp_med.ensure(npx * 2))) return rc;
     if (e->confidence && ((rc = e->conf_raw.ensure(npx)) || (rc = e->conf.ensure(npx)))) return rc;
+    if (e->right_view) {
+        if ((rc = e->right_raw.ensure(npx * 2)) || (rc = e->right.ensure(npx * 2))) return rc;
+        if (g.W1 > 0 && (rc = e->rrec.ensure((size_t)H * g.W1 * 8))) return rc;
+    }
     if ((rc = e->headroom.ensure(8))) return rc;
     e->g.hr = (uint32_t *)e->headroom.p;
     if (g.W1 > 0 && !p.v1 && p.nbands > 1 && p.nvol < 4) {
@@ -1434,9 +1445,59 @@ static int stage_confidence(sgm_engine *e, const int16_t *d_disp, uint8_t *d_con
     });
 }
 
+// SGM_OPT_RIGHT_VIEW: the right-view map behind the left map's epilogue on the pair's stream (kernels_right.h) -- diagonal
+// winner-take-all over the volumes the left one read, sub-pixel step + right-to-left check against the left WTA record,
+// then the left map's own median and speckle stages (the speckle scratch is free again: same stream).  The final map goes
+// into the engine's buffer, or to the pointer bound for this pair (sgm_bind_right_device).
+static int stage_right_view(sgm_engine *e, const Plan &p, int16_t *d_rmap)
+{
+    const Geom &g = e->g;
+    const int H = g.H, W = g.W;
+    int16_t *raw = (int16_t *)e->right_raw.p, *out = d_rmap ? d_rmap : (int16_t *)e->right.p;
+    e->right_last = d_rmap ? 2 : 1;
+    int rc;
+    if (g.W1 <= 0) {  // no matched column: no volume, nothing to scan
+        const int64_t npx = (int64_t)H * W;
+        rc = run_stage(e, "right_fill_invalid", e->stream, [&] {
+            hipLaunchKernelGGL(k_fill_i16, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, e->stream, raw, npx, (int16_t)g.invalid_scaled);
+            return 1;
+        });
+        if (rc) return rc;
+    } else {
+        rc = run_stage(e, "right_wta", e->stream, [&] {
+            RightVols v{};
+            // (SGM_OPT_KEEP_AGGR: stage_wta has folded the other volumes into S already)
+            v.nv = e->keep_aggr ? 1 : p.nvol;
+            const DevBuf *vol[5] = {&e->aggr, &e->aggr2, &e->aggr3, &e->aggr4, &e->aggr5};
+            for (int k = 0; k < v.nv; k++) v.S[k] = (const int16_t *)vol[k]->p;
+            hipLaunchKernelGGL(k_right_wta, dim3((g.W1 + RV_T - 1) / RV_T, H), dim3(RV_T), 0, e->stream, g, v, (uint2 *)e->rrec.p);
+            return 1;
+        });
+        if (rc) return rc;
+        rc = run_stage(e, "right_check", e->stream, [&]() -> int {
+            const size_t lds = (size_t)W * 2;
+            if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_right_check, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(k_right_check, dim3(H), dim3(256), lds, e->stream, g, (const uint2 *)e->wta.p, (const uint2 *)e->rrec.p, raw);
+            return 1;
+        });
+        if (rc) return rc;
+    }
+    rc = run_stage(e, "right_median3", e->stream, [&] {
+        hipLaunchKernelGGL(k_median3, dim3((W + 255) / 256, H), dim3(256), 0, e->stream, (const int16_t *)raw, out, (int16_t *)nullptr, H, W);
+        return 1;
+    });
+    if (rc || !p.speckle) return rc;
+    const sgm_params &q = e->params;
+    return run_stage(e, "right_speckle", e->stream, [&] {
+        const int r = run_speckles(e, out, H, W, (q.minDisparity - 1) * 16, q.speckleWindowSize, 16 * q.speckleRange);
+        return r ? r : 4;
+    });
+}
+
 // d_conf: SGM_OPT_CONFIDENCE only -- where this pair's final confidence map goes (null: the engine's own buffer)
+// d_rmap: SGM_OPT_RIGHT_VIEW only -- likewise for this pair's final right-view map
 static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_right, int H, int W,
-                       int64_t stride, int16_t *d_disp, int phases = PH_ALL, uint8_t *d_conf = nullptr)
+                       int64_t stride, int16_t *d_disp, int phases = PH_ALL, uint8_t *d_conf = nullptr, int16_t *d_rmap = nullptr)
 {
     if (!e || !d_left || !d_right || !d_disp) return set_err(SGM_ERR_INVALID_ARG, "null pointer");
     if (H <= 0 || W < 2 || stride < (int64_t)W * e->cn)
@@ -1456,6 +1517,7 @@ static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_ri
         e->last_end_ev = -1;
         e->plan = p;
         e->conf_last = 0;
+        e->right_last = 0;
     } else {
         stage_break(e);
     }
@@ -1491,8 +1553,9 @@ static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_ri
         }
         if ((rc = stage_wta(e, p)) || (rc = stage_select(e))) return rc;
     }
-    if ((rc = stage_median_speckle(e, p, d_disp)) || !e->confidence) return rc;
-    return stage_confidence(e, d_disp, d_conf);
+    if ((rc = stage_median_speckle(e, p, d_disp))) return rc;
+    if (e->confidence && (rc = stage_confidence(e, d_disp, d_conf))) return rc;
+    return e->right_view ? stage_right_view(e, p, d_rmap) : SGM_OK;
 }
 
 static int run_to_float(sgm_engine *e, const int16_t *d_disp, int64_t n, float *d_out)
@@ -1572,8 +1635,8 @@ int sgm_geometry(const sgm_params *params, int W, int *minX1, int *W1)
 
 // csrc/sgm_debug.h: the plan of one compute, read out on the host.  The options go through sgm_set_option into an engine
 // that is never handed out (it owns no stream and no buffer), then the very calls run_compute makes.
-int sgm_debug_plan(const sgm_params *params, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
-                   int debug, int frames, sgm_debug_plan_t *out)
+static int debug_plan_on(const sgm_params *params, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
+                         int debug, int frames, int confidence, int right_view, sgm_debug_plan_t *out)
 {
     if (!params || !out) return set_err(SGM_ERR_INVALID_ARG, "params/out is null");
     if (H <= 0 || W < 2 || W > 32767 || H > 32767) return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d", H, W);
@@ -1582,7 +1645,8 @@ int sgm_debug_plan(const sgm_params *params, int H, int W, int channels, int sch
     int rc;
     if ((rc = sgm_set_option(&e, SGM_OPT_CHANNELS, channels)) || (rc = sgm_set_option(&e, SGM_OPT_SCHEDULE, schedule)) ||
         (rc = sgm_set_option(&e, SGM_OPT_SWEEP_ROWS, sweep_rows)) || (rc = sgm_set_option(&e, SGM_OPT_PREPASS_ROWS, prepass_rows)) ||
-        (rc = sgm_set_option(&e, SGM_OPT_DEBUG, debug)))
+        (rc = sgm_set_option(&e, SGM_OPT_DEBUG, debug)) || (rc = sgm_set_option(&e, SGM_OPT_CONFIDENCE, confidence)) ||
+        (rc = sgm_set_option(&e, SGM_OPT_RIGHT_VIEW, right_view)))
         return rc;
     Geom g;
     if ((rc = normalise(&e.params, H, W, &g))) return rc;
@@ -1614,6 +1678,19 @@ int sgm_debug_plan(const sgm_params *params, int H, int W, int channels, int sch
     out->speckle = p.speckle;
     out->chain_window = p.chain && g.W1 > 0 ? chain_window(g, p.R, p.nbands, std::max(frames, 1), 0) : 0;
     return SGM_OK;
+}
+
+int sgm_debug_plan(const sgm_params *params, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
+                   int debug, int frames, sgm_debug_plan_t *out)
+{
+    return debug_plan_on(params, H, W, channels, schedule, sweep_rows, prepass_rows, debug, frames, 0, 0, out);
+}
+
+// the same readout with the options that change the plan but came after sgm_debug_plan's signature was fixed
+int sgm_debug_plan_opts(const sgm_params *params, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
+                        int debug, int frames, int confidence, int right_view, sgm_debug_plan_t *out)
+{
+    return debug_plan_on(params, H, W, channels, schedule, sweep_rows, prepass_rows, debug, frames, confidence, right_view, out);
 }
 
 int sgm_create(const sgm_params *params, int device_id, void *stream, sgm_engine **out)
@@ -1653,7 +1730,8 @@ static void release_buffers(sgm_engine *e)
 {
     DevBuf *bufs[] = {&e->in_left, &e->in_right, &e->lrec, &e->rplanes, &e->hsum, &e->cost, &e->aggr, &e->aggr2, &e->rmap1, &e->rmap2, &e->rsrc, &e->rdst, &e->wta, &e->bndL, &e->bndL2, &e->pstate, &e->pstate2,
                       &e->disp_raw, &e->disp_med, &e->disp_out, &e->label, &e->csize, &e->rlen, &e->f32, &e->xyz, &e->mask,
-                      &e->minkey, &e->ccount, &e->cpts, &e->crgb, &e->crgb_in, &e->headroom, &e->chain_ctl, &e->chain_err, &e->aggr3, &e->aggr4, &e->aggr5, &e->conf_raw, &e->conf};
+                      &e->minkey, &e->ccount, &e->cpts, &e->crgb, &e->crgb_in, &e->headroom, &e->chain_ctl, &e->chain_err, &e->aggr3, &e->aggr4, &e->aggr5, &e->conf_raw, &e->conf,
+                      &e->rrec, &e->right_raw, &e->right};
     for (DevBuf *b : bufs) (void)b->release();
     for (auto &slot : e->io)
         for (DevBuf &b : slot) (void)b.release();
@@ -1672,7 +1750,7 @@ static int poison_buffers(sgm_engine *e, int byte)
                       &e->aggr5, &e->wta, &e->bndL, &e->bndL2, &e->pstate, &e->pstate2, &e->disp_raw, &e->disp_med, &e->disp_out,
                       &e->label, &e->csize, &e->rlen, &e->f32, &e->xyz, &e->mask, &e->minkey, &e->rmap1, &e->rmap2, &e->rsrc,
                       &e->rdst, &e->ccount, &e->cpts, &e->crgb, &e->crgb_in, &e->headroom, &e->chain_ctl, &e->chain_err,
-                      &e->conf_raw, &e->conf,
+                      &e->conf_raw, &e->conf, &e->rrec, &e->right_raw, &e->right,
                       &e->io[0][0], &e->io[0][1], &e->io[0][2], &e->io[0][3], &e->io[0][4],
                       &e->io[1][0], &e->io[1][1], &e->io[1][2], &e->io[1][3], &e->io[1][4]};
     static_assert(sizeof(e->io) == 10 * sizeof(DevBuf), "poison_buffers names every slot of io");
@@ -1757,6 +1835,11 @@ int sgm_set_option(sgm_engine *e, int option, int value)
         e->confidence = value;
         if (!value) e->conf_bind.clear();
     }
+    else if (option == SGM_OPT_RIGHT_VIEW) {
+        if (value != 0 && value != 1) return set_err(SGM_ERR_INVALID_ARG, "SGM_OPT_RIGHT_VIEW %d: 0 (off) or 1 (on)", value);
+        e->right_view = value;
+        if (!value) e->right_bind.clear();
+    }
     else if (option == SGM_OPT_POISON) {
         // csrc/sgm_debug.h: 0..255 fills every buffer now and arms DevBuf::ensure; anything else disarms
         g_poison_byte = value >= 0 && value <= 255 ? value : -1;
@@ -1831,6 +1914,29 @@ static int take_conf_binding(sgm_engine *e, int n, std::vector<void *> *out)
     return SGM_OK;
 }
 
+// the same for sgm_bind_right_device.  An image call takes BOTH bindings before it looks at either result.
+static int take_right_binding(sgm_engine *e, int n, std::vector<void *> *out)
+{
+    out->clear();
+    out->swap(e->right_bind);
+    if (!out->empty() && (int)out->size() != n)
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_bind_right_device bound %d maps, this call has %d pair(s)", (int)out->size(), n);
+    return SGM_OK;
+}
+
+int sgm_bind_right_device(sgm_engine *e, int N, void *const *d_right_i16)
+{
+    if (!e) return set_err(SGM_ERR_INVALID_ARG, "engine is null");
+    e->right_bind.clear();
+    if (N == 0) return SGM_OK;
+    if (N < 0 || !d_right_i16) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
+    if (!e->right_view) return set_err(SGM_ERR_INVALID_ARG, "sgm_bind_right_device needs SGM_OPT_RIGHT_VIEW=1");
+    for (int i = 0; i < N; i++)
+        if (!d_right_i16[i]) return set_err(SGM_ERR_INVALID_ARG, "null right-view pointer for pair %d", i);
+    e->right_bind.assign(d_right_i16, d_right_i16 + N);
+    return SGM_OK;
+}
+
 int sgm_bind_confidence_device(sgm_engine *e, int N, void *const *d_conf_u8)
 {
     if (!e) return set_err(SGM_ERR_INVALID_ARG, "engine is null");
@@ -1848,10 +1954,11 @@ int sgm_compute_device(sgm_engine *e, const void *d_left, const void *d_right, i
                        void *d_disp_i16)
 {
     if (!e) return set_err(SGM_ERR_INVALID_ARG, "null pointer");
-    std::vector<void *> bound;
-    if (int rc = take_conf_binding(e, 1, &bound)) return rc;
+    std::vector<void *> bound, rbound;
+    const int brc = take_conf_binding(e, 1, &bound), rrc = take_right_binding(e, 1, &rbound);
+    if (brc || rrc) return brc ? brc : rrc;
     return run_compute(e, (const uint8_t *)d_left, (const uint8_t *)d_right, H, W, stride_bytes, (int16_t *)d_disp_i16, PH_ALL,
-                       bound.empty() ? nullptr : (uint8_t *)bound[0]);
+                       bound.empty() ? nullptr : (uint8_t *)bound[0], rbound.empty() ? nullptr : (int16_t *)rbound[0]);
 }
 
 int sgm_disp_to_float_device(sgm_engine *e, const void *d_disp_i16, int64_t n, void *d_out_f32)
@@ -1996,9 +2103,10 @@ int sgm_remap_linear_u8(sgm_engine *e, const uint8_t *src, int sH, int sW, int64
     return SGM_OK;
 }
 
-// one pair through cell c13 on e; d_conf as in run_compute
+// one pair through cell c13 on e; d_conf, d_rmap as in run_compute
 static int pipeline_one(sgm_engine *e, const void *d_left, const void *d_right, int H, int W, int64_t stride_bytes,
-                        const double Q[16], void *d_disp_i16, void *d_disp_f32, void *d_xyz_f32, uint8_t *d_conf)
+                        const double Q[16], void *d_disp_i16, void *d_disp_f32, void *d_xyz_f32, uint8_t *d_conf,
+                        int16_t *d_rmap = nullptr)
 {
     const int64_t n = (int64_t)H * W;
     int rc;
@@ -2007,7 +2115,7 @@ static int pipeline_one(sgm_engine *e, const void *d_left, const void *d_right, 
         if ((rc = e->disp_out.ensure((size_t)n * 2))) return rc;
         di = (int16_t *)e->disp_out.p;
     }
-    if ((rc = run_compute(e, (const uint8_t *)d_left, (const uint8_t *)d_right, H, W, stride_bytes, di, PH_ALL, d_conf))) return rc;
+    if ((rc = run_compute(e, (const uint8_t *)d_left, (const uint8_t *)d_right, H, W, stride_bytes, di, PH_ALL, d_conf, d_rmap))) return rc;
     // float scaling + reprojection in one launch (the float map is stored only if asked for)
     return run_float_xyz(e, di, H, W, Q, d_disp_f32, d_xyz_f32);
 }
@@ -2016,10 +2124,11 @@ int sgm_pipeline_device(sgm_engine *e, const void *d_left, const void *d_right, 
                         const double Q[16], void *d_disp_i16, void *d_disp_f32, void *d_xyz_f32)
 {
     if (!e) return set_err(SGM_ERR_INVALID_ARG, "engine is null");
-    std::vector<void *> bound;
-    if (int rc = take_conf_binding(e, 1, &bound)) return rc;
+    std::vector<void *> bound, rbound;
+    const int brc = take_conf_binding(e, 1, &bound), rrc = take_right_binding(e, 1, &rbound);
+    if (brc || rrc) return brc ? brc : rrc;
     return pipeline_one(e, d_left, d_right, H, W, stride_bytes, Q, d_disp_i16, d_disp_f32, d_xyz_f32,
-                        bound.empty() ? nullptr : (uint8_t *)bound[0]);
+                        bound.empty() ? nullptr : (uint8_t *)bound[0], rbound.empty() ? nullptr : (int16_t *)rbound[0]);
 }
 
 // ---- N pairs, throughput mode --------------------------------------------------------------------------------
@@ -2040,6 +2149,7 @@ static void inherit_options(sgm_engine *q, const sgm_engine *e)
     q->prepass_rows = e->prepass_rows;
     q->cn = e->cn;
     q->confidence = e->confidence;
+    q->right_view = e->right_view;
     q->keep_aggr = 0;
     q->profile = 0;
 }
@@ -2129,7 +2239,7 @@ struct BatchGuard {
 static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &pl, const void *const *d_left, const void *const *d_right,
                      int H, int W, int64_t stride_bytes, const double Q[16], void *const *d_disp_i16, void *const *d_disp_f32,
                      void *const *d_xyz_f32, const hipEvent_t *in_ready, const hipEvent_t *in_used, const hipEvent_t *out_done,
-                     void *const *d_conf = nullptr)
+                     void *const *d_conf = nullptr, void *const *d_rmap = nullptr)
 {
     int rc;
     // cost stage of every pair on the stream of its own engine, from where `e`'s stream stands now (the caller's
@@ -2187,7 +2297,8 @@ static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &p
         // whole group's download would follow the last kernel).
         if (out_done && k >= 3 && out_done[k - 3]) HIP_TRY(hipStreamWaitEvent(eng[k]->stream, out_done[k - 3], 0));
         if ((rc = run_compute(eng[k], (const uint8_t *)d_left[k], (const uint8_t *)d_right[k], H, W, stride_bytes,
-                              (int16_t *)d_disp_i16[k], PH_POST, d_conf ? (uint8_t *)d_conf[k] : nullptr)))
+                              (int16_t *)d_disp_i16[k], PH_POST, d_conf ? (uint8_t *)d_conf[k] : nullptr,
+                              d_rmap ? (int16_t *)d_rmap[k] : nullptr)))
             return rc;
         if ((rc = run_float_xyz(eng[k], (const int16_t *)d_disp_i16[k], H, W, Q, d_disp_f32 ? d_disp_f32[k] : nullptr,
                                 d_xyz_f32 ? d_xyz_f32[k] : nullptr)))
@@ -2226,11 +2337,12 @@ int sgm_pipeline_batch_device(sgm_engine *e, int N, const void *const *d_left, c
                               void *const *d_xyz_f32)
 {
     if (!e) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
-    std::vector<void *> bound;
-    const int brc = take_conf_binding(e, N, &bound);   // (consumed before anything else can fail)
+    std::vector<void *> bound, rbound;
+    const int brc = take_conf_binding(e, N, &bound), rrc = take_right_binding(e, N, &rbound);   // (consumed before anything else can fail)
     if (N <= 0 || !d_left || !d_right || !d_disp_i16) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
-    if (brc) return brc;
+    if (brc || rrc) return brc ? brc : rrc;
     void *const *d_conf = bound.empty() ? nullptr : bound.data();
+    void *const *d_rmap = rbound.empty() ? nullptr : rbound.data();
     for (int i = 0; i < N; i++)
         if (!d_left[i] || !d_right[i] || !d_disp_i16[i]) return set_err(SGM_ERR_INVALID_ARG, "null pointer for pair %d", i);
     if (stride_bytes < (int64_t)W * e->cn)
@@ -2251,7 +2363,8 @@ int sgm_pipeline_batch_device(sgm_engine *e, int N, const void *const *d_left, c
         for (int i = 0; i < N; i++) {
             e->hr_accumulate = i > 0;     // (the headroom record of the call covers every pair)
             if ((rc = pipeline_one(e, d_left[i], d_right[i], H, W, stride_bytes, Q, d_disp_i16[i], d_disp_f32 ? d_disp_f32[i] : nullptr,
-                                   d_xyz_f32 ? d_xyz_f32[i] : nullptr, d_conf ? (uint8_t *)d_conf[i] : nullptr)))
+                                   d_xyz_f32 ? d_xyz_f32[i] : nullptr, d_conf ? (uint8_t *)d_conf[i] : nullptr,
+                                   d_rmap ? (int16_t *)d_rmap[i] : nullptr)))
                 return rc;
         }
         guard.ok = true;
@@ -2266,13 +2379,14 @@ int sgm_pipeline_batch_device(sgm_engine *e, int N, const void *const *d_left, c
         for (int k = 0; k < n; k++) eng[k]->hr_accumulate = i0 > 0;
         if (n == 1) {
             if ((rc = pipeline_one(e, d_left[i0], d_right[i0], H, W, stride_bytes, Q, d_disp_i16[i0], d_disp_f32 ? d_disp_f32[i0] : nullptr,
-                                   d_xyz_f32 ? d_xyz_f32[i0] : nullptr, d_conf ? (uint8_t *)d_conf[i0] : nullptr)))
+                                   d_xyz_f32 ? d_xyz_f32[i0] : nullptr, d_conf ? (uint8_t *)d_conf[i0] : nullptr,
+                                   d_rmap ? (int16_t *)d_rmap[i0] : nullptr)))
                 return rc;
             continue;
         }
         if ((rc = run_group(e, eng.data(), n, pl, d_left + i0, d_right + i0, H, W, stride_bytes, Q, d_disp_i16 + i0,
                             d_disp_f32 ? d_disp_f32 + i0 : nullptr, d_xyz_f32 ? d_xyz_f32 + i0 : nullptr, nullptr, nullptr, nullptr,
-                            d_conf ? d_conf + i0 : nullptr)))
+                            d_conf ? d_conf + i0 : nullptr, d_rmap ? d_rmap + i0 : nullptr)))
             return rc;
     }
     guard.ok = true;
@@ -2284,6 +2398,7 @@ int sgm_compute(sgm_engine *e, const uint8_t *left, const uint8_t *right, int H,
 {
     if (!e || !left || !right || !disp_out) return set_err(SGM_ERR_INVALID_ARG, "null pointer");
     e->conf_bind.clear();   // (a binding is for the device entries; the host entry's map is read through the taps)
+    e->right_bind.clear();
     const int64_t rowb = (int64_t)W * e->cn;  // bytes of one image row (SGM_OPT_CHANNELS)
     if (H <= 0 || W < 2 || stride_bytes < rowb)
         return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld (channels %d)", H, W, (long long)stride_bytes, e->cn);
@@ -2331,6 +2446,7 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
 {
     if (!e || !lefts || !rights || !disps_out || N <= 0) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
     e->conf_bind.clear();   // (no per-pair confidence from this entry: sgm_hip.h)
+    e->right_bind.clear();  // (nor a per-pair right-view map)
     if (xyz_out && !Q16) return set_err(SGM_ERR_INVALID_ARG, "xyz_out requested without Q");
     if (H <= 0 || W < 2) return set_err(SGM_ERR_INVALID_ARG, "bad shape");
     HIP_TRY(hipSetDevice(e->device));
@@ -2676,6 +2792,12 @@ int sgm_get_tap(sgm_engine *e, int tap, void *host_dst, int64_t bytes)
         if (tap == SGM_TAP_CONF && e->conf_last == 2)
             return set_err(SGM_ERR_INVALID_ARG, "SGM_TAP_CONF: the last compute wrote its map to the pointer bound with sgm_bind_confidence_device");
         src = tap == SGM_TAP_CONF_RAW ? e->conf_raw.p : e->conf.p; need = npx; break;
+    case SGM_TAP_RIGHT_RAW:
+    case SGM_TAP_RIGHT:
+        if (!e->right_last) return set_err(SGM_ERR_INVALID_ARG, "tap %d needs SGM_OPT_RIGHT_VIEW=1 before compute", tap);
+        if (tap == SGM_TAP_RIGHT && e->right_last == 2)
+            return set_err(SGM_ERR_INVALID_ARG, "SGM_TAP_RIGHT: the last compute wrote its map to the pointer bound with sgm_bind_right_device");
+        src = tap == SGM_TAP_RIGHT_RAW ? e->right_raw.p : e->right.p; need = npx * 2; break;
     default: return set_err(SGM_ERR_INVALID_ARG, "unknown tap %d", tap);
     }
     if (bytes != need) return set_err(SGM_ERR_INVALID_ARG, "tap %d holds %lld bytes, caller passed %lld", tap, (long long)need, (long long)bytes);

@@ -123,6 +123,8 @@ class Engine:
         if which in (_lib.SGM_TAP_COST, _lib.SGM_TAP_AGGR):
             _, W1 = self.geometry(W)
             out = np.empty((H, max(W1, 0), self.params["numDisparities"]), np.int16)
+        elif which in (_lib.SGM_TAP_RIGHT_RAW, _lib.SGM_TAP_RIGHT):   # needs SGM_OPT_RIGHT_VIEW = 1 before the compute
+            out = np.empty((H, W), np.int16)
         elif which in (_lib.SGM_TAP_CONF_RAW, _lib.SGM_TAP_CONF):     # needs SGM_OPT_CONFIDENCE = 1 before the compute
             out = np.empty((H, W), np.uint8)
         else:
@@ -246,18 +248,27 @@ class Engine:
         arr = (C.c_void_p * n)(*[int(x) if x else None for x in ptrs]) if n else None
         _check(self._L.sgm_bind_confidence_device(self._h, n, arr))
 
+    def bind_right_device(self, ptrs) -> None:
+        """Device addresses of tight int16 (H, W) maps for the NEXT image call on this engine (sgm_bind_right_device; needs
+        SGM_OPT_RIGHT_VIEW = 1): pair i's final right-view map goes to ptrs[i].  An empty sequence clears the binding."""
+        n = len(ptrs)
+        arr = (C.c_void_p * n)(*[int(x) if x else None for x in ptrs]) if n else None
+        _check(self._L.sgm_bind_right_device(self._h, n, arr))
+
     # (cn: interleaved channels of the images, 1 or 3; stride is the row pitch in bytes; d_conf / d_confs: where the
-    #  confidence maps of the call go, bind_confidence_device)
+    #  confidence maps of the call go, bind_confidence_device; d_rmap / d_rmaps: the right-view maps, bind_right_device)
     def compute_device(self, d_left: int, d_right: int, H: int, W: int, stride: int, d_disp: int, cn: int = 1,
-                       d_conf: int | None = None) -> None:
+                       d_conf: int | None = None, d_rmap: int | None = None) -> None:
         self._channels(cn)
         if d_conf is not None:
             self.bind_confidence_device([d_conf])
+        if d_rmap is not None:
+            self.bind_right_device([d_rmap])
         _check(self._L.sgm_compute_device(self._h, d_left, d_right, H, W, stride, d_disp))
 
     def pipeline_device(self, d_left: int, d_right: int, H: int, W: int, stride: int, Q: np.ndarray | None,
                         d_disp: int | None, d_dispf: int | None, d_xyz: int | None, cn: int = 1,
-                        d_conf: int | None = None) -> None:
+                        d_conf: int | None = None, d_rmap: int | None = None) -> None:
         qp = None
         if Q is not None:
             Q = np.ascontiguousarray(Q, np.float64)
@@ -265,10 +276,12 @@ class Engine:
         self._channels(cn)
         if d_conf is not None:
             self.bind_confidence_device([d_conf])
+        if d_rmap is not None:
+            self.bind_right_device([d_rmap])
         _check(self._L.sgm_pipeline_device(self._h, d_left, d_right, H, W, stride, qp, d_disp, d_dispf, d_xyz))
 
     def pipeline_batch_device(self, d_lefts, d_rights, H: int, W: int, stride: int, Q: np.ndarray | None,
-                              d_disps, d_dispfs=None, d_xyzs=None, cn: int = 1, d_confs=None) -> None:
+                              d_disps, d_dispfs=None, d_xyzs=None, cn: int = 1, d_confs=None, d_rmaps=None) -> None:
         """N resident pairs in throughput mode (sgm_pipeline_batch_device): sequences of N device addresses.
         With SGM_OPT_SCHEDULE = 2 the pairs share one chained sweep launch per pass.  Asynchronous."""
         n = len(d_lefts)
@@ -281,6 +294,8 @@ class Engine:
         self._channels(cn)
         if d_confs is not None:
             self.bind_confidence_device(list(d_confs))
+        if d_rmaps is not None:
+            self.bind_right_device(list(d_rmaps))
         _check(self._L.sgm_pipeline_batch_device(self._h, n, a, b, H, W, stride, qp, c, d, f))
 
     def disp_to_float_device(self, d_disp: int, n: int, d_out: int) -> None:
@@ -398,12 +413,22 @@ class StereoSGBM:
         in cv2."""
         return self._compute(left, right, True)
 
-    def _compute(self, left, right, with_conf: bool):
+    def computeLeftRight(self, left, right):
+        """(disp16_left, disp16_right): compute()'s map and the disparity map referenced to the RIGHT image, int16 (H, W) at
+        the same scale and with the same invalid value (minDisparity - 1) * 16; a valid right pixel (y, xr) with disparity d
+        matches left pixel (y, xr + d).  Same inputs and validation as compute(); numpy in, numpy out; HIP tensors in, tensors
+        out.  The right map comes from ONE more pass over the aggregated cost of this compute (right pixel xr at disparity d
+        costs what left pixel xr + d paid for d), with the left map's uniqueness test, sub-pixel step, mirrored LR check,
+        median and speckle filter -- not from a second compute.  It is NOT what cv2.ximgproc.createRightMatcher gives: that
+        aggregates the paths again on the swapped pair; here they are the left view's."""
+        return self._compute(left, right, False, True)
+
+    def _compute(self, left, right, with_conf: bool, with_right: bool = False):
         if self._p["mode"] not in (STEREO_SGBM_MODE_SGBM, STEREO_SGBM_MODE_HH, STEREO_SGBM_MODE_HH4):
             raise error("StereoSGBM.compute: MODE_SGBM, MODE_HH and MODE_HH4 are implemented; MODE_SGBM_3WAY is not "
                         "(its result depends on a stripe size upstream derives from the cache size)")
         if _is_torch(left) or _is_torch(right):
-            return self._compute_torch(left, right, with_conf)
+            return self._compute_torch(left, right, with_conf, with_right)
         left, right = np.asarray(left), np.asarray(right)
         # upstream: CV_Assert(left.size() == right.size() && left.type() == right.type() && depth == CV_8U)
         if left.shape != right.shape or left.dtype != right.dtype or left.dtype != np.uint8:
@@ -424,6 +449,14 @@ class StereoSGBM:
         if left.shape[1] < 2:
             raise error("StereoSGBM.compute: image width < 2")
         eng = get_engine(self._p)
+        if with_right:
+            eng.set_option(_lib.SGM_OPT_RIGHT_VIEW, 1)
+            try:
+                disp = eng.compute_host(left, right)
+                rmap = eng.tap(_lib.SGM_TAP_RIGHT, *disp.shape)
+            finally:
+                eng.set_option(_lib.SGM_OPT_RIGHT_VIEW, 0)
+            return disp, rmap
         if not with_conf:
             return eng.compute_host(left, right)
         # the cached engine produces the maps for this call only: plain compute() calls do not pay for them
@@ -435,7 +468,7 @@ class StereoSGBM:
             eng.set_option(_lib.SGM_OPT_CONFIDENCE, 0)
         return disp, conf
 
-    def _compute_torch(self, left, right, with_conf: bool = False):
+    def _compute_torch(self, left, right, with_conf: bool = False, with_right: bool = False):
         import torch
         if not (_is_torch(left) and _is_torch(right)) or not left.is_cuda or not right.is_cuda:
             raise error("StereoSGBM.compute: torch inputs must both be CUDA (HIP) tensors")
@@ -453,6 +486,15 @@ class StereoSGBM:
         out = torch.empty((H, W), dtype=torch.int16, device=left.device)
         # the engine runs on its own stream: order it after torch's current stream and wait for it
         torch.cuda.current_stream(left.device).synchronize()
+        if with_right:
+            rmap = torch.empty((H, W), dtype=torch.int16, device=left.device)
+            eng.set_option(_lib.SGM_OPT_RIGHT_VIEW, 1)
+            try:
+                eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn, d_rmap=rmap.data_ptr())
+                eng.synchronize()
+            finally:
+                eng.set_option(_lib.SGM_OPT_RIGHT_VIEW, 0)
+            return out, rmap
         if not with_conf:
             eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn)
             eng.synchronize()
