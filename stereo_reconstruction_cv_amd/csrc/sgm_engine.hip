@@ -231,6 +231,54 @@ struct Plan {
     bool speckle;          // the speckle filter runs
 };
 
+// Every device buffer an engine owns, ONCE: BUF(name) a member of the engine, ARR(name, dims) a two-dimensional array member,
+// MAP(name) a member of SideMap, which the engine holds twice (conf.name, right.name).  The list expands to the member
+// declarations and to the walk over all of them (each_devbuf) behind release_buffers, poison_buffers and plan_bytes_held: a
+// buffer added here is released, poisoned and counted; tests/test_history_walks.py refuses a DevBuf declared anywhere else.
+#define SGM_ENGINE_DEVBUFS(BUF, ARR, MAP) \
+    BUF(in_left) BUF(in_right)                   /* staging for host-pointer calls */ \
+    BUF(lrec) BUF(rplanes)                       /* features */ \
+    BUF(hsum) BUF(cost) BUF(aggr)                /* int16 [H][W1][D] volumes */ \
+    BUF(aggr2) BUF(aggr3)                        /* MODE_SGBM: the fifth path's own volume (D <= 128; added to S by the winner-take-all), the other in-row path's (D <= 64) */ \
+    BUF(aggr4) BUF(aggr5)                        /* MODE_SGBM, D <= 64: the volumes of the vertical and the second diagonal direction (k_paths5_g) */ \
+    BUF(wta)                                     /* uint2 [H][W] */ \
+    BUF(bndL) BUF(bndL2)                         /* band-boundary state of the sweep pre-pass (down / up) */ \
+    BUF(pstate) BUF(pstate2)                     /* line state between the row chunks of the pre-pass (ping-pong, down / up) */ \
+    BUF(disp_raw) BUF(disp_med) BUF(disp_out)    /* int16 [H][W] */ \
+    MAP(raw) MAP(fin)                            /* [H][W], option on only.  conf: uint8, the margin of the winner-take-all; masked by the final map.  right: int16 */ \
+    BUF(rrec)                                    /* SGM_OPT_RIGHT_VIEW only: uint2 [H][W1] record of the diagonal winner-take-all */ \
+    BUF(label) BUF(csize) BUF(rlen)              /* int32 [H][W] each */ \
+    BUF(f32) BUF(xyz) BUF(mask) BUF(minkey)      /* host-pointer post stages */ \
+    BUF(rmap1) BUF(rmap2) BUF(rsrc) BUF(rdst)    /* host-pointer rectification stages */ \
+    BUF(ccount) BUF(cpts) BUF(crgb) BUF(crgb_in) /* point compaction */ \
+    BUF(headroom)                                /* uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r */ \
+    BUF(chain_ctl) BUF(chain_err)                /* chained sweeps: ticket + progress words (zeroed before every launch); sticky give-up flag */ \
+    ARR(io, [2][5])                              /* sgm_compute_batch, throughput mode: the transfer slots (sgm_engine says what they hold) */
+#define SGM_DEVBUF_DECL(name) DevBuf name;
+#define SGM_DEVBUF_DECL_ARR(name, dims) DevBuf name dims;
+#define SGM_DEVBUF_NONE(...)
+#define SGM_DEVBUF_VISIT(name) f(e->name);   // (these three: each_devbuf, its e and f)
+#define SGM_DEVBUF_VISIT_ARR(name, dims) for (auto &row : e->name) for (auto &b : row) f(b);
+#define SGM_DEVBUF_VISIT_MAP(name) f(e->conf.name); f(e->right.name);
+
+// The optional per-pair map.  SGM_OPT_CONFIDENCE and SGM_OPT_RIGHT_VIEW are one mechanism: an option, two maps [H][W] (raw, and
+// final behind the left map's epilogue), a tap on each, and a bind entry that sends the final maps of the next image call to
+// the caller's memory.  The constants that differ come first; the kernels are stage_confidence / stage_right_view.
+struct SideMap {
+    const int bpp;                                                // bytes per pixel of either map
+    const char *const opt_name, *const bind_name, *const noun;    // as the error texts spell them
+    const int tap_raw, tap_fin;
+    const char *const tap_fin_name;
+    int on = 0;                // the option
+    int last = 0;              // what the last compute on this engine left: 0 no maps, 1 raw + fin, 2 fin went to a bound pointer
+    std::vector<void *> bind;  // the bind entry: where the next image call writes its pairs' final maps
+    SGM_ENGINE_DEVBUFS(SGM_DEVBUF_NONE, SGM_DEVBUF_NONE, SGM_DEVBUF_DECL)
+};
+
+// The device pointers of one pair, as one value.  Null: no float map / no XYZ image; conf and rmap -- the engine's own buffer
+// (SideMap::fin); disp_i16 -- in pipeline_one only -- the engine's disp_out.
+struct PairIO { const void *left, *right; void *disp_i16, *disp_f32, *xyz_f32; uint8_t *conf; int16_t *rmap; };
+
 struct sgm_engine {
     sgm_params params;
     int device = 0;
@@ -249,12 +297,9 @@ struct sgm_engine {
     int debug = 0;       // timing experiments (SweepArgs::dbg)
     int prepass_rows = 0;  // rows per chunk of the boundary pre-pass (0 = automatic, about 135, a multiple of 8)
     int cn = 1;          // SGM_OPT_CHANNELS: 1 or 3 interleaved 8-bit channels per image pixel
-    int confidence = 0;  // SGM_OPT_CONFIDENCE: every compute also produces the uniqueness margin (conf_raw, conf)
-    int conf_last = 0;   // what the last compute on this engine left: 0 no maps, 1 conf_raw + conf, 2 conf went to a bound pointer
-    std::vector<void *> conf_bind;        // sgm_bind_confidence_device: where the next image call writes its pairs' conf
-    int right_view = 0;  // SGM_OPT_RIGHT_VIEW: every compute also produces the right-view map (right_raw, right)
-    int right_last = 0;  // what the last compute left: 0 no maps, 1 right_raw + right, 2 right went to a bound pointer
-    std::vector<void *> right_bind;       // sgm_bind_right_device: where the next image call writes its pairs' right map
+    // SGM_OPT_CONFIDENCE: every compute also produces the uniqueness margin; SGM_OPT_RIGHT_VIEW: the right-view map
+    SideMap conf{1, "SGM_OPT_CONFIDENCE", "sgm_bind_confidence_device", "confidence", SGM_TAP_CONF_RAW, SGM_TAP_CONF, "SGM_TAP_CONF"};
+    SideMap right{2, "SGM_OPT_RIGHT_VIEW", "sgm_bind_right_device", "right-view", SGM_TAP_RIGHT_RAW, SGM_TAP_RIGHT, "SGM_TAP_RIGHT"};
     // sgm_compute_batch: up to three pairs in flight = this engine + two peers (own stream and device
     // buffers), each with page-locked staging buffers for the images and the disparity map
     sgm_engine *peer = nullptr, *peer2 = nullptr;
@@ -268,7 +313,7 @@ struct sgm_engine {
     // group g).  Each engine of a group keeps the device images of ITS pair twice -- slot g & 1: left, right, int16 map,
     // float map, XYZ -- with an event behind the upload and one behind the pair's last kernel; the engine the caller
     // holds owns the two copy streams.
-    DevBuf io[2][5];
+    // (the slots themselves, DevBuf io[2][5], are declared by the list below)
     HostBuf pin_io[2][3];                 // page-locked staging of the slot's images (left, right) and of its int16 map
     // events of a slot: images uploaded / images consumed by the cost stage / last kernel of the pair done / map downloaded
     hipEvent_t ev_io_in[2] = {nullptr, nullptr}, ev_io_used[2] = {nullptr, nullptr}, ev_io_out[2] = {nullptr, nullptr},
@@ -282,24 +327,8 @@ struct sgm_engine {
     int H = 0, W = 0;
     Geom g{};
 
-    DevBuf in_left, in_right;           // staging for host-pointer calls
-    DevBuf lrec, rplanes;               // features
-    DevBuf hsum, cost, aggr;            // int16 [H][W1][D] volumes
-    DevBuf aggr2;                       // MODE_SGBM, D <= 128: the fifth path's own volume (added to S by the winner-take-all)
-    DevBuf aggr3;                       // MODE_SGBM, D <= 64: the other in-row path's own volume
-    DevBuf aggr4, aggr5;                // MODE_SGBM, D <= 64: the volumes of the vertical and the second diagonal direction (k_paths5_g)
-    DevBuf wta;                         // uint2 [H][W]
-    DevBuf bndL, bndL2;                 // band-boundary state of the sweep pre-pass (down / up)
-    DevBuf pstate, pstate2;             // line state between the row chunks of the pre-pass (ping-pong, down / up)
-    DevBuf disp_raw, disp_med, disp_out;  // int16 [H][W]
-    DevBuf conf_raw, conf;              // uint8 [H][W], SGM_OPT_CONFIDENCE only: the margin of the winner-take-all; masked by the final map
-    DevBuf rrec, right_raw, right;      // SGM_OPT_RIGHT_VIEW only: uint2 [H][W1] record of the diagonal winner-take-all; int16 [H][W] maps
-    DevBuf label, csize, rlen;          // int32 [H][W] each
-    DevBuf f32, xyz, mask, minkey;      // host-pointer post stages
-    DevBuf rmap1, rmap2, rsrc, rdst;    // host-pointer rectification stages
-    DevBuf ccount, cpts, crgb, crgb_in; // point compaction
-    DevBuf headroom;                    // uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r
-    DevBuf chain_ctl, chain_err;        // chained sweeps: ticket + progress words (zeroed before every launch); sticky give-up flag
+    // device buffers: the list above, each entry once
+    SGM_ENGINE_DEVBUFS(SGM_DEVBUF_DECL, SGM_DEVBUF_DECL_ARR, SGM_DEVBUF_NONE)
 
     // profiling
     std::vector<hipEvent_t> events;
@@ -312,6 +341,13 @@ struct sgm_engine {
     int last_end_ev = -1;                 // end event of the stage that was closed last, and its stream
     hipStream_t last_end_stream = nullptr;
 };
+
+// f(DevBuf &) for every device buffer of e (an engine, or a const one), in the order of the list
+template <class E, class F>
+static void each_devbuf(E *e, F f)
+{
+    SGM_ENGINE_DEVBUFS(SGM_DEVBUF_VISIT, SGM_DEVBUF_VISIT_ARR, SGM_DEVBUF_VISIT_MAP)
+}
 
 static int normalise(const sgm_params *p, int H, int W, Geom *g)
 {
@@ -730,7 +766,7 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     // SGM_OPT_CONFIDENCE: always the separate pass -- the confidence byte comes from k_wta_conf_t alone, so
     // the routes that fuse by default (v1, MODE_SGBM with D > 128, D > 512) store S once more and read it back: 2 V more.
     // SGM_OPT_RIGHT_VIEW: likewise -- the diagonal winner-take-all (k_right_wta) reads S from device memory.
-    const bool conf = e->confidence != 0 || e->right_view != 0;
+    const bool conf = e->conf.on != 0 || e->right.on != 0;
     p.fused_wta = !conf && (p.v1 || (!p.axis && !(dbg & SGM_DBG_WTA_SEPARATE) && (((dbg & SGM_DBG_WTA_IN_LAST_PATH) && !p.rows4) ||
                                                                                   (g.mode == 0 && ((dbg & SGM_DBG_NO_LANE_GROUPS) || g.D > 128)))));
     // MODE_SGBM with the separate winner-take-all (D <= 128): the fifth path (in-row, right to left) needs
@@ -789,15 +825,13 @@ static size_t chain_ctl_bytes(int nf, int nbands) { return ((size_t)(1 + (size_t
 
 // Every device buffer one compute of this shape needs under plan p, allocated BEFORE anything is enqueued (a pair of a
 // chained group that does not fit then costs nothing but a smaller group).  Records the shape in e->g.
-// device bytes of the buffers ensure_plan_buffers sizes (it allocated something iff this grew)
+// device bytes the engine holds.  Only ever compared with itself across one ensure_plan_buffers call (prepare_group: that
+// call allocated something iff this grew), and the call touches none of the buffers it does not size: summing EVERY buffer
+// gives the comparison the same outcome as summing those alone.
 static size_t plan_bytes_held(const sgm_engine *e)
 {
-    const DevBuf *bufs[] = {&e->lrec, &e->rplanes, &e->hsum, &e->cost, &e->aggr, &e->aggr2, &e->aggr3, &e->aggr4, &e->aggr5,
-                            &e->wta, &e->disp_raw, &e->disp_med, &e->headroom, &e->bndL, &e->bndL2, &e->pstate, &e->pstate2,
-                            &e->label, &e->csize, &e->rlen, &e->chain_ctl, &e->chain_err, &e->conf_raw, &e->conf,
-                            &e->rrec, &e->right_raw, &e->right};
     size_t n = 0;
-    for (const DevBuf *b : bufs) n += b->cap;
+    each_devbuf(e, [&](const DevBuf &b) { n += b.cap; });
     return n;
 }
 static int ensure_plan_buffers(sgm_engine *e, const Plan &p, int H, int W)
@@ -832,11 +866,9 @@ static int ensure_plan_buffers(sgm_engine *e, const Plan &p, int H, int W)
     if ((rc = e->wta.ensure(npx * 8))) return rc;
     if ((rc = e->disp_raw.ensure(npx * 2))) return rc;
     if ((rc = e->disp_med.ensure(npx * 2))) return rc;
-    if (e->confidence && ((rc = e->conf_raw.ensure(npx)) || (rc = e->conf.ensure(npx)))) return rc;
-    if (e->right_view) {
-        if ((rc = e->right_raw.ensure(npx * 2)) || (rc = e->right.ensure(npx * 2))) return rc;
-        if (g.W1 > 0 && (rc = e->rrec.ensure((size_t)H * g.W1 * 8))) return rc;
-    }
+    for (SideMap *m : {&e->conf, &e->right})
+        if (m->on && ((rc = m->raw.ensure(npx * m->bpp)) || (rc = m->fin.ensure(npx * m->bpp)))) return rc;
+    if (e->right.on && g.W1 > 0 && (rc = e->rrec.ensure((size_t)H * g.W1 * 8))) return rc;
     if ((rc = e->headroom.ensure(8))) return rc;
     e->g.hr = (uint32_t *)e->headroom.p;
     if (g.W1 > 0 && !p.v1 && p.nbands > 1 && p.nvol < 4) {
@@ -1119,7 +1151,7 @@ static int launch_wta_lg(int lg, const Geom &g, int16_t *const Sv[5], uint2 *wta
     else if (lg == LG) return launch_wta_t<POSW, LG, NV, CONF>(g, Sv, wta, conf, npix, st);
     else return launch_wta_lg<POSW, NV, CONF, LG + 1>(lg, g, Sv, wta, conf, npix, st);
 }
-// conf: null, or the conf_raw map of a confidence compute (already cleared)
+// conf: null, or the raw map of a confidence compute (already cleared)
 static int launch_wta(const Geom &g, int nvol, int16_t *const Sv[5], uint2 *wta, uint8_t *conf, hipStream_t st)
 {
     const int64_t npix = (int64_t)g.H * g.W1;
@@ -1380,7 +1412,7 @@ static int stage_wta(sgm_engine *e, const Plan &p)
 {
     if (p.fused_wta) return SGM_OK;
     const Geom &g = e->g;
-    uint8_t *conf = e->confidence ? (uint8_t *)e->conf_raw.p : nullptr;
+    uint8_t *conf = e->conf.on ? (uint8_t *)e->conf.raw.p : nullptr;
     return run_stage(e, conf ? "wta_conf" : "wta", e->stream, [&] {
         int16_t *const Sv[5] = {(int16_t *)e->aggr.p, p.nvol >= 2 ? (int16_t *)e->aggr2.p : nullptr,
                                 p.nvol >= 3 ? (int16_t *)e->aggr3.p : nullptr, p.nvol >= 4 ? (int16_t *)e->aggr4.p : nullptr,
@@ -1425,15 +1457,15 @@ static int stage_median_speckle(sgm_engine *e, const Plan &p, int16_t *d_disp)
     });
 }
 
-// SGM_OPT_CONFIDENCE: conf = conf_raw masked by the final map, behind the speckle filter on the pair's stream; into the
+// SGM_OPT_CONFIDENCE: conf.fin = conf.raw masked by the final map, behind the speckle filter on the pair's stream; into the
 // engine's buffer, or to the pointer bound for this pair (sgm_bind_confidence_device)
 static int stage_confidence(sgm_engine *e, const int16_t *d_disp, uint8_t *d_conf)
 {
     const int64_t n = (int64_t)e->g.H * e->g.W;
-    uint8_t *out = d_conf ? d_conf : (uint8_t *)e->conf.p;
-    e->conf_last = d_conf ? 2 : 1;
+    uint8_t *out = d_conf ? d_conf : (uint8_t *)e->conf.fin.p;
+    e->conf.last = d_conf ? 2 : 1;
     return run_stage(e, "conf", e->stream, [&] {
-        const uint8_t *raw = (const uint8_t *)e->conf_raw.p;
+        const uint8_t *raw = (const uint8_t *)e->conf.raw.p;
         const bool vec = (((uintptr_t)raw | (uintptr_t)out) & 3) == 0 && ((uintptr_t)d_disp & 7) == 0;
         if (vec)
             hipLaunchKernelGGL(k_conf_final<true>, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, e->stream, raw, d_disp,
@@ -1453,8 +1485,8 @@ static int stage_right_view(sgm_engine *e, const Plan &p, int16_t *d_rmap)
 {
     const Geom &g = e->g;
     const int H = g.H, W = g.W;
-    int16_t *raw = (int16_t *)e->right_raw.p, *out = d_rmap ? d_rmap : (int16_t *)e->right.p;
-    e->right_last = d_rmap ? 2 : 1;
+    int16_t *raw = (int16_t *)e->right.raw.p, *out = d_rmap ? d_rmap : (int16_t *)e->right.fin.p;
+    e->right.last = d_rmap ? 2 : 1;
     int rc;
     if (g.W1 <= 0) {  // no matched column: no volume, nothing to scan
         const int64_t npx = (int64_t)H * W;
@@ -1494,11 +1526,12 @@ static int stage_right_view(sgm_engine *e, const Plan &p, int16_t *d_rmap)
     });
 }
 
-// d_conf: SGM_OPT_CONFIDENCE only -- where this pair's final confidence map goes (null: the engine's own buffer)
-// d_rmap: SGM_OPT_RIGHT_VIEW only -- likewise for this pair's final right-view map
-static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_right, int H, int W,
-                       int64_t stride, int16_t *d_disp, int phases = PH_ALL, uint8_t *d_conf = nullptr, int16_t *d_rmap = nullptr)
+// io.conf: SGM_OPT_CONFIDENCE only -- where this pair's final confidence map goes (null: the engine's own buffer)
+// io.rmap: SGM_OPT_RIGHT_VIEW only -- likewise for this pair's final right-view map
+static int run_compute(sgm_engine *e, const PairIO &io, int H, int W, int64_t stride, int phases = PH_ALL)
 {
+    const uint8_t *d_left = (const uint8_t *)io.left, *d_right = (const uint8_t *)io.right;
+    int16_t *d_disp = (int16_t *)io.disp_i16;
     if (!e || !d_left || !d_right || !d_disp) return set_err(SGM_ERR_INVALID_ARG, "null pointer");
     if (H <= 0 || W < 2 || stride < (int64_t)W * e->cn)
         return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld (channels %d)", H, W, (long long)stride, e->cn);
@@ -1516,8 +1549,7 @@ static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_ri
         e->nevents = 0;
         e->last_end_ev = -1;
         e->plan = p;
-        e->conf_last = 0;
-        e->right_last = 0;
+        e->conf.last = e->right.last = 0;
     } else {
         stage_break(e);
     }
@@ -1531,8 +1563,8 @@ static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_ri
         // no column can be matched: the whole map is invalid (upstream early-out), then median
         // and speckle act on a constant image
         const int64_t npx = (int64_t)H * W;
-        if (e->confidence) {
-            HIP_TRY(hipMemsetAsync(e->conf_raw.p, 0, (size_t)npx, e->stream));
+        if (e->conf.on) {
+            HIP_TRY(hipMemsetAsync(e->conf.raw.p, 0, (size_t)npx, e->stream));
             stage_break(e);
         }
         rc = run_stage(e, "fill_invalid", e->stream, [&] {
@@ -1547,15 +1579,15 @@ static int run_compute(sgm_engine *e, const uint8_t *d_left, const uint8_t *d_ri
         if (do_mid && (rc = p.v1 ? paths_v1(e, p) : paths_fused(e, p))) return rc;
         if (!do_post) return SGM_OK;
         if ((rc = stage_join(e, p))) return rc;
-        if (e->confidence) {  // columns no disparity can be matched at keep 0: k_wta_conf_t writes minX1 .. minX1 + W1 only
-            HIP_TRY(hipMemsetAsync(e->conf_raw.p, 0, (size_t)H * W, e->stream));
+        if (e->conf.on) {  // columns no disparity can be matched at keep 0: k_wta_conf_t writes minX1 .. minX1 + W1 only
+            HIP_TRY(hipMemsetAsync(e->conf.raw.p, 0, (size_t)H * W, e->stream));
             stage_break(e);
         }
         if ((rc = stage_wta(e, p)) || (rc = stage_select(e))) return rc;
     }
     if ((rc = stage_median_speckle(e, p, d_disp))) return rc;
-    if (e->confidence && (rc = stage_confidence(e, d_disp, d_conf))) return rc;
-    return e->right_view ? stage_right_view(e, p, d_rmap) : SGM_OK;
+    if (e->conf.on && (rc = stage_confidence(e, d_disp, io.conf))) return rc;
+    return e->right.on ? stage_right_view(e, p, io.rmap) : SGM_OK;
 }
 
 static int run_to_float(sgm_engine *e, const int16_t *d_disp, int64_t n, float *d_out)
@@ -1728,13 +1760,7 @@ int sgm_create(const sgm_params *params, int device_id, void *stream, sgm_engine
 // every device buffer of an engine (the engine stays usable: buffers come back on the next call that needs them)
 static void release_buffers(sgm_engine *e)
 {
-    DevBuf *bufs[] = {&e->in_left, &e->in_right, &e->lrec, &e->rplanes, &e->hsum, &e->cost, &e->aggr, &e->aggr2, &e->rmap1, &e->rmap2, &e->rsrc, &e->rdst, &e->wta, &e->bndL, &e->bndL2, &e->pstate, &e->pstate2,
-                      &e->disp_raw, &e->disp_med, &e->disp_out, &e->label, &e->csize, &e->rlen, &e->f32, &e->xyz, &e->mask,
-                      &e->minkey, &e->ccount, &e->cpts, &e->crgb, &e->crgb_in, &e->headroom, &e->chain_ctl, &e->chain_err, &e->aggr3, &e->aggr4, &e->aggr5, &e->conf_raw, &e->conf,
-                      &e->rrec, &e->right_raw, &e->right};
-    for (DevBuf *b : bufs) (void)b->release();
-    for (auto &slot : e->io)
-        for (DevBuf &b : slot) (void)b.release();
+    each_devbuf(e, [](DevBuf &b) { (void)b.release(); });
     e->g.hr = nullptr;
 }
 
@@ -1743,20 +1769,15 @@ static void release_buffers(sgm_engine *e)
 // the same for the engines behind it (peer, peer2, group), each on its own stream.  Every stream is waited for at the end:
 // the batch entries order the engines of a group with events of their own, not with the caller's stream.
 // chain_err is the one member that is state by contract (the sticky give-up flag that check_chain reports and clears); it is
-// LEFT ALONE, neither filled nor re-cleared.  tests/test_history_walks.py checks that every DevBuf member of sgm_engine is named here.
+// LEFT ALONE, neither filled nor re-cleared.  (Every buffer: the walk over SGM_ENGINE_DEVBUFS, tests/test_history_walks.py.)
 static int poison_buffers(sgm_engine *e, int byte)
 {
-    DevBuf *bufs[] = {&e->in_left, &e->in_right, &e->lrec, &e->rplanes, &e->hsum, &e->cost, &e->aggr, &e->aggr2, &e->aggr3, &e->aggr4,
-                      &e->aggr5, &e->wta, &e->bndL, &e->bndL2, &e->pstate, &e->pstate2, &e->disp_raw, &e->disp_med, &e->disp_out,
-                      &e->label, &e->csize, &e->rlen, &e->f32, &e->xyz, &e->mask, &e->minkey, &e->rmap1, &e->rmap2, &e->rsrc,
-                      &e->rdst, &e->ccount, &e->cpts, &e->crgb, &e->crgb_in, &e->headroom, &e->chain_ctl, &e->chain_err,
-                      &e->conf_raw, &e->conf, &e->rrec, &e->right_raw, &e->right,
-                      &e->io[0][0], &e->io[0][1], &e->io[0][2], &e->io[0][3], &e->io[0][4],
-                      &e->io[1][0], &e->io[1][1], &e->io[1][2], &e->io[1][3], &e->io[1][4]};
-    static_assert(sizeof(e->io) == 10 * sizeof(DevBuf), "poison_buffers names every slot of io");
     HIP_TRY(hipSetDevice(e->device));
-    for (DevBuf *b : bufs)
-        if (b != &e->chain_err && b->p && b->cap) HIP_TRY(hipMemsetAsync(b->p, byte, b->cap, e->stream));
+    hipError_t he = hipSuccess;
+    each_devbuf(e, [&](DevBuf &b) {
+        if (&b != &e->chain_err && b.p && b.cap && he == hipSuccess) he = hipMemsetAsync(b.p, byte, b.cap, e->stream);
+    });
+    if (he != hipSuccess) return set_err(SGM_ERR_HIP, "SGM_OPT_POISON: hipMemsetAsync failed: %s", hipGetErrorString(he));
     int rc;
     if (e->peer && (rc = poison_buffers(e->peer, byte))) return rc;
     if (e->peer2 && (rc = poison_buffers(e->peer2, byte))) return rc;
@@ -1830,15 +1851,11 @@ int sgm_set_option(sgm_engine *e, int option, int value)
             return set_err(SGM_ERR_INVALID_ARG, "SGM_OPT_CHANNELS %d: only 1 and 3 interleaved 8-bit channels are supported", value);
         e->cn = value;
     }
-    else if (option == SGM_OPT_CONFIDENCE) {
-        if (value != 0 && value != 1) return set_err(SGM_ERR_INVALID_ARG, "SGM_OPT_CONFIDENCE %d: 0 (off) or 1 (on)", value);
-        e->confidence = value;
-        if (!value) e->conf_bind.clear();
-    }
-    else if (option == SGM_OPT_RIGHT_VIEW) {
-        if (value != 0 && value != 1) return set_err(SGM_ERR_INVALID_ARG, "SGM_OPT_RIGHT_VIEW %d: 0 (off) or 1 (on)", value);
-        e->right_view = value;
-        if (!value) e->right_bind.clear();
+    else if (option == SGM_OPT_CONFIDENCE || option == SGM_OPT_RIGHT_VIEW) {
+        SideMap &m = option == SGM_OPT_CONFIDENCE ? e->conf : e->right;
+        if (value != 0 && value != 1) return set_err(SGM_ERR_INVALID_ARG, "%s %d: 0 (off) or 1 (on)", m.opt_name, value);
+        m.on = value;
+        if (!value) m.bind.clear();
     }
     else if (option == SGM_OPT_POISON) {
         // csrc/sgm_debug.h: 0..255 fills every buffer now and arms DevBuf::ensure; anything else disarms
@@ -1903,51 +1920,47 @@ int sgm_trim(sgm_engine *e)
     return check_chain(e);
 }
 
-// The binding of sgm_bind_confidence_device belongs to the next image call, whatever becomes of that call: taken off the
-// engine here.  *out: the n pointers (empty: none bound).
-static int take_conf_binding(sgm_engine *e, int n, std::vector<void *> *out)
+// The binding of a bind entry belongs to the next image call, whatever becomes of that call: taken off the engine here.
+// *out: the n pointers (empty: none bound).
+static int take_binding(SideMap &m, int n, std::vector<void *> *out)
 {
     out->clear();
-    out->swap(e->conf_bind);
+    out->swap(m.bind);
     if (!out->empty() && (int)out->size() != n)
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_bind_confidence_device bound %d maps, this call has %d pair(s)", (int)out->size(), n);
+        return set_err(SGM_ERR_INVALID_ARG, "%s bound %d maps, this call has %d pair(s)", m.bind_name, (int)out->size(), n);
     return SGM_OK;
 }
-
-// the same for sgm_bind_right_device.  An image call takes BOTH bindings before it looks at either result.
-static int take_right_binding(sgm_engine *e, int n, std::vector<void *> *out)
+// an image call takes BOTH bindings before it looks at either result
+static int take_bindings(sgm_engine *e, int n, std::vector<void *> *conf, std::vector<void *> *right)
 {
-    out->clear();
-    out->swap(e->right_bind);
-    if (!out->empty() && (int)out->size() != n)
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_bind_right_device bound %d maps, this call has %d pair(s)", (int)out->size(), n);
+    const int brc = take_binding(e->conf, n, conf), rrc = take_binding(e->right, n, right);
+    return brc ? brc : rrc;
+}
+// the host entries: a binding is for the device entries (the host entries' maps are read through the taps)
+static void clear_bindings(sgm_engine *e) { e->conf.bind.clear(), e->right.bind.clear(); }
+// pair i's pointer of a binding taken (null: none bound)
+static void *bound_at(const std::vector<void *> &b, int i) { return b.empty() ? nullptr : b[i]; }
+
+static int bind(SideMap &m, int N, void *const *ptrs)
+{
+    m.bind.clear();
+    if (N == 0) return SGM_OK;
+    if (N < 0 || !ptrs) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
+    if (!m.on) return set_err(SGM_ERR_INVALID_ARG, "%s needs %s=1", m.bind_name, m.opt_name);
+    for (int i = 0; i < N; i++)
+        if (!ptrs[i]) return set_err(SGM_ERR_INVALID_ARG, "null %s pointer for pair %d", m.noun, i);
+    m.bind.assign(ptrs, ptrs + N);
     return SGM_OK;
 }
 
 int sgm_bind_right_device(sgm_engine *e, int N, void *const *d_right_i16)
 {
-    if (!e) return set_err(SGM_ERR_INVALID_ARG, "engine is null");
-    e->right_bind.clear();
-    if (N == 0) return SGM_OK;
-    if (N < 0 || !d_right_i16) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
-    if (!e->right_view) return set_err(SGM_ERR_INVALID_ARG, "sgm_bind_right_device needs SGM_OPT_RIGHT_VIEW=1");
-    for (int i = 0; i < N; i++)
-        if (!d_right_i16[i]) return set_err(SGM_ERR_INVALID_ARG, "null right-view pointer for pair %d", i);
-    e->right_bind.assign(d_right_i16, d_right_i16 + N);
-    return SGM_OK;
+    return e ? bind(e->right, N, d_right_i16) : set_err(SGM_ERR_INVALID_ARG, "engine is null");
 }
 
 int sgm_bind_confidence_device(sgm_engine *e, int N, void *const *d_conf_u8)
 {
-    if (!e) return set_err(SGM_ERR_INVALID_ARG, "engine is null");
-    e->conf_bind.clear();
-    if (N == 0) return SGM_OK;
-    if (N < 0 || !d_conf_u8) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
-    if (!e->confidence) return set_err(SGM_ERR_INVALID_ARG, "sgm_bind_confidence_device needs SGM_OPT_CONFIDENCE=1");
-    for (int i = 0; i < N; i++)
-        if (!d_conf_u8[i]) return set_err(SGM_ERR_INVALID_ARG, "null confidence pointer for pair %d", i);
-    e->conf_bind.assign(d_conf_u8, d_conf_u8 + N);
-    return SGM_OK;
+    return e ? bind(e->conf, N, d_conf_u8) : set_err(SGM_ERR_INVALID_ARG, "engine is null");
 }
 
 int sgm_compute_device(sgm_engine *e, const void *d_left, const void *d_right, int H, int W, int64_t stride_bytes,
@@ -1955,10 +1968,9 @@ int sgm_compute_device(sgm_engine *e, const void *d_left, const void *d_right, i
 {
     if (!e) return set_err(SGM_ERR_INVALID_ARG, "null pointer");
     std::vector<void *> bound, rbound;
-    const int brc = take_conf_binding(e, 1, &bound), rrc = take_right_binding(e, 1, &rbound);
-    if (brc || rrc) return brc ? brc : rrc;
-    return run_compute(e, (const uint8_t *)d_left, (const uint8_t *)d_right, H, W, stride_bytes, (int16_t *)d_disp_i16, PH_ALL,
-                       bound.empty() ? nullptr : (uint8_t *)bound[0], rbound.empty() ? nullptr : (int16_t *)rbound[0]);
+    if (int rc = take_bindings(e, 1, &bound, &rbound)) return rc;
+    const PairIO io{d_left, d_right, d_disp_i16, nullptr, nullptr, (uint8_t *)bound_at(bound, 0), (int16_t *)bound_at(rbound, 0)};
+    return run_compute(e, io, H, W, stride_bytes);
 }
 
 int sgm_disp_to_float_device(sgm_engine *e, const void *d_disp_i16, int64_t n, void *d_out_f32)
@@ -2103,21 +2115,17 @@ int sgm_remap_linear_u8(sgm_engine *e, const uint8_t *src, int sH, int sW, int64
     return SGM_OK;
 }
 
-// one pair through cell c13 on e; d_conf, d_rmap as in run_compute
-static int pipeline_one(sgm_engine *e, const void *d_left, const void *d_right, int H, int W, int64_t stride_bytes,
-                        const double Q[16], void *d_disp_i16, void *d_disp_f32, void *d_xyz_f32, uint8_t *d_conf,
-                        int16_t *d_rmap = nullptr)
+// one pair through cell c13 on e
+static int pipeline_one(sgm_engine *e, const PairIO &io, int H, int W, int64_t stride_bytes, const double Q[16])
 {
-    const int64_t n = (int64_t)H * W;
-    int rc;
-    int16_t *di = (int16_t *)d_disp_i16;
-    if (!di) {
-        if ((rc = e->disp_out.ensure((size_t)n * 2))) return rc;
-        di = (int16_t *)e->disp_out.p;
+    PairIO p = io;
+    if (!p.disp_i16) {
+        if (int rc = e->disp_out.ensure((size_t)H * W * 2)) return rc;
+        p.disp_i16 = e->disp_out.p;
     }
-    if ((rc = run_compute(e, (const uint8_t *)d_left, (const uint8_t *)d_right, H, W, stride_bytes, di, PH_ALL, d_conf, d_rmap))) return rc;
+    if (int rc = run_compute(e, p, H, W, stride_bytes)) return rc;
     // float scaling + reprojection in one launch (the float map is stored only if asked for)
-    return run_float_xyz(e, di, H, W, Q, d_disp_f32, d_xyz_f32);
+    return run_float_xyz(e, (const int16_t *)p.disp_i16, H, W, Q, p.disp_f32, p.xyz_f32);
 }
 
 int sgm_pipeline_device(sgm_engine *e, const void *d_left, const void *d_right, int H, int W, int64_t stride_bytes,
@@ -2125,10 +2133,9 @@ int sgm_pipeline_device(sgm_engine *e, const void *d_left, const void *d_right, 
 {
     if (!e) return set_err(SGM_ERR_INVALID_ARG, "engine is null");
     std::vector<void *> bound, rbound;
-    const int brc = take_conf_binding(e, 1, &bound), rrc = take_right_binding(e, 1, &rbound);
-    if (brc || rrc) return brc ? brc : rrc;
-    return pipeline_one(e, d_left, d_right, H, W, stride_bytes, Q, d_disp_i16, d_disp_f32, d_xyz_f32,
-                        bound.empty() ? nullptr : (uint8_t *)bound[0], rbound.empty() ? nullptr : (int16_t *)rbound[0]);
+    if (int rc = take_bindings(e, 1, &bound, &rbound)) return rc;
+    const PairIO io{d_left, d_right, d_disp_i16, d_disp_f32, d_xyz_f32, (uint8_t *)bound_at(bound, 0), (int16_t *)bound_at(rbound, 0)};
+    return pipeline_one(e, io, H, W, stride_bytes, Q);
 }
 
 // ---- N pairs, throughput mode --------------------------------------------------------------------------------
@@ -2148,8 +2155,8 @@ static void inherit_options(sgm_engine *q, const sgm_engine *e)
     q->chain_wgs = e->chain_wgs;
     q->prepass_rows = e->prepass_rows;
     q->cn = e->cn;
-    q->confidence = e->confidence;
-    q->right_view = e->right_view;
+    q->conf.on = e->conf.on;
+    q->right.on = e->right.on;
     q->keep_aggr = 0;
     q->profile = 0;
 }
@@ -2235,11 +2242,9 @@ struct BatchGuard {
 // One group (n >= 2 pairs on eng[0 .. n-1], eng[0] = e) through cost stages, joint sweeps, epilogues.  The host entry
 // passes three event arrays (all null for resident pairs): in_ready[k] -- pair k's cost stage waits for it (its images have
 // arrived); in_used[k] -- recorded when pair k's images have been read for the last time (k_features); out_done[k] -- recorded
-// behind pair k's last kernel.
-static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &pl, const void *const *d_left, const void *const *d_right,
-                     int H, int W, int64_t stride_bytes, const double Q[16], void *const *d_disp_i16, void *const *d_disp_f32,
-                     void *const *d_xyz_f32, const hipEvent_t *in_ready, const hipEvent_t *in_used, const hipEvent_t *out_done,
-                     void *const *d_conf = nullptr, void *const *d_rmap = nullptr)
+// behind pair k's last kernel.  io[k]: the pointers of pair k.
+static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &pl, const PairIO *io, int H, int W, int64_t stride_bytes,
+                     const double Q[16], const hipEvent_t *in_ready, const hipEvent_t *in_used, const hipEvent_t *out_done)
 {
     int rc;
     // cost stage of every pair on the stream of its own engine, from where `e`'s stream stands now (the caller's
@@ -2250,9 +2255,7 @@ static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &p
     for (int k = 1; k < n; k++) HIP_TRY(hipStreamWaitEvent(eng[k]->stream, e->ev_group, 0));
     for (int k = 0; k < n; k++) {
         if (in_ready && in_ready[k]) HIP_TRY(hipStreamWaitEvent(eng[k]->stream, in_ready[k], 0));
-        if ((rc = run_compute(eng[k], (const uint8_t *)d_left[k], (const uint8_t *)d_right[k], H, W, stride_bytes,
-                              (int16_t *)d_disp_i16[k], PH_PRE)))
-            return rc;
+        if ((rc = run_compute(eng[k], io[k], H, W, stride_bytes, PH_PRE))) return rc;
         const Plan &q = eng[k]->plan;
         if (!q.chain || q.R != pl.R || q.nbands != pl.nbands || q.axis != pl.axis)
             return set_err(SGM_ERR_HIP, "internal: a pair of a chained group did not plan the group's chained sweep");
@@ -2296,13 +2299,8 @@ static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &p
         // can travel to the host while the epilogues of the pairs behind it still run (all n at once end together: the
         // whole group's download would follow the last kernel).
         if (out_done && k >= 3 && out_done[k - 3]) HIP_TRY(hipStreamWaitEvent(eng[k]->stream, out_done[k - 3], 0));
-        if ((rc = run_compute(eng[k], (const uint8_t *)d_left[k], (const uint8_t *)d_right[k], H, W, stride_bytes,
-                              (int16_t *)d_disp_i16[k], PH_POST, d_conf ? (uint8_t *)d_conf[k] : nullptr,
-                              d_rmap ? (int16_t *)d_rmap[k] : nullptr)))
-            return rc;
-        if ((rc = run_float_xyz(eng[k], (const int16_t *)d_disp_i16[k], H, W, Q, d_disp_f32 ? d_disp_f32[k] : nullptr,
-                                d_xyz_f32 ? d_xyz_f32[k] : nullptr)))
-            return rc;
+        if ((rc = run_compute(eng[k], io[k], H, W, stride_bytes, PH_POST))) return rc;
+        if ((rc = run_float_xyz(eng[k], (const int16_t *)io[k].disp_i16, H, W, Q, io[k].disp_f32, io[k].xyz_f32))) return rc;
         if (out_done && out_done[k]) HIP_TRY(hipEventRecord(out_done[k], eng[k]->stream));
     }
     // e's stream ends behind everything the group did
@@ -2327,6 +2325,15 @@ static int batch_plan(sgm_engine *e, int N, int H, int W, Plan *pl, bool *joint)
     return SGM_OK;
 }
 
+// N pairs in groups of at most `cap`: groups of equal size, and the engines that run a group's pairs (e + its internal ones)
+static std::vector<sgm_engine *> group_engines(sgm_engine *e, int N, int cap, int *ngroups)
+{
+    *ngroups = (N + cap - 1) / cap;
+    std::vector<sgm_engine *> eng((N + *ngroups - 1) / *ngroups);
+    for (size_t k = 0; k < eng.size(); k++) eng[k] = k == 0 ? e : e->group[k - 1];
+    return eng;
+}
+
 // N pairs resident in device memory.  Chained groups when the configuration allows (groups as large as device memory
 // holds, up to CHAIN_MAX_FRAMES or SGM_OPT_GROUP_MAX; a batch larger than a group is cut into groups of equal size);
 // otherwise pair after pair on `e` (the schedule `e` is set to).  Results equal N calls of sgm_pipeline_device.
@@ -2338,16 +2345,18 @@ int sgm_pipeline_batch_device(sgm_engine *e, int N, const void *const *d_left, c
 {
     if (!e) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
     std::vector<void *> bound, rbound;
-    const int brc = take_conf_binding(e, N, &bound), rrc = take_right_binding(e, N, &rbound);   // (consumed before anything else can fail)
+    const int brc = take_bindings(e, N, &bound, &rbound);   // (consumed before anything else can fail)
     if (N <= 0 || !d_left || !d_right || !d_disp_i16) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
-    if (brc || rrc) return brc ? brc : rrc;
-    void *const *d_conf = bound.empty() ? nullptr : bound.data();
-    void *const *d_rmap = rbound.empty() ? nullptr : rbound.data();
+    if (brc) return brc;
     for (int i = 0; i < N; i++)
         if (!d_left[i] || !d_right[i] || !d_disp_i16[i]) return set_err(SGM_ERR_INVALID_ARG, "null pointer for pair %d", i);
     if (stride_bytes < (int64_t)W * e->cn)
         return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld (channels %d)", H, W, (long long)stride_bytes, e->cn);
     if (d_xyz_f32 && !Q) return set_err(SGM_ERR_INVALID_ARG, "Q is null");
+    std::vector<PairIO> io(N);
+    for (int i = 0; i < N; i++)
+        io[i] = PairIO{d_left[i], d_right[i], d_disp_i16[i], d_disp_f32 ? d_disp_f32[i] : nullptr, d_xyz_f32 ? d_xyz_f32[i] : nullptr,
+                       (uint8_t *)bound_at(bound, i), (int16_t *)bound_at(rbound, i)};
     HIP_TRY(hipSetDevice(e->device));
     int rc;
     Plan pl;
@@ -2362,32 +2371,23 @@ int sgm_pipeline_batch_device(sgm_engine *e, int N, const void *const *d_left, c
     if (!joint || cap < 2) {
         for (int i = 0; i < N; i++) {
             e->hr_accumulate = i > 0;     // (the headroom record of the call covers every pair)
-            if ((rc = pipeline_one(e, d_left[i], d_right[i], H, W, stride_bytes, Q, d_disp_i16[i], d_disp_f32 ? d_disp_f32[i] : nullptr,
-                                   d_xyz_f32 ? d_xyz_f32[i] : nullptr, d_conf ? (uint8_t *)d_conf[i] : nullptr,
-                                   d_rmap ? (int16_t *)d_rmap[i] : nullptr)))
-                return rc;
+            if ((rc = pipeline_one(e, io[i], H, W, stride_bytes, Q))) return rc;
         }
         guard.ok = true;
         return SGM_OK;
     }
-    const int ngroups = (N + cap - 1) / cap, per = (N + ngroups - 1) / ngroups;   // groups of equal size
+    int ngroups;
+    const std::vector<sgm_engine *> eng = group_engines(e, N, cap, &ngroups);
+    const int per = (int)eng.size();
     e->last_group = std::min(per, N) - 1;
-    std::vector<sgm_engine *> eng(per);
-    for (int k = 0; k < per; k++) eng[k] = k == 0 ? e : e->group[k - 1];
     for (int i0 = 0; i0 < N; i0 += per) {
         const int n = std::min(N - i0, per);
         for (int k = 0; k < n; k++) eng[k]->hr_accumulate = i0 > 0;
         if (n == 1) {
-            if ((rc = pipeline_one(e, d_left[i0], d_right[i0], H, W, stride_bytes, Q, d_disp_i16[i0], d_disp_f32 ? d_disp_f32[i0] : nullptr,
-                                   d_xyz_f32 ? d_xyz_f32[i0] : nullptr, d_conf ? (uint8_t *)d_conf[i0] : nullptr,
-                                   d_rmap ? (int16_t *)d_rmap[i0] : nullptr)))
-                return rc;
+            if ((rc = pipeline_one(e, io[i0], H, W, stride_bytes, Q))) return rc;
             continue;
         }
-        if ((rc = run_group(e, eng.data(), n, pl, d_left + i0, d_right + i0, H, W, stride_bytes, Q, d_disp_i16 + i0,
-                            d_disp_f32 ? d_disp_f32 + i0 : nullptr, d_xyz_f32 ? d_xyz_f32 + i0 : nullptr, nullptr, nullptr, nullptr,
-                            d_conf ? d_conf + i0 : nullptr, d_rmap ? d_rmap + i0 : nullptr)))
-            return rc;
+        if ((rc = run_group(e, eng.data(), n, pl, io.data() + i0, H, W, stride_bytes, Q, nullptr, nullptr, nullptr))) return rc;
     }
     guard.ok = true;
     return SGM_OK;
@@ -2397,8 +2397,7 @@ int sgm_compute(sgm_engine *e, const uint8_t *left, const uint8_t *right, int H,
                 int16_t *disp_out)
 {
     if (!e || !left || !right || !disp_out) return set_err(SGM_ERR_INVALID_ARG, "null pointer");
-    e->conf_bind.clear();   // (a binding is for the device entries; the host entry's map is read through the taps)
-    e->right_bind.clear();
+    clear_bindings(e);
     const int64_t rowb = (int64_t)W * e->cn;  // bytes of one image row (SGM_OPT_CHANNELS)
     if (H <= 0 || W < 2 || stride_bytes < rowb)
         return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld (channels %d)", H, W, (long long)stride_bytes, e->cn);
@@ -2408,7 +2407,8 @@ int sgm_compute(sgm_engine *e, const uint8_t *left, const uint8_t *right, int H,
     if ((rc = e->in_left.ensure(ib)) || (rc = e->in_right.ensure(ib)) || (rc = e->disp_out.ensure(npx * 2))) return rc;
     HIP_TRY(hipMemcpy2DAsync(e->in_left.p, rowb, left, (size_t)stride_bytes, rowb, H, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpy2DAsync(e->in_right.p, rowb, right, (size_t)stride_bytes, rowb, H, hipMemcpyHostToDevice, e->stream));
-    if ((rc = run_compute(e, (const uint8_t *)e->in_left.p, (const uint8_t *)e->in_right.p, H, W, rowb, (int16_t *)e->disp_out.p))) return rc;
+    const PairIO io{e->in_left.p, e->in_right.p, e->disp_out.p, nullptr, nullptr, nullptr, nullptr};
+    if ((rc = run_compute(e, io, H, W, rowb))) return rc;
     HIP_TRY(hipMemcpyAsync(disp_out, e->disp_out.p, npx * 2, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return check_chain(e);
@@ -2445,8 +2445,7 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
                       int16_t *disps_out, float *xyz_out, const double *Q16)
 {
     if (!e || !lefts || !rights || !disps_out || N <= 0) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
-    e->conf_bind.clear();   // (no per-pair confidence from this entry: sgm_hip.h)
-    e->right_bind.clear();  // (nor a per-pair right-view map)
+    clear_bindings(e);   // (no per-pair confidence or right-view map from this entry: sgm_hip.h)
     if (xyz_out && !Q16) return set_err(SGM_ERR_INVALID_ARG, "xyz_out requested without Q");
     if (H <= 0 || W < 2) return set_err(SGM_ERR_INVALID_ARG, "bad shape");
     HIP_TRY(hipSetDevice(e->device));
@@ -2479,11 +2478,11 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
         if (cap >= 2) {
             if (!e->copy_in) HIP_TRY(hipStreamCreateWithFlags(&e->copy_in, hipStreamNonBlocking));
             if (!e->copy_out) HIP_TRY(hipStreamCreateWithFlags(&e->copy_out, hipStreamNonBlocking));
-            const int ngroups = (N + cap - 1) / cap, per = (N + ngroups - 1) / ngroups;
+            int ngroups;
+            const std::vector<sgm_engine *> eng = group_engines(e, N, cap, &ngroups);
+            const int per = (int)eng.size();
             e->last_group = per - 1;
-            std::vector<sgm_engine *> eng(per);
-            for (int k = 0; k < per; k++) {
-                sgm_engine *q = eng[k] = k == 0 ? e : e->group[k - 1];
+            for (sgm_engine *q : eng) {
                 for (int sl = 0; sl < (ngroups > 1 ? 2 : 1); sl++) {
                     if ((rc = q->io[sl][0].ensure(ib)) || (rc = q->io[sl][1].ensure(ib)) || (rc = q->io[sl][2].ensure(npx * 2))) return rc;
                     if ((rc = q->pin_io[sl][0].ensure(ib)) || (rc = q->pin_io[sl][1].ensure(ib)) || (rc = q->pin_io[sl][2].ensure(npx * 2))) return rc;
@@ -2492,8 +2491,7 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
                         if (!*ev) HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
                 }
             }
-            std::vector<const void *> dl(per), dr(per);
-            std::vector<void *> dd(per), df(per), dx(per);
+            std::vector<PairIO> io(per);
             std::vector<hipEvent_t> evi(per), evu(per), evo(per);
             auto upload = [&](int gi) -> int {     // images of group gi -> slot gi & 1, pair by pair
                 const int sl = gi & 1, i0 = gi * per, n = std::min(N - i0, per);
@@ -2517,24 +2515,20 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
                 for (int k = 0; k < n; k++) {
                     sgm_engine *q = eng[k];
                     q->hr_accumulate = gi > 0;
-                    dl[k] = q->io[sl][0].p;
-                    dr[k] = q->io[sl][1].p;
-                    dd[k] = q->io[sl][2].p;
-                    df[k] = xyz_out ? q->io[sl][3].p : nullptr;
-                    dx[k] = xyz_out ? q->io[sl][4].p : nullptr;
+                    io[k] = PairIO{q->io[sl][0].p, q->io[sl][1].p, q->io[sl][2].p, xyz_out ? q->io[sl][3].p : nullptr,
+                                   xyz_out ? q->io[sl][4].p : nullptr, nullptr, nullptr};
                     evi[k] = q->ev_io_in[sl];
                     evu[k] = q->ev_io_used[sl];
                     evo[k] = q->ev_io_out[sl];
                 }
                 if (n == 1) {   // (a last group of one pair: the plain entry on e, behind its upload)
                     HIP_TRY(hipStreamWaitEvent(e->stream, evi[0], 0));
-                    int r2 = sgm_pipeline_device(e, dl[0], dr[0], H, W, rowb, Q16, dd[0], df[0], dx[0]);
+                    int r2 = pipeline_one(e, io[0], H, W, rowb, Q16);
                     if (r2) return r2;
                     HIP_TRY(hipEventRecord(evu[0], e->stream));
                     HIP_TRY(hipEventRecord(evo[0], e->stream));
                 } else {
-                    int r2 = run_group(e, eng.data(), n, pl, dl.data(), dr.data(), H, W, rowb, Q16, dd.data(), xyz_out ? df.data() : nullptr,
-                                       xyz_out ? dx.data() : nullptr, evi.data(), evu.data(), evo.data());
+                    int r2 = run_group(e, eng.data(), n, pl, io.data(), H, W, rowb, Q16, evi.data(), evu.data(), evo.data());
                     if (r2) return r2;
                 }
                 for (int k = 0; k < n; k++) {
@@ -2614,9 +2608,9 @@ int sgm_compute_batch(sgm_engine *e, int N, const uint8_t *lefts, const uint8_t 
         HIP_TRY(hipMemcpyAsync(q->in_left.p, q->pin_left.p, ib, hipMemcpyHostToDevice, q->stream));
         HIP_TRY(hipMemcpyAsync(q->in_right.p, q->pin_right.p, ib, hipMemcpyHostToDevice, q->stream));
         q->hr_accumulate = i >= neng;   // (the headroom record of the call covers every pair: each engine keeps its pairs' maximum)
-        rc = sgm_pipeline_device(q, q->in_left.p, q->in_right.p, H, W, rowb, Q16, q->disp_out.p, xyz_out ? q->f32.p : nullptr,
-                                 xyz_out ? q->xyz.p : nullptr);
-        if (rc) return rc;
+        const PairIO io{q->in_left.p, q->in_right.p, q->disp_out.p, xyz_out ? q->f32.p : nullptr, xyz_out ? q->xyz.p : nullptr,
+                        nullptr, nullptr};
+        if ((rc = pipeline_one(q, io, H, W, rowb, Q16))) return rc;
         HIP_TRY(hipMemcpyAsync(q->pin_disp.p, q->disp_out.p, npx * 2, hipMemcpyDeviceToHost, q->stream));
         HIP_TRY(hipEventRecord(q->ev_done, q->stream));
     }
@@ -2788,16 +2782,14 @@ int sgm_get_tap(sgm_engine *e, int tap, void *host_dst, int64_t bytes)
     case SGM_TAP_DISP_MEDIAN: src = e->disp_med.p; need = npx * 2; break;
     case SGM_TAP_CONF_RAW:
     case SGM_TAP_CONF:
-        if (!e->conf_last) return set_err(SGM_ERR_INVALID_ARG, "tap %d needs SGM_OPT_CONFIDENCE=1 before compute", tap);
-        if (tap == SGM_TAP_CONF && e->conf_last == 2)
-            return set_err(SGM_ERR_INVALID_ARG, "SGM_TAP_CONF: the last compute wrote its map to the pointer bound with sgm_bind_confidence_device");
-        src = tap == SGM_TAP_CONF_RAW ? e->conf_raw.p : e->conf.p; need = npx; break;
     case SGM_TAP_RIGHT_RAW:
-    case SGM_TAP_RIGHT:
-        if (!e->right_last) return set_err(SGM_ERR_INVALID_ARG, "tap %d needs SGM_OPT_RIGHT_VIEW=1 before compute", tap);
-        if (tap == SGM_TAP_RIGHT && e->right_last == 2)
-            return set_err(SGM_ERR_INVALID_ARG, "SGM_TAP_RIGHT: the last compute wrote its map to the pointer bound with sgm_bind_right_device");
-        src = tap == SGM_TAP_RIGHT_RAW ? e->right_raw.p : e->right.p; need = npx * 2; break;
+    case SGM_TAP_RIGHT: {
+        const SideMap &m = tap == SGM_TAP_CONF_RAW || tap == SGM_TAP_CONF ? e->conf : e->right;
+        if (!m.last) return set_err(SGM_ERR_INVALID_ARG, "tap %d needs %s=1 before compute", tap, m.opt_name);
+        if (tap == m.tap_fin && m.last == 2)
+            return set_err(SGM_ERR_INVALID_ARG, "%s: the last compute wrote its map to the pointer bound with %s", m.tap_fin_name, m.bind_name);
+        src = tap == m.tap_raw ? m.raw.p : m.fin.p; need = npx * m.bpp; break;
+    }
     default: return set_err(SGM_ERR_INVALID_ARG, "unknown tap %d", tap);
     }
     if (bytes != need) return set_err(SGM_ERR_INVALID_ARG, "tap %d holds %lld bytes, caller passed %lld", tap, (long long)need, (long long)bytes);

@@ -12,6 +12,7 @@ points and come back as torch tensors on the same device, without touching the h
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -241,19 +242,20 @@ class Engine:
         return out.astype(bool)
 
     # -- device-pointer path (raw addresses; torch only supplies the memory)
+    def _bind(self, fn, ptrs) -> None:
+        n = len(ptrs)
+        arr = (C.c_void_p * n)(*[int(x) if x else None for x in ptrs]) if n else None
+        _check(fn(self._h, n, arr))
+
     def bind_confidence_device(self, ptrs) -> None:
         """Device addresses of tight uint8 (H, W) maps for the NEXT image call on this engine (sgm_bind_confidence_device;
         needs SGM_OPT_CONFIDENCE = 1): pair i's final confidence goes to ptrs[i].  An empty sequence clears the binding."""
-        n = len(ptrs)
-        arr = (C.c_void_p * n)(*[int(x) if x else None for x in ptrs]) if n else None
-        _check(self._L.sgm_bind_confidence_device(self._h, n, arr))
+        self._bind(self._L.sgm_bind_confidence_device, ptrs)
 
     def bind_right_device(self, ptrs) -> None:
         """Device addresses of tight int16 (H, W) maps for the NEXT image call on this engine (sgm_bind_right_device; needs
         SGM_OPT_RIGHT_VIEW = 1): pair i's final right-view map goes to ptrs[i].  An empty sequence clears the binding."""
-        n = len(ptrs)
-        arr = (C.c_void_p * n)(*[int(x) if x else None for x in ptrs]) if n else None
-        _check(self._L.sgm_bind_right_device(self._h, n, arr))
+        self._bind(self._L.sgm_bind_right_device, ptrs)
 
     # (cn: interleaved channels of the images, 1 or 3; stride is the row pitch in bytes; d_conf / d_confs: where the
     #  confidence maps of the call go, bind_confidence_device; d_rmap / d_rmaps: the right-view maps, bind_right_device)
@@ -372,6 +374,17 @@ def clear_engine_cache() -> None:
     _engine_cache.clear()
 
 
+@contextlib.contextmanager
+def _option_for_this_call(eng: Engine, opt: int):
+    """The cached engine produces the optional map (SGM_OPT_CONFIDENCE, SGM_OPT_RIGHT_VIEW) for this call only: plain
+    compute() calls do not pay for it."""
+    eng.set_option(opt, 1)
+    try:
+        yield
+    finally:
+        eng.set_option(opt, 0)
+
+
 def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
 
@@ -449,24 +462,12 @@ class StereoSGBM:
         if left.shape[1] < 2:
             raise error("StereoSGBM.compute: image width < 2")
         eng = get_engine(self._p)
-        if with_right:
-            eng.set_option(_lib.SGM_OPT_RIGHT_VIEW, 1)
-            try:
-                disp = eng.compute_host(left, right)
-                rmap = eng.tap(_lib.SGM_TAP_RIGHT, *disp.shape)
-            finally:
-                eng.set_option(_lib.SGM_OPT_RIGHT_VIEW, 0)
-            return disp, rmap
-        if not with_conf:
+        if not (with_right or with_conf):
             return eng.compute_host(left, right)
-        # the cached engine produces the maps for this call only: plain compute() calls do not pay for them
-        eng.set_option(_lib.SGM_OPT_CONFIDENCE, 1)
-        try:
+        opt, tap = (_lib.SGM_OPT_RIGHT_VIEW, _lib.SGM_TAP_RIGHT) if with_right else (_lib.SGM_OPT_CONFIDENCE, _lib.SGM_TAP_CONF)
+        with _option_for_this_call(eng, opt):
             disp = eng.compute_host(left, right)
-            conf = eng.tap(_lib.SGM_TAP_CONF, *disp.shape)
-        finally:
-            eng.set_option(_lib.SGM_OPT_CONFIDENCE, 0)
-        return disp, conf
+            return disp, eng.tap(tap, *disp.shape)
 
     def _compute_torch(self, left, right, with_conf: bool = False, with_right: bool = False):
         import torch
@@ -486,27 +487,16 @@ class StereoSGBM:
         out = torch.empty((H, W), dtype=torch.int16, device=left.device)
         # the engine runs on its own stream: order it after torch's current stream and wait for it
         torch.cuda.current_stream(left.device).synchronize()
-        if with_right:
-            rmap = torch.empty((H, W), dtype=torch.int16, device=left.device)
-            eng.set_option(_lib.SGM_OPT_RIGHT_VIEW, 1)
-            try:
-                eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn, d_rmap=rmap.data_ptr())
-                eng.synchronize()
-            finally:
-                eng.set_option(_lib.SGM_OPT_RIGHT_VIEW, 0)
-            return out, rmap
-        if not with_conf:
+        if not (with_right or with_conf):
             eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn)
             eng.synchronize()
             return out
-        conf = torch.empty((H, W), dtype=torch.uint8, device=left.device)
-        eng.set_option(_lib.SGM_OPT_CONFIDENCE, 1)
-        try:
-            eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn, d_conf=conf.data_ptr())
+        side = torch.empty((H, W), dtype=torch.int16 if with_right else torch.uint8, device=left.device)
+        bound = dict(d_rmap=side.data_ptr()) if with_right else dict(d_conf=side.data_ptr())
+        with _option_for_this_call(eng, _lib.SGM_OPT_RIGHT_VIEW if with_right else _lib.SGM_OPT_CONFIDENCE):
+            eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn, **bound)
             eng.synchronize()
-        finally:
-            eng.set_option(_lib.SGM_OPT_CONFIDENCE, 0)
-        return out, conf
+        return out, side
 
 
 def _check_channels(ndim: int, cn: int) -> None:

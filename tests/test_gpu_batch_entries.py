@@ -64,6 +64,60 @@ def test_batches_larger_than_a_group(H, W, D, bs, mode, rows, N, gmax):
                           max_delta=max(t["max_delta"] for _, t in oracle)), hr
 
 
+def test_both_maps_bound_through_groups_of_two_two_and_one():
+    """Five different pairs with a confidence AND a right-view pointer bound for each, SGM_OPT_GROUP_MAX = 2: one batch call
+    runs two chained groups (pairs 0-1, 2-3) and the single-pair tail (pair 4), so every place where the call indexes its
+    array of per-pair pointers is passed with all seven pointers set.  All five outputs of every pair equal, bit for bit,
+    those of the same pair run alone through the single-pair entry of a fresh engine; the binding is consumed by that one
+    call -- a second batch call without a new binding writes to none of the ten bound maps."""
+    import torch
+    H, W, D, N = 40, 300, 128, 5
+    p = U.params(D, 5, 0, 1, speckleWindowSize=30, speckleRange=2)
+    Q = synth.default_Q(W)
+    pairs = [synth.make_pair(H, W, D, 5900 + i)[:2] for i in range(N)]
+    dev = torch.device("cuda", 0)
+
+    def outputs():
+        dl, dr, dd, df, dx = _resident(pairs, H, W, True)
+        dc = [torch.full((H, W), 201, dtype=torch.uint8, device=dev) for _ in range(N)]
+        dm = [torch.full((H, W), -7, dtype=torch.int16, device=dev) for _ in range(N)]
+        torch.cuda.synchronize()
+        return dl, dr, (dd, df, dx, dc, dm)
+
+    def engine():
+        eng = Engine(p)
+        for opt, v in ((_lib.SGM_OPT_SCHEDULE, 2), (_lib.SGM_OPT_SWEEP_ROWS, 3), (_lib.SGM_OPT_GROUP_MAX, 2),
+                       (_lib.SGM_OPT_CONFIDENCE, 1), (_lib.SGM_OPT_RIGHT_VIEW, 1)):
+            eng.set_option(opt, v)
+        return eng
+
+    bits = lambda t: t.cpu().numpy().view(np.uint8)      # floats compare as their bytes (NaN and inf included)
+    dl, dr, got = outputs()
+    eng = engine()
+    assert (H + 2) // 3 == 14                            # bands of the chained sweep: the groups do run chained
+    eng.pipeline_batch_device(ptr(dl), ptr(dr), H, W, W, Q, ptr(got[0]), ptr(got[1]), ptr(got[2]), d_confs=ptr(got[3]),
+                              d_rmaps=ptr(got[4]))
+    eng.synchronize()
+    names = ("disp_i16", "disp_f32", "xyz_f32", "conf", "right")
+    sl, sr, alone = outputs()
+    for i in range(N):
+        one = engine()
+        one.pipeline_device(sl[i].data_ptr(), sr[i].data_ptr(), H, W, W, Q, alone[0][i].data_ptr(), alone[1][i].data_ptr(),
+                            alone[2][i].data_ptr(), d_conf=alone[3][i].data_ptr(), d_rmap=alone[4][i].data_ptr())
+        one.synchronize()
+        for name, g, a in zip(names, got, alone):
+            assert np.array_equal(bits(g[i]), bits(a[i])), (i, name)
+        assert (alone[0][i] != -7).any() and (alone[3][i] != 201).any() and (alone[4][i] != -7).any(), i   # (they were written)
+    # the binding belonged to that call alone
+    for t in got[3] + got[4]:
+        t.fill_(99)
+    torch.cuda.synchronize()
+    eng.pipeline_batch_device(ptr(dl), ptr(dr), H, W, W, Q, ptr(got[0]), ptr(got[1]), ptr(got[2]))
+    eng.synchronize()
+    for k, t in enumerate(got[3] + got[4]):
+        assert bool((t == 99).all()), k
+
+
 def test_headroom_of_a_batch_sees_an_overflowing_pair_at_any_index():
     """One pair of a batch leaves the int16 regime (constant 0 against constant 255 at blockSize = 11 with P2 = 24500: C + P2 =
     32 816) among low-contrast pairs that stay inside; it sits at index 2 of 4 -- on an internal engine of the group.  Round 3

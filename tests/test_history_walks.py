@@ -9,40 +9,66 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "stereo_reconstruction_cv_amd", "csrc")
 
 
-def _engine_devbufs(text):
-    """names (and array extents) of the DevBuf members of struct sgm_engine"""
-    body = text[text.index("struct sgm_engine {"):]
-    body = body[:body.index("\n};")]
+def _struct_body(text, name):
+    body = text[text.index("struct %s {" % name):]
+    return body[:body.index("\n};")]
+
+
+def _routine(text, head):
+    start = text.index(head)
+    return text[start:text.index("\n}\n", start)]
+
+
+def _devbuf_list(text):
+    """the entries of SGM_ENGINE_DEVBUFS, as the buffers of an engine e: BUF(name) -> name, ARR(name, dims) -> name + dims,
+    MAP(name) -> conf.name and right.name"""
+    start = text.index("#define SGM_ENGINE_DEVBUFS(BUF, ARR, MAP)")
+    body = re.sub(r"/\*.*?\*/", "", text[start:text.index("\n#define SGM_DEVBUF_DECL(", start)].split("\n", 1)[1], flags=re.S)
     names = []
-    for m in re.finditer(r"^\s*DevBuf\s+([^;]+);", body, flags=re.M):
-        for decl in m.group(1).split(","):
-            names.append(decl.strip())
+    for kind, arg in re.findall(r"\b(BUF|ARR|MAP)\(([^)]*)\)", body):
+        arg = [a.strip() for a in arg.split(",")]
+        names += [arg[0]] if kind == "BUF" else [arg[0] + arg[1]] if kind == "ARR" else ["conf." + arg[0], "right." + arg[0]]
+    assert not re.sub(r"\b(BUF|ARR|MAP)\([^)]*\)|[\s\\\\]", "", body), body        # nothing but entries
     return names
 
 
 def test_poison_routine_names_every_device_buffer_of_the_engine():
-    """A DevBuf added to struct sgm_engine later cannot be forgotten: every declared member appears in poison_buffers
-    (SGM_OPT_POISON, csrc/sgm_debug.h), an array member with each of its elements, and the one member that is state by
-    contract -- chain_err, the sticky give-up flag -- is named there and excluded by name."""
+    """A DevBuf added to the engine later cannot be forgotten.  Every DevBuf of struct sgm_engine, and of SideMap which it
+    holds as conf and right, is declared by ONE list (SGM_ENGINE_DEVBUFS), and by nothing else; poison_buffers (SGM_OPT_POISON,
+    csrc/sgm_debug.h), release_buffers and plan_bytes_held walk that list -- members, both SideMaps' members and every element
+    of an array member; and the one member that is state by contract -- chain_err, the sticky give-up flag -- is excluded by
+    name from the poisoning, and from nothing else."""
     text = open(os.path.join(CSRC, "sgm_engine.hip")).read()
-    decls = _engine_devbufs(text)
-    assert len(decls) >= 38 and "io[2][5]" in decls and "chain_err" in decls, decls
-    start = text.index("static int poison_buffers(sgm_engine *e, int byte)")
-    routine = text[start:text.index("\n}\n", start)]
-    for d in decls:
-        m = re.fullmatch(r"(\w+)((?:\[\d+\])*)", d)
-        assert m, d
-        name, dims = m.group(1), [int(x) for x in re.findall(r"\[(\d+)\]", m.group(2))]
-        if not dims:
-            assert re.search(rf"&e->{name}\b(?!\[)", routine), f"poison_buffers does not name {name}"
-            continue
-        idx = [[]]
-        for n in dims:
-            idx = [i + [k] for i in idx for k in range(n)]
-        for i in idx:
-            el = name + "".join(f"[{k}]" for k in i)
-            assert f"&e->{el}" in routine, f"poison_buffers does not name {el}"
-    assert "b != &e->chain_err" in routine                       # left alone: neither filled nor re-cleared
+    decls = _devbuf_list(text)
+    assert len(decls) >= 38 and len(set(decls)) == len(decls) and "io[2][5]" in decls and "chain_err" in decls, decls
+    assert {"conf.raw", "conf.fin", "right.raw", "right.fin"} <= set(decls), decls
+    # no DevBuf is declared outside the list: not in sgm_engine, not in a struct it embeds, nowhere in the file -- the only
+    # declarators are the two macros, and they are only ever handed to the list, once in sgm_engine and once in SideMap
+    assert not re.search(r"^\s*DevBuf\s+\w", text, flags=re.M), "a DevBuf declared outside SGM_ENGINE_DEVBUFS"
+    assert len(re.findall(r"^#define \w+\([^)]*\) DevBuf\b", text, flags=re.M)) == 2
+    uses = [l.strip() for l in text.splitlines() if "SGM_DEVBUF_DECL" in l and not l.startswith("#define")]
+    assert sorted(uses) == ["SGM_ENGINE_DEVBUFS(SGM_DEVBUF_DECL, SGM_DEVBUF_DECL_ARR, SGM_DEVBUF_NONE)",
+                            "SGM_ENGINE_DEVBUFS(SGM_DEVBUF_NONE, SGM_DEVBUF_NONE, SGM_DEVBUF_DECL)"], uses
+    assert "SGM_ENGINE_DEVBUFS(SGM_DEVBUF_NONE, SGM_DEVBUF_NONE, SGM_DEVBUF_DECL)" in _struct_body(text, "SideMap")
+    engine = _struct_body(text, "sgm_engine")
+    assert "SGM_ENGINE_DEVBUFS(SGM_DEVBUF_DECL, SGM_DEVBUF_DECL_ARR, SGM_DEVBUF_NONE)" in engine
+    assert sorted(re.findall(r"^\s*SideMap\s+(\w+)", engine, flags=re.M)) == ["conf", "right"]   # the two the walk visits
+    # the walk reaches every entry: members, both SideMaps, every element of a two-dimensional array
+    assert "#define SGM_DEVBUF_VISIT(name) f(e->name);" in text
+    assert "#define SGM_DEVBUF_VISIT_ARR(name, dims) for (auto &row : e->name) for (auto &b : row) f(b);" in text
+    assert "#define SGM_DEVBUF_VISIT_MAP(name) f(e->conf.name); f(e->right.name);" in text
+    assert all(len(re.findall(r"\[\d+\]", d)) == 2 for d in decls if "[" in d), decls
+    walk = _routine(text, "static void each_devbuf(E *e, F f)")
+    assert "SGM_ENGINE_DEVBUFS(SGM_DEVBUF_VISIT, SGM_DEVBUF_VISIT_ARR, SGM_DEVBUF_VISIT_MAP)" in walk
+    # ... and the three routines are that walk
+    routine = _routine(text, "static int poison_buffers(sgm_engine *e, int byte)")
+    release = _routine(text, "static void release_buffers(sgm_engine *e)")
+    held = _routine(text, "static size_t plan_bytes_held(const sgm_engine *e)")
+    for r in (routine, release, held):
+        assert "each_devbuf(e, [" in r and "&e->" not in r.replace("&e->chain_err", ""), r
+    assert "&b != &e->chain_err" in routine                      # left alone: neither filled nor re-cleared
+    assert "chain_err" not in release and "chain_err" not in held
+    assert "e->g.hr = nullptr" in release
     for behind in ("e->peer", "e->peer2", "e->group"):            # the engines behind it
         assert re.search(rf"poison_buffers\({re.escape(behind)}\b|: {re.escape(behind)}\)", routine), behind
     # armed, DevBuf::ensure fills what it allocates -- on both allocation paths
