@@ -130,6 +130,13 @@ def load():
     L.sgm_debug_plan.restype = i32
     L.sgm_debug_plan_opts.argtypes = [pp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(SgmDebugPlan)]
     L.sgm_debug_plan_opts.restype = i32
+    # ... and the readouts of the split winner-take-all
+    L.sgm_debug_uniq_threshold.argtypes = [i32, i32]
+    L.sgm_debug_uniq_threshold.restype = i32
+    L.sgm_debug_wta_split.argtypes = [pp, i32, i32, i32, i32, i32, i32, i32, i32]
+    L.sgm_debug_wta_split.restype = i32
+    L.sgm_debug_wta_raw_bytes.argtypes = [vp]
+    L.sgm_debug_wta_raw_bytes.restype = C.c_longlong
     for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("sgm_abi_version", "sgm_device_count"):
@@ -157,3 +164,13 @@ def debug_plan(params: dict, H: int, W: int, channels: int = 1, schedule: int = 
     if rc != SGM_OK:
         raise ValueError(f"sgm_debug_plan failed ({rc}): {last_error()}")
     return {n: getattr(out, n) for n, _ in SgmDebugPlan._fields_}
+
+
+def debug_wta_split(params: dict, H: int, W: int, schedule: int = 2, sweep_rows: int = 0, debug: int = 0, confidence: int = 0,
+                    right_view: int = 0, keep_aggr: int = 0) -> bool:
+    """Whether one compute of an H x W frame with these options takes the split winner-take-all (csrc/sgm_debug.h:
+    sgm_debug_wta_split; Plan::wta_split is not part of sgm_debug_plan_t).  Needs no GPU."""
+    rc = load().sgm_debug_wta_split(C.byref(SgmParams(**params)), H, W, schedule, sweep_rows, debug, confidence, right_view, keep_aggr)
+    if rc < 0:
+        raise ValueError(f"sgm_debug_wta_split failed ({rc}): {last_error()}")
+    return bool(rc)

@@ -284,6 +284,111 @@ __device__ __forceinline__ void wta_pixel(const Pack<NP> &Sn, int lane, bool act
     wta_pixels<NP, PARTIAL, POSW, 1>(S1, lane, active, D, uniq, r1);
 }
 
+// ---- split winner-take-all (k_sweep_chain<.., SWEEP_REDUCE> + k_wta_select) -------------------------------------------
+// The chained second sweep holds the finished S of a pixel in registers; storing it (1 V) only for k_wta_t to read it back
+// (1 V) is a fifth of what a MODE_HH pair moves.  wta_pixels in the sweep costs about as much as it saves (55-60 vector
+// instructions per pixel), so the work is SPLIT: the sweep does only what needs the whole vector -- the lane reductions --
+// and leaves a 16-byte raw record per pixel; the decisions (uniqueness, rejection) are taken by k_wta_select (kernels_post.h),
+// one thread per pixel, which writes the record k_wta_t writes.
+//
+//   raw record: { key = minS << 16 | first best d,  nb = S[max(best-1, 0)] | S[min(best+1, D-1)] << 16,  nq,  0 }
+//
+// Uniqueness as a COUNT.  Upstream rejects iff some d with |d - best| > 1 has S[d] * wgt < thr, wgt = 100 - uniquenessRatio in
+// 1 .. 100, thr = 100 * minS.  With T1 = ceil(thr / wgt) (= floor((thr - 1) / wgt) + 1 for thr >= 1, and 0 for thr = 0, where no d
+// qualifies) S * wgt < thr <=> S < T1.  The sweep counts nq = #{d : S[d] < T1}; k_wta_select counts how many of S[best-1],
+// S[best], S[best+1] (inside [0, D)) are below T1 from the three values the record holds and rejects iff nq is larger.
+// T1 comes from an integer reciprocal: n = thr + wgt - 1 < 2^22, rcp = ceil(2^29 / wgt), T1 = (8 n * rcp) >> 32 -- the error of
+// rcp adds less than 2^22 / 2^29 = 1/128 to n / wgt, whose fractional part is at most 1 - 1/100: exact (tests/
+// test_wta_split_reference.py checks every minS and ratio).  No division and no per-element product in the sweep.
+struct UniqRecip {
+    uint32_t c8, rcp;  // 8 (wgt - 1), ceil(2^29 / wgt)
+};
+__host__ __device__ inline UniqRecip uniq_recip(int uniq)
+{
+    const uint32_t wgt = (uint32_t)(100 - uniq);  // callers: uniquenessRatio < 100
+    return UniqRecip{8u * (wgt - 1u), (uint32_t)((((uint64_t)1 << 29) + wgt - 1u) / wgt)};
+}
+// T1 = ceil(100 minS / wgt), for minS <= 32767
+__host__ __device__ inline uint32_t uniq_t1(uint32_t minS, UniqRecip q)
+{
+    return (uint32_t)(((uint64_t)(800u * minS + q.c8) * q.rcp) >> 32);
+}
+// the same, as the kernels compare it with packed unsigned 16-bit values: S <= 0x7fff, so 0x8000 stands for every larger T1
+__host__ __device__ inline uint32_t uniq_t1_clamped(uint32_t minS, UniqRecip q)
+{
+    const uint32_t t = uniq_t1(minS, q);
+    return t < 0x8000u ? t : 0x8000u;
+}
+
+// index of the first set bit of a lane mask, -1 for an empty one (the builtin count is undefined there)
+__device__ __forceinline__ uint32_t mask_first(uint64_t m)
+{
+    uint32_t r;
+    asm("s_ff1_i32_b64 %0, %1" : "=s"(r) : "s"(m));
+    return r;
+}
+// min(a, b) on the scalar unit (both wave-uniform).  Written as asm for the reason smax_u32 is (sgm_device.h): left to the
+// compiler a chain of such minima turns into v_mov_b32 + v_min3_u32 + v_readfirstlane in the vector stream.
+__device__ __forceinline__ uint32_t smin_u32(uint32_t a, uint32_t b)
+{
+    uint32_t r;
+    asm("s_min_u32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc");
+    return r;
+}
+// S[d] of a full wave's pixel (d wave-uniform): one v_readlane per register of the lane that holds d, the rest on the scalar unit
+template <int NP> __device__ __forceinline__ uint32_t wave_pick(const Pack<NP> &S, uint32_t d)
+{
+    static_assert(NP == 1 || NP == 2, "split winner-take-all: D = 128 and D = 256");
+    const uint32_t ln = d / (2 * NP);
+    uint32_t w = __builtin_amdgcn_readlane(S.r[0], ln);
+    if constexpr (NP == 2) {
+        const uint32_t w1 = __builtin_amdgcn_readlane(S.r[1], ln);
+        w = (d & 2u) ? w1 : w;
+    }
+    return (w >> ((d & 1u) * 16u)) & 0xffffu;
+}
+// The reductions of N = PPS pixels of a step (full waves only; their minima share one fold chain).  rec[n] = the first
+// three words of pixel n's raw record, wave-uniform.
+template <int NP, int N>
+__device__ __forceinline__ void wta_reduce_pixels(const Pack<NP> (&Sn)[N], UniqRecip q, uint32_t (&rec)[N][3])
+{
+    constexpr int D = 128 * NP;  // full waves
+    static_assert(N == 2 || N == 4, "pixels per lockstep step of NP = 2 / NP = 1");
+    uint32_t r[N], ms[N], rows;
+#pragma unroll
+    for (int n = 0; n < N; n++) {
+        uint32_t v = Sn[n].r[0];
+#pragma unroll
+        for (int i = 1; i < NP; i++) v = pk_min_s(v, Sn[n].r[i]);
+        r[n] = v;
+    }
+    if constexpr (N == 2) wave_min2_splat(r[0], r[1], ms, rows);
+    else wave_min4_splat(r[0], r[1], r[2], r[3], ms, rows);
+#pragma unroll
+    for (int n = 0; n < N; n++) {
+        const uint32_t m = ms[n] & 0xffffu;
+        const uint32_t t1 = uniq_t1_clamped(m, q);
+        const uint32_t t1s = t1 | (t1 << 16);
+        uint32_t best = 0xffffffffu, nq = 0;
+#pragma unroll
+        for (int i = 0; i < NP; i++) {
+            // zero exactly in the halves that hold the minimum / non-zero exactly in the halves below T1
+            const uint32_t x = pk_sub(Sn[n].r[i], ms[n]);
+            const uint32_t y = pk_subs_u(t1s, Sn[n].r[i]);
+            // (both halves as 16-bit compares against zero -- SDWA operand selects, no constant held in a scalar register)
+            const uint64_t zlo = __builtin_amdgcn_ballot_w64((uint16_t)x == 0), zhi = __builtin_amdgcn_ballot_w64((uint16_t)(x >> 16) == 0);
+            const uint64_t qlo = __builtin_amdgcn_ballot_w64((uint16_t)y != 0), qhi = __builtin_amdgcn_ballot_w64((uint16_t)(y >> 16) != 0);
+            // d = 2 (NP lane + i) + half; an empty mask gives a huge value; ties go to the lowest d, like the (S << 16) | d key
+            best = smin_u32(best, smin_u32(mask_first(zlo) * (2 * NP) + 2 * i, mask_first(zhi) * (2 * NP) + 2 * i + 1));
+            nq += (uint32_t)__builtin_popcountll(qlo) + (uint32_t)__builtin_popcountll(qhi);
+        }
+        const uint32_t dm = (uint32_t)max((int)best - 1, 0), dp = (uint32_t)min((int)best + 1, D - 1);
+        rec[n][0] = (m << 16) | best;
+        rec[n][1] = wave_pick<NP>(Sn[n], dm) | (wave_pick<NP>(Sn[n], dp) << 16);
+        rec[n][2] = nq;
+    }
+}
+
 #ifndef SGM_PREPASS_PB
 #define SGM_PREPASS_PB 4
 #endif

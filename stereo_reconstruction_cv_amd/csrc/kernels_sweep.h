@@ -25,7 +25,9 @@
 
 namespace sgm {
 
-enum { SWEEP_FIRST = 0, SWEEP_ACCUM = 1, SWEEP_LAST = 2 };
+// SWEEP_REDUCE (k_sweep_chain only): the second pass of MODE_HH without the store of S -- the lane reductions of the
+// winner-take-all on the S it holds in registers, one 16-byte raw record per pixel (kernels_path.h: wta_reduce_pixels)
+enum { SWEEP_FIRST = 0, SWEEP_ACCUM = 1, SWEEP_LAST = 2, SWEEP_REDUCE = 3 };
 
 struct SweepArgs {
     int ydir, xdir;  // (+1,+1): rows top->bottom, x ascending; (-1,-1): second pass of MODE_HH
@@ -33,7 +35,7 @@ struct SweepArgs {
     const int16_t *C;
     int16_t *S;
     const int16_t *bndL;  // [band][x][3 roles][D], normalised (axis-only sweeps: [band][x][1][D])
-    uint2 *wta;
+    uint2 *wta;      // SWEEP_LAST: the records [H][W]; SWEEP_REDUCE: the raw records [H][W] uint4 (ChainFrames::raw)
     int keepS;
     int dbg;  // timing experiments only (results become wrong): 64 = loader wave skips its HBM loads
     // chained schedule only (k_sweep_chain): bndL is then the record the bands hand to each other
@@ -46,14 +48,16 @@ struct SweepArgs {
 
 // Frames of one chained launch (sgm_pipeline_batch_device: several pairs per launch, so that the GPU is full although
 // one frame's chain keeps only T / LAG workgroups busy).  Tickets go round the frames: ticket t = band t / nf of frame t % nf.
-constexpr int CHAIN_MAX_FRAMES = 64;   // (the four pointer arrays of ChainFrames: 2 KB of the 4 KB a kernel's arguments may take)
+constexpr int CHAIN_MAX_FRAMES = 64;   // (the five pointer arrays of ChainFrames: 2.5 KB of the 4 KB a kernel's arguments may take)
 struct ChainFrames {
     int nf;
     const int16_t *C[CHAIN_MAX_FRAMES];
     int16_t *S[CHAIN_MAX_FRAMES];
     int16_t *bnd[CHAIN_MAX_FRAMES];   // hand-off record [band][x][3][D] of each frame ([band][x][1][D]: k_axis_chain)
     uint32_t *hr[CHAIN_MAX_FRAMES];   // headroom record of each frame
+    uint4 *raw[CHAIN_MAX_FRAMES];     // SWEEP_REDUCE: raw winner-take-all records [H][W] of each frame (unused otherwise)
 };
+static_assert(sizeof(Geom) + sizeof(SweepArgs) + sizeof(ChainFrames) + 64 <= 4096, "a kernel's arguments must stay within 4 KB");
 
 constexpr int SWEEP_MAX_ROWS = 11;  // compute waves per workgroup (768 threads = 3 waves per SIMD -> 168 VGPRs per lane)
 // pixels a wave advances per lockstep step (one barrier per step): two give the scheduler two
@@ -331,6 +335,29 @@ __device__ __forceinline__ void sweep_loader_wave(const Geom &g, const SweepArgs
     }
 }
 
+// What SWEEP_REDUCE alone needs of an image row: the matched columns of this row of the raw records as a buffer resource, the
+// per-lane store offset and the uniqueness reciprocal.  Lane 0 stores a record; the other lanes' offset lies past the
+// descriptor's end, so the bounds check drops their part -- no EXEC mask and no branch inside the step.
+template <bool ON>
+struct ReduceRow {  // every other form: nothing
+    __device__ __forceinline__ ReduceRow(const Geom &, const SweepArgs &, int, int) {}
+};
+template <>
+struct ReduceRow<true> {
+    __amdgpu_buffer_rsrc_t Rrow;
+    int rvoff;
+    UniqRecip uq;
+    __device__ __forceinline__ ReduceRow(const Geom &g, const SweepArgs &a, int y, int lane)
+        : Rrow(__builtin_amdgcn_make_buffer_rsrc((void *)(reinterpret_cast<uint4 *>(a.wta) + (int64_t)y * g.W + g.minX1), 0,
+                                                 g.W1 * 16, 0x00020000)),
+          rvoff(lane == 0 ? 0 : 0x40000000), uq(uniq_recip(g.uniq))  // (the reciprocal once per band: no division in the loop)
+    {
+        // (opaque to the optimiser: it would fold every pixel's constant offset into the select -- sixteen more VGPRs held
+        //  across the loop instead of sixteen immediate offsets of the store instructions)
+        asm volatile("" : "+v"(rvoff));
+    }
+};
+
 // ==== compute wave: one image row ======================================================================
 // NR = 1 (axis-only form, MODE_HH4): per pixel the in-row path and role B only -- two recurrences, their minima reduced
 // together (wave_min2_splat), one role handed to the row below; same path_elem / path_normalise_splat, same lockstep.
@@ -391,6 +418,7 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
     // bounds check) when the last sweep need not keep S -- no branch inside the step
     const __amdgpu_buffer_rsrc_t Sst = __builtin_amdgcn_make_buffer_rsrc(
         (void *)(a.S + (int64_t)y * W1 * D), 0, (MODE != SWEEP_LAST || a.keepS) ? row_bytes : 0, 0x00020000);
+    const ReduceRow<MODE == SWEEP_REDUCE> rr(g, a, y, lane);  // (SWEEP_REDUCE alone: every other form declares nothing here)
     const int voff = lane_off * 2;
     const int bk = a.xdir > 0 ? D * 2 : -D * 2;
     const int b0 = a.xdir > 0 ? 0 : (W1 - 1) * D * 2;
@@ -462,7 +490,8 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
             if (READS_S) v = pk_adds_s(v, Sp.r[i]);
             Sn.r[i] = v;
         }
-        if (!PARTIAL || active) buf_store<NP>(Sn, Sst, vo, so);
+        if constexpr (MODE != SWEEP_REDUCE)
+            if (!PARTIAL || active) buf_store<NP>(Sn, Sst, vo, so);
         return Sn;
     };
     // one pixel of the axis-only form: the in-row path and role B
@@ -533,6 +562,40 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
                         for (int p = 0; p < PPS; p++)
                             if (k0 + u0 + p < W1)
                                 wta_pixel<NP, PARTIAL, POSW>(Sn[p], lane, active, D, g.uniq, wrow + (k0 + u0 + p) * wk);
+                    }
+                }
+                if constexpr (MODE == SWEEP_REDUCE) {  // the lane reductions of the step's pixels; all stores come last
+                    static_assert(MODE != SWEEP_REDUCE || (!PARTIAL && NR == 3 && PPS >= 2), "SWEEP_REDUCE: full waves of NP = 1, 2");
+                    if constexpr (!FULL) {
+#pragma unroll
+                        for (int p = 0; p < PPS; p++)
+                            if (k0 + u0 + p >= W1) Sn[p].fill(0u);  // (a pixel past the row's end: reduced with the others, never stored)
+                    }
+                    uint32_t rec[PPS][3];
+                    wta_reduce_pixels<NP, PPS>(Sn, rr.uq, rec);
+                    // The step's PPS records lie side by side (the second pass walks x downwards: pixel p of the step sits
+                    // PPS - 1 - p records above the step's lowest address): ONE scalar offset per step and 2 PPS per-lane
+                    // offsets for the whole kernel, instead of a per-lane offset register for every store of a block.
+                    // (guarded blocks -- the row's tail: a scalar offset per pixel, never a negative one)
+                    const int so = (int)((unsigned)sbase / (PXB / 16)) + (PB - PPS - u0) * 16;
+#pragma unroll
+                    for (int p = 0; p < PPS; p++) {
+                        Pack<2> lo, hi;
+                        lo.r[0] = rec[p][0];
+                        lo.r[1] = rec[p][1];
+                        hi.r[0] = rec[p][2];
+                        hi.r[1] = 0u;
+                        // as in wta_pixels: what is stored sits in registers of its own ("masked writes after wide stores")
+                        asm volatile("" : "+v"(lo.r[0]), "+v"(lo.r[1]), "+v"(hi.r[0]), "+v"(hi.r[1]));
+                        if constexpr (FULL) {
+                            const int vo = rr.rvoff + (PPS - 1 - p) * 16;
+                            buf_store<2>(lo, rr.Rrow, vo, so);
+                            buf_store<2>(hi, rr.Rrow, vo + 8, so);
+                        } else if (k0 + u0 + p < W1) {
+                            const int sp = (W1 - 1 - (k0 + u0 + p)) * 16;
+                            buf_store<2>(lo, rr.Rrow, rr.rvoff, sp);
+                            buf_store<2>(hi, rr.Rrow, rr.rvoff + 8, sp);
+                        }
                     }
                 }
                 wg_barrier();
@@ -705,6 +768,7 @@ __global__ __launch_bounds__(CHAIN_MAX_ROWS * 64 + 128) void k_sweep_chain(Geom 
         a.bndL = fr.bnd[f];
         a.prog = a.ctl + 1 + f * a.nbands;
         g.hr = fr.hr[f];
+        if constexpr (MODE == SWEEP_REDUCE) a.wta = reinterpret_cast<uint2 *>(fr.raw[f]);
         if (wave == a.R) sweep_loader_wave<NP, PARTIAL, true>(g, a, band, lane, lds);
         else if (wave == a.R + 1) chain_publisher_wave<NP, PARTIAL>(g, a, band, lane, lds);
         else sweep_compute_wave<NP, PARTIAL, MODE, true>(g, a, band, wave, lane, lds);

@@ -58,4 +58,21 @@ extern "C"
 int sgm_debug_plan_opts(const sgm_params *p, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
                         int debug, int frames, int confidence, int right_view, sgm_debug_plan_t *out);
 
+/* Split winner-take-all (kernels_path.h: wta_reduce_pixels, kernels_post.h: k_wta_select), for tests; none needs a GPU.
+ * sgm_debug_uniq_threshold: T1 = ceil(100 minS / (100 - uniquenessRatio)) as the kernels compute it from the integer
+ *   reciprocal (before they clamp it to 0x8000); -1 outside minS 0 .. 32767, uniquenessRatio 0 .. 99.
+ * sgm_debug_wta_split: 1 if one compute of an H x W frame with these options takes the split form (Plan::wta_split), else 0
+ *   (negative: an error code).
+ * sgm_debug_wta_raw_bytes: bytes of raw-record buffers that e and the engines of its chained group hold. */
+#ifdef __cplusplus
+extern "C" {
+#endif
+int sgm_debug_uniq_threshold(int minS, int uniquenessRatio);
+int sgm_debug_wta_split(const sgm_params *p, int H, int W, int schedule, int sweep_rows, int debug, int confidence, int right_view,
+                        int keep_aggr);
+long long sgm_debug_wta_raw_bytes(const sgm_engine *e);
+#ifdef __cplusplus
+}
+#endif
+
 #endif

@@ -225,6 +225,8 @@ struct Plan {
     bool overlap, fork_early;  // MODE_HH: upward pre-pass on the auxiliary stream; forked right after the cost stage
     // winner-take-all
     bool fused_wta;        // inside the last path kernel (else k_wta_t)
+    bool wta_split;        // (never with fused_wta) the chained second sweep leaves raw records instead of S (SWEEP_REDUCE), the
+                           // wta stage is k_wta_select; private: not part of sgm_debug_plan_t
     int nvol;              // volumes k_wta_t adds up: 1 (S), 2 (+ the fifth path's), 3 (+ the other in-row path's), 5 (k_paths5_g),
                            // 4 (k_axis_paths4_g: MODE_HH4 in the small-D schedule)
     bool path_w_main, path_w_lines;  // MODE_SGBM's fifth path on the main stream behind the sweeps; as the general line kernel
@@ -242,6 +244,7 @@ struct Plan {
     BUF(aggr2) BUF(aggr3)                        /* MODE_SGBM: the fifth path's own volume (D <= 128; added to S by the winner-take-all), the other in-row path's (D <= 64) */ \
     BUF(aggr4) BUF(aggr5)                        /* MODE_SGBM, D <= 64: the volumes of the vertical and the second diagonal direction (k_paths5_g) */ \
     BUF(wta)                                     /* uint2 [H][W] */ \
+    BUF(wta_raw)                                 /* Plan::wta_split only: uint4 [H][W] raw records of the chained second sweep */ \
     BUF(bndL) BUF(bndL2)                         /* band-boundary state of the sweep pre-pass (down / up) */ \
     BUF(pstate) BUF(pstate2)                     /* line state between the row chunks of the pre-pass (ping-pong, down / up) */ \
     BUF(disp_raw) BUF(disp_med) BUF(disp_out)    /* int16 [H][W] */ \
@@ -289,6 +292,7 @@ struct sgm_engine {
     hipStream_t aux2 = nullptr;           // third stream (D <= 64, MODE_SGBM: the left-to-right in-row path beside everything else)
     hipEvent_t ev_join2 = nullptr;
     int keep_aggr = 0;
+    bool no_wta_split = false;            // internal engines: the caller's engine keeps S (inherit_options), so the group's sweep stores it
     int profile = 0;
     int schedule = 1;    // 0: one kernel per direction (v1); 1: fused 4-direction sweeps; 2: chained sweeps, no pre-pass (throughput mode)
     int chain_wgs = 0;   // schedule 2: workgroups (= bands in flight) per sweep launch; 0 = automatic
@@ -631,11 +635,16 @@ template <int NP, bool PARTIAL>
 static int launch_chain_np(const Geom &g, const SweepArgs &a, const ChainFrames &fr, int mode, int wgs, hipStream_t st)
 {
     if (mode == SWEEP_FIRST) return launch_chain_one<NP, PARTIAL, SWEEP_FIRST>(g, a, fr, wgs, st);
+    // (SWEEP_REDUCE: full waves of NP = 1, 2 -- make_plan sets Plan::wta_split for nothing else)
+    if constexpr (!PARTIAL && NP <= 2)
+        if (mode == SWEEP_REDUCE) return launch_chain_one<NP, PARTIAL, SWEEP_REDUCE>(g, a, fr, wgs, st);
+    if (mode == SWEEP_REDUCE) return set_err(SGM_ERR_INVALID_ARG, "internal: no SWEEP_REDUCE form of this chained sweep");
     return launch_chain_one<NP, PARTIAL, SWEEP_ACCUM>(g, a, fr, wgs, st);
 }
 static int launch_chain(const Geom &g, const SweepArgs &a, const ChainFrames &fr, int mode, int wgs, hipStream_t st, bool axis = false)
 {
     if (int rc = check_sweep_direction(a, mode)) return rc;
+    if (axis && mode == SWEEP_REDUCE) return set_err(SGM_ERR_INVALID_ARG, "internal: the axis-only sweeps have no SWEEP_REDUCE form");
     if (axis)
         return with_np(g, [&](auto np, auto part) {
             return mode == SWEEP_FIRST ? launch_axis_chain_one<np, part, SWEEP_FIRST>(g, a, fr, wgs, st)
@@ -774,6 +783,12 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     // own (2 V of traffic instead of the 3 V of "S +="), beside the pre-pass and the sweep -- which at these
     // D are bound by instruction issue, not by HBM; k_wta_t adds the two volumes while it stages them.
     // debug 65536: the fifth path after the sweep, accumulating into S (A/B).
+    // Split winner-take-all (kernels_path.h: wta_reduce_pixels): the chained second sweep of MODE_HH does the lane reductions on
+    // the S it holds and stores a raw record per pixel instead of S; the wta stage is then k_wta_select.  2 V less traffic
+    // per pair.  Full waves of D = 128 / 256 with a positive uniqueness weight, and only where nothing else wants S: not with
+    // SGM_OPT_KEEP_AGGR, the confidence map or the right view.  debug 2048 takes the separate pass here too (A/B, cross-check).
+    p.wta_split = p.chain && g.mode == 1 && !p.axis && !p.fused_wta && !np_partial(g) && g.NP <= 2 && g.uniq < 100 &&
+                  !e->keep_aggr && !e->no_wta_split && !conf && !(dbg & SGM_DBG_WTA_SEPARATE);
     const bool two_vol = g.mode == 0 && !p.fused_wta && !p.v1 && g.D <= 128 && !(dbg & SGM_DBG_NO_LANE_GROUPS) &&
                          !(dbg & SGM_DBG_FIFTH_PATH_AFTER_SWEEP);
     // D <= 64 (small-D schedule): the OTHER in-row path (left to right) needs nothing but C either.  It used to follow
@@ -808,6 +823,7 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
         p.overlap = p.fork_early = p.path_w_main = false;
         p.GWs = 64;
         p.fused_wta = !conf;
+        p.wta_split = false;
         p.nvol = 1;
     }
     return p;
@@ -864,6 +880,7 @@ static int ensure_plan_buffers(sgm_engine *e, const Plan &p, int H, int W)
             if ((rc = more[k - 1]->ensure(vol))) return rc;
     }
     if ((rc = e->wta.ensure(npx * 8))) return rc;
+    if (p.wta_split && (rc = e->wta_raw.ensure(npx * 16))) return rc;
     if ((rc = e->disp_raw.ensure(npx * 2))) return rc;
     if ((rc = e->disp_med.ensure(npx * 2))) return rc;
     for (SideMap *m : {&e->conf, &e->right})
@@ -1359,6 +1376,7 @@ static int paths_fused(sgm_engine *e, const Plan &p)
             fr.S[0] = S;
             fr.bnd[0] = (int16_t *)e->bndL.p;
             fr.hr[0] = g.hr;
+            fr.raw[0] = (uint4 *)e->wta_raw.p;
             a.ctl = (uint32_t *)e->chain_ctl.p;
             a.err = (uint32_t *)e->chain_err.p;
             HIP_TRY(hipMemsetAsync(e->chain_ctl.p, 0, chain_ctl_bytes(1, p.nbands), st));
@@ -1376,7 +1394,8 @@ static int paths_fused(sgm_engine *e, const Plan &p)
                 // only the in-row direction is a recurrence (k_rows_g, S +=) -- unless it runs on a stream of its own
                 if (p.nvol < 3) launch_rows_grouped(g, g.H, p.GWs, xdir, PATH_ACCUM, C, S, 1, wta, st);
             } else if (p.chain) {
-                if (int r = launch_chain(g, a, fr, pass == 0 ? SWEEP_FIRST : SWEEP_ACCUM, chain_window(g, p.R, p.nbands, 1, e->chain_wgs), st, p.axis)) return r;
+                const int cm = pass == 0 ? SWEEP_FIRST : (p.wta_split ? SWEEP_REDUCE : SWEEP_ACCUM);
+                if (int r = launch_chain(g, a, fr, cm, chain_window(g, p.R, p.nbands, 1, e->chain_wgs), st, p.axis)) return r;
             } else if (int r = launch_sweep(g, a, pass == 0 ? SWEEP_FIRST : (last ? SWEEP_LAST : SWEEP_ACCUM), p.nbands, st, p.axis)) {
                 return r;
             }
@@ -1412,6 +1431,12 @@ static int stage_wta(sgm_engine *e, const Plan &p)
 {
     if (p.fused_wta) return SGM_OK;
     const Geom &g = e->g;
+    if (p.wta_split)  // the sweep left raw records: one thread per pixel decides (the stage keeps its name and its one launch)
+        return run_stage(e, "wta", e->stream, [&] {
+            hipLaunchKernelGGL(k_wta_select, dim3((g.W1 + 255) / 256, g.H), dim3(256), 0, e->stream, g, (const uint4 *)e->wta_raw.p,
+                               (uint2 *)e->wta.p, uniq_recip(g.uniq));
+            return 1;
+        });
     uint8_t *conf = e->conf.on ? (uint8_t *)e->conf.raw.p : nullptr;
     return run_stage(e, conf ? "wta_conf" : "wta", e->stream, [&] {
         int16_t *const Sv[5] = {(int16_t *)e->aggr.p, p.nvol >= 2 ? (int16_t *)e->aggr2.p : nullptr,
@@ -1723,6 +1748,37 @@ int sgm_debug_plan_opts(const sgm_params *params, int H, int W, int channels, in
                         int debug, int frames, int confidence, int right_view, sgm_debug_plan_t *out)
 {
     return debug_plan_on(params, H, W, channels, schedule, sweep_rows, prepass_rows, debug, frames, confidence, right_view, out);
+}
+
+// csrc/sgm_debug.h: the split winner-take-all -- its threshold as the kernels compute it, whether a plan takes it, and what an
+// engine holds for it
+int sgm_debug_uniq_threshold(int minS, int uniquenessRatio)
+{
+    if (minS < 0 || minS > SGM_MAX_COST || uniquenessRatio < 0 || uniquenessRatio > 99) return -1;
+    return (int)uniq_t1((uint32_t)minS, uniq_recip(uniquenessRatio));
+}
+int sgm_debug_wta_split(const sgm_params *params, int H, int W, int schedule, int sweep_rows, int debug, int confidence, int right_view,
+                        int keep_aggr)
+{
+    if (!params) return set_err(SGM_ERR_INVALID_ARG, "params is null");
+    if (H <= 0 || W < 2 || W > 32767 || H > 32767) return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d", H, W);
+    sgm_engine e;
+    e.params = *params;
+    int rc;
+    if ((rc = sgm_set_option(&e, SGM_OPT_SCHEDULE, schedule)) || (rc = sgm_set_option(&e, SGM_OPT_SWEEP_ROWS, sweep_rows)) ||
+        (rc = sgm_set_option(&e, SGM_OPT_DEBUG, debug)) || (rc = sgm_set_option(&e, SGM_OPT_CONFIDENCE, confidence)) ||
+        (rc = sgm_set_option(&e, SGM_OPT_RIGHT_VIEW, right_view)) || (rc = sgm_set_option(&e, SGM_OPT_KEEP_AGGR, keep_aggr)))
+        return rc;
+    Geom g;
+    if ((rc = normalise(&e.params, H, W, &g))) return rc;
+    return make_plan(&e, g, H).wta_split ? 1 : 0;
+}
+long long sgm_debug_wta_raw_bytes(const sgm_engine *e)
+{
+    if (!e) return -1;
+    long long n = (long long)e->wta_raw.cap;
+    for (const sgm_engine *q : e->group) n += (long long)q->wta_raw.cap;
+    return n;
 }
 
 int sgm_create(const sgm_params *params, int device_id, void *stream, sgm_engine **out)
@@ -2157,6 +2213,9 @@ static void inherit_options(sgm_engine *q, const sgm_engine *e)
     q->cn = e->cn;
     q->conf.on = e->conf.on;
     q->right.on = e->right.on;
+    // e keeps S: its plan keeps the store of S, and the group runs ONE sweep kernel.  (Read before keep_aggr is cleared: the
+    // host batch path calls this with q == e, and e's own plan follows its own keep_aggr.)
+    q->no_wta_split = q != e && e->keep_aggr != 0;
     q->keep_aggr = 0;
     q->profile = 0;
 }
@@ -2257,7 +2316,7 @@ static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &p
         if (in_ready && in_ready[k]) HIP_TRY(hipStreamWaitEvent(eng[k]->stream, in_ready[k], 0));
         if ((rc = run_compute(eng[k], io[k], H, W, stride_bytes, PH_PRE))) return rc;
         const Plan &q = eng[k]->plan;
-        if (!q.chain || q.R != pl.R || q.nbands != pl.nbands || q.axis != pl.axis)
+        if (!q.chain || q.R != pl.R || q.nbands != pl.nbands || q.axis != pl.axis || q.wta_split != pl.wta_split)
             return set_err(SGM_ERR_HIP, "internal: a pair of a chained group did not plan the group's chained sweep");
         if (in_used && in_used[k]) HIP_TRY(hipEventRecord(in_used[k], eng[k]->stream));   // (behind the whole cost stage: the images are read by its first kernel only)
     }
@@ -2278,6 +2337,7 @@ static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &p
         fr.S[k] = (int16_t *)eng[k]->aggr.p;
         fr.bnd[k] = (int16_t *)eng[k]->bndL.p;
         fr.hr[k] = eng[k]->g.hr;
+        fr.raw[k] = (uint4 *)eng[k]->wta_raw.p;
     }
     for (int pass = 0; pass < npass; pass++) {
         const int ydir = pass == 0 ? 1 : -1;
@@ -2286,8 +2346,8 @@ static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &p
         HIP_TRY(hipMemsetAsync(e->chain_ctl.p, 0, ctl_bytes, e->stream));
         stage_break(e);
         if ((rc = stage_begin(e, pass == 0 ? "chain_dn" : "chain_up"))) return rc;
-        if ((rc = launch_chain(g, a, fr, pass == 0 ? SWEEP_FIRST : SWEEP_ACCUM, chain_window(g, R, nbands, n, e->chain_wgs), e->stream, pl.axis)))
-            return rc;
+        const int cm = pass == 0 ? SWEEP_FIRST : (pl.wta_split ? SWEEP_REDUCE : SWEEP_ACCUM);
+        if ((rc = launch_chain(g, a, fr, cm, chain_window(g, R, nbands, n, e->chain_wgs), e->stream, pl.axis))) return rc;
         KCHECK();
         if ((rc = stage_end(e, 1))) return rc;
     }

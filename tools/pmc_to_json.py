@@ -27,10 +27,10 @@ STAGE_KERNEL = [  # stage -> regex on the demangled kernel name
     ("cost_hsum", r"k_hsum"), ("cost_vsum", r"k_vsum"),
     ("prepass", r"k_prepass3|k_path<\d+, \w+, 3"),
     ("paths5", r"k_paths5_g"),
-    ("chain_dn", r"k_sweep_chain<\d+, \w+, 0"), ("chain_up", r"k_sweep_chain<\d+, \w+, 1"),
+    ("chain_dn", r"k_sweep_chain<\d+, \w+, 0"), ("chain_up", r"k_sweep_chain<\d+, \w+, [13]"),
     ("sweep_dn", r"k_sweep<\d+, \w+, 0|k_vert3_g<\d+, 0"), ("sweep_up", r"k_sweep<\d+, \w+, 1|k_vert3_g<\d+, 1"),
     ("sweep_up_wta", r"k_sweep<\d+, \w+, 2"), ("path_W_wta", r"k_rows_g<\d+, \d+, \w+, 2"), ("path_W", r"k_rows_g<\d+, \d+, \w+, [01]"),
-    ("wta", r"k_wta_t"), ("select_lr", r"k_select"), ("median3", r"k_median3"), ("speckle", r"k_ccl_"),
+    ("wta", r"k_wta_t|k_wta_select"), ("select_lr", r"k_select"), ("median3", r"k_median3"), ("speckle", r"k_ccl_"),
     ("to_float", r"k_disp_to_float"), ("reproject", r"k_reproject"), ("post", r"k_post"), ("float_xyz", r"k_float_xyz"),
 ]
 
