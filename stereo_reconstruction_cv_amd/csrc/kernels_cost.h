@@ -4,13 +4,17 @@
 // (/root/reference/main.ipynb:668; arithmetic restated in SURVEY.md A.2-A.4 and
 // oracle/sgbm_oracle.c: row_features, bt_row, hsum_row, the C update in sgbm_core).
 //
-//   k_features : u8 image -> per-pixel (value, interval lo, interval hi) for the gradient
-//                and raw channels.  Left image: one packed 8-byte record per pixel (read
-//                wave-uniformly).  Right image: six byte planes stored MIRRORED in x so that
-//                ascending disparity is ascending address.
+//   k_features : u8 image, CN interleaved channels (1: gray, 3: SGM_OPT_CHANNELS = 3) -> per pixel and channel
+//                (value, interval lo, interval hi) of the gradient and raw planes.  Left image: CN packed 8-byte
+//                records per pixel, [H][W][CN] (read wave-uniformly).  Right image: 6 * CN byte planes (channel c:
+//                planes 6c .. 6c+5) stored MIRRORED in x so that ascending disparity is ascending address.
 //   k_hsum     : one wave per (row, column chunk); lanes span the disparities, the wave walks
 //                x keeping a sliding window of right-image features in registers and a ring of
 //                the last blockSize+1 pixel-cost vectors in LDS -> horizontal running box sum.
+//                The pixel cost of a colour pair is the sum of the three single-channel costs of the channel images
+//                (upstream's calcPixelCostBT with cn = 3; at most 3 * (2 * ftzero + 63) = 567 at
+//                preFilterCap 63, 3 * (255 + 63) = 954 once the byte-valued prefilter wraps), added in registers
+//                before it enters the ring: nothing downstream of it differs from gray.
 //   k_vsum     : vertical running box sum of hsum rows -> block cost C (no +P2 bias).
 #pragma once
 #include "sgm_device.h"
@@ -33,7 +37,10 @@ struct Geom {
 };
 
 // ------------------------------------------------------------------------------------------
+// CN interleaved channels per pixel (1: gray, 3: colour).  Every channel gets the A.2 prefilter from its own neighbours
+// (same channel at x-1 / x+1 of rows y-1, y, y+1) and a raw plane (A.10).
 // blockIdx.z = 0: left image -> left_rec; 1: right image -> right_planes (one launch for the pair)
+template <int CN>
 __global__ __launch_bounds__(256) void k_features(const uint8_t *__restrict__ imgL, const uint8_t *__restrict__ imgR,
                                                   int64_t stride, int H, int W, int ftzero,
                                                   uint2 *__restrict__ left_rec_,
@@ -44,47 +51,48 @@ __global__ __launch_bounds__(256) void k_features(const uint8_t *__restrict__ im
     if (x >= W) return;
     const bool is_right = blockIdx.z != 0;
     const uint8_t *img = is_right ? imgR : imgL;
-    uint2 *left_rec = is_right ? nullptr : left_rec_;
-    uint8_t *right_planes = is_right ? right_planes_ : nullptr;
     const uint8_t *row = img + (int64_t)y * stride;
     const uint8_t *up = y > 0 ? row - stride : row;
     const uint8_t *dn = y < H - 1 ? row + stride : row;
-
-    // Upstream's clip table and row buffers hold bytes: from ftzero = 129 (preFilterCap >= 128) on, the prefilter value
-    // and the border value wrap mod 256 before the interval is formed (A.2), and every record byte stays a byte.
-    int pf[3], rw[3];  // values at x-1, x, x+1 (only read where they exist)
+    const int64_t psz = (int64_t)H * W;
+    const int64_t o = (int64_t)y * W + (W - 1 - x);  // mirrored position in a right plane
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const int xx = x + k - 1;
-        if (xx <= 0 || xx >= W - 1) {  // border columns hold ftzero in BOTH channels (A.2)
-            pf[k] = ftzero & 0xff;
-            rw[k] = ftzero & 0xff;
-        } else {
-            int g = 2 * ((int)row[xx + 1] - (int)row[xx - 1]) + ((int)up[xx + 1] - (int)up[xx - 1]) +
-                    ((int)dn[xx + 1] - (int)dn[xx - 1]);
-            pf[k] = (min(max(g, -ftzero), ftzero) + ftzero) & 0xff;
-            rw[k] = row[xx];
+    for (int ch = 0; ch < CN; ch++) {
+        // Upstream's clip table and row buffers hold bytes: from ftzero = 129 (preFilterCap >= 128) on, the prefilter
+        // value and the border value wrap mod 256 before the interval is formed (A.2), and every record byte stays a byte.
+        int pf[3], rw[3];  // values at x-1, x, x+1 of this channel (only read where they exist)
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int xx = x + k - 1;
+            if (xx <= 0 || xx >= W - 1) {  // border columns hold ftzero in the gradient AND the raw planes (A.2, A.10)
+                pf[k] = ftzero & 0xff;
+                rw[k] = ftzero & 0xff;
+            } else {
+                const int a = CN * (xx + 1) + ch, b = CN * (xx - 1) + ch;
+                int g = 2 * ((int)row[a] - (int)row[b]) + ((int)up[a] - (int)up[b]) + ((int)dn[a] - (int)dn[b]);
+                pf[k] = (min(max(g, -ftzero), ftzero) + ftzero) & 0xff;
+                rw[k] = row[CN * xx + ch];
+            }
         }
-    }
-    uint32_t out[2];
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-        const int *v = c == 0 ? pf : rw;
-        const int a = v[1];
-        const int l = x > 0 ? (a + v[0]) / 2 : a;
-        const int r = x < W - 1 ? (a + v[2]) / 2 : a;
-        const int lo = min(a, min(l, r)), hi = max(a, max(l, r));
-        out[c] = (uint32_t)a | ((uint32_t)lo << 8) | ((uint32_t)hi << 16);
-    }
-    if (left_rec) left_rec[(int64_t)y * W + x] = make_uint2(out[0], out[1]);
-    if (right_planes) {
-        const int64_t psz = (int64_t)H * W;
-        const int64_t o = (int64_t)y * W + (W - 1 - x);
+        uint32_t out[2];
 #pragma unroll
         for (int c = 0; c < 2; c++) {
-            right_planes[(c * 3 + 0) * psz + o] = (uint8_t)(out[c] & 0xff);
-            right_planes[(c * 3 + 1) * psz + o] = (uint8_t)((out[c] >> 8) & 0xff);
-            right_planes[(c * 3 + 2) * psz + o] = (uint8_t)((out[c] >> 16) & 0xff);
+            const int *v = c == 0 ? pf : rw;
+            const int a = v[1];
+            const int l = x > 0 ? (a + v[0]) / 2 : a;
+            const int r = x < W - 1 ? (a + v[2]) / 2 : a;
+            const int lo = min(a, min(l, r)), hi = max(a, max(l, r));
+            out[c] = (uint32_t)a | ((uint32_t)lo << 8) | ((uint32_t)hi << 16);
+        }
+        if (!is_right) {
+            left_rec_[((int64_t)y * W + x) * CN + ch] = make_uint2(out[0], out[1]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                right_planes_[(ch * 6 + c * 3 + 0) * psz + o] = (uint8_t)(out[c] & 0xff);
+                right_planes_[(ch * 6 + c * 3 + 1) * psz + o] = (uint8_t)((out[c] >> 8) & 0xff);
+                right_planes_[(ch * 6 + c * 3 + 2) * psz + o] = (uint8_t)((out[c] >> 16) & 0xff);
+            }
         }
     }
 }
@@ -98,18 +106,18 @@ __device__ __forceinline__ uint32_t bt_pair(uint32_t U, uint32_t U0, uint32_t U1
     return pk_min_u(c0, c1);
 }
 
-// LDS layout of one k_hsum workgroup (one wave): [ring RS*64*NP dwords][left records][6 planes]
+// LDS layout of one k_hsum workgroup (one wave): [ring RS*64*NP dwords][CN left records per column][6 * CN planes]
 struct HsumLds {
     int ring_bytes, lrec_bytes, seg_len, total_bytes;
 };
-static inline HsumLds hsum_lds_layout(int NP, int RS, int XL, int SW2)
+static inline HsumLds hsum_lds_layout(int NP, int RS, int XL, int SW2, int CN)
 {
     HsumLds l;
     l.ring_bytes = RS * 64 * NP * 4;
-    int nj = XL + 2 * SW2 + 2;
-    l.lrec_bytes = ((nj * 8) + 15) & ~15;
+    const int nj = XL + 2 * SW2 + 2;
+    l.lrec_bytes = ((nj * CN * 8) + 15) & ~15;
     l.seg_len = (nj + 128 * NP + 15) & ~15;
-    l.total_bytes = l.ring_bytes + l.lrec_bytes + 6 * l.seg_len;
+    l.total_bytes = l.ring_bytes + l.lrec_bytes + 6 * CN * l.seg_len;
     return l;
 }
 
@@ -119,38 +127,60 @@ template <int B> __device__ __forceinline__ uint32_t splat_byte(uint32_t x)
     return __builtin_amdgcn_perm(x, x, 0x0c000c00u | (uint32_t)B | ((uint32_t)B << 16));
 }
 
-// One wave per (row, chunk of XL output columns).  Column j of the pixel cost is computed once (BT
-// of the left record against the sliding windows of the six right-image planes), kept in an LDS
-// ring of RS columns, and the running horizontal sum hs(x) = hs(x-1) + pix(x+r) - pix(x-r-1)
-// (A.4, clamped at the domain edges) is stored as soon as its right-most tap exists.
+// pix of one column for this lane's NP packed disparity pairs: the sum over the CN channels of
+// BT(gradient plane) + (BT(raw plane) >> 2), i.e. of the single-channel costs of the channel images (A.3, A.10)
+template <int NP, int CN>
+__device__ __forceinline__ void pix_cost(const uint2 *recs, const uint32_t (&w)[6 * CN][NP], uint32_t (&pix)[NP])
+{
+#pragma unroll
+    for (int i = 0; i < NP; i++) pix[i] = 0;
+#pragma unroll
+    for (int ch = 0; ch < CN; ch++) {
+        const uint2 rec = recs[ch];
+        const uint32_t U = splat_byte<0>(rec.x), U0 = splat_byte<1>(rec.x), U1 = splat_byte<2>(rec.x);
+        const uint32_t R = splat_byte<0>(rec.y), R0 = splat_byte<1>(rec.y), R1 = splat_byte<2>(rec.y);
+#pragma unroll
+        for (int i = 0; i < NP; i++) {
+            const uint32_t a = bt_pair(U, U0, U1, w[6 * ch + 0][i], w[6 * ch + 1][i], w[6 * ch + 2][i]);
+            const uint32_t b = bt_pair(R, R0, R1, w[6 * ch + 3][i], w[6 * ch + 4][i], w[6 * ch + 5][i]);
+            pix[i] = pk_add(pix[i], pk_add(a, pk_shr_u(b, 2)));
+        }
+    }
+}
+
+// One wave per (row, chunk of XL output columns), lanes span the disparities.  Column j of the pixel cost is computed
+// once (pix_cost of the column's CN left records against the sliding windows of the 6 * CN right-image planes), kept in
+// an LDS ring of RS columns, and the running horizontal sum hs(x) = hs(x-1) + pix(x+r) - pix(x-r-1) (A.4, clamped at the
+// domain edges) is stored as int16 as soon as its right-most tap exists (the input of k_vsum_ring / k_vsum).
 //
-// RS_T > 0 (= RS, a power of two) adds the interior fast path: RS_T columns per iteration,
-// unrolled, so ring slots, window taps and record reads are immediate offsets and the only
-// scalar work per column is the store offset; it covers every column whose window is not
-// clamped.  The generic per-column step handles the first and last columns of a chunk / row.
-template <int NP, int RS_T>
-__global__ __launch_bounds__(64) void k_hsum(Geom g, const uint2 *__restrict__ lrec,
-                                             const uint8_t *__restrict__ rplanes,
-                                             int16_t *__restrict__ hsum, int XL, int nchunks, int RS,
-                                             int ring_bytes, int lrec_bytes, int seg_len, int y_base)
+// RS_T > 0 (= RS, a power of two) adds the interior fast path: RS_T columns per iteration, unrolled, so ring slots,
+// window taps and record reads are immediate offsets and the only scalar work per column is the store offset; it covers
+// every column whose window is not clamped.  The generic per-column step handles the first and last columns of a
+// chunk / row.
+template <int NP, int RS_T, int CN>
+__global__ __launch_bounds__(64) void k_hsum(Geom g, const uint2 *__restrict__ lrec, const uint8_t *__restrict__ rplanes,
+                                             int16_t *__restrict__ hsum, int XL, int nchunks, int RS, int ring_bytes,
+                                             int lrec_bytes, int seg_len)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t *ring = reinterpret_cast<uint32_t *>(smem);
-    uint2 *lds_lrec = reinterpret_cast<uint2 *>(smem + ring_bytes);
+    uint2 *lds_lrec = reinterpret_cast<uint2 *>(smem + ring_bytes);  // [column - j0][channel]
     uint8_t *seg = smem + ring_bytes + lrec_bytes;
 
     const int lane = threadIdx.x;
     const int unit = blockIdx.x;
-    const int yr = __builtin_amdgcn_readfirstlane(unit / nchunks), ck = unit - yr * nchunks;  // (uniform: see uniform_rsrc)
-    const int y = y_base + yr;  // the launch covers rows y_base .. y_base + gridDim.x / nchunks - 1
+    const int y = __builtin_amdgcn_readfirstlane(unit / nchunks), ck = unit - y * nchunks;  // (uniform: see uniform_rsrc)
     const int W1 = g.W1, SW2 = g.SW2, W = g.W;
     const int xs = ck * XL, xe = min(xs + XL, W1);
     const int j0 = max(xs - SW2 - 1, 0), j1 = min(xe - 1 + SW2, W1 - 1);
     const int nj = j1 - j0 + 1;
     const bool active = 2 * NP * lane < g.D;
 
-    // ---- stage this row's features for the chunk ----
-    for (int k = lane; k < nj; k += 64) lds_lrec[k] = lrec[(int64_t)y * W + (j0 + k + g.minX1)];
+    // ---- stage this row's features for the chunk (the CN records of a column are adjacent in lrec) ----
+    {
+        const uint2 *src = lrec + ((int64_t)y * W + (j0 + g.minX1)) * CN;
+        for (int k = lane; k < CN * nj; k += 64) lds_lrec[k] = src[k];
+    }
     {
         // mirrored position of (column j, disparity index e): (W-1-(j+minX1)) + minD + e
         const int base_j1 = W - 1 - (j1 + g.minX1) + g.minD;
@@ -160,18 +190,18 @@ __global__ __launch_bounds__(64) void k_hsum(Geom g, const uint2 *__restrict__ l
             const int pos = base_j1 + s;
             const bool ok = pos >= 0 && pos < W;
 #pragma unroll
-            for (int c = 0; c < 6; c++)
+            for (int c = 0; c < 6 * CN; c++)
                 seg[c * seg_len + s] = ok ? rplanes[c * psz + (int64_t)y * W + pos] : (uint8_t)0;
         }
     }
     __syncthreads();  // single wave; orders the LDS staging before the reads below
 
-    // ---- sliding windows of the six right-image planes ----
-    uint32_t w[6][NP];
+    // ---- sliding windows of the 6 * CN right-image planes ----
+    uint32_t w[6 * CN][NP];
     {
         const int off = (j1 - j0) + 2 * NP * lane;
 #pragma unroll
-        for (int c = 0; c < 6; c++)
+        for (int c = 0; c < 6 * CN; c++)
 #pragma unroll
             for (int i = 0; i < NP; i++)
                 w[c][i] = (uint32_t)seg[c * seg_len + off + 2 * i] | ((uint32_t)seg[c * seg_len + off + 2 * i + 1] << 16);
@@ -181,8 +211,8 @@ __global__ __launch_bounds__(64) void k_hsum(Geom g, const uint2 *__restrict__ l
 #pragma unroll
     for (int i = 0; i < NP; i++) hs[i] = 0;
     int next_x = xs;
-    // this row of the output as a buffer resource; lanes past D get an out-of-range offset, so
-    // their stores are dropped by the bounds check instead of by a branch
+    // this row of the output as a buffer resource; lanes past D get an out-of-range offset, so their stores are dropped
+    // by the bounds check instead of by a branch
     const int row_bytes = W1 * g.D * 2;
     const __amdgpu_buffer_rsrc_t orow = uniform_rsrc(hsum, (int64_t)y * g.rowsz * 2, row_bytes);
     const int voff = active ? 4 * NP * lane : row_bytes;
@@ -193,23 +223,18 @@ __global__ __launch_bounds__(64) void k_hsum(Geom g, const uint2 *__restrict__ l
         if (j > j0) {
             const int off = (j1 - j) + 2 * NP * lane;
 #pragma unroll
-            for (int c = 0; c < 6; c++) {
+            for (int c = 0; c < 6 * CN; c++) {
                 const uint32_t nw = seg[c * seg_len + off];
 #pragma unroll
                 for (int i = NP - 1; i >= 1; i--) w[c][i] = __builtin_amdgcn_alignbit(w[c][i], w[c][i - 1], 16);
                 w[c][0] = (w[c][0] << 16) | nw;
             }
         }
-        const uint2 rec = lds_lrec[j - j0];
-        const uint32_t U = splat_byte<0>(rec.x), U0 = splat_byte<1>(rec.x), U1 = splat_byte<2>(rec.x);
-        const uint32_t R = splat_byte<0>(rec.y), R0 = splat_byte<1>(rec.y), R1 = splat_byte<2>(rec.y);
+        uint32_t pix[NP];
+        pix_cost<NP, CN>(lds_lrec + CN * (j - j0), w, pix);
         uint32_t *slot = ring + ((j & (RS - 1)) * 64 + lane) * NP;
 #pragma unroll
-        for (int i = 0; i < NP; i++) {
-            uint32_t a = bt_pair(U, U0, U1, w[0][i], w[1][i], w[2][i]);
-            uint32_t b = bt_pair(R, R0, R1, w[3][i], w[4][i], w[5][i]);
-            slot[i] = pk_add(a, pk_shr_u(b, 2));
-        }
+        for (int i = 0; i < NP; i++) slot[i] = pix[i];
         // every output column whose right-most (clamped) tap is now available
         while (next_x < xe && min(next_x + SW2, W1 - 1) <= j) {
             const int x = next_x;
@@ -248,46 +273,38 @@ __global__ __launch_bounds__(64) void k_hsum(Geom g, const uint2 *__restrict__ l
             for (; j < ja; j++) column(j);
             const uint32_t *ring_lane = ring + lane * NP;
             uint32_t *ring_lane_w = ring + lane * NP;
-            // per-lane tap addresses of the six planes for the block's LAST column (offsets then
-            // count up towards the block's first column), and the record address of its first
-            int tap[6];
-#pragma unroll
-            for (int c = 0; c < 6; c++) tap[c] = c * seg_len + 2 * NP * lane + (j1 - j) - (RS_T - 1);
-            // the record address is the same in every lane; hidden from the compiler so that the
-            // record stays in VGPRs (v_perm splats) instead of a readfirstlane + scalar unpack
-            int recp = j - j0;
+            // per-lane tap address of plane 0 for the block's LAST column (plane c is seg_len * c further on)
+            int tap = 2 * NP * lane + (j1 - j) - (RS_T - 1);
+            // the record address is the same in every lane; hidden from the compiler so that the records stay in VGPRs
+            // (v_perm splats) instead of a readfirstlane + scalar unpack
+            int recp = CN * (j - j0);
             asm volatile("" : "+v"(recp));
             int so = (j - SW2) * pxb;
             for (; j + RS_T - 1 <= jb; j += RS_T) {
 #pragma unroll
                 for (int u = 0; u < RS_T; u++) {  // column j + u, ring slot u
 #pragma unroll
-                    for (int c = 0; c < 6; c++) {
-                        const uint32_t nw = seg[tap[c] + (RS_T - 1 - u)];
+                    for (int c = 0; c < 6 * CN; c++) {
+                        const uint32_t nw = seg[c * seg_len + tap + (RS_T - 1 - u)];
 #pragma unroll
                         for (int i = NP - 1; i >= 1; i--) w[c][i] = __builtin_amdgcn_alignbit(w[c][i], w[c][i - 1], 16);
                         w[c][0] = (w[c][0] << 16) | nw;
                     }
-                    const uint2 rec = lds_lrec[recp + u];
-                    const uint32_t U = splat_byte<0>(rec.x), U0 = splat_byte<1>(rec.x), U1 = splat_byte<2>(rec.x);
-                    const uint32_t R = splat_byte<0>(rec.y), R0 = splat_byte<1>(rec.y), R1 = splat_byte<2>(rec.y);
+                    uint32_t pix[NP];
+                    pix_cost<NP, CN>(lds_lrec + recp + CN * u, w, pix);
                     const uint32_t *old = ring_lane + ((u - bs) & (RS_T - 1)) * 64 * NP;  // column j + u - bs
                     Pack<NP> o;
 #pragma unroll
                     for (int i = 0; i < NP; i++) {
-                        const uint32_t a = bt_pair(U, U0, U1, w[0][i], w[1][i], w[2][i]);
-                        const uint32_t b = bt_pair(R, R0, R1, w[3][i], w[4][i], w[5][i]);
-                        const uint32_t pix = pk_add(a, pk_shr_u(b, 2));
-                        hs[i] = pk_sub(pk_add(hs[i], pix), old[i]);
-                        ring_lane_w[u * 64 * NP + i] = pix;
+                        hs[i] = pk_sub(pk_add(hs[i], pix[i]), old[i]);
+                        ring_lane_w[u * 64 * NP + i] = pix[i];
                         o.r[i] = hs[i];
                     }
                     buf_store<NP>(o, orow, voff, so);
                     so += pxb;
                 }
-#pragma unroll
-                for (int c = 0; c < 6; c++) tap[c] -= RS_T;
-                recp += RS_T;
+                tap -= RS_T;
+                recp += CN * RS_T;
             }
             next_x = j - SW2;
         }

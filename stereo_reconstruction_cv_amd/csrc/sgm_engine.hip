@@ -25,7 +25,6 @@
 #include "kernels_rectify.h"
 #include "kernels_sweep.h"
 #include "kernels_group.h"
-#include "kernels_color.h"
 #include "kernels_right.h"
 
 using namespace sgm;
@@ -209,7 +208,7 @@ struct Plan {
     bool pix_px;           // int16 pipeline: k_pix_px + k_hsum_px (D <= 32) in place of k_hsum
     int GWc, RBb;          // k_box_u8: lane-group width, rows per band
     bool vsum_ring, vsum_wide;  // int16 pipeline: k_vsum_ring (else the generic k_vsum), with 8 int16 per thread (else 4)
-    int cn;                // channels of the images (SGM_OPT_CHANNELS): 3 takes k_features_c3 + k_hsum_c3 into the vertical sum
+    int cn;                // channels of the images (SGM_OPT_CHANNELS), the CN of k_features / k_hsum: 3 always takes the int16 pipeline
     // path stage
     bool v1;               // schedule 0: one kernel per direction
     int GWs;               // lane-group width of the small-D kernels (64: none)
@@ -467,9 +466,9 @@ static void stage_break(sgm_engine *e) { e->last_end_ev = -1; }
 
 // ---- template ladders --------------------------------------------------------------------------
 // f(NP, PARTIAL) as std::integral_constant for the geometry: NP 128-disparity pieces per lane, PARTIAL = the last piece is not full
-// NP = 1, 2, 4 only.  D > 512 (NP = 8) never comes here: its plan (make_plan: wide_d) runs three kernels -- k_path, k_hsum,
-// k_hsum_c3 -- and those go through with_np_wide; a fourth rung HERE would instantiate every sweep, pre-pass and lane-group
-// kernel for a packing their registers and LDS do not hold.
+// NP = 1, 2, 4 only.  D > 512 (NP = 8) never comes here: its plan (make_plan: wide_d) runs two kernel templates -- k_path
+// and k_hsum (gray and colour) -- and those go through with_np_wide; a fourth rung HERE would instantiate every sweep,
+// pre-pass and lane-group kernel for a packing their registers and LDS do not hold.
 static bool np_partial(const Geom &g) { return g.D != 128 * g.NP; }
 template <class F>
 static auto with_np(const Geom &g, F &&f)
@@ -864,7 +863,7 @@ static int ensure_plan_buffers(sgm_engine *e, const Plan &p, int H, int W)
     // compiler may merge or widen them (the widest scalar load is 64 bytes).  Every load STARTS at a record of the
     // frame, so none can leave the allocation.  (Not in the guarded mode: there the buffer ends where its mapping
     // ends, and the parity cases of tests/test_gpu_guard.py show that no load goes past the last record at all.)
-    // (colour pairs: three records per pixel and 18 planes, kernels_color.h)
+    // (colour pairs: three records per pixel and 18 planes, k_features<3>)
     if ((rc = e->lrec.ensure(npx * 8 * p.cn + (debug_alloc_mode() ? 0 : 64)))) return rc;
     if ((rc = e->rplanes.ensure(npx * 6 * p.cn))) return rc;
     if (vol) {
@@ -970,57 +969,37 @@ static void launch_box(const Geom &g, const Plan &p, const uint8_t *px, int16_t 
     });
 }
 
-// int16 pipeline: horizontal box sum of the pixel cost, all rows (k_hsum); RS_T = RS instantiations carry the unrolled
-// interior fast path (block sizes up to 15)
-template <int NP, int RS_T>
+// int16 pipeline: pixel cost (summed over the cn channels) + horizontal box sum, all rows (k_hsum); RS_T = RS
+// instantiations carry the unrolled interior fast path (block sizes up to 15)
+template <int NP, int RS_T, int CN>
 static int launch_hsum_t(const Geom &g, const uint2 *lrec, const uint8_t *rpl, int16_t *HS, int RS, hipStream_t st)
 {
     const int nchunks = cost_chunks(g);
-    // (largest: NP = 8, blockSize 31 -> RS = 32: a 64 KiB ring + 1.3 KiB of records + 7 KiB of planes, of 160 KiB)
-    const HsumLds l = hsum_lds_layout(g.NP, RS, COST_XL, g.SW2);
-    if (l.total_bytes > 160 * 1024) return set_err(SGM_ERR_UNSUPPORTED, "k_hsum needs %d bytes of LDS", l.total_bytes);
+    // (largest: NP = 8, blockSize 31 -> RS = 32: a 64 KiB ring + 1.3 KiB of records + 7 KiB of planes, of 160 KiB; colour
+    // pairs 3.8 KiB of records + 20.8 KiB of planes)
+    const HsumLds l = hsum_lds_layout(g.NP, RS, COST_XL, g.SW2, CN);
+    if (l.total_bytes > 160 * 1024)
+        return set_err(SGM_ERR_UNSUPPORTED, "k_hsum%s needs %d bytes of LDS", CN == 3 ? "_c3" : "", l.total_bytes);
     if (l.total_bytes > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)k_hsum<NP, RS_T>, hipFuncAttributeMaxDynamicSharedMemorySize, l.total_bytes));
-    hipLaunchKernelGGL((k_hsum<NP, RS_T>), dim3((unsigned)((int64_t)g.H * nchunks)), dim3(64), l.total_bytes, st, g, lrec, rpl,
-                       HS, COST_XL, nchunks, RS, l.ring_bytes, l.lrec_bytes, l.seg_len, 0);
+        HIP_TRY(hipFuncSetAttribute((const void *)k_hsum<NP, RS_T, CN>, hipFuncAttributeMaxDynamicSharedMemorySize, l.total_bytes));
+    hipLaunchKernelGGL((k_hsum<NP, RS_T, CN>), dim3((unsigned)((int64_t)g.H * nchunks)), dim3(64), l.total_bytes, st, g, lrec,
+                       rpl, HS, COST_XL, nchunks, RS, l.ring_bytes, l.lrec_bytes, l.seg_len);
     return SGM_OK;
 }
-static int launch_hsum(const Geom &g, const uint2 *lrec, const uint8_t *rpl, int16_t *HS, hipStream_t st)
+static int launch_hsum(const Geom &g, int cn, const uint2 *lrec, const uint8_t *rpl, int16_t *HS, hipStream_t st)
 {
     int RS = 1;  // ring of the last blockSize+1 cost vectors, rounded to a power of two
     while (RS < 2 * g.SW2 + 2) RS <<= 1;
-    return with_np_wide(g, [&](auto np, auto) {
-        if (RS == 4) return launch_hsum_t<np, 4>(g, lrec, rpl, HS, RS, st);
-        if (RS == 8) return launch_hsum_t<np, 8>(g, lrec, rpl, HS, RS, st);
-        if (RS == 16) return launch_hsum_t<np, 16>(g, lrec, rpl, HS, RS, st);
-        return launch_hsum_t<np, 0>(g, lrec, rpl, HS, RS, st);
-    });
-}
-
-// colour pairs: pixel cost of the three channels + horizontal box sum, all rows (k_hsum_c3)
-template <int NP, int RS_T>
-static int launch_hsum_c3_t(const Geom &g, const uint2 *lrec, const uint8_t *rpl, int16_t *HS, int RS, hipStream_t st)
-{
-    const int nchunks = cost_chunks(g);
-    // (largest: NP = 8, blockSize 31 -> RS = 32: a 64 KiB ring + 3.8 KiB of records + 20.8 KiB of planes, of 160 KiB)
-    const HsumLds l = hsum_c3_lds_layout(g.NP, RS, COST_XL, g.SW2);
-    if (l.total_bytes > 160 * 1024) return set_err(SGM_ERR_UNSUPPORTED, "k_hsum_c3 needs %d bytes of LDS", l.total_bytes);
-    if (l.total_bytes > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)k_hsum_c3<NP, RS_T>, hipFuncAttributeMaxDynamicSharedMemorySize, l.total_bytes));
-    hipLaunchKernelGGL((k_hsum_c3<NP, RS_T>), dim3((unsigned)((int64_t)g.H * nchunks)), dim3(64), l.total_bytes, st, g, lrec, rpl,
-                       HS, COST_XL, nchunks, RS, l.ring_bytes, l.lrec_bytes, l.seg_len);
-    return SGM_OK;
-}
-static int launch_hsum_c3(const Geom &g, const uint2 *lrec, const uint8_t *rpl, int16_t *HS, hipStream_t st)
-{
-    int RS = 1;  // ring of the last blockSize+1 cost vectors, rounded to a power of two
-    while (RS < 2 * g.SW2 + 2) RS <<= 1;
-    return with_np_wide(g, [&](auto np, auto) {
-        if (RS == 4) return launch_hsum_c3_t<np, 4>(g, lrec, rpl, HS, RS, st);
-        if (RS == 8) return launch_hsum_c3_t<np, 8>(g, lrec, rpl, HS, RS, st);
-        if (RS == 16) return launch_hsum_c3_t<np, 16>(g, lrec, rpl, HS, RS, st);
-        return launch_hsum_c3_t<np, 0>(g, lrec, rpl, HS, RS, st);
-    });
+    auto go = [&](auto c) {
+        constexpr int CN = decltype(c)::value;
+        return with_np_wide(g, [&](auto np, auto) {
+            if (RS == 4) return launch_hsum_t<np, 4, CN>(g, lrec, rpl, HS, RS, st);
+            if (RS == 8) return launch_hsum_t<np, 8, CN>(g, lrec, rpl, HS, RS, st);
+            if (RS == 16) return launch_hsum_t<np, 16, CN>(g, lrec, rpl, HS, RS, st);
+            return launch_hsum_t<np, 0, CN>(g, lrec, rpl, HS, RS, st);
+        });
+    };
+    return cn == 3 ? go(std::integral_constant<int, 3>()) : go(std::integral_constant<int, 1>());
 }
 
 // int16 pipeline: vertical box sum -> block cost C (k_vsum_ring in bands of 96 rows; the generic k_vsum for radii above 5)
@@ -1224,15 +1203,9 @@ static int ensure_aux(sgm_engine *e, bool second)
 static int stage_features(sgm_engine *e, const Plan &p, const uint8_t *d_left, const uint8_t *d_right, int64_t stride)
 {
     const Geom &g = e->g;
-    if (p.cn == 3)
-        return run_stage(e, "features_c3", e->stream, [&] {
-            hipLaunchKernelGGL(k_features_c3, dim3((g.W + 255) / 256, g.H, 2), dim3(256), 0, e->stream, d_left, d_right, stride, g.H,
-                               g.W, g.ftzero, (uint2 *)e->lrec.p, (uint8_t *)e->rplanes.p);
-            return 1;
-        });
-    return run_stage(e, "features", e->stream, [&] {
-        hipLaunchKernelGGL(k_features, dim3((g.W + 255) / 256, g.H, 2), dim3(256), 0, e->stream, d_left, d_right, stride, g.H, g.W,
-                           g.ftzero, (uint2 *)e->lrec.p, (uint8_t *)e->rplanes.p);
+    return run_stage(e, p.cn == 3 ? "features_c3" : "features", e->stream, [&] {
+        hipLaunchKernelGGL(p.cn == 3 ? k_features<3> : k_features<1>, dim3((g.W + 255) / 256, g.H, 2), dim3(256), 0, e->stream,
+                           d_left, d_right, stride, g.H, g.W, g.ftzero, (uint2 *)e->lrec.p, (uint8_t *)e->rplanes.p);
         return 1;
     });
 }
@@ -1256,12 +1229,8 @@ static int stage_cost(sgm_engine *e, const Plan &p)
         return run_stage(e, "cost_box", st, [&] { launch_box(g, p, px, C, st); return 1; });
     }
     rc = run_stage(e, p.cn == 3 ? "cost_hsum_c3" : "cost_hsum", st, [&] {
-        if (p.cn == 3) {
-            const int r = launch_hsum_c3(g, lrec, rpl, HS, st);
-            return r ? r : 1;
-        }
         if (!p.pix_px) {
-            const int r = launch_hsum(g, lrec, rpl, HS, st);
+            const int r = launch_hsum(g, p.cn, lrec, rpl, HS, st);
             return r ? r : 1;
         }
         launch_pix(g, lrec, rpl, px, st);

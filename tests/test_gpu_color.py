@@ -1,4 +1,4 @@
-"""Colour (8-bit, 3-channel) pairs through the engine (needs an MI355X): SGM_OPT_CHANNELS = 3, k_features_c3 + k_hsum_c3
+"""Colour (8-bit, 3-channel) pairs through the engine (needs an MI355X): SGM_OPT_CHANNELS = 3, k_features<3> + k_hsum<., ., 3>
 into the int16 vertical box sum.  Checked against an implementation-independent known answer, against the C oracle through
 two exact relations (the block cost is the sum of the three channel images' block costs; (I, I, I) with tripled penalties
 is the gray map of I) and end to end against the colour brute force of tests/bruteforce_color.py."""
@@ -133,6 +133,13 @@ LIN = [  # H, W, D, minD, bs, mode, cap, P1, P2
     (40, 360, 96, 0, 15, 1, 15, 30, 135),
     (40, 400, 128, 0, 17, 0, 15, 34, 153),
     (24, 90, 16, 0, 19, 1, 15, 38, 171),
+    # k_hsum<NP, RS_T, 3> instantiations at W1 just above one 128-column chunk (the second chunk is short and mostly takes
+    # the generic step)
+    (30, 420, 256, 0, 13, 1, 15, 26, 117),                # NP = 2, RS_T = 16
+    (30, 400, 192, 0, 19, 0, 15, 38, 171),                # NP = 2 partial, RS_T = 0
+    (30, 660, 512, 0, 3, 1, 63, 18, 72),                  # NP = 4, RS_T = 4
+    (30, 640, 480, -2, 13, 0, 15, 26, 117),               # NP = 4 partial, RS_T = 16
+    (30, 660, 512, 0, 17, 1, 15, 34, 153),                # NP = 4, RS_T = 0
 ]
 
 

@@ -73,7 +73,7 @@ HH4 = [
     case(611, 1777, 48, -3, 5, 3, 40, W1=1729, rows4=1, nvol=4, partial=1),
     case(150, 1801, 128, 0, 7, 3, W1=1673, R=4, last_band=2, RBb=48),
 ]
-# colour pairs (the int16 cost pipeline: k_features_c3, k_hsum_c3): modes 0, 1, 3; schedules 1 and 2; D <= 32 and D = 192
+# colour pairs (the int16 cost pipeline: k_features<3>, k_hsum<., ., 3>): modes 0, 1, 3; schedules 1 and 2; D <= 32 and D = 192
 COLOUR = [
     case(431, 1933, 192, -5, 5, 1, 31, 15, 1, cn=3, W1=1741, byte_cost=0, R=4, last_band=3, pre_nch=3, last_chunk=143),
     case(517, 1699, 32, 3, 5, 0, cn=3, W1=1664, byte_cost=0, pix_px=0, rows4=1, GWs=16, nvol=5),

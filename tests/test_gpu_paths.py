@@ -21,7 +21,11 @@ def _low_contrast_pair(H, W, D, seed):
 
 @pytest.mark.parametrize("H,W,D,bs,cap,mode", [
     (40, 200, 32, 13, 100, 0), (36, 260, 64, 15, 127, 1), (44, 300, 128, 21, 97, 0),
-    (70, 420, 256, 31, 63, 1), (50, 200, 16, 31, 127, 0), (33, 700, 512, 13, 120, 1)])
+    (70, 420, 256, 31, 63, 1), (50, 200, 16, 31, 127, 0), (33, 700, 512, 13, 120, 1),
+    # k_hsum<NP, RS_T, 1> instantiations at W1 just above one 128-column chunk (the second chunk is short and mostly takes
+    # the generic step): NP 2 partial RS_T 16; NP 4 RS_T 0; NP 1, 2, 4 RS_T 4; NP 4 partial RS_T 8
+    (30, 330, 192, 13, 100, 0), (30, 660, 512, 19, 100, 1), (30, 300, 128, 3, 100, 0), (30, 400, 256, 3, 100, 1),
+    (30, 660, 512, 3, 100, 0), (30, 640, 480, 7, 100, 1)])
 def test_large_blocks_and_high_prefilter_caps(H, W, D, bs, cap, mode):
     l, r = _low_contrast_pair(H, W, D, 900 + bs)
     p = dict(minDisparity=0, numDisparities=D, blockSize=bs, P1=2 * bs, P2=9 * bs, disp12MaxDiff=1, preFilterCap=cap,

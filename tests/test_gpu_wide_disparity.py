@@ -1,4 +1,4 @@
-"""numDisparities 528 ... 1024 on the GPU (needs an MI355X): 16 disparities per lane (NP = 8) through k_hsum / k_hsum_c3,
+"""numDisparities 528 ... 1024 on the GPU (needs an MI355X): 16 disparities per lane (NP = 8) through k_hsum (gray and colour),
 the element-wise vertical sum and one k_path launch per direction, bit for bit against the oracles.
 
 Yardsticks: gray pairs in modes 0 and 1 -- the frozen oracle (oracle/sgbm_oracle.c); MODE_HH4 and colour pairs -- the

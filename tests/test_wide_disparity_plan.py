@@ -107,12 +107,15 @@ def _scratch(body):
 def test_isa_has_the_np8_route_without_scratch_and_nothing_else_at_np8():
     K = _kernels()
     path8 = sorted(n for n in K if re.search(r"k_pathILi8E", n))
-    hsum8 = sorted(n for n in K if re.search(r"k_hsum(?:_c3)?ILi8E", n))
+    # k_hsum<8, RS_T, CN>: the four ring sizes, gray (CN = 1) and colour (CN = 3)
+    gray8 = sorted(n for n in K if re.search(r"k_hsumILi8ELi\d+ELi1EE", n))
+    color8 = sorted(n for n in K if re.search(r"k_hsumILi8ELi\d+ELi3EE", n))
     # k_path<8, PARTIAL, MODE, POSW>: first / accumulate / last with both uniqueness forms, full and partial waves
     assert len(path8) == 8, path8
-    assert any("k_hsumILi8E" in n for n in hsum8) and any("k_hsum_c3ILi8E" in n for n in hsum8), hsum8
+    assert len(gray8) == 4 and len(color8) == 4, (gray8, color8)
+    assert sorted(gray8 + color8) == sorted(n for n in K if "k_hsumILi8E" in n)
     counts = {}
-    for n in path8 + [h for h in hsum8 if "k_hsumILi8E" in h]:
+    for n in path8 + gray8:
         twin = n.replace("ILi8E", "ILi4E", 1)
         assert twin in K, twin
         counts[n] = (_scratch(K[n]), _scratch(K[twin]))

@@ -34,7 +34,7 @@ def main():
         bad = [U.describe_mismatch(k, h[k], t[k]) for k, n in rep.items() if n]
         assert not bad, f"{(H, W, D, bs, mode, sched)}: " + "\n".join(bad)
         ncase += 1
-    # one colour pair (k_hsum_c3<8, .>)
+    # one colour pair (k_hsum<8, ., 3>)
     H, W, D = 9, 1024 + 130, 1024
     L3, R3 = BC.colour_pair(H, W, D, seed=9800)
     p = U.params(D, 3, 0, 1, penalty="plain", speckleWindowSize=12, speckleRange=2)
