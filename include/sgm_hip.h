@@ -53,7 +53,7 @@ extern "C" {
                              * 4: sgm_check, sgm_trim, sgm_compact_points_device_async, SGM_OPT_GROUP_MAX (round 4);
                              * additive since, version unchanged: SGM_OPT_CHANNELS; mode 3; SGM_OPT_CONFIDENCE, SGM_TAP_CONF_RAW,
                              * SGM_TAP_CONF, sgm_bind_confidence_device (sgm_hip_confidence.h); SGM_OPT_RIGHT_VIEW, SGM_TAP_RIGHT_RAW,
-                             * SGM_TAP_RIGHT, sgm_bind_right_device (sgm_hip_right.h) */
+                             * SGM_TAP_RIGHT, sgm_bind_right_device (sgm_hip_right.h); SGM_OPT_COST, SGM_COST_BT, SGM_COST_CENSUS */
 
 typedef enum {
     SGM_OK = 0,
@@ -150,9 +150,29 @@ typedef enum {
                               * the internal engines of the batch entries inherit the option; the two options may be on together
                               * (confidence stays a left-view quantity).  sgm_compute_batch computes as before and returns NO per-pair
                               * right-view map: a host-batch form is a follow-up. */
+    SGM_OPT_COST = 12,       /* the matching cost of every compute on the engine: SGM_COST_BT (0, default) or SGM_COST_CENSUS (1); any
+                              * other value is refused with SGM_ERR_INVALID_ARG.  The internal engines of the batch entries inherit
+                              * the option; SGM_OPT_CONFIDENCE and SGM_OPT_RIGHT_VIEW work with it unchanged (they read S).
+                              * SGM_COST_BT: OpenCV's prefilter + Birchfield-Tomasi, box-summed over blockSize.
+                              * SGM_COST_CENSUS, for 8-bit single-channel images I of H x W (geometry minX1, W1 as for BT):
+                              *   descriptor c(y, x): 62 bits, one per offset dy in -3..3, dx in -4..4 without the centre; the bit is 1
+                              *     iff I[clamp(y + dy, 0, H-1)][clamp(x + dx, 0, W-1)] < I[y][x] (strict).  The bit order is not
+                              *     observable: only Hamming distances are.
+                              *   pixel cost pix(y, xi, k) = popcount(cL(y, xi + minX1) XOR cR(y, xi + minX1 - (minDisparity + k))),
+                              *     0 .. 62, for xi in [0, W1), k in [0, numDisparities) (the right column is always inside the image).
+                              *   block cost C = the sum of pix over the blockSize x blockSize window, indices clamped in the
+                              *     (H, W1) domain -- the box sum BT's pixel cost gets; blockSize 1 is the plain census cost.
+                              *     SGM_TAP_COST returns it (no +P2 bias), and sgm_get_headroom keeps its definition.
+                              *   Everything behind C is unchanged, P1 / P2 as given.  preFilterCap has no effect.  The cost, and so
+                              *     the disparity map, is exactly invariant under any strictly increasing map of either image's
+                              *     intensities (exposure, gain, gamma between the cameras).
+                              * Census with SGM_OPT_CHANNELS = 3 is refused at compute time with SGM_ERR_UNSUPPORTED (nothing is
+                              * enqueued, the engine stays usable): a colour census is a follow-up. */
     /* 4 = SGM_OPT_DEBUG: A/B switches for measurements -- not part of this interface (csrc/sgm_debug.h) */
     SGM_OPT_RESERVED_4 = 4
 } sgm_option;
+
+typedef enum { SGM_COST_BT = 0, SGM_COST_CENSUS = 1 } sgm_cost; /* values of SGM_OPT_COST */
 
 #define SGM_MAX_STAGES 32
 typedef struct {

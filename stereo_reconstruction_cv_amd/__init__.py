@@ -3,7 +3,7 @@ cv2.StereoSGBM_create(...).compute() / cv2.reprojectImageTo3D() path (main.ipynb
 
     import stereo_reconstruction_cv_amd as cv2   # for this path only
 """
-from .stereo import (CV_32F, STEREO_SGBM_MODE_HH, STEREO_SGBM_MODE_HH4, STEREO_SGBM_MODE_SGBM,
+from .stereo import (CV_32F, STEREO_COST_BT, STEREO_COST_CENSUS, STEREO_SGBM_MODE_HH, STEREO_SGBM_MODE_HH4, STEREO_SGBM_MODE_SGBM,
                      STEREO_SGBM_MODE_SGBM_3WAY, Engine, StereoSGBM, StereoSGBM_create, clear_engine_cache, error,
                      get_device, get_engine, reprojectImageTo3D, set_device, initUndistortRectifyMap, remap, CV_32FC1,
                      INTER_LINEAR, BORDER_CONSTANT)
@@ -18,5 +18,5 @@ __all__ = [
     "run_disparity", "valid_points", "write_point_cloud", "read_point_cloud", "STEREO_SGBM_MODE_SGBM", "STEREO_SGBM_MODE_HH", "STEREO_SGBM_MODE_SGBM_3WAY",
     "STEREO_SGBM_MODE_HH4", "CV_32F", "CV_32FC1", "INTER_LINEAR", "BORDER_CONSTANT", "initUndistortRectifyMap", "remap", "rectify_pair",
     "mask_by_confidence", "SGM_OPT_CONFIDENCE", "SGM_TAP_CONF_RAW", "SGM_TAP_CONF",
-    "SGM_OPT_RIGHT_VIEW", "SGM_TAP_RIGHT_RAW", "SGM_TAP_RIGHT",
+    "SGM_OPT_RIGHT_VIEW", "SGM_TAP_RIGHT_RAW", "SGM_TAP_RIGHT", "STEREO_COST_BT", "STEREO_COST_CENSUS",
 ]

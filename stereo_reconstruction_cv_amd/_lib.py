@@ -20,6 +20,8 @@ SGM_OPT_KEEP_AGGR, SGM_OPT_PROFILE, SGM_OPT_SCHEDULE, SGM_OPT_SWEEP_ROWS, SGM_OP
 SGM_OPT_CHANNELS = 8    # 1 (default) or 3: interleaved 8-bit channels per image pixel
 SGM_OPT_CONFIDENCE = 10  # 1: every compute also produces the confidence maps (SGM_TAP_CONF_RAW, SGM_TAP_CONF)
 SGM_OPT_RIGHT_VIEW = 11  # 1: every compute also produces the right-view map (SGM_TAP_RIGHT_RAW, SGM_TAP_RIGHT)
+SGM_OPT_COST = 12        # the matching cost of every compute on the engine: SGM_COST_BT (default) or SGM_COST_CENSUS
+SGM_COST_BT, SGM_COST_CENSUS = 0, 1
 SGM_OPT_DEBUG = 4    # csrc/sgm_debug.h: A/B switches for tools/ and tests/, not part of the public interface
 SGM_OPT_POISON = 9   # csrc/sgm_debug.h: fill every device buffer with a byte (0..255) and arm the same for new ones; -1 disarms (tests only)
 SGM_MAX_STAGES = 32
@@ -130,6 +132,8 @@ def load():
     L.sgm_debug_plan.restype = i32
     L.sgm_debug_plan_opts.argtypes = [pp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(SgmDebugPlan)]
     L.sgm_debug_plan_opts.restype = i32
+    L.sgm_debug_plan_cost.argtypes = [pp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(SgmDebugPlan)]
+    L.sgm_debug_plan_cost.restype = i32
     # ... and the readouts of the split winner-take-all
     L.sgm_debug_uniq_threshold.argtypes = [i32, i32]
     L.sgm_debug_uniq_threshold.restype = i32
@@ -150,12 +154,16 @@ def last_error() -> str:
 
 
 def debug_plan(params: dict, H: int, W: int, channels: int = 1, schedule: int = 1, sweep_rows: int = 0, prepass_rows: int = 0,
-               debug: int = 0, frames: int = 1, confidence: int = 0, right_view: int = 0) -> dict:
+               debug: int = 0, frames: int = 1, confidence: int = 0, right_view: int = 0, cost: int = SGM_COST_BT) -> dict:
     """The schedule one compute of an H x W frame takes with these arguments and options (csrc/sgm_debug.h: sgm_debug_plan),
     as a dict of the fields of sgm_debug_plan_t.  Needs no GPU.  For tests: which plan a case takes is read, not assumed.
-    confidence / right_view: SGM_OPT_CONFIDENCE / SGM_OPT_RIGHT_VIEW of the engine (the sibling readout sgm_debug_plan_opts)."""
+    confidence / right_view: SGM_OPT_CONFIDENCE / SGM_OPT_RIGHT_VIEW of the engine (the sibling readout sgm_debug_plan_opts);
+    cost: its SGM_OPT_COST (sgm_debug_plan_cost)."""
     out = SgmDebugPlan()
-    if confidence or right_view:
+    if cost != SGM_COST_BT:
+        rc = load().sgm_debug_plan_cost(C.byref(SgmParams(**params)), H, W, channels, schedule, sweep_rows, prepass_rows, debug,
+                                        frames, confidence, right_view, cost, C.byref(out))
+    elif confidence or right_view:
         rc = load().sgm_debug_plan_opts(C.byref(SgmParams(**params)), H, W, channels, schedule, sweep_rows, prepass_rows, debug,
                                         frames, confidence, right_view, C.byref(out))
     else:

@@ -57,6 +57,13 @@ extern "C"
 #endif
 int sgm_debug_plan_opts(const sgm_params *p, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
                         int debug, int frames, int confidence, int right_view, sgm_debug_plan_t *out);
+/* ... and SGM_OPT_COST: cost = SGM_COST_BT gives what sgm_debug_plan_opts gives; with SGM_COST_CENSUS byte_cost says which box
+ * route the census bytes take (k_box_u8, or k_hsum_u8 + k_vsum*), and 3 channels return the compute's error code */
+#ifdef __cplusplus
+extern "C"
+#endif
+int sgm_debug_plan_cost(const sgm_params *p, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
+                        int debug, int frames, int confidence, int right_view, int cost, sgm_debug_plan_t *out);
 
 /* Split winner-take-all (kernels_path.h: wta_reduce_pixels, kernels_post.h: k_wta_select), for tests; none needs a GPU.
  * sgm_debug_uniq_threshold: T1 = ceil(100 minS / (100 - uniquenessRatio)) as the kernels compute it from the integer

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "kernels_cost.h"
+#include "kernels_census.h"
 #include "kernels_path.h"
 #include "kernels_post.h"
 #include "kernels_rectify.h"
@@ -209,6 +210,8 @@ struct Plan {
     int GWc, RBb;          // k_box_u8: lane-group width, rows per band
     bool vsum_ring, vsum_wide;  // int16 pipeline: k_vsum_ring (else the generic k_vsum), with 8 int16 per thread (else 4)
     int cn;                // channels of the images (SGM_OPT_CHANNELS), the CN of k_features / k_hsum: 3 always takes the int16 pipeline
+    bool census;           // SGM_OPT_COST = SGM_COST_CENSUS: k_census + k_pix_census* in front of the box stages (byte_cost: k_box_u8,
+                           // else k_hsum_u8 + k_vsum*); private: not part of sgm_debug_plan_t
     // path stage
     bool v1;               // schedule 0: one kernel per direction
     int GWs;               // lane-group width of the small-D kernels (64: none)
@@ -238,7 +241,7 @@ struct Plan {
 // buffer added here is released, poisoned and counted; tests/test_history_walks.py refuses a DevBuf declared anywhere else.
 #define SGM_ENGINE_DEVBUFS(BUF, ARR, MAP) \
     BUF(in_left) BUF(in_right)                   /* staging for host-pointer calls */ \
-    BUF(lrec) BUF(rplanes)                       /* features */ \
+    BUF(lrec) BUF(rplanes)                       /* features (census: the 64-bit descriptors of the left / the mirrored right image) */ \
     BUF(hsum) BUF(cost) BUF(aggr)                /* int16 [H][W1][D] volumes */ \
     BUF(aggr2) BUF(aggr3)                        /* MODE_SGBM: the fifth path's own volume (D <= 128; added to S by the winner-take-all), the other in-row path's (D <= 64) */ \
     BUF(aggr4) BUF(aggr5)                        /* MODE_SGBM, D <= 64: the volumes of the vertical and the second diagonal direction (k_paths5_g) */ \
@@ -300,6 +303,7 @@ struct sgm_engine {
     int debug = 0;       // timing experiments (SweepArgs::dbg)
     int prepass_rows = 0;  // rows per chunk of the boundary pre-pass (0 = automatic, about 135, a multiple of 8)
     int cn = 1;          // SGM_OPT_CHANNELS: 1 or 3 interleaved 8-bit channels per image pixel
+    int cost_fn = SGM_COST_BT;  // SGM_OPT_COST: the matching cost of every compute on the engine
     // SGM_OPT_CONFIDENCE: every compute also produces the uniqueness margin; SGM_OPT_RIGHT_VIEW: the right-view map
     SideMap conf{1, "SGM_OPT_CONFIDENCE", "sgm_bind_confidence_device", "confidence", SGM_TAP_CONF_RAW, SGM_TAP_CONF, "SGM_TAP_CONF"};
     SideMap right{2, "SGM_OPT_RIGHT_VIEW", "sgm_bind_right_device", "right-view", SGM_TAP_RIGHT_RAW, SGM_TAP_RIGHT, "SGM_TAP_RIGHT"};
@@ -699,11 +703,15 @@ static Plan make_plan(const sgm_engine *e, const Geom &g, int H)
     // Colour pairs (cn = 3) take the int16 pipeline: their per-pixel cost (up to 3 * (min(2 * ftzero, 255) + 63)) does not
     // fit a byte.  A gray pixel cost is at most min(2 * ftzero, 255) + 63 (the prefilter values are bytes, k_features), so
     // 2 * ftzero + 63 <= 255 below is the exact bound for ftzero <= 96 and keeps every larger ftzero off the byte volumes.
+    // Census (SGM_OPT_COST; gray pairs only, census_refused): the per-pixel cost is a Hamming distance of 62 bits, a byte
+    // whatever preFilterCap says -- the ftzero bound falls away, the others stay.
     p.cn = e->cn;
+    p.census = e->cost_fn == SGM_COST_CENSUS;
     p.byte_cost = p.cn == 1 && !(dbg & SGM_DBG_INT16_COST) && (g.D > 64 || !(dbg & SGM_DBG_NO_LANE_GROUPS)) && g.SW2 >= 1 && g.SW2 <= 5 &&
-                  g.SH2 == g.SW2 && 2 * g.ftzero + 63 <= 255 && (int64_t)H * g.rowsz < (int64_t)0x7ff00000;
+                  g.SH2 == g.SW2 && (p.census || 2 * g.ftzero + 63 <= 255) && (int64_t)H * g.rowsz < (int64_t)0x7ff00000;
     // int16 pipeline, D <= 32: one thread per pixel (lanes spanning D would mostly idle; at D = 64 the wave-per-
     // chunk kernel is still ahead); the byte volume borrows the S buffer, unused before the paths
+    // (census: not read -- its int16 pipeline is always the byte costs + k_hsum_u8, at every D)
     p.pix_px = p.cn == 1 && g.D <= 32 && !(dbg & SGM_DBG_NO_LANE_GROUPS) && 2 * g.ftzero + 63 <= 255;
     p.GWc = g.D > 64 ? 64 : (g.D <= 16 ? 8 : (g.D <= 32 ? 16 : 32));  // lane-group width of k_box_u8
     // rows per band of k_box_u8 (a band re-reads 2 * SH2 rows above it; multiples of 16: the register rings): 96, less
@@ -864,8 +872,11 @@ static int ensure_plan_buffers(sgm_engine *e, const Plan &p, int H, int W)
     // frame, so none can leave the allocation.  (Not in the guarded mode: there the buffer ends where its mapping
     // ends, and the parity cases of tests/test_gpu_guard.py show that no load goes past the last record at all.)
     // (colour pairs: three records per pixel and 18 planes, k_features<3>)
+    // (census: one 8-byte descriptor per pixel and image -- the left ones fit lrec as it is, the right ones take 8 bytes
+    // per pixel of rplanes instead of 6; k_pix_census* read both with plain global loads, each behind an explicit test
+    // that its position lies inside the row: no scalar loads, no slack needed)
     if ((rc = e->lrec.ensure(npx * 8 * p.cn + (debug_alloc_mode() ? 0 : 64)))) return rc;
-    if ((rc = e->rplanes.ensure(npx * 6 * p.cn))) return rc;
+    if ((rc = e->rplanes.ensure(p.census ? npx * 8 : npx * 6 * p.cn))) return rc;
     if (vol) {
         // The byte pipeline keeps its per-pixel costs (V / 2) in the S buffer: they are dead when the block cost C is
         // complete, and no kernel writes S before that (the sweeps, the in-row paths and k_paths5_g all read C; in a batch
@@ -951,6 +962,23 @@ static void launch_pix(const Geom &g, const uint2 *lrec, const uint8_t *rpl, uin
     if (g.NP == 1) hipLaunchKernelGGL(k_pix<1>, grid, block, lds, st, g, lrec, rpl, px, COST_XL, nchunks, lrec_b, seg_l, 0);
     else if (g.NP == 2) hipLaunchKernelGGL(k_pix<2>, grid, block, lds, st, g, lrec, rpl, px, COST_XL, nchunks, lrec_b, seg_l, 0);
     else hipLaunchKernelGGL(k_pix<4>, grid, block, lds, st, g, lrec, rpl, px, COST_XL, nchunks, lrec_b, seg_l, 0);
+}
+
+// census: Hamming distances of the descriptors as bytes, where launch_pix puts its bytes.  D <= 32: one thread per pixel
+// (debug 4, "no lane groups": the wave form with idle lanes, for A/B timing -- tools/census_stages.py)
+static_assert(CENSUS_XL == COST_XL, "k_pix_census chunks are the cost stage's");
+static void launch_pix_census(const Geom &g, int dbg, const uint64_t *dl, const uint64_t *dr, uint8_t *px, hipStream_t st)
+{
+    if (g.D <= 32 && !(dbg & SGM_DBG_NO_LANE_GROUPS)) {
+        hipLaunchKernelGGL(k_pix_census_px, dim3((g.W1 + 255) / 256, g.H), dim3(256), (size_t)8 * (256 + g.D), st, g, dl, dr, px);
+        return;
+    }
+    const int nchunks = cost_chunks(g);
+    dim3 grid((unsigned)((int64_t)g.H * nchunks)), block(64);
+    if (g.NP == 1) hipLaunchKernelGGL(k_pix_census<1>, grid, block, 0, st, g, dl, dr, px, nchunks);
+    else if (g.NP == 2) hipLaunchKernelGGL(k_pix_census<2>, grid, block, 0, st, g, dl, dr, px, nchunks);
+    else if (g.NP == 4) hipLaunchKernelGGL(k_pix_census<4>, grid, block, 0, st, g, dl, dr, px, nchunks);
+    else hipLaunchKernelGGL(k_pix_census<8>, grid, block, 0, st, g, dl, dr, px, nchunks);
 }
 
 // box filter of the byte costs -> block cost C (k_box_u8), bands of p.RBb rows
@@ -1203,6 +1231,12 @@ static int ensure_aux(sgm_engine *e, bool second)
 static int stage_features(sgm_engine *e, const Plan &p, const uint8_t *d_left, const uint8_t *d_right, int64_t stride)
 {
     const Geom &g = e->g;
+    if (p.census)
+        return run_stage(e, "census", e->stream, [&] {
+            hipLaunchKernelGGL(k_census, dim3((g.W + 255) / 256, g.H, 2), dim3(256), 0, e->stream, d_left, d_right, stride, g.H, g.W,
+                               (uint64_t *)e->lrec.p, (uint64_t *)e->rplanes.p);
+            return 1;
+        });
     return run_stage(e, p.cn == 3 ? "features_c3" : "features", e->stream, [&] {
         hipLaunchKernelGGL(p.cn == 3 ? k_features<3> : k_features<1>, dim3((g.W + 255) / 256, g.H, 2), dim3(256), 0, e->stream,
                            d_left, d_right, stride, g.H, g.W, g.ftzero, (uint2 *)e->lrec.p, (uint8_t *)e->rplanes.p);
@@ -1224,6 +1258,25 @@ static int stage_cost(sgm_engine *e, const Plan &p)
     uint8_t *px = (uint8_t *)e->aggr.p;  // (the byte costs live in the S buffer until C is complete: ensure_plan_buffers)
     int16_t *C = (int16_t *)e->cost.p, *HS = (int16_t *)e->hsum.p;
     int rc;
+    if (p.census) {
+        // the bytes of k_pix_census*, then the box stages on the bytes: k_box_u8, or k_hsum_u8 + k_vsum* (blockSize 1 and
+        // above 11, D > 512, byte volumes from 2 GiB, debug 256); either commits the headroom word.  (k_hsum_px, which the
+        // BT pipeline runs for D <= 32, is one thread per PIXEL: at 4K D = 256 its 16-byte reads 256 bytes apart took
+        // 12.7 ms for this stage; k_hsum_u8's threads span the disparities.)
+        rc = run_stage(e, "cost_pix_census", st, [&] {
+            launch_pix_census(g, e->debug, (const uint64_t *)e->lrec.p, (const uint64_t *)e->rplanes.p, px, st);
+            return 1;
+        });
+        if (rc) return rc;
+        if (p.byte_cost) return run_stage(e, "cost_box", st, [&] { launch_box(g, p, px, C, st); return 1; });
+        rc = run_stage(e, "cost_hsum", st, [&] {
+            hipLaunchKernelGGL(k_hsum_u8, dim3((unsigned)(((int64_t)g.W1 * (g.D / 8) + 255) / 256), g.H), dim3(256), 0, st, g,
+                               (const uint8_t *)px, HS);
+            return 1;
+        });
+        if (rc) return rc;
+        return run_stage(e, "cost_vsum", st, [&] { launch_vsum(g, p, HS, C, st); return 1; });
+    }
     if (p.byte_cost) {
         if ((rc = run_stage(e, "cost_pix", st, [&] { launch_pix(g, lrec, rpl, px, st); return 1; }))) return rc;
         return run_stage(e, "cost_box", st, [&] { launch_box(g, p, px, C, st); return 1; });
@@ -1522,11 +1575,21 @@ static int stage_right_view(sgm_engine *e, const Plan &p, int16_t *d_rmap)
 
 // io.conf: SGM_OPT_CONFIDENCE only -- where this pair's final confidence map goes (null: the engine's own buffer)
 // io.rmap: SGM_OPT_RIGHT_VIEW only -- likewise for this pair's final right-view map
+// SGM_OPT_COST: the census cost is built for gray pairs (include/sgm_hip.h); asked at compute time, before anything is
+// allocated or enqueued, so the engine stays usable
+static int census_refused(const sgm_engine *e)
+{
+    if (e && e->cost_fn == SGM_COST_CENSUS && e->cn == 3)
+        return set_err(SGM_ERR_UNSUPPORTED, "SGM_OPT_COST = SGM_COST_CENSUS with SGM_OPT_CHANNELS = 3: the census cost takes single-channel images");
+    return SGM_OK;
+}
+
 static int run_compute(sgm_engine *e, const PairIO &io, int H, int W, int64_t stride, int phases = PH_ALL)
 {
     const uint8_t *d_left = (const uint8_t *)io.left, *d_right = (const uint8_t *)io.right;
     int16_t *d_disp = (int16_t *)io.disp_i16;
     if (!e || !d_left || !d_right || !d_disp) return set_err(SGM_ERR_INVALID_ARG, "null pointer");
+    if (census_refused(e)) return SGM_ERR_UNSUPPORTED;
     if (H <= 0 || W < 2 || stride < (int64_t)W * e->cn)
         return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld (channels %d)", H, W, (long long)stride, e->cn);
     if (W > 32767 || H > 32767) return set_err(SGM_ERR_UNSUPPORTED, "image larger than 32767 in a dimension");
@@ -1662,7 +1725,7 @@ int sgm_geometry(const sgm_params *params, int W, int *minX1, int *W1)
 // csrc/sgm_debug.h: the plan of one compute, read out on the host.  The options go through sgm_set_option into an engine
 // that is never handed out (it owns no stream and no buffer), then the very calls run_compute makes.
 static int debug_plan_on(const sgm_params *params, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
-                         int debug, int frames, int confidence, int right_view, sgm_debug_plan_t *out)
+                         int debug, int frames, int confidence, int right_view, int cost, sgm_debug_plan_t *out)
 {
     if (!params || !out) return set_err(SGM_ERR_INVALID_ARG, "params/out is null");
     if (H <= 0 || W < 2 || W > 32767 || H > 32767) return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d", H, W);
@@ -1672,7 +1735,8 @@ static int debug_plan_on(const sgm_params *params, int H, int W, int channels, i
     if ((rc = sgm_set_option(&e, SGM_OPT_CHANNELS, channels)) || (rc = sgm_set_option(&e, SGM_OPT_SCHEDULE, schedule)) ||
         (rc = sgm_set_option(&e, SGM_OPT_SWEEP_ROWS, sweep_rows)) || (rc = sgm_set_option(&e, SGM_OPT_PREPASS_ROWS, prepass_rows)) ||
         (rc = sgm_set_option(&e, SGM_OPT_DEBUG, debug)) || (rc = sgm_set_option(&e, SGM_OPT_CONFIDENCE, confidence)) ||
-        (rc = sgm_set_option(&e, SGM_OPT_RIGHT_VIEW, right_view)))
+        (rc = sgm_set_option(&e, SGM_OPT_RIGHT_VIEW, right_view)) || (rc = sgm_set_option(&e, SGM_OPT_COST, cost)) ||
+        (rc = census_refused(&e)))
         return rc;
     Geom g;
     if ((rc = normalise(&e.params, H, W, &g))) return rc;
@@ -1709,14 +1773,21 @@ static int debug_plan_on(const sgm_params *params, int H, int W, int channels, i
 int sgm_debug_plan(const sgm_params *params, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
                    int debug, int frames, sgm_debug_plan_t *out)
 {
-    return debug_plan_on(params, H, W, channels, schedule, sweep_rows, prepass_rows, debug, frames, 0, 0, out);
+    return debug_plan_on(params, H, W, channels, schedule, sweep_rows, prepass_rows, debug, frames, 0, 0, SGM_COST_BT, out);
 }
 
 // the same readout with the options that change the plan but came after sgm_debug_plan's signature was fixed
 int sgm_debug_plan_opts(const sgm_params *params, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
                         int debug, int frames, int confidence, int right_view, sgm_debug_plan_t *out)
 {
-    return debug_plan_on(params, H, W, channels, schedule, sweep_rows, prepass_rows, debug, frames, confidence, right_view, out);
+    return debug_plan_on(params, H, W, channels, schedule, sweep_rows, prepass_rows, debug, frames, confidence, right_view, SGM_COST_BT, out);
+}
+
+// ... and with SGM_OPT_COST (0 gives what sgm_debug_plan_opts gives; census with 3 channels: the error code of the compute)
+int sgm_debug_plan_cost(const sgm_params *params, int H, int W, int channels, int schedule, int sweep_rows, int prepass_rows,
+                        int debug, int frames, int confidence, int right_view, int cost, sgm_debug_plan_t *out)
+{
+    return debug_plan_on(params, H, W, channels, schedule, sweep_rows, prepass_rows, debug, frames, confidence, right_view, cost, out);
 }
 
 // csrc/sgm_debug.h: the split winner-take-all -- its threshold as the kernels compute it, whether a plan takes it, and what an
@@ -1875,6 +1946,11 @@ int sgm_set_option(sgm_engine *e, int option, int value)
         if (value != 1 && value != 3)
             return set_err(SGM_ERR_INVALID_ARG, "SGM_OPT_CHANNELS %d: only 1 and 3 interleaved 8-bit channels are supported", value);
         e->cn = value;
+    }
+    else if (option == SGM_OPT_COST) {
+        if (value != SGM_COST_BT && value != SGM_COST_CENSUS)
+            return set_err(SGM_ERR_INVALID_ARG, "SGM_OPT_COST %d: SGM_COST_BT (0) or SGM_COST_CENSUS (1)", value);
+        e->cost_fn = value;
     }
     else if (option == SGM_OPT_CONFIDENCE || option == SGM_OPT_RIGHT_VIEW) {
         SideMap &m = option == SGM_OPT_CONFIDENCE ? e->conf : e->right;
@@ -2180,6 +2256,7 @@ static void inherit_options(sgm_engine *q, const sgm_engine *e)
     q->chain_wgs = e->chain_wgs;
     q->prepass_rows = e->prepass_rows;
     q->cn = e->cn;
+    q->cost_fn = e->cost_fn;
     q->conf.on = e->conf.on;
     q->right.on = e->right.on;
     // e keeps S: its plan keeps the store of S, and the group runs ONE sweep kernel.  (Read before keep_aggr is cleared: the
@@ -2346,6 +2423,7 @@ static int batch_plan(sgm_engine *e, int N, int H, int W, Plan *pl, bool *joint)
 {
     if (H <= 0 || W < 2) return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d", H, W);
     if (W > 32767 || H > 32767) return set_err(SGM_ERR_UNSUPPORTED, "image larger than 32767 in a dimension");
+    if (census_refused(e)) return SGM_ERR_UNSUPPORTED;
     Geom g;
     int rc = normalise(&e->params, H, W, &g);
     if (rc) return rc;
@@ -2430,6 +2508,7 @@ int sgm_compute(sgm_engine *e, const uint8_t *left, const uint8_t *right, int H,
     const int64_t rowb = (int64_t)W * e->cn;  // bytes of one image row (SGM_OPT_CHANNELS)
     if (H <= 0 || W < 2 || stride_bytes < rowb)
         return set_err(SGM_ERR_INVALID_ARG, "bad shape H=%d W=%d stride=%lld (channels %d)", H, W, (long long)stride_bytes, e->cn);
+    if (census_refused(e)) return SGM_ERR_UNSUPPORTED;
     HIP_TRY(hipSetDevice(e->device));
     const size_t npx = (size_t)H * W, ib = (size_t)H * rowb;
     int rc;

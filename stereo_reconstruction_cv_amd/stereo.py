@@ -25,6 +25,10 @@ STEREO_SGBM_MODE_SGBM = 0
 STEREO_SGBM_MODE_HH = 1
 STEREO_SGBM_MODE_SGBM_3WAY = 2
 STEREO_SGBM_MODE_HH4 = 3
+# the matching cost (setCostFunction; no counterpart in cv2): OpenCV's prefilter + Birchfield-Tomasi, or the 9 x 7 census
+# transform with Hamming distance -- exactly invariant under strictly increasing intensity changes of either image
+STEREO_COST_BT = _lib.SGM_COST_BT
+STEREO_COST_CENSUS = _lib.SGM_COST_CENSUS
 CV_32F = 5
 
 
@@ -393,9 +397,10 @@ class StereoSGBM:
     """Mirror of cv2.StereoSGBM (the subset of the interface the reference exercises, plus the
     parameter getters/setters of the cv2 class)."""
 
-    def __init__(self, **kw):
+    def __init__(self, costFunction=STEREO_COST_BT, **kw):
         self._p = {n: 0 for n in _PARAM_NAMES}
         self._p.update(numDisparities=16, blockSize=3)
+        self.setCostFunction(costFunction)
         for k, v in kw.items():
             if k not in self._p:
                 raise TypeError(f"StereoSGBM_create() got an unexpected keyword argument '{k}'")
@@ -411,6 +416,28 @@ class StereoSGBM:
                     return lambda: self._p[field]
                 return lambda v: self._p.__setitem__(field, int(v))
         raise AttributeError(name)
+
+    def setCostFunction(self, costFunction):
+        """STEREO_COST_BT (default) or STEREO_COST_CENSUS: the matching cost of this object's compute(),
+        computeWithConfidence() and computeLeftRight() (SGM_OPT_COST, include/sgm_hip.h).  Census takes single-channel images."""
+        if isinstance(costFunction, bool) or not isinstance(costFunction, (int, np.integer)) or \
+                int(costFunction) not in (STEREO_COST_BT, STEREO_COST_CENSUS):
+            raise error(f"StereoSGBM.setCostFunction: {costFunction!r} is neither STEREO_COST_BT (0) nor STEREO_COST_CENSUS (1)")
+        self._cost = int(costFunction)
+
+    def getCostFunction(self):
+        return self._cost
+
+    def _engine(self, cn: int, device: int | None = None) -> Engine:
+        """The cached engine of these parameters, set to this object's cost function: the cache is keyed by the parameters
+        alone and shared between matcher objects, so the option is set before EVERY compute, to 0 as well as to 1, and the
+        callers set it back to STEREO_COST_BT behind the compute: other users of get_engine() (dist.py, pipeline.py) find the
+        engine as they always did."""
+        if self._cost == STEREO_COST_CENSUS and cn != 1:
+            raise error("StereoSGBM.compute: STEREO_COST_CENSUS takes 8-bit single-channel (H, W) images; a colour census is not implemented")
+        eng = get_engine(self._p, device)
+        eng.set_option(_lib.SGM_OPT_COST, self._cost)
+        return eng
 
     def compute(self, left, right):
         """int16 (H, W) disparity * 16, invalid = (minDisparity - 1) * 16  (main.ipynb:668).  left / right: uint8
@@ -461,13 +488,16 @@ class StereoSGBM:
             right = np.ascontiguousarray(right)
         if left.shape[1] < 2:
             raise error("StereoSGBM.compute: image width < 2")
-        eng = get_engine(self._p)
-        if not (with_right or with_conf):
-            return eng.compute_host(left, right)
-        opt, tap = (_lib.SGM_OPT_RIGHT_VIEW, _lib.SGM_TAP_RIGHT) if with_right else (_lib.SGM_OPT_CONFIDENCE, _lib.SGM_TAP_CONF)
-        with _option_for_this_call(eng, opt):
-            disp = eng.compute_host(left, right)
-            return disp, eng.tap(tap, *disp.shape)
+        eng = self._engine(cn)
+        try:
+            if not (with_right or with_conf):
+                return eng.compute_host(left, right)
+            opt, tap = (_lib.SGM_OPT_RIGHT_VIEW, _lib.SGM_TAP_RIGHT) if with_right else (_lib.SGM_OPT_CONFIDENCE, _lib.SGM_TAP_CONF)
+            with _option_for_this_call(eng, opt):
+                disp = eng.compute_host(left, right)
+                return disp, eng.tap(tap, *disp.shape)
+        finally:
+            eng.set_option(_lib.SGM_OPT_COST, STEREO_COST_BT)   # the cached engine goes back as get_engine() hands it out
 
     def _compute_torch(self, left, right, with_conf: bool = False, with_right: bool = False):
         import torch
@@ -483,19 +513,22 @@ class StereoSGBM:
         H, W = left.shape[:2]
         cn = 1 if left.dim() == 2 else 3
         dev = left.device.index or 0
-        eng = get_engine(self._p, dev)
-        out = torch.empty((H, W), dtype=torch.int16, device=left.device)
-        # the engine runs on its own stream: order it after torch's current stream and wait for it
-        torch.cuda.current_stream(left.device).synchronize()
-        if not (with_right or with_conf):
-            eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn)
-            eng.synchronize()
-            return out
-        side = torch.empty((H, W), dtype=torch.int16 if with_right else torch.uint8, device=left.device)
-        bound = dict(d_rmap=side.data_ptr()) if with_right else dict(d_conf=side.data_ptr())
-        with _option_for_this_call(eng, _lib.SGM_OPT_RIGHT_VIEW if with_right else _lib.SGM_OPT_CONFIDENCE):
-            eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn, **bound)
-            eng.synchronize()
+        eng = self._engine(cn, dev)
+        try:
+            out = torch.empty((H, W), dtype=torch.int16, device=left.device)
+            # the engine runs on its own stream: order it after torch's current stream and wait for it
+            torch.cuda.current_stream(left.device).synchronize()
+            if not (with_right or with_conf):
+                eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn)
+                eng.synchronize()
+                return out
+            side = torch.empty((H, W), dtype=torch.int16 if with_right else torch.uint8, device=left.device)
+            bound = dict(d_rmap=side.data_ptr()) if with_right else dict(d_conf=side.data_ptr())
+            with _option_for_this_call(eng, _lib.SGM_OPT_RIGHT_VIEW if with_right else _lib.SGM_OPT_CONFIDENCE):
+                eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn, **bound)
+                eng.synchronize()
+        finally:
+            eng.set_option(_lib.SGM_OPT_COST, STEREO_COST_BT)   # (as in _compute)
         return out, side
 
 
@@ -508,9 +541,10 @@ def _check_channels(ndim: int, cn: int) -> None:
 
 def StereoSGBM_create(minDisparity=0, numDisparities=16, blockSize=3, P1=0, P2=0, disp12MaxDiff=0,
                       preFilterCap=0, uniquenessRatio=0, speckleWindowSize=0, speckleRange=0,
-                      mode=STEREO_SGBM_MODE_SGBM) -> StereoSGBM:
-    """Same signature and defaults as cv2.StereoSGBM_create (OpenCV 4.11)."""
-    return StereoSGBM(minDisparity=minDisparity, numDisparities=numDisparities, blockSize=blockSize, P1=P1, P2=P2,
+                      mode=STEREO_SGBM_MODE_SGBM, costFunction=STEREO_COST_BT) -> StereoSGBM:
+    """Same signature and defaults as cv2.StereoSGBM_create (OpenCV 4.11), and one trailing keyword of this package's own:
+    costFunction, STEREO_COST_BT (default) or STEREO_COST_CENSUS (StereoSGBM.setCostFunction)."""
+    return StereoSGBM(costFunction=costFunction, minDisparity=minDisparity, numDisparities=numDisparities, blockSize=blockSize, P1=P1, P2=P2,
                       disp12MaxDiff=disp12MaxDiff, preFilterCap=preFilterCap, uniquenessRatio=uniquenessRatio,
                       speckleWindowSize=speckleWindowSize, speckleRange=speckleRange, mode=mode)
 
