@@ -141,6 +141,8 @@ def load():
     L.sgm_debug_wta_split.restype = i32
     L.sgm_debug_wta_raw_bytes.argtypes = [vp]
     L.sgm_debug_wta_raw_bytes.restype = C.c_longlong
+    L.sgm_debug_wta_select_n.argtypes = [i32, i32, vp, i32, vp]
+    L.sgm_debug_wta_select_n.restype = i32
     for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("sgm_abi_version", "sgm_device_count"):

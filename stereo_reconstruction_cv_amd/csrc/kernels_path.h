@@ -291,12 +291,19 @@ __device__ __forceinline__ void wta_pixel(const Pack<NP> &Sn, int lane, bool act
 // and leaves a 16-byte raw record per pixel; the decisions (uniqueness, rejection) are taken by k_wta_select (kernels_post.h),
 // one thread per pixel, which writes the record k_wta_t writes.
 //
-//   raw record: { key = minS << 16 | first best d,  nb = S[max(best-1, 0)] | S[min(best+1, D-1)] << 16,  nq,  0 }
+//   raw record: { minS << 16 | nq << 6 | ln,  w0,  w1,  pv >> 16 | nx << 16 }
+//
+// ln (6 bits) = the first lane that holds a minimum of S; lane l holds d = 2 NP l .. 2 NP l + 2 NP - 1 in the halves of its
+// NP registers, so the first best d lies in lane ln.  w0, w1 = that lane's registers as they are (w1 = 0 for NP = 1),
+// pv = the last register of lane ln - 1, nx = the first register of lane ln + 1: their facing halves are S[2 NP ln - 1] and
+// S[2 NP (ln + 1)].  (At the wave's ends the lane index wraps; what is read there is never used.)  nq <= 256 takes 9 bits.
+// Which half of w0 / w1 is the best, and which halves are its neighbours, selects a 16-bit value out of words the scalar
+// unit holds: work that does not need the wave, so it is k_wta_select's (wta_select_words below), not the sweep's.
 //
 // Uniqueness as a COUNT.  Upstream rejects iff some d with |d - best| > 1 has S[d] * wgt < thr, wgt = 100 - uniquenessRatio in
 // 1 .. 100, thr = 100 * minS.  With T1 = ceil(thr / wgt) (= floor((thr - 1) / wgt) + 1 for thr >= 1, and 0 for thr = 0, where no d
 // qualifies) S * wgt < thr <=> S < T1.  The sweep counts nq = #{d : S[d] < T1}; k_wta_select counts how many of S[best-1],
-// S[best], S[best+1] (inside [0, D)) are below T1 from the three values the record holds and rejects iff nq is larger.
+// S[best], S[best+1] (inside [0, D)) are below T1 from the words the record holds and rejects iff nq is larger.
 // T1 comes from an integer reciprocal: n = thr + wgt - 1 < 2^22, rcp = ceil(2^29 / wgt), T1 = (8 n * rcp) >> 32 -- the error of
 // rcp adds less than 2^22 / 2^29 = 1/128 to n / wgt, whose fractional part is at most 1 - 1/100: exact (tests/
 // test_wta_split_reference.py checks every minS and ratio).  No division and no per-element product in the sweep.
@@ -320,6 +327,37 @@ __host__ __device__ inline uint32_t uniq_t1_clamped(uint32_t minS, UniqRecip q)
     return t < 0x8000u ? t : 0x8000u;
 }
 
+// The deciding half, on one raw record {r0, w0, w1, w3} of a pixel with D = 128 NP disparities (NP = 1, 2): the record
+// {reject ? ~0 : (minS << 16 | first best d), S[max(best-1, 0)] | S[min(best+1, D-1)] << 16} that k_wta_t writes.  The halves of
+// w0 (and w1) in d order are S[2 NP ln + k], k = 0 .. 2 NP - 1; the first of them equal to minS is the best.  Its neighbours
+// are the halves beside it, or the low / high half of w3 where they lie in the lane below / above.  At d = 0 and d = D - 1
+// the clamped neighbour is S[best] itself.  `near` = how many of S[best-1], S[best], S[best+1] inside [0, D) lie below T1,
+// nq = how many of all D values do: some d outside best-1 .. best+1 passes upstream's uniqueness test, and the pixel is
+// rejected, iff nq > near.  Host and device: k_wta_select runs it per pixel, sgm_debug_wta_select_n over records of a test.
+__host__ __device__ inline void wta_select_words(int NP, UniqRecip q, uint32_t r0, uint32_t w0, uint32_t w1, uint32_t w3,
+                                                 uint32_t &key, uint32_t &nb)
+{
+    const uint32_t minS = r0 >> 16, nq = (r0 >> 6) & 0x1ffu, ln = r0 & 63u;
+    const uint32_t nh = 2u * (uint32_t)NP, D = 64u * nh;
+    const uint64_t w = NP == 2 ? ((uint64_t)w1 << 32) | w0 : (uint64_t)w0;   // the lane's halves, S[2 NP ln] in bits 0-15
+    // (a record of the sweep always has a half equal to minS in lane ln's words; for any other words -- the debug export takes
+    //  what it is given -- the search ends on the lane's last half, and ln, nq are taken as they come: no index leaves [0, D))
+    uint32_t k = 0;
+    while (k + 1u < nh && (uint32_t)(w >> (16u * k) & 0xffffu) != minS) k++;
+    const uint32_t best = ln * nh + k;
+    uint32_t sm = k > 0u ? (uint32_t)(w >> (16u * (k - 1u)) & 0xffffu) : (w3 & 0xffffu);
+    uint32_t sp = k + 1u < nh ? (uint32_t)(w >> (16u * (k + 1u)) & 0xffffu) : (w3 >> 16);
+    if (best == 0u) sm = minS;
+    if (best + 1u == D) sp = minS;
+    const uint32_t t1 = uniq_t1_clamped(minS, q);
+    uint32_t near = minS < t1 ? 1u : 0u;
+    if (best > 0u && sm < t1) near++;
+    if (best + 1u < D && sp < t1) near++;
+    const bool reject = nq > near || minS == 32767u;   // all costs saturated: upstream keeps bestDisp = -1
+    key = reject ? 0xffffffffu : (minS << 16) | best;
+    nb = sm | (sp << 16);
+}
+
 // index of the first set bit of a lane mask, -1 for an empty one (the builtin count is undefined there)
 __device__ __forceinline__ uint32_t mask_first(uint64_t m)
 {
@@ -327,32 +365,12 @@ __device__ __forceinline__ uint32_t mask_first(uint64_t m)
     asm("s_ff1_i32_b64 %0, %1" : "=s"(r) : "s"(m));
     return r;
 }
-// min(a, b) on the scalar unit (both wave-uniform).  Written as asm for the reason smax_u32 is (sgm_device.h): left to the
-// compiler a chain of such minima turns into v_mov_b32 + v_min3_u32 + v_readfirstlane in the vector stream.
-__device__ __forceinline__ uint32_t smin_u32(uint32_t a, uint32_t b)
-{
-    uint32_t r;
-    asm("s_min_u32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc");
-    return r;
-}
-// S[d] of a full wave's pixel (d wave-uniform): one v_readlane per register of the lane that holds d, the rest on the scalar unit
-template <int NP> __device__ __forceinline__ uint32_t wave_pick(const Pack<NP> &S, uint32_t d)
+// The reductions of N = PPS pixels of a step (full waves only; their minima share one fold chain).  rec[n] = pixel n's raw
+// record, wave-uniform.
+template <int NP, int N>
+__device__ __forceinline__ void wta_reduce_pixels(const Pack<NP> (&Sn)[N], UniqRecip q, uint32_t (&rec)[N][4])
 {
     static_assert(NP == 1 || NP == 2, "split winner-take-all: D = 128 and D = 256");
-    const uint32_t ln = d / (2 * NP);
-    uint32_t w = __builtin_amdgcn_readlane(S.r[0], ln);
-    if constexpr (NP == 2) {
-        const uint32_t w1 = __builtin_amdgcn_readlane(S.r[1], ln);
-        w = (d & 2u) ? w1 : w;
-    }
-    return (w >> ((d & 1u) * 16u)) & 0xffffu;
-}
-// The reductions of N = PPS pixels of a step (full waves only; their minima share one fold chain).  rec[n] = the first
-// three words of pixel n's raw record, wave-uniform.
-template <int NP, int N>
-__device__ __forceinline__ void wta_reduce_pixels(const Pack<NP> (&Sn)[N], UniqRecip q, uint32_t (&rec)[N][3])
-{
-    constexpr int D = 128 * NP;  // full waves
     static_assert(N == 2 || N == 4, "pixels per lockstep step of NP = 2 / NP = 1");
     uint32_t r[N], ms[N], rows;
 #pragma unroll
@@ -368,24 +386,27 @@ __device__ __forceinline__ void wta_reduce_pixels(const Pack<NP> (&Sn)[N], UniqR
     for (int n = 0; n < N; n++) {
         const uint32_t m = ms[n] & 0xffffu;
         const uint32_t t1 = uniq_t1_clamped(m, q);
-        const uint32_t t1s = t1 | (t1 << 16);
-        uint32_t best = 0xffffffffu, nq = 0;
+        // the first lane with a minimum: a half of its own packed minimum equals the wave's.  The lowest lane holds the lowest
+        // d, so ties go where the (S << 16) | d key sends them.  Never an empty mask.  (Here and below the halves are compared
+        // with the scalar as they are -- 16-bit operand selects of the compare, no packed subtraction in front of it.)
+        const uint64_t z = __builtin_amdgcn_ballot_w64((uint16_t)r[n] == (uint16_t)m) | __builtin_amdgcn_ballot_w64((uint16_t)(r[n] >> 16) == (uint16_t)m);
+        const uint32_t ln = mask_first(z);
+        uint32_t nq = 0;
 #pragma unroll
         for (int i = 0; i < NP; i++) {
-            // zero exactly in the halves that hold the minimum / non-zero exactly in the halves below T1
-            const uint32_t x = pk_sub(Sn[n].r[i], ms[n]);
-            const uint32_t y = pk_subs_u(t1s, Sn[n].r[i]);
-            // (both halves as 16-bit compares against zero -- SDWA operand selects, no constant held in a scalar register)
-            const uint64_t zlo = __builtin_amdgcn_ballot_w64((uint16_t)x == 0), zhi = __builtin_amdgcn_ballot_w64((uint16_t)(x >> 16) == 0);
-            const uint64_t qlo = __builtin_amdgcn_ballot_w64((uint16_t)y != 0), qhi = __builtin_amdgcn_ballot_w64((uint16_t)(y >> 16) != 0);
-            // d = 2 (NP lane + i) + half; an empty mask gives a huge value; ties go to the lowest d, like the (S << 16) | d key
-            best = smin_u32(best, smin_u32(mask_first(zlo) * (2 * NP) + 2 * i, mask_first(zhi) * (2 * NP) + 2 * i + 1));
+            // the halves below T1 (unsigned: T1 = 0x8000 admits every S)
+            const uint32_t v = Sn[n].r[i];
+            const uint64_t qlo = __builtin_amdgcn_ballot_w64((uint16_t)v < (uint16_t)t1), qhi = __builtin_amdgcn_ballot_w64((uint16_t)(v >> 16) < (uint16_t)t1);
             nq += (uint32_t)__builtin_popcountll(qlo) + (uint32_t)__builtin_popcountll(qhi);
         }
-        const uint32_t dm = (uint32_t)max((int)best - 1, 0), dp = (uint32_t)min((int)best + 1, D - 1);
-        rec[n][0] = (m << 16) | best;
-        rec[n][1] = wave_pick<NP>(Sn[n], dm) | (wave_pick<NP>(Sn[n], dp) << 16);
-        rec[n][2] = nq;
+        // (the `& 63` costs nothing: the compiler takes v_readlane's lane select as modulo 64 and emits s_add_i32 ln, 63 / ln, 1
+        //  with no s_and behind it -- the block is the same with and without the mask in the source, which states the wrap)
+        const uint32_t pv = __builtin_amdgcn_readlane(Sn[n].r[NP - 1], (ln - 1u) & 63u);
+        const uint32_t nx = __builtin_amdgcn_readlane(Sn[n].r[0], (ln + 1u) & 63u);
+        rec[n][0] = (m << 16) | (nq << 6) | ln;
+        rec[n][1] = __builtin_amdgcn_readlane(Sn[n].r[0], ln);
+        rec[n][2] = NP == 2 ? __builtin_amdgcn_readlane(Sn[n].r[NP - 1], ln) : 0u;
+        rec[n][3] = (pv >> 16) | (nx << 16);
     }
 }
 

@@ -134,22 +134,18 @@ __global__ __launch_bounds__(64) void k_wta_conf_t(Geom g, const int16_t *__rest
 
 // ------------------------------------------------------------------------------------------
 // The deciding half of the split winner-take-all (kernels_path.h: wta_reduce_pixels did the lane reductions inside the chained
-// second sweep).  One thread per matched pixel: raw = {minS << 16 | best, S[best-1] | S[best+1] << 16 (clamped at 0 / D-1), nq};
-// `near` = how many of S[best-1], S[best], S[best+1] inside [0, D) lie below T1, nq = how many of all D values do: some d
-// outside best-1 .. best+1 passes upstream's uniqueness test, and the pixel is rejected, iff nq > near.  Writes k_wta_t's record.
+// second sweep).  One thread per matched pixel: raw = {minS << 16 | nq << 6 | ln, w0, w1, pv >> 16 | nx << 16}, the words of the
+// first lane that holds a minimum and the facing halves of its neighbours' (layout: kernels_path.h).  wta_select_words finds
+// the best d and its clamped neighbours among them and takes the uniqueness decision.  Writes k_wta_t's record.
 __global__ __launch_bounds__(256) void k_wta_select(Geom g, const uint4 *__restrict__ raw, uint2 *__restrict__ wta, UniqRecip q)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= g.W1) return;
     const int64_t i = (int64_t)y * g.W + g.minX1 + x;
     const uint4 r = raw[i];
-    const uint32_t minS = r.x >> 16, best = r.x & 0xffffu;
-    const uint32_t t1 = uniq_t1_clamped(minS, q);
-    uint32_t near = minS < t1 ? 1u : 0u;
-    if (best > 0u && (r.y & 0xffffu) < t1) near++;
-    if (best + 1u < (uint32_t)g.D && (r.y >> 16) < t1) near++;
-    const bool reject = r.z > near || minS == (uint32_t)SGM_MAX_COST;
-    wta[i] = make_uint2(reject ? 0xffffffffu : r.x, r.y);
+    uint2 o;
+    wta_select_words(g.D / 128, q, r.x, r.y, r.z, r.w, o.x, o.y);
+    wta[i] = o;
 }
 
 // conf = conf_raw where the final disparity (after LR check, median and speckle filter) is valid, 0 where it is the

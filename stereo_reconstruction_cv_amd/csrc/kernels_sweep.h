@@ -26,7 +26,8 @@
 namespace sgm {
 
 // SWEEP_REDUCE (k_sweep_chain only): the second pass of MODE_HH without the store of S -- the lane reductions of the
-// winner-take-all on the S it holds in registers, one 16-byte raw record per pixel (kernels_path.h: wta_reduce_pixels)
+// winner-take-all on the S it holds in registers, one 16-byte raw record per pixel: the minimum, the count below the uniqueness
+// threshold, the first lane with a minimum and that lane's and its neighbours' words (kernels_path.h: wta_reduce_pixels)
 enum { SWEEP_FIRST = 0, SWEEP_ACCUM = 1, SWEEP_LAST = 2, SWEEP_REDUCE = 3 };
 
 struct SweepArgs {
@@ -571,7 +572,7 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
                         for (int p = 0; p < PPS; p++)
                             if (k0 + u0 + p >= W1) Sn[p].fill(0u);  // (a pixel past the row's end: reduced with the others, never stored)
                     }
-                    uint32_t rec[PPS][3];
+                    uint32_t rec[PPS][4];
                     wta_reduce_pixels<NP, PPS>(Sn, rr.uq, rec);
                     // The step's PPS records lie side by side (the second pass walks x downwards: pixel p of the step sits
                     // PPS - 1 - p records above the step's lowest address): ONE scalar offset per step and 2 PPS per-lane
@@ -584,7 +585,7 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
                         lo.r[0] = rec[p][0];
                         lo.r[1] = rec[p][1];
                         hi.r[0] = rec[p][2];
-                        hi.r[1] = 0u;
+                        hi.r[1] = rec[p][3];
                         // as in wta_pixels: what is stored sits in registers of its own ("masked writes after wide stores")
                         asm volatile("" : "+v"(lo.r[0]), "+v"(lo.r[1]), "+v"(hi.r[0]), "+v"(hi.r[1]));
                         if constexpr (FULL) {

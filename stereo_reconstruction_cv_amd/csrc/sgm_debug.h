@@ -70,7 +70,10 @@ int sgm_debug_plan_cost(const sgm_params *p, int H, int W, int channels, int sch
  *   reciprocal (before they clamp it to 0x8000); -1 outside minS 0 .. 32767, uniquenessRatio 0 .. 99.
  * sgm_debug_wta_split: 1 if one compute of an H x W frame with these options takes the split form (Plan::wta_split), else 0
  *   (negative: an error code).
- * sgm_debug_wta_raw_bytes: bytes of raw-record buffers that e and the engines of its chained group hold. */
+ * sgm_debug_wta_raw_bytes: bytes of raw-record buffers that e and the engines of its chained group hold.
+ * sgm_debug_wta_select_n: the deciding half on the host -- the function k_wta_select runs per pixel (kernels_path.h:
+ *   wta_select_words), over n raw records of four words each; writes the two words of k_wta_t's record per pixel.  An error
+ *   code for D outside {128, 256} or uniquenessRatio outside 0 .. 99. */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -78,6 +81,7 @@ int sgm_debug_uniq_threshold(int minS, int uniquenessRatio);
 int sgm_debug_wta_split(const sgm_params *p, int H, int W, int schedule, int sweep_rows, int debug, int confidence, int right_view,
                         int keep_aggr);
 long long sgm_debug_wta_raw_bytes(const sgm_engine *e);
+int sgm_debug_wta_select_n(int D, int uniquenessRatio, const uint32_t *raw /* n x 4 */, int n, uint32_t *wta /* n x 2 */);
 #ifdef __cplusplus
 }
 #endif

@@ -1813,6 +1813,15 @@ int sgm_debug_wta_split(const sgm_params *params, int H, int W, int schedule, in
     if ((rc = normalise(&e.params, H, W, &g))) return rc;
     return make_plan(&e, g, H).wta_split ? 1 : 0;
 }
+int sgm_debug_wta_select_n(int D, int uniquenessRatio, const uint32_t *raw, int n, uint32_t *wta)
+{
+    if (D != 128 && D != 256) return set_err(SGM_ERR_INVALID_ARG, "split winner-take-all: D = 128 or 256, not %d", D);
+    if (uniquenessRatio < 0 || uniquenessRatio > 99) return set_err(SGM_ERR_INVALID_ARG, "uniquenessRatio %d outside 0..99", uniquenessRatio);
+    if (n < 0 || (n > 0 && (!raw || !wta))) return set_err(SGM_ERR_INVALID_ARG, "raw/wta is null or n < 0");
+    const UniqRecip q = uniq_recip(uniquenessRatio);
+    for (int i = 0; i < n; i++) wta_select_words(D / 128, q, raw[4 * i], raw[4 * i + 1], raw[4 * i + 2], raw[4 * i + 3], wta[2 * i], wta[2 * i + 1]);
+    return SGM_OK;
+}
 long long sgm_debug_wta_raw_bytes(const sgm_engine *e)
 {
     if (!e) return -1;
