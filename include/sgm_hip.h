@@ -53,7 +53,8 @@ extern "C" {
                              * 4: sgm_check, sgm_trim, sgm_compact_points_device_async, SGM_OPT_GROUP_MAX (round 4);
                              * additive since, version unchanged: SGM_OPT_CHANNELS; mode 3; SGM_OPT_CONFIDENCE, SGM_TAP_CONF_RAW,
                              * SGM_TAP_CONF, sgm_bind_confidence_device (sgm_hip_confidence.h); SGM_OPT_RIGHT_VIEW, SGM_TAP_RIGHT_RAW,
-                             * SGM_TAP_RIGHT, sgm_bind_right_device (sgm_hip_right.h); SGM_OPT_COST, SGM_COST_BT, SGM_COST_CENSUS */
+                             * SGM_TAP_RIGHT, sgm_bind_right_device (sgm_hip_right.h); SGM_OPT_COST, SGM_COST_BT, SGM_COST_CENSUS;
+                             * the disparity post-filter of sgm_hip_wls.h */
 
 typedef enum {
     SGM_OK = 0,
@@ -303,4 +304,7 @@ int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_r
 #include "sgm_hip_confidence.h"
 /* likewise for SGM_OPT_RIGHT_VIEW: sgm_bind_right_device */
 #include "sgm_hip_right.h"
+/* the edge-aware disparity post-filter, a stage of its own behind any of the maps above: sgm_wls_weights, sgm_wls_filter,
+ * sgm_wls_filter_device */
+#include "sgm_hip_wls.h"
 #endif

@@ -11,6 +11,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +28,7 @@
 #include "kernels_sweep.h"
 #include "kernels_group.h"
 #include "kernels_right.h"
+#include "kernels_wls.h"
 
 using namespace sgm;
 
@@ -256,6 +258,7 @@ struct Plan {
     BUF(f32) BUF(xyz) BUF(mask) BUF(minkey)      /* host-pointer post stages */ \
     BUF(rmap1) BUF(rmap2) BUF(rsrc) BUF(rdst)    /* host-pointer rectification stages */ \
     BUF(ccount) BUF(cpts) BUF(crgb) BUF(crgb_in) /* point compaction */ \
+    BUF(wls_u) BUF(wls_v) BUF(wls_c)             /* sgm_wls_filter: float [H][W] planes u, v, c' (kernels_wls.h); sgm_trim releases these three by name */ \
     BUF(headroom)                                /* uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r */ \
     BUF(chain_ctl) BUF(chain_err)                /* chained sweeps: ticket + progress words (zeroed before every launch); sticky give-up flag */ \
     ARR(io, [2][5])                              /* sgm_compute_batch, throughput mode: the transfer slots (sgm_engine says what they hold) */
@@ -2027,6 +2030,7 @@ int sgm_trim(sgm_engine *e)
     e->pin_disp.release();
     for (auto &slot : e->pin_io)
         for (HostBuf &b : slot) b.release();
+    for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c}) (void)b->release();   // the filter's planes come back on its next call
     return check_chain(e);
 }
 
@@ -2863,6 +2867,103 @@ int sgm_median3x3(sgm_engine *e, const int16_t *src, int H, int W, int16_t *dst)
                        (int16_t *)e->disp_med.p, (int16_t *)nullptr, H, W);
     KCHECK();
     HIP_TRY(hipMemcpyAsync(dst, e->disp_med.p, npx * 2, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SGM_OK;
+}
+
+// ---- the edge-aware disparity filter (include/sgm_hip_wls.h, kernels_wls.h) -----------------------------------------------
+int sgm_wls_weights(double sigma, float lut[256])
+{
+    if (!lut || !std::isfinite(sigma) || sigma <= 0.0) return set_err(SGM_ERR_INVALID_ARG, "sgm_wls_weights: null table or sigma %g not a positive finite number", sigma);
+    for (int k = 0; k < 256; k++) lut[k] = (float)exp(-(double)k / sigma);
+    return SGM_OK;
+}
+
+static int wls_check_args(const sgm_engine *e, const void *disp, const void *guide, int cn, int H, int W, int invalid, double lambda,
+                          const float *lut, const void *out)
+{
+    if (!e || !disp || !guide || !lut || !out) return set_err(SGM_ERR_INVALID_ARG, "sgm_wls_filter: null pointer");
+    if (H <= 0 || W <= 0) return set_err(SGM_ERR_INVALID_ARG, "sgm_wls_filter: bad shape H=%d W=%d", H, W);
+    if (cn != 1 && cn != 3) return set_err(SGM_ERR_INVALID_ARG, "sgm_wls_filter: guide with %d channels (1 or 3)", cn);
+    if (!std::isfinite(lambda) || lambda < 0.0 || lambda > 1e7) return set_err(SGM_ERR_INVALID_ARG, "sgm_wls_filter: lambda %g outside [0, 1e7]", lambda);
+    if (invalid < -32768 || invalid > 32767) return set_err(SGM_ERR_INVALID_ARG, "sgm_wls_filter: invalid value %d outside int16", invalid);
+    return SGM_OK;
+}
+
+// arguments checked; everything a device pointer but lut.  Enqueues init, three times (rows, columns), final.
+static int run_wls(sgm_engine *e, const int16_t *d_disp, const uint8_t *d_guide, int cn, const uint8_t *d_conf, int H, int W, int invalid,
+                   double lambda, const float *lut, int16_t *d_out, float *d_out_f32)
+{
+    const int64_t npx = (int64_t)H * W;
+    int rc;
+    if ((rc = e->wls_u.ensure((size_t)npx * 4)) || (rc = e->wls_v.ensure((size_t)npx * 4)) || (rc = e->wls_c.ensure((size_t)npx * 4))) return rc;
+    float *u = (float *)e->wls_u.p, *v = (float *)e->wls_v.p, *c = (float *)e->wls_c.p;
+    WlsLut t;
+    memcpy(t.w, lut, sizeof(t.w));
+    const dim3 px((unsigned)((npx + 255) / 256));
+    if (e->profile) {   // the stage record is the filter's from here on (one stage name per kernel)
+        e->nstages = 0;
+        e->nevents = 0;
+        e->last_end_ev = -1;
+    }
+    if ((rc = stage_begin(e, "wls_init"))) return rc;
+    hipLaunchKernelGGL(k_wls_init, px, dim3(256), 0, e->stream, d_disp, d_conf, invalid, npx, u, v);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    const int T = 3;
+    for (int it = 1; it <= T; it++) {
+        const float lam = (float)(1.5 * lambda * (double)(1 << (2 * (T - it))) / (double)((1 << (2 * T)) - 1));
+        if (W > 1) {   // (a line of one element is the identity)
+            const dim3 grid((H + WLS_T - 1) / WLS_T);
+            if ((rc = stage_begin(e, "wls_rows"))) return rc;
+            if (cn == 3) hipLaunchKernelGGL(k_wls_rows<3>, grid, dim3(WLS_RT), 0, e->stream, u, v, c, d_guide, t, lam, H, W);
+            else hipLaunchKernelGGL(k_wls_rows<1>, grid, dim3(WLS_RT), 0, e->stream, u, v, c, d_guide, t, lam, H, W);
+            KCHECK();
+            if ((rc = stage_end(e, 1))) return rc;
+        }
+        if (H > 1) {
+            const dim3 grid((W + WLS_T - 1) / WLS_T);
+            if ((rc = stage_begin(e, "wls_cols"))) return rc;
+            if (cn == 3) hipLaunchKernelGGL(k_wls_cols<3>, grid, dim3(WLS_T), 0, e->stream, u, v, c, d_guide, t, lam, H, W);
+            else hipLaunchKernelGGL(k_wls_cols<1>, grid, dim3(WLS_T), 0, e->stream, u, v, c, d_guide, t, lam, H, W);
+            KCHECK();
+            if ((rc = stage_end(e, 1))) return rc;
+        }
+    }
+    if ((rc = stage_begin(e, "wls_final"))) return rc;
+    hipLaunchKernelGGL(k_wls_final, px, dim3(256), 0, e->stream, (const float *)u, (const float *)v, invalid, npx, d_out, d_out_f32);
+    KCHECK();
+    return stage_end(e, 1);
+}
+
+int sgm_wls_filter_device(sgm_engine *e, const void *d_disp_i16, const void *d_guide_u8, int cn, const void *d_conf_u8, int H, int W,
+                          int invalid, double lambda, const float lut[256], void *d_out_i16, void *d_out_f32)
+{
+    if (int rc = wls_check_args(e, d_disp_i16, d_guide_u8, cn, H, W, invalid, lambda, lut, d_out_i16)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    return run_wls(e, (const int16_t *)d_disp_i16, (const uint8_t *)d_guide_u8, cn, (const uint8_t *)d_conf_u8, H, W, invalid, lambda, lut,
+                   (int16_t *)d_out_i16, (float *)d_out_f32);
+}
+
+int sgm_wls_filter(sgm_engine *e, const int16_t *disp, const uint8_t *guide, int cn, const uint8_t *conf, int H, int W, int invalid,
+                   double lambda, const float lut[256], int16_t *out, float *out_f32)
+{
+    if (int rc = wls_check_args(e, disp, guide, cn, H, W, invalid, lambda, lut, out)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t npx = (size_t)H * W;
+    int rc;
+    // staging: the map in disp_out (filtered in place), the guide in in_left, the confidence in in_right, the float map in f32
+    if ((rc = e->disp_out.ensure(npx * 2)) || (rc = e->in_left.ensure(npx * cn)) || (conf && (rc = e->in_right.ensure(npx))) ||
+        (out_f32 && (rc = e->f32.ensure(npx * 4))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(e->disp_out.p, disp, npx * 2, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->in_left.p, guide, npx * cn, hipMemcpyHostToDevice, e->stream));
+    if (conf) HIP_TRY(hipMemcpyAsync(e->in_right.p, conf, npx, hipMemcpyHostToDevice, e->stream));
+    if ((rc = run_wls(e, (const int16_t *)e->disp_out.p, (const uint8_t *)e->in_left.p, cn, conf ? (const uint8_t *)e->in_right.p : nullptr, H, W,
+                      invalid, lambda, lut, (int16_t *)e->disp_out.p, out_f32 ? (float *)e->f32.p : nullptr)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out, e->disp_out.p, npx * 2, hipMemcpyDeviceToHost, e->stream));
+    if (out_f32) HIP_TRY(hipMemcpyAsync(out_f32, e->f32.p, npx * 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return SGM_OK;
 }

@@ -354,6 +354,30 @@ class Engine:
     def valid_mask_device(self, d_xyz: int, d_disp: int, n: int, d_mask: int) -> None:
         _check(self._L.sgm_valid_mask_device(self._h, d_xyz, d_disp, n, d_mask))
 
+    # -- the edge-aware disparity filter (include/sgm_hip_wls.h) --
+    def wls_filter_host(self, disp: np.ndarray, guide: np.ndarray, conf: np.ndarray | None, invalid: int, lambda_: float,
+                        lut: np.ndarray, return_float: bool = False):
+        """sgm_wls_filter: int16 (H, W) map, uint8 (H, W) or (H, W, 3) guide, uint8 (H, W) confidence or None, the 256 float32
+        edge weights; returns the filtered int16 map, or (map, float32 map in pixels) with return_float."""
+        disp = np.ascontiguousarray(disp, np.int16)
+        guide = np.ascontiguousarray(guide, np.uint8)
+        conf = None if conf is None else np.ascontiguousarray(conf, np.uint8)
+        lut = np.ascontiguousarray(lut, np.float32)
+        H, W = disp.shape
+        out = np.empty((H, W), np.int16)
+        outf = np.empty((H, W), np.float32) if return_float else None
+        _check(self._L.sgm_wls_filter(self._h, disp.ctypes.data, guide.ctypes.data, 1 if guide.ndim == 2 else guide.shape[2],
+                                      None if conf is None else conf.ctypes.data, H, W, int(invalid), float(lambda_),
+                                      lut.ctypes.data, out.ctypes.data, None if outf is None else outf.ctypes.data))
+        return (out, outf) if return_float else out
+
+    def wls_filter_device(self, d_disp: int, d_guide: int, cn: int, d_conf: int | None, H: int, W: int, invalid: int,
+                          lambda_: float, lut: np.ndarray, d_out: int, d_out_f32: int | None = None) -> None:
+        """sgm_wls_filter_device: device addresses (lut stays a host array), in the order of the engine's stream."""
+        lut = np.ascontiguousarray(lut, np.float32)
+        _check(self._L.sgm_wls_filter_device(self._h, d_disp, d_guide, int(cn), d_conf, H, W, int(invalid), float(lambda_),
+                                             lut.ctypes.data, d_out, d_out_f32))
+
 
 # The notebook builds a matcher per call and throws it away (main.ipynb:655-668); engines are
 # cached per (parameters, device) so device buffers survive between such calls.
@@ -463,6 +487,20 @@ class StereoSGBM:
         aggregates the paths again on the swapped pair; here they are the left view's."""
         return self._compute(left, right, False, True)
 
+    def computeFiltered(self, left, right, lambda_=8000.0, sigmaColor=1.5):
+        """computeWithConfidence() followed by the edge-aware filter (createDisparityWLSFilter) with `left` as the guide and the
+        confidence map as its weights: int16 (H, W) disparity * 16 with the holes filled from confident neighbours, invalid
+        (minDisparity - 1) * 16 only where no confidence reaches.  Colour pairs guide with all three channels.  numpy in, numpy
+        out; HIP tensors in, a tensor out without leaving the device."""
+        disp, conf = self.computeWithConfidence(left, right)
+        f = DisparityWLSFilter(self)
+        f.setLambda(lambda_)
+        f.setSigmaColor(sigmaColor)
+        guide = left if _is_torch(left) else np.asarray(left)
+        if len(guide.shape) == 3 and guide.shape[2] == 1:
+            guide = guide[:, :, 0]
+        return f.filter(disp, guide, conf)
+
     def _compute(self, left, right, with_conf: bool, with_right: bool = False):
         if self._p["mode"] not in (STEREO_SGBM_MODE_SGBM, STEREO_SGBM_MODE_HH, STEREO_SGBM_MODE_HH4):
             raise error("StereoSGBM.compute: MODE_SGBM, MODE_HH and MODE_HH4 are implemented; MODE_SGBM_3WAY is not "
@@ -549,6 +587,102 @@ def StereoSGBM_create(minDisparity=0, numDisparities=16, blockSize=3, P1=0, P2=0
                       speckleWindowSize=speckleWindowSize, speckleRange=speckleRange, mode=mode)
 
 
+
+
+def wls_weights(sigma: float) -> np.ndarray:
+    """The filter's default edge weights (sgm_wls_weights): float32 [256], exp(-k / sigma).  Needs no GPU."""
+    lut = np.empty(256, np.float32)
+    _check(_lib.load().sgm_wls_weights(float(sigma), lut.ctypes.data))
+    return lut
+
+
+class DisparityWLSFilter:
+    """The place cv2.ximgproc.createDisparityWLSFilter takes in cv2 user code: a confidence-weighted, image-guided fast global
+    smoother over a disparity map (definition: include/sgm_hip_wls.h).  It is this package's own definition, NOT cv2's filter
+    bit for bit: cv2's ROI handling, its LR-consistency confidence and its depthDiscontinuityRadius are not built."""
+
+    def __init__(self, matcher_left=None):
+        self._matcher = matcher_left
+        self._lambda = 8000.0
+        self._sigma = 1.5
+
+    def setLambda(self, lambda_):
+        v = float(lambda_)
+        if not (0.0 <= v <= 1e7):
+            raise error(f"DisparityWLSFilter.setLambda: {lambda_!r} outside [0, 1e7]")
+        self._lambda = v
+
+    def getLambda(self):
+        return self._lambda
+
+    def setSigmaColor(self, sigma):
+        v = float(sigma)
+        if not (0.0 < v < float("inf")):
+            raise error(f"DisparityWLSFilter.setSigmaColor: {sigma!r} is not a positive finite number")
+        self._sigma = v
+
+    def getSigmaColor(self):
+        return self._sigma
+
+    def defaultInvalid(self):
+        """The value filter() takes for invalid pixels when it is given none: what the matcher's maps use"""
+        return (int(self._matcher.getMinDisparity()) - 1) * 16 if self._matcher is not None else -16
+
+    def _params(self):
+        return self._matcher._p if self._matcher is not None else _DEFAULT
+
+    def filter(self, disparity_map_left, left_view, confidence=None, invalid=None, return_float=False):
+        """disparity_map_left: int16 (H, W), disparity * 16; left_view: the uint8 guide, (H, W) or (H, W, 3); confidence: uint8
+        (H, W) in 0 .. 100 (computeWithConfidence's map) or None for full confidence on every valid pixel; invalid: the value
+        that marks invalid pixels, by default (matcher_left.minDisparity - 1) * 16, -16 without a matcher.  Returns the filtered
+        int16 map, with return_float (map, float32 disparity in pixels, 0 where invalid).  numpy in, numpy out; HIP tensors in,
+        tensors out on the same device."""
+        inv = self.defaultInvalid() if invalid is None else int(invalid)
+        if not -32768 <= inv <= 32767:
+            raise error(f"DisparityWLSFilter.filter: invalid value {inv} outside int16")
+        maps = [disparity_map_left, left_view] + ([] if confidence is None else [confidence])
+        on_device = any(_is_torch(m) for m in maps)
+        if on_device:
+            import torch
+            if not all(_is_torch(m) and m.is_cuda for m in maps):
+                raise error("DisparityWLSFilter.filter: torch inputs must all be CUDA (HIP) tensors")
+            i16, u8 = torch.int16, torch.uint8
+            d, g, c = disparity_map_left, left_view, confidence
+        else:
+            i16, u8 = np.int16, np.uint8
+            d, g = np.asarray(disparity_map_left), np.asarray(left_view)
+            c = None if confidence is None else np.asarray(confidence)
+        if d.dtype != i16 or g.dtype != u8 or (c is not None and c.dtype != u8):
+            raise error("DisparityWLSFilter.filter: (-215:Assertion failed) disparity_map_left.type() == CV_16SC1, "
+                        "left_view.depth() == CV_8U, confidence.type() == CV_8UC1")
+        if len(d.shape) != 2 or len(g.shape) not in (2, 3) or (len(g.shape) == 3 and g.shape[2] != 3):
+            raise error("DisparityWLSFilter.filter: the map must be (H, W) and the guide (H, W) or (H, W, 3)")
+        if tuple(g.shape[:2]) != tuple(d.shape) or (c is not None and tuple(c.shape) != tuple(d.shape)):
+            raise error("DisparityWLSFilter.filter: (-215:Assertion failed) the map, the guide and the confidence must have the same size")
+        H, W = int(d.shape[0]), int(d.shape[1])
+        if H == 0 or W == 0:
+            raise error("DisparityWLSFilter.filter: empty image")
+        lut = wls_weights(self._sigma)
+        cn = 1 if len(g.shape) == 2 else 3
+        if not on_device:
+            return get_engine(self._params()).wls_filter_host(d, g, c, inv, self._lambda, lut, return_float)
+        import torch
+        d, g = d.contiguous(), g.contiguous()
+        c = None if c is None else c.contiguous()
+        eng = get_engine(self._params(), d.device.index or 0)
+        out = torch.empty((H, W), dtype=torch.int16, device=d.device)
+        outf = torch.empty((H, W), dtype=torch.float32, device=d.device) if return_float else None
+        # the engine runs on its own stream: order it after torch's current stream and wait for it (as _compute_torch does)
+        torch.cuda.current_stream(d.device).synchronize()
+        eng.wls_filter_device(d.data_ptr(), g.data_ptr(), cn, None if c is None else c.data_ptr(), H, W, inv, self._lambda, lut,
+                              out.data_ptr(), None if outf is None else outf.data_ptr())
+        eng.synchronize()
+        return (out, outf) if return_float else out
+
+
+def createDisparityWLSFilter(matcher_left=None) -> DisparityWLSFilter:
+    """Call shape of cv2.ximgproc.createDisparityWLSFilter(matcher_left); see DisparityWLSFilter for what differs."""
+    return DisparityWLSFilter(matcher_left)
 
 
 def reprojectImageTo3D(disparity, Q, _3dImage=None, handleMissingValues=False, ddepth=-1):
