@@ -307,4 +307,6 @@ int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_r
 /* the edge-aware disparity post-filter, a stage of its own behind any of the maps above: sgm_wls_weights, sgm_wls_filter,
  * sgm_wls_filter_device */
 #include "sgm_hip_wls.h"
+/* ... and its batch form, N maps of one shape per call */
+#include "sgm_hip_wls_batch.h"
 #endif

@@ -257,4 +257,226 @@ __global__ __launch_bounds__(256) void k_wls_final(const float *__restrict__ u, 
     if (out_f32) out_f32[i] = ok ? q * 0.0625f : 0.f;
 }
 
+// ---- the batch form (include/sgm_hip_wls_batch.h: sgm_wls_filter_batch) -----------------------------------------------------------
+// The same four kernels over a chunk of up to WLS_BATCH_MAX maps of one shape: blockIdx.y is the map.  The planes u, v, c' of map m
+// are the m-th [H][W] slice of the engine's three buffers (64-bit offsets: 64 planes of a 4K map pass 2^31 bytes); the maps'
+// own pointers -- map, guide, confidence, outputs -- travel as by-value tables in the kernel arguments, each kernel with the
+// tables it reads (512 bytes each), so nothing is copied to the device for them and nothing of them outlives the launch.  The
+// arithmetic of a line is wls_forward / wls_gdiff and the order of the single-map kernels: one lane, one line, end to end; a
+// map's tail workgroup is cut to its own rows / columns exactly as there, so it touches no neighbour's plane.
+// What a batch changes is who shares a CU: the single map has one workgroup per CU at most and pays for its own waiting; here
+// several workgroups of different maps sit on a CU and walk while the others move their tiles.  So the shape of the row
+// kernel is a template argument -- RW waves per workgroup (wave 0 walks, all move tiles), tiles of TC columns (LDS:
+// 3 * 64 * (TC + 1) floats + the table) -- and so are the rows in flight of the column kernel; sgm_engine.hip says which are
+// used and DESIGN.md 4.16 what each gave.
+constexpr int WLS_BATCH_MAX = 64;
+struct WlsPtrs { void *p[WLS_BATCH_MAX]; };
+
+__global__ __launch_bounds__(256) void k_wls_init_b(WlsPtrs disps, WlsPtrs confs, int invalid, int64_t n, float *__restrict__ u,
+                                                    float *__restrict__ v)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int16_t *__restrict__ disp = (const int16_t *)disps.p[blockIdx.y];
+    const uint8_t *__restrict__ conf = (const uint8_t *)confs.p[blockIdx.y];
+    const int64_t o = (int64_t)blockIdx.y * n + i;
+    const int d = disp[i];
+    const bool ok = d != invalid;
+    const float c = ok ? (conf ? (float)conf[i] : 100.f) : 0.f;
+    u[o] = ok ? (float)d * c : 0.f;
+    v[o] = c;
+}
+
+template <int CN, int RW, int TC>
+__global__ __launch_bounds__(RW * WLS_T) void k_wls_rows_b(float *__restrict__ u, float *__restrict__ v, float *__restrict__ cpl,
+                                                           WlsPtrs guides, WlsLut lut, float lam, int H, int W)
+{
+    constexpr int LD = TC + 1;                  // floats per LDS tile row: odd, so the 64 lanes of a column step hit 64 banks
+    constexpr int RS = RW * WLS_T / TC;         // tile rows the workgroup's threads cover at once
+    static_assert(RW * WLS_T % TC == 0 && WLS_T % RS == 0, "the threads cover whole tile rows, and the tile in whole sweeps");
+    __shared__ float su[WLS_T * LD], sv[WLS_T * LD], sc[WLS_T * LD], sl[256];
+    wls_lut_to_lds(lut, sl);
+    const int64_t plane = (int64_t)blockIdx.y * H * W;
+    u += plane;
+    v += plane;
+    cpl += plane;
+    const uint8_t *__restrict__ guide = (const uint8_t *)guides.p[blockIdx.y];
+    const int tc = threadIdx.x % TC, tr = threadIdx.x / TC, y0 = blockIdx.x * WLS_T;
+    const int rows = min(WLS_T, H - y0), ntile = (W + TC - 1) / TC;
+    const bool walker = (int)threadIdx.x < rows;                                       // (rows <= 64: lanes of wave 0)
+    const int wl = threadIdx.x & (WLS_T - 1);
+    float *const mu = su + wl * LD, *const mv = sv + wl * LD, *const mc = sc + wl * LD;   // the walker's row
+    float kp = 0.f, cp = 0.f, up = 0.f, vp = 0.f;
+    for (int t = 0; t < ntile; t++) {
+        const int x0 = t * TC, x = x0 + tc, nc = min(TC, W - x0);
+        if (x < W) {
+#pragma unroll
+            for (int j = 0; j < WLS_T / RS; j++) {
+                const int r = tr + RS * j;
+                if (r < rows) {
+                    const int64_t i = (int64_t)(y0 + r) * W + x;
+                    su[r * LD + tc] = u[i];
+                    sv[r * LD + tc] = v[i];
+                    sc[r * LD + tc] = x < W - 1 ? sl[wls_gdiff<CN>(guide, i, i + 1)] : 0.f;   // the weight w_x
+                }
+            }
+        }
+        __syncthreads();
+        if (walker) {
+            for (int c = 0; c < nc; c++) {
+                const float k = lam * mc[c];
+                wls_forward(x0 + c == 0, x0 + c == W - 1, kp, k, mu[c], mv[c], cp, up, vp);
+                mc[c] = cp;
+                mu[c] = up;
+                mv[c] = vp;
+                kp = k;
+            }
+        }
+        __syncthreads();
+        if (x < W) {
+#pragma unroll
+            for (int j = 0; j < WLS_T / RS; j++) {
+                const int r = tr + RS * j;
+                if (r < rows) {
+                    const int64_t i = (int64_t)(y0 + r) * W + x;
+                    u[i] = su[r * LD + tc];
+                    v[i] = sv[r * LD + tc];
+                    cpl[i] = sc[r * LD + tc];
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // back substitution, the tiles in reverse: up / vp now carry x_{i+1}
+    for (int t = ntile - 1; t >= 0; t--) {
+        const int x0 = t * TC, x = x0 + tc, nc = min(TC, W - x0);
+        if (x < W) {
+#pragma unroll
+            for (int j = 0; j < WLS_T / RS; j++) {
+                const int r = tr + RS * j;
+                if (r < rows) {
+                    const int64_t i = (int64_t)(y0 + r) * W + x;
+                    su[r * LD + tc] = u[i];
+                    sv[r * LD + tc] = v[i];
+                    sc[r * LD + tc] = cpl[i];
+                }
+            }
+        }
+        __syncthreads();
+        if (walker) {
+            for (int c = nc - 1; c >= 0; c--) {
+                if (x0 + c == W - 1) {
+                    up = mu[c];
+                    vp = mv[c];
+                } else {
+                    const float cc = mc[c];
+                    up = mu[c] - cc * up;
+                    vp = mv[c] - cc * vp;
+                }
+                mu[c] = up;
+                mv[c] = vp;
+            }
+        }
+        __syncthreads();
+        if (x < W) {
+#pragma unroll
+            for (int j = 0; j < WLS_T / RS; j++) {
+                const int r = tr + RS * j;
+                if (r < rows) {
+                    const int64_t i = (int64_t)(y0 + r) * W + x;
+                    u[i] = su[r * LD + tc];
+                    v[i] = sv[r * LD + tc];
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+template <int CN, int UNR>
+__global__ __launch_bounds__(WLS_T) void k_wls_cols_b(float *__restrict__ u, float *__restrict__ v, float *__restrict__ cpl,
+                                                      WlsPtrs guides, WlsLut lut, float lam, int H, int W)
+{
+    __shared__ float sl[256];
+    wls_lut_to_lds(lut, sl);
+    const int x = blockIdx.x * WLS_T + threadIdx.x;
+    if (x >= W) return;
+    const int64_t plane = (int64_t)blockIdx.y * H * W;
+    u += plane;
+    v += plane;
+    cpl += plane;
+    const uint8_t *__restrict__ guide = (const uint8_t *)guides.p[blockIdx.y];
+    float kp = 0.f, cp = 0.f, up = 0.f, vp = 0.f;
+    for (int y0 = 0; y0 < H; y0 += UNR) {
+        float uu[UNR], vv[UNR], ww[UNR];
+#pragma unroll
+        for (int j = 0; j < UNR; j++) {
+            const int y = y0 + j;
+            if (y < H) {
+                const int64_t i = (int64_t)y * W + x;
+                uu[j] = u[i];
+                vv[j] = v[i];
+                ww[j] = y < H - 1 ? sl[wls_gdiff<CN>(guide, i, i + W)] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < UNR; j++) {
+            const int y = y0 + j;
+            if (y < H) {
+                const int64_t i = (int64_t)y * W + x;
+                const float k = lam * ww[j];
+                wls_forward(y == 0, y == H - 1, kp, k, uu[j], vv[j], cp, up, vp);
+                cpl[i] = cp;
+                u[i] = up;
+                v[i] = vp;
+                kp = k;
+            }
+        }
+    }
+    for (int y0 = (H - 1) / UNR * UNR; y0 >= 0; y0 -= UNR) {
+        float uu[UNR], vv[UNR], cc[UNR];
+#pragma unroll
+        for (int j = UNR - 1; j >= 0; j--) {
+            const int y = y0 + j;
+            if (y < H) {
+                const int64_t i = (int64_t)y * W + x;
+                uu[j] = u[i];
+                vv[j] = v[i];
+                cc[j] = cpl[i];
+            }
+        }
+#pragma unroll
+        for (int j = UNR - 1; j >= 0; j--) {
+            const int y = y0 + j;
+            if (y < H) {
+                const int64_t i = (int64_t)y * W + x;
+                if (y == H - 1) {
+                    up = uu[j];
+                    vp = vv[j];
+                } else {
+                    up = uu[j] - cc[j] * up;
+                    vp = vv[j] - cc[j] * vp;
+                }
+                u[i] = up;
+                v[i] = vp;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_wls_final_b(const float *__restrict__ u, const float *__restrict__ v, int invalid, int64_t n,
+                                                     WlsPtrs outs, WlsPtrs outfs)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int16_t *__restrict__ out = (int16_t *)outs.p[blockIdx.y];
+    float *__restrict__ out_f32 = (float *)outfs.p[blockIdx.y];
+    const int64_t o = (int64_t)blockIdx.y * n + i;
+    const float vi = v[o];
+    const bool ok = vi >= 1.f;
+    const float q = ok ? u[o] / vi : 0.f;
+    out[i] = ok ? (int16_t)fminf(fmaxf(rintf(q), -32768.f), 32767.f) : (int16_t)invalid;
+    if (out_f32) out_f32[i] = ok ? q * 0.0625f : 0.f;
+}
+
 }  // namespace sgm

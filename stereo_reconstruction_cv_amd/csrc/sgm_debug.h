@@ -30,7 +30,11 @@ enum {
     SGM_DBG_WTA_SEPARATE = 2048,         /* winner-take-all always as its own pass */
     SGM_DBG_SMALL_D_RECORD = 8192,       /* D <= 64, MODE_SGBM: per-row record + element-wise vertical kernel (k_prepass3_g + k_vert3_g) instead of k_lines3_g's volumes */
     SGM_DBG_IN_ROW_ON_MAIN_STREAM = 4096, /* D <= 64, MODE_SGBM: the left-to-right in-row path after the vertical kernel (S +=) instead of beside it */
-    SGM_DBG_FIFTH_PATH_AFTER_SWEEP = 65536 /* MODE_SGBM, D <= 128: the fifth path after the sweep (S +=) instead of beside it */
+    SGM_DBG_FIFTH_PATH_AFTER_SWEEP = 65536, /* MODE_SGBM, D <= 128: the fifth path after the sweep (S +=) instead of beside it */
+    /* sgm_wls_filter_batch*: the other shapes of the batched line kernels that DESIGN.md 4.16 measured (tools/wls_batch_times.py);
+     * two small fields, not flags.  0 in a field is the shape the library uses; the results are the same bits for every value. */
+    SGM_DBG_WLS_BATCH_ROWS_SHIFT = 17,     /* 3 bits: k_wls_rows_b<CN, RW, TC>, the index into wls_rows_shapes (sgm_engine.hip) */
+    SGM_DBG_WLS_BATCH_COLS_SHIFT = 20      /* 2 bits: k_wls_cols_b<CN, UNR>, the index into wls_cols_shapes */
 };
 
 /* Plan readout: what normalise + make_plan decide for one compute of a frame of H x W pixels on an engine with these

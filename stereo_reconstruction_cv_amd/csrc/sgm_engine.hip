@@ -2968,6 +2968,196 @@ int sgm_wls_filter(sgm_engine *e, const int16_t *disp, const uint8_t *guide, int
     return SGM_OK;
 }
 
+// ---- the batch form of the filter (include/sgm_hip_wls_batch.h; kernels_wls.h: k_wls_*_b) ------------------------------------------
+// The shapes of the batched line kernels.  Entry 0 is the one the library uses; the others are what DESIGN.md 4.16 measured
+// against it and stay reachable through SGM_OPT_DEBUG (sgm_debug.h) for tools/wls_batch_times.py.  Every shape gives the same bits.
+struct WlsRowsShape { int rw, tc; };   // k_wls_rows_b<CN, RW, TC>: waves per workgroup, columns per tile
+static const WlsRowsShape wls_rows_shapes[] = {{4, 32}, {2, 64}, {1, 64}, {4, 64}, {2, 32}};
+static const int wls_cols_shapes[] = {8, 16, 32, 4};   // k_wls_cols_b<CN, UNR>: rows in flight per lane
+
+extern "C++" {   // (templates: this part of the file has C linkage)
+template <int CN>
+static void launch_wls_rows_b(int shape, dim3 grid, hipStream_t st, float *u, float *v, float *c, const WlsPtrs &g, const WlsLut &t,
+                              float lam, int H, int W)
+{
+    switch (shape) {
+    case 1: hipLaunchKernelGGL((k_wls_rows_b<CN, 2, 64>), grid, dim3(2 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    case 2: hipLaunchKernelGGL((k_wls_rows_b<CN, 1, 64>), grid, dim3(1 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    case 3: hipLaunchKernelGGL((k_wls_rows_b<CN, 4, 64>), grid, dim3(4 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    case 4: hipLaunchKernelGGL((k_wls_rows_b<CN, 2, 32>), grid, dim3(2 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    default: hipLaunchKernelGGL((k_wls_rows_b<CN, 4, 32>), grid, dim3(4 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    }
+}
+template <int CN>
+static void launch_wls_cols_b(int shape, dim3 grid, hipStream_t st, float *u, float *v, float *c, const WlsPtrs &g, const WlsLut &t,
+                              float lam, int H, int W)
+{
+    switch (shape) {
+    case 1: hipLaunchKernelGGL((k_wls_cols_b<CN, 16>), grid, dim3(WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    case 2: hipLaunchKernelGGL((k_wls_cols_b<CN, 32>), grid, dim3(WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    case 3: hipLaunchKernelGGL((k_wls_cols_b<CN, 4>), grid, dim3(WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    default: hipLaunchKernelGGL((k_wls_cols_b<CN, 8>), grid, dim3(WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    }
+}
+}  // extern "C++"
+
+static int wls_batch_check_args(const sgm_engine *e, int N, const void *const *disp, const void *const *guide, int cn,
+                                const void *const *conf, int H, int W, int invalid, double lambda, const float *lut,
+                                const void *const *out, const void *const *outf, bool arrays)
+{
+    if (N <= 0) return set_err(SGM_ERR_INVALID_ARG, "sgm_wls_filter_batch: N=%d maps", N);
+    if (int rc = wls_check_args(e, disp, guide, cn, H, W, invalid, lambda, lut, out)) return rc;
+    if (!arrays) return SGM_OK;
+    for (int i = 0; i < N; i++)
+        if (!disp[i] || !guide[i] || !out[i] || (conf && !conf[i]) || (outf && !outf[i]))
+            return set_err(SGM_ERR_INVALID_ARG, "sgm_wls_filter_batch: null pointer for map %d", i);
+    return SGM_OK;
+}
+
+// Maps per chunk, and the buffers of the call sized for it.  C = min(N, WLS_BATCH_MAX, SGM_OPT_GROUP_MAX if set), cut to what
+// free device memory allows beside the reserve of prepare_group (4 GiB or 5 %) when a buffer has to grow; at least 1.  All
+// allocations of the call happen here, before anything is enqueued.
+struct WlsNeed { DevBuf *b; size_t per_map; };
+static int wls_batch_reserve(sgm_engine *e, int N, std::initializer_list<WlsNeed> needs, int *C_out)
+{
+    int C = std::min(N, WLS_BATCH_MAX);
+    if (e->group_max > 0) C = std::min(C, e->group_max);
+    size_t per_map = 0, freed = 0;   // of the buffers that grow: bytes per map, and what they give back first (DevBuf::ensure)
+    for (const WlsNeed &n : needs)
+        if (n.b->cap < n.per_map * (size_t)C) {
+            per_map += n.per_map;
+            freed += n.b->cap;
+        }
+    size_t fr = 0, tot = 0;
+    if (per_map && hipMemGetInfo(&fr, &tot) == hipSuccess) {
+        const size_t reserve = std::max<size_t>((size_t)4 << 30, tot / 20), have = fr + freed;
+        const size_t room = have > reserve ? have - reserve : 0;
+        C = (int)std::max<size_t>(1, std::min<size_t>((size_t)C, room / per_map));
+    }
+    for (const WlsNeed &n : needs)
+        if (int rc = n.b->ensure(n.per_map * (size_t)C)) return rc;
+    *C_out = C;
+    return SGM_OK;
+}
+
+// One chunk of n <= WLS_BATCH_MAX maps: init, three times (rows, columns), final, every launch over all n maps.  conf / outf: null
+// for none.  The planes hold n maps (wls_batch_reserve).
+static int run_wls_batch(sgm_engine *e, int n, const void *const *d_disp, const void *const *d_guide, int cn, const void *const *d_conf,
+                         int H, int W, int invalid, double lambda, const float *lut, void *const *d_out, void *const *d_outf)
+{
+    const int64_t npx = (int64_t)H * W;
+    float *u = (float *)e->wls_u.p, *v = (float *)e->wls_v.p, *c = (float *)e->wls_c.p;
+    WlsLut t;
+    memcpy(t.w, lut, sizeof(t.w));
+    WlsPtrs disps{}, guides{}, confs{}, outs{}, outfs{};
+    for (int i = 0; i < n; i++) {
+        disps.p[i] = (void *)d_disp[i];
+        guides.p[i] = (void *)d_guide[i];
+        confs.p[i] = d_conf ? (void *)d_conf[i] : nullptr;
+        outs.p[i] = d_out[i];
+        outfs.p[i] = d_outf ? d_outf[i] : nullptr;
+    }
+    const unsigned rsh = ((unsigned)e->debug >> SGM_DBG_WLS_BATCH_ROWS_SHIFT) & 7, csh = ((unsigned)e->debug >> SGM_DBG_WLS_BATCH_COLS_SHIFT) & 3;
+    const int rshape = rsh < sizeof(wls_rows_shapes) / sizeof(wls_rows_shapes[0]) ? (int)rsh : 0;
+    const int cshape = csh < sizeof(wls_cols_shapes) / sizeof(wls_cols_shapes[0]) ? (int)csh : 0;
+    const dim3 px((unsigned)((npx + 255) / 256), n);
+    int rc;
+    stage_break(e);   // (the host entry's copies lie between the chunks)
+    if ((rc = stage_begin(e, "wls_init"))) return rc;
+    hipLaunchKernelGGL(k_wls_init_b, px, dim3(256), 0, e->stream, disps, confs, invalid, npx, u, v);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    const int T = 3;
+    for (int it = 1; it <= T; it++) {
+        const float lam = (float)(1.5 * lambda * (double)(1 << (2 * (T - it))) / (double)((1 << (2 * T)) - 1));
+        if (W > 1) {   // (a line of one element is the identity)
+            const dim3 grid((H + WLS_T - 1) / WLS_T, n);
+            if ((rc = stage_begin(e, "wls_rows"))) return rc;
+            if (cn == 3) launch_wls_rows_b<3>(rshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
+            else launch_wls_rows_b<1>(rshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
+            KCHECK();
+            if ((rc = stage_end(e, 1))) return rc;
+        }
+        if (H > 1) {
+            const dim3 grid((W + WLS_T - 1) / WLS_T, n);
+            if ((rc = stage_begin(e, "wls_cols"))) return rc;
+            if (cn == 3) launch_wls_cols_b<3>(cshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
+            else launch_wls_cols_b<1>(cshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
+            KCHECK();
+            if ((rc = stage_end(e, 1))) return rc;
+        }
+    }
+    if ((rc = stage_begin(e, "wls_final"))) return rc;
+    hipLaunchKernelGGL(k_wls_final_b, px, dim3(256), 0, e->stream, (const float *)u, (const float *)v, invalid, npx, outs, outfs);
+    KCHECK();
+    return stage_end(e, 1);
+}
+
+int sgm_wls_filter_batch_device(sgm_engine *e, int N, const void *const *d_disp_i16, const void *const *d_guide_u8, int cn,
+                                const void *const *d_conf_u8, int H, int W, int invalid, double lambda, const float lut[256],
+                                void *const *d_out_i16, void *const *d_out_f32)
+{
+    if (int rc = wls_batch_check_args(e, N, d_disp_i16, d_guide_u8, cn, d_conf_u8, H, W, invalid, lambda, lut, d_out_i16, d_out_f32, true))
+        return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t pb = (size_t)H * W * 4;
+    int rc, C = 1;
+    if ((rc = wls_batch_reserve(e, N, {{&e->wls_u, pb}, {&e->wls_v, pb}, {&e->wls_c, pb}}, &C))) return rc;
+    if (e->profile) {   // the stage record is the call's from here on
+        e->nstages = 0;
+        e->nevents = 0;
+        e->last_end_ev = -1;
+    }
+    for (int i0 = 0; i0 < N; i0 += C)
+        if ((rc = run_wls_batch(e, std::min(C, N - i0), d_disp_i16 + i0, d_guide_u8 + i0, cn, d_conf_u8 ? d_conf_u8 + i0 : nullptr, H, W,
+                                invalid, lambda, lut, d_out_i16 + i0, d_out_f32 ? d_out_f32 + i0 : nullptr)))
+            return rc;
+    return SGM_OK;
+}
+
+int sgm_wls_filter_batch(sgm_engine *e, int N, const int16_t *disp, const uint8_t *guide, int cn, const uint8_t *conf, int H, int W,
+                         int invalid, double lambda, const float lut[256], int16_t *out, float *out_f32)
+{
+    if (int rc = wls_batch_check_args(e, N, (const void *const *)disp, (const void *const *)guide, cn, nullptr, H, W, invalid, lambda, lut,
+                                      (const void *const *)out, nullptr, false))
+        return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t npx = (size_t)H * W, pb = npx * 4;
+    // staging, [C] of each: the maps in disp_out (filtered in place), the guides in in_left, the confidence maps in in_right, the
+    // float maps in f32
+    int rc, C = 1;
+    if ((rc = wls_batch_reserve(e, N, {{&e->wls_u, pb}, {&e->wls_v, pb}, {&e->wls_c, pb}, {&e->disp_out, npx * 2}, {&e->in_left, npx * cn},
+                                       {&e->in_right, conf ? npx : 0}, {&e->f32, out_f32 ? pb : 0}}, &C)))
+        return rc;
+    if (e->profile) {
+        e->nstages = 0;
+        e->nevents = 0;
+        e->last_end_ev = -1;
+    }
+    std::vector<void *> pd(C), pg(C), pc(C), pf(C);
+    for (int k = 0; k < C; k++) {
+        pd[k] = (char *)e->disp_out.p + (size_t)k * npx * 2;
+        pg[k] = (char *)e->in_left.p + (size_t)k * npx * cn;
+        pc[k] = conf ? (char *)e->in_right.p + (size_t)k * npx : nullptr;
+        pf[k] = out_f32 ? (char *)e->f32.p + (size_t)k * pb : nullptr;
+    }
+    for (int i0 = 0; i0 < N; i0 += C) {
+        const size_t n = (size_t)std::min(C, N - i0), o = (size_t)i0 * npx;
+        HIP_TRY(hipMemcpyAsync(e->disp_out.p, disp + o, n * npx * 2, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(e->in_left.p, guide + o * cn, n * npx * cn, hipMemcpyHostToDevice, e->stream));
+        if (conf) HIP_TRY(hipMemcpyAsync(e->in_right.p, conf + o, n * npx, hipMemcpyHostToDevice, e->stream));
+        if ((rc = run_wls_batch(e, (int)n, pd.data(), pg.data(), cn, conf ? pc.data() : nullptr, H, W, invalid, lambda, lut, pd.data(),
+                                out_f32 ? pf.data() : nullptr))) {
+            (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the target of nothing when the call returns)
+            return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(out + o, e->disp_out.p, n * npx * 2, hipMemcpyDeviceToHost, e->stream));
+        if (out_f32) HIP_TRY(hipMemcpyAsync(out_f32 + o, e->f32.p, n * pb, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SGM_OK;
+}
+
 int sgm_filter_speckles(sgm_engine *e, int16_t *img, int H, int W, int newVal, int maxSpeckleSize, int maxDiff)
 {
     if (!e || !img || H <= 0 || W <= 0) return set_err(SGM_ERR_INVALID_ARG, "bad argument");

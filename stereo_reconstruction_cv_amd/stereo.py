@@ -378,6 +378,37 @@ class Engine:
         _check(self._L.sgm_wls_filter_device(self._h, d_disp, d_guide, int(cn), d_conf, H, W, int(invalid), float(lambda_),
                                              lut.ctypes.data, d_out, d_out_f32))
 
+    # -- ... and its batch form (include/sgm_hip_wls_batch.h): N maps of one shape per call --
+    def wls_filter_batch_host(self, disps: np.ndarray, guides: np.ndarray, confs: np.ndarray | None, invalid: int, lambda_: float,
+                              lut: np.ndarray, return_float: bool = False):
+        """sgm_wls_filter_batch: int16 (N, H, W) maps, uint8 (N, H, W) or (N, H, W, 3) guides, uint8 (N, H, W) confidence maps or
+        None, the 256 float32 edge weights; returns the filtered int16 stack, or (stack, float32 stack in pixels) with
+        return_float."""
+        disps = np.ascontiguousarray(disps, np.int16)
+        guides = np.ascontiguousarray(guides, np.uint8)
+        confs = None if confs is None else np.ascontiguousarray(confs, np.uint8)
+        lut = np.ascontiguousarray(lut, np.float32)
+        N, H, W = disps.shape
+        out = np.empty((N, H, W), np.int16)
+        outf = np.empty((N, H, W), np.float32) if return_float else None
+        _check(self._L.sgm_wls_filter_batch(self._h, N, disps.ctypes.data, guides.ctypes.data, 1 if guides.ndim == 3 else guides.shape[3],
+                                            None if confs is None else confs.ctypes.data, H, W, int(invalid), float(lambda_),
+                                            lut.ctypes.data, out.ctypes.data, None if outf is None else outf.ctypes.data))
+        return (out, outf) if return_float else out
+
+    def wls_filter_batch_device(self, d_disps, d_guides, cn: int, d_confs, H: int, W: int, invalid: int, lambda_: float,
+                                lut: np.ndarray, d_outs, d_out_f32s=None) -> None:
+        """sgm_wls_filter_batch_device: sequences of N device addresses (d_confs / d_out_f32s: such a sequence, or None for none;
+        lut stays a host array), in the order of the engine's stream."""
+        n = len(d_disps)
+        arr = lambda xs: (C.c_void_p * len(xs))(*[int(x) if x else None for x in xs]) if xs is not None and len(xs) else None
+        for xs in (d_guides, d_confs, d_outs, d_out_f32s):
+            if xs is not None and len(xs) != n:
+                raise error(f"wls_filter_batch_device: {n} maps, but a sequence of {len(xs)} addresses")
+        lut = np.ascontiguousarray(lut, np.float32)
+        _check(self._L.sgm_wls_filter_batch_device(self._h, n, arr(d_disps), arr(d_guides), int(cn), arr(d_confs), H, W, int(invalid),
+                                                   float(lambda_), lut.ctypes.data, arr(d_outs), arr(d_out_f32s)))
+
 
 # The notebook builds a matcher per call and throws it away (main.ipynb:655-668); engines are
 # cached per (parameters, device) so device buffers survive between such calls.
@@ -501,6 +532,69 @@ class StereoSGBM:
             guide = guide[:, :, 0]
         return f.filter(disp, guide, conf)
 
+    def computeFilteredBatch(self, lefts, rights, lambda_=8000.0, sigmaColor=1.5):
+        """computeFiltered() over N pairs of one shape: ONE batch compute with the confidence maps delivered per pair (the
+        engine's sgm_pipeline_batch_device behind sgm_bind_confidence_device) and ONE batch filter call
+        (sgm_wls_filter_batch_device) with `lefts` as the guides, both on the same engine.  lefts / rights: uint8 stacks
+        (N, H, W) or (N, H, W, 3), or sequences of N equal-shaped images; numpy (uploaded through torch, a numpy stack comes
+        back) or HIP tensors (a tensor (N, H, W) comes back without leaving the device).  Result i equals
+        computeFiltered(lefts[i], rights[i]) bit for bit.
+        No synchronisation lies between the two calls: the batch compute leaves the engine's stream behind everything its
+        internal engines did (run_group joins their streams into it; without a chained group the pairs run on that stream
+        itself), and the filter is enqueued on the same stream."""
+        if self._p["mode"] not in (STEREO_SGBM_MODE_SGBM, STEREO_SGBM_MODE_HH, STEREO_SGBM_MODE_HH4):
+            raise error("StereoSGBM.compute: MODE_SGBM, MODE_HH and MODE_HH4 are implemented; MODE_SGBM_3WAY is not "
+                        "(its result depends on a stripe size upstream derives from the cache size)")
+        f = DisparityWLSFilter(self)
+        f.setLambda(lambda_)
+        f.setSigmaColor(sigmaColor)
+        L, R = _batch_items(lefts), _batch_items(rights)
+        on_device = any(_is_torch(m) for m in L + R)
+        if on_device:
+            if not all(_is_torch(m) and m.is_cuda for m in L + R):
+                raise error("StereoSGBM.computeFilteredBatch: torch inputs must all be CUDA (HIP) tensors")
+            import torch
+            u8 = torch.uint8
+        else:
+            L, R = [np.asarray(m) for m in L], [np.asarray(m) for m in R]
+            u8 = np.uint8
+        if len(L) == 0 or len(L) != len(R):
+            raise error(f"StereoSGBM.computeFilteredBatch: {len(L)} left and {len(R)} right images (the same number, at least one)")
+        shape = tuple(L[0].shape)
+        if any(tuple(m.shape) != shape or m.dtype != u8 for m in L + R):
+            raise error("StereoSGBM.compute: (-215:Assertion failed) left.size() == right.size() && "
+                        "left.type() == right.type() && left.depth() == CV_8U")
+        if len(shape) == 3 and shape[2] == 1:
+            L, R, shape = [m[:, :, 0] for m in L], [m[:, :, 0] for m in R], shape[:2]
+        _check_channels(len(shape), shape[2] if len(shape) == 3 else 1)
+        if shape[0] == 0 or shape[1] == 0:
+            raise error("StereoSGBM.compute: empty image")
+        if shape[1] < 2:
+            raise error("StereoSGBM.compute: image width < 2")
+        import torch
+        N, (H, W), cn = len(L), shape[:2], 1 if len(shape) == 2 else 3
+        dev = L[0].device if on_device else torch.device("cuda", get_device())
+        eng = self._engine(cn, dev.index or 0)      # (refuses a colour census before anything is uploaded)
+        try:
+            if not on_device:
+                L = [torch.from_numpy(np.ascontiguousarray(m)).to(dev) for m in L]
+                R = [torch.from_numpy(np.ascontiguousarray(m)).to(dev) for m in R]
+            L, R = [m.contiguous() for m in L], [m.contiguous() for m in R]
+            disp = torch.empty((N, H, W), dtype=torch.int16, device=dev)
+            conf = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+            out = torch.empty((N, H, W), dtype=torch.int16, device=dev)
+            ptrs = lambda ts: [t.data_ptr() for t in ts]
+            # the engine runs on its own stream: order it after torch's current stream and wait for it (as _compute_torch does)
+            torch.cuda.current_stream(dev).synchronize()
+            with _option_for_this_call(eng, _lib.SGM_OPT_CONFIDENCE):
+                eng.pipeline_batch_device(ptrs(L), ptrs(R), H, W, cn * W, None, ptrs(disp), cn=cn, d_confs=ptrs(conf))
+            eng.wls_filter_batch_device(ptrs(disp), ptrs(L), cn, ptrs(conf), H, W, f.defaultInvalid(), lambda_, wls_weights(sigmaColor),
+                                        ptrs(out))
+            eng.synchronize()
+        finally:
+            eng.set_option(_lib.SGM_OPT_COST, STEREO_COST_BT)   # (as in _compute)
+        return out if on_device else out.cpu().numpy()
+
     def _compute(self, left, right, with_conf: bool, with_right: bool = False):
         if self._p["mode"] not in (STEREO_SGBM_MODE_SGBM, STEREO_SGBM_MODE_HH, STEREO_SGBM_MODE_HH4):
             raise error("StereoSGBM.compute: MODE_SGBM, MODE_HH and MODE_HH4 are implemented; MODE_SGBM_3WAY is not "
@@ -568,6 +662,15 @@ class StereoSGBM:
         finally:
             eng.set_option(_lib.SGM_OPT_COST, STEREO_COST_BT)   # (as in _compute)
         return out, side
+
+
+def _batch_items(x) -> list:
+    """the maps of a batch argument, one by one: the entries of a list or tuple, else the slices of a stack along its first axis"""
+    if isinstance(x, (list, tuple)):
+        return list(x)
+    if not _is_torch(x):
+        x = np.asarray(x)
+    return [x[i] for i in range(x.shape[0])] if len(x.shape) >= 1 else [x]
 
 
 def _check_channels(ndim: int, cn: int) -> None:
@@ -676,6 +779,64 @@ class DisparityWLSFilter:
         torch.cuda.current_stream(d.device).synchronize()
         eng.wls_filter_device(d.data_ptr(), g.data_ptr(), cn, None if c is None else c.data_ptr(), H, W, inv, self._lambda, lut,
                               out.data_ptr(), None if outf is None else outf.data_ptr())
+        eng.synchronize()
+        return (out, outf) if return_float else out
+
+
+    def filterBatch(self, disparity_maps, left_views, confidences=None, invalid=None, return_float=False):
+        """filter() over N maps of one shape in one engine call (sgm_wls_filter_batch): disparity_maps int16 (N, H, W), left_views
+        uint8 (N, H, W) or (N, H, W, 3), confidences uint8 (N, H, W) or None -- stacks, or sequences of N equal-shaped maps;
+        invalid and return_float as in filter().  numpy in, a numpy stack (N, H, W) out (with return_float: two); HIP tensors in
+        (a stacked tensor or a sequence of tensors), a tensor (N, H, W) out without leaving the device.  Map i of the result
+        equals filter() on map i alone, bit for bit."""
+        inv = self.defaultInvalid() if invalid is None else int(invalid)
+        if not -32768 <= inv <= 32767:
+            raise error(f"DisparityWLSFilter.filter: invalid value {inv} outside int16")
+        D, G = _batch_items(disparity_maps), _batch_items(left_views)
+        Cf = None if confidences is None else _batch_items(confidences)
+        maps = D + G + (Cf or [])
+        on_device = any(_is_torch(m) for m in maps)
+        if on_device:
+            import torch
+            if not all(_is_torch(m) and m.is_cuda for m in maps):
+                raise error("DisparityWLSFilter.filter: torch inputs must all be CUDA (HIP) tensors")
+            i16, u8 = torch.int16, torch.uint8
+        else:
+            i16, u8 = np.int16, np.uint8
+            D, G = [np.asarray(m) for m in D], [np.asarray(m) for m in G]
+            Cf = None if Cf is None else [np.asarray(m) for m in Cf]
+        if any(m.dtype != i16 for m in D) or any(m.dtype != u8 for m in G + (Cf or [])):
+            raise error("DisparityWLSFilter.filter: (-215:Assertion failed) disparity_map_left.type() == CV_16SC1, "
+                        "left_view.depth() == CV_8U, confidence.type() == CV_8UC1")
+        if len(D) == 0:
+            raise error("DisparityWLSFilter.filterBatch: empty batch")
+        if any(len(m.shape) != 2 for m in D) or any(len(m.shape) not in (2, 3) or (len(m.shape) == 3 and m.shape[2] != 3) for m in G):
+            raise error("DisparityWLSFilter.filterBatch: the maps must be (N, H, W) and the guides (N, H, W) or (N, H, W, 3)")
+        shape, gshape = tuple(D[0].shape), tuple(G[0].shape) if G else ()
+        if len(G) != len(D) or (Cf is not None and len(Cf) != len(D)) or any(tuple(m.shape) != shape for m in D + (Cf or [])) or \
+                any(tuple(m.shape) != gshape for m in G) or gshape[:2] != shape:
+            raise error("DisparityWLSFilter.filter: (-215:Assertion failed) the map, the guide and the confidence must have the same size")
+        N, (H, W) = len(D), shape
+        if H == 0 or W == 0:
+            raise error("DisparityWLSFilter.filter: empty image")
+        lut = wls_weights(self._sigma)
+        cn = 1 if len(gshape) == 2 else 3
+        if not on_device:
+            stack = lambda x, items: np.ascontiguousarray(x) if isinstance(x, np.ndarray) else np.stack(items)
+            return get_engine(self._params()).wls_filter_batch_host(stack(disparity_maps, D), stack(left_views, G),
+                                                                    None if Cf is None else stack(confidences, Cf), inv, self._lambda,
+                                                                    lut, return_float)
+        import torch
+        D, G = [m.contiguous() for m in D], [m.contiguous() for m in G]
+        Cf = None if Cf is None else [m.contiguous() for m in Cf]
+        dev = D[0].device
+        eng = get_engine(self._params(), dev.index or 0)
+        out = torch.empty((N, H, W), dtype=torch.int16, device=dev)
+        outf = torch.empty((N, H, W), dtype=torch.float32, device=dev) if return_float else None
+        ptrs = lambda ts: None if ts is None else [t.data_ptr() for t in ts]
+        # the engine runs on its own stream: order it after torch's current stream and wait for it (as filter() does)
+        torch.cuda.current_stream(dev).synchronize()
+        eng.wls_filter_batch_device(ptrs(D), ptrs(G), cn, ptrs(Cf), H, W, inv, self._lambda, lut, ptrs(out), ptrs(outf))
         eng.synchronize()
         return (out, outf) if return_float else out
 
