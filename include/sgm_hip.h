@@ -54,7 +54,8 @@ extern "C" {
                              * additive since, version unchanged: SGM_OPT_CHANNELS; mode 3; SGM_OPT_CONFIDENCE, SGM_TAP_CONF_RAW,
                              * SGM_TAP_CONF, sgm_bind_confidence_device (sgm_hip_confidence.h); SGM_OPT_RIGHT_VIEW, SGM_TAP_RIGHT_RAW,
                              * SGM_TAP_RIGHT, sgm_bind_right_device (sgm_hip_right.h); SGM_OPT_COST, SGM_COST_BT, SGM_COST_CENSUS;
-                             * the disparity post-filter of sgm_hip_wls.h */
+                             * the disparity post-filter of sgm_hip_wls.h and sgm_hip_wls_batch.h; the left-right
+                             * consistency confidence of sgm_hip_lrc.h */
 
 typedef enum {
     SGM_OK = 0,
@@ -309,4 +310,6 @@ int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_r
 #include "sgm_hip_wls.h"
 /* ... and its batch form, N maps of one shape per call */
 #include "sgm_hip_wls_batch.h"
+/* the left-right consistency confidence from a left-view and a right-view map, which that filter can be fed with */
+#include "sgm_hip_lrc.h"
 #endif

@@ -8,8 +8,9 @@
  * symbol for symbol, against lists fixed earlier; these are bound beside them (_lib.py: WLS_EXPORTS).
  *
  * In cv2 user code the place of this filter is taken by cv2.ximgproc.createDisparityWLSFilter.  This is NOT that filter bit
- * for bit: it is the definition below, our own.  cv2's filter adds ROI handling, an LR-consistency confidence of its own and a
- * depth-discontinuity heuristic that are not restated here.
+ * for bit: it is the definition below, our own.  cv2's filter computes an LR-consistency confidence with a depth-discontinuity
+ * radius when it is given both maps; what this library offers in that place is the confidence of sgm_hip_lrc.h (a definition of
+ * our own as well), fed into this filter as `conf`.  What remains unbuilt: cv2's ROI handling, and bit parity with cv2.
  *
  * Definition.  Inputs: disp int16 [H][W] (disparity * 16); `invalid`, the value that marks invalid pixels (the engine's maps
  * use (minDisparity - 1) * 16); guide uint8 [H][W] or interleaved [H][W][3] (cn = 1 or 3), tight; conf uint8 [H][W] in

@@ -6,7 +6,8 @@ cv2.StereoSGBM_create(...).compute() / cv2.reprojectImageTo3D() path (main.ipynb
 from .stereo import (CV_32F, STEREO_COST_BT, STEREO_COST_CENSUS, STEREO_SGBM_MODE_HH, STEREO_SGBM_MODE_HH4, STEREO_SGBM_MODE_SGBM,
                      STEREO_SGBM_MODE_SGBM_3WAY, Engine, StereoSGBM, StereoSGBM_create, clear_engine_cache, error,
                      get_device, get_engine, reprojectImageTo3D, set_device, initUndistortRectifyMap, remap, CV_32FC1,
-                     INTER_LINEAR, BORDER_CONSTANT, DisparityWLSFilter, createDisparityWLSFilter, wls_weights)
+                     INTER_LINEAR, BORDER_CONSTANT, DisparityWLSFilter, createDisparityWLSFilter, wls_weights,
+                     lrcConfidence)
 from .pipeline import compute_disparity_map, reconstruct_3D, rectify_pair, run_disparity, valid_point_mask
 from .pointcloud import mask_by_confidence, read_point_cloud, valid_points, write_point_cloud
 from ._lib import SGM_OPT_CONFIDENCE, SGM_TAP_CONF, SGM_TAP_CONF_RAW
@@ -19,5 +20,5 @@ __all__ = [
     "STEREO_SGBM_MODE_HH4", "CV_32F", "CV_32FC1", "INTER_LINEAR", "BORDER_CONSTANT", "initUndistortRectifyMap", "remap", "rectify_pair",
     "mask_by_confidence", "SGM_OPT_CONFIDENCE", "SGM_TAP_CONF_RAW", "SGM_TAP_CONF",
     "SGM_OPT_RIGHT_VIEW", "SGM_TAP_RIGHT_RAW", "SGM_TAP_RIGHT", "STEREO_COST_BT", "STEREO_COST_CENSUS",
-    "DisparityWLSFilter", "createDisparityWLSFilter", "wls_weights",
+    "DisparityWLSFilter", "createDisparityWLSFilter", "wls_weights", "lrcConfidence",
 ]

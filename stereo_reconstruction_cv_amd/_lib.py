@@ -45,6 +45,8 @@ RIGHT_EXPORTS = ("sgm_bind_right_device",)
 WLS_EXPORTS = ("sgm_wls_weights", "sgm_wls_filter", "sgm_wls_filter_device")
 # include/sgm_hip_wls_batch.h (likewise): the filter over N maps of one shape per call
 WLS_BATCH_EXPORTS = ("sgm_wls_filter_batch", "sgm_wls_filter_batch_device")
+# include/sgm_hip_lrc.h (likewise): the left-right consistency confidence from a left-view and a right-view map
+LRC_EXPORTS = ("sgm_lrc_confidence", "sgm_lrc_confidence_device", "sgm_lrc_confidence_batch_device")
 
 
 class SgmParams(C.Structure):
@@ -128,6 +130,9 @@ def load():
     L.sgm_wls_filter_device.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, C.c_double, vp, vp, vp]
     L.sgm_wls_filter_batch.argtypes = [vp, i32, vp, vp, i32, vp, i32, i32, i32, C.c_double, vp, vp, vp]
     L.sgm_wls_filter_batch_device.argtypes = [vp, i32, vp, vp, i32, vp, i32, i32, i32, C.c_double, vp, vp, vp]
+    L.sgm_lrc_confidence.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+    L.sgm_lrc_confidence_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+    L.sgm_lrc_confidence_batch_device.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
     L.sgm_synchronize.argtypes = [vp]
     L.sgm_get_stage_times.argtypes = [vp, C.POINTER(SgmStageTimes)]
     L.sgm_algorithmic_bytes.argtypes = [pp, i32, i32, i32]
@@ -152,7 +157,7 @@ def load():
     L.sgm_debug_wta_raw_bytes.restype = C.c_longlong
     L.sgm_debug_wta_select_n.argtypes = [i32, i32, vp, i32, vp]
     L.sgm_debug_wta_select_n.restype = i32
-    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS:
+    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("sgm_abi_version", "sgm_device_count"):
             fn.restype = i32

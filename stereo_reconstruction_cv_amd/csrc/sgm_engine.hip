@@ -29,6 +29,7 @@
 #include "kernels_group.h"
 #include "kernels_right.h"
 #include "kernels_wls.h"
+#include "kernels_lrc.h"
 
 using namespace sgm;
 
@@ -259,6 +260,7 @@ struct Plan {
     BUF(rmap1) BUF(rmap2) BUF(rsrc) BUF(rdst)    /* host-pointer rectification stages */ \
     BUF(ccount) BUF(cpts) BUF(crgb) BUF(crgb_in) /* point compaction */ \
     BUF(wls_u) BUF(wls_v) BUF(wls_c)             /* sgm_wls_filter: float [H][W] planes u, v, c' (kernels_wls.h); sgm_trim releases these three by name */ \
+    BUF(lrc_f)                                   /* sgm_lrc_confidence: uint8 [pairs of a chunk][2][H][W], the smoothness factors (kernels_lrc.h); sgm_trim releases it by name */ \
     BUF(headroom)                                /* uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r */ \
     BUF(chain_ctl) BUF(chain_err)                /* chained sweeps: ticket + progress words (zeroed before every launch); sticky give-up flag */ \
     ARR(io, [2][5])                              /* sgm_compute_batch, throughput mode: the transfer slots (sgm_engine says what they hold) */
@@ -2030,7 +2032,7 @@ int sgm_trim(sgm_engine *e)
     e->pin_disp.release();
     for (auto &slot : e->pin_io)
         for (HostBuf &b : slot) b.release();
-    for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c}) (void)b->release();   // the filter's planes come back on its next call
+    for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f}) (void)b->release();   // the filter's planes and the LR confidence's factors come back on the next call
     return check_chain(e);
 }
 
@@ -3154,6 +3156,134 @@ int sgm_wls_filter_batch(sgm_engine *e, int N, const int16_t *disp, const uint8_
         HIP_TRY(hipMemcpyAsync(out + o, e->disp_out.p, n * npx * 2, hipMemcpyDeviceToHost, e->stream));
         if (out_f32) HIP_TRY(hipMemcpyAsync(out_f32 + o, e->f32.p, n * pb, hipMemcpyDeviceToHost, e->stream));
     }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SGM_OK;
+}
+
+// ---- the left-right consistency confidence (include/sgm_hip_lrc.h, kernels_lrc.h) ---------------------------------------------
+// One pair is a batch of one: the single entries and the batch entry run the same two kernels.
+static int lrc_check_args(const sgm_engine *e, const void *left, const void *right, int H, int W, int invalid, int thresh, int radius,
+                          int var_max, const void *cl, const void *cr)
+{
+    if (!e || !left || !right) return set_err(SGM_ERR_INVALID_ARG, "sgm_lrc_confidence: null pointer");
+    if (!cl && !cr) return set_err(SGM_ERR_INVALID_ARG, "sgm_lrc_confidence: both outputs are null");
+    if (H <= 0 || W <= 0) return set_err(SGM_ERR_INVALID_ARG, "sgm_lrc_confidence: bad shape H=%d W=%d", H, W);
+    if (invalid < -32768 || invalid > 32767) return set_err(SGM_ERR_INVALID_ARG, "sgm_lrc_confidence: invalid value %d outside int16", invalid);
+    if (thresh < 0 || thresh > 32767) return set_err(SGM_ERR_INVALID_ARG, "sgm_lrc_confidence: thresh %d outside 0 .. 32767", thresh);
+    if (radius < 0 || radius > LRC_RMAX) return set_err(SGM_ERR_INVALID_ARG, "sgm_lrc_confidence: radius %d outside 0 .. %d", radius, LRC_RMAX);
+    if (var_max < 1 || var_max > (1 << 30)) return set_err(SGM_ERR_INVALID_ARG, "sgm_lrc_confidence: var_max %d outside 1 .. 2^30", var_max);
+    return SGM_OK;
+}
+
+// no output of any pair is an input of any pair, or another output
+static int lrc_check_overlap(int N, const void *const *left, const void *const *right, const void *const *base, const void *const *cl,
+                             const void *const *cr)
+{
+    std::vector<const void *> in, out;
+    for (int i = 0; i < N; i++) {
+        in.push_back(left[i]);
+        in.push_back(right[i]);
+        if (base) in.push_back(base[i]);
+        if (cl) out.push_back(cl[i]);
+        if (cr) out.push_back(cr[i]);
+    }
+    std::sort(in.begin(), in.end());
+    std::sort(out.begin(), out.end());
+    for (size_t k = 0; k < out.size(); k++)
+        if (std::binary_search(in.begin(), in.end(), out[k]) || (k && out[k] == out[k - 1]))
+            return set_err(SGM_ERR_INVALID_ARG, "sgm_lrc_confidence: an output is also an input or another output (outputs must not overlap anything)");
+    return SGM_OK;
+}
+
+// One chunk of n <= WLS_BATCH_MAX pairs, arguments checked, lrc_f holding n pairs of planes: factor, match.
+static int run_lrc_batch(sgm_engine *e, int n, const void *const *d_left, const void *const *d_right, const void *const *d_base, int H,
+                         int W, int invalid, int thresh, int radius, int var_max, void *const *d_cl, void *const *d_cr)
+{
+    WlsPtrs lefts{}, rights{}, bases{}, cls{}, crs{};
+    for (int i = 0; i < n; i++) {
+        lefts.p[i] = (void *)d_left[i];
+        rights.p[i] = (void *)d_right[i];
+        bases.p[i] = d_base ? (void *)d_base[i] : nullptr;
+        cls.p[i] = d_cl ? d_cl[i] : nullptr;
+        crs.p[i] = d_cr ? d_cr[i] : nullptr;
+    }
+    uint8_t *fac = (uint8_t *)e->lrc_f.p;
+    int rc;
+    stage_break(e);
+    if ((rc = stage_begin(e, "lrc_factor"))) return rc;
+    hipLaunchKernelGGL(k_lrc_factor, dim3((W + LRC_TW - 1) / LRC_TW, (H + LRC_TH - 1) / LRC_TH, 2 * n), dim3(LRC_THREADS),
+                       lrc_lds_bytes(radius), e->stream, lefts, rights, invalid, radius, (int64_t)var_max, H, W, fac);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    if ((rc = stage_begin(e, "lrc_match"))) return rc;
+    hipLaunchKernelGGL(k_lrc_match, dim3((W + 255) / 256, H, n), dim3(256), 0, e->stream, lefts, rights, bases, invalid, thresh, H, W,
+                       (const uint8_t *)fac, cls, crs);
+    KCHECK();
+    return stage_end(e, 1);
+}
+
+int sgm_lrc_confidence_batch_device(sgm_engine *e, int N, const void *const *d_lefts, const void *const *d_rights,
+                                    const void *const *d_bases, int H, int W, int invalid, int thresh, int radius, int var_max,
+                                    void *const *d_conf_lefts, void *const *d_conf_rights)
+{
+    if (N <= 0) return set_err(SGM_ERR_INVALID_ARG, "sgm_lrc_confidence_batch: N=%d pairs", N);
+    if (int rc = lrc_check_args(e, d_lefts, d_rights, H, W, invalid, thresh, radius, var_max, d_conf_lefts, d_conf_rights)) return rc;
+    for (int i = 0; i < N; i++)
+        if (!d_lefts[i] || !d_rights[i] || (d_bases && !d_bases[i]) || (d_conf_lefts && !d_conf_lefts[i]) ||
+            (d_conf_rights && !d_conf_rights[i]))
+            return set_err(SGM_ERR_INVALID_ARG, "sgm_lrc_confidence_batch: null pointer for pair %d", i);
+    if (int rc = lrc_check_overlap(N, d_lefts, d_rights, d_bases, d_conf_lefts, d_conf_rights)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    int rc, C = 1;
+    if ((rc = wls_batch_reserve(e, N, {{&e->lrc_f, (size_t)H * W * 2}}, &C))) return rc;
+    if (e->profile) {   // the stage record is the call's from here on
+        e->nstages = 0;
+        e->nevents = 0;
+        e->last_end_ev = -1;
+    }
+    for (int i0 = 0; i0 < N; i0 += C)
+        if ((rc = run_lrc_batch(e, std::min(C, N - i0), d_lefts + i0, d_rights + i0, d_bases ? d_bases + i0 : nullptr, H, W, invalid,
+                                thresh, radius, var_max, d_conf_lefts ? d_conf_lefts + i0 : nullptr,
+                                d_conf_rights ? d_conf_rights + i0 : nullptr)))
+            return rc;
+    return SGM_OK;
+}
+
+int sgm_lrc_confidence_device(sgm_engine *e, const void *d_left_i16, const void *d_right_i16, const void *d_base_u8, int H, int W,
+                              int invalid, int thresh, int radius, int var_max, void *d_conf_left_u8, void *d_conf_right_u8)
+{
+    if (int rc = lrc_check_args(e, d_left_i16, d_right_i16, H, W, invalid, thresh, radius, var_max, d_conf_left_u8, d_conf_right_u8))
+        return rc;
+    return sgm_lrc_confidence_batch_device(e, 1, &d_left_i16, &d_right_i16, d_base_u8 ? &d_base_u8 : nullptr, H, W, invalid, thresh,
+                                           radius, var_max, d_conf_left_u8 ? &d_conf_left_u8 : nullptr,
+                                           d_conf_right_u8 ? &d_conf_right_u8 : nullptr);
+}
+
+int sgm_lrc_confidence(sgm_engine *e, const int16_t *disp_left, const int16_t *disp_right, const uint8_t *base, int H, int W,
+                       int invalid, int thresh, int radius, int var_max, uint8_t *conf_left, uint8_t *conf_right)
+{
+    if (int rc = lrc_check_args(e, disp_left, disp_right, H, W, invalid, thresh, radius, var_max, conf_left, conf_right)) return rc;
+    {
+        const void *l = disp_left, *r = disp_right, *b = base, *cl = conf_left, *cr = conf_right;
+        if (int rc = lrc_check_overlap(1, &l, &r, base ? &b : nullptr, conf_left ? &cl : nullptr, conf_right ? &cr : nullptr)) return rc;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t npx = (size_t)H * W;
+    int rc;
+    // staging: the left map in disp_out, the right map in disp_raw, base in in_left, the two results in in_right and mask
+    if ((rc = e->disp_out.ensure(npx * 2)) || (rc = e->disp_raw.ensure(npx * 2)) || (base && (rc = e->in_left.ensure(npx))) ||
+        (conf_left && (rc = e->in_right.ensure(npx))) || (conf_right && (rc = e->mask.ensure(npx))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(e->disp_out.p, disp_left, npx * 2, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->disp_raw.p, disp_right, npx * 2, hipMemcpyHostToDevice, e->stream));
+    if (base) HIP_TRY(hipMemcpyAsync(e->in_left.p, base, npx, hipMemcpyHostToDevice, e->stream));
+    if ((rc = sgm_lrc_confidence_device(e, e->disp_out.p, e->disp_raw.p, base ? e->in_left.p : nullptr, H, W, invalid, thresh, radius,
+                                        var_max, conf_left ? e->in_right.p : nullptr, conf_right ? e->mask.p : nullptr))) {
+        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
+        return rc;
+    }
+    if (conf_left) HIP_TRY(hipMemcpyAsync(conf_left, e->in_right.p, npx, hipMemcpyDeviceToHost, e->stream));
+    if (conf_right) HIP_TRY(hipMemcpyAsync(conf_right, e->mask.p, npx, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return SGM_OK;
 }

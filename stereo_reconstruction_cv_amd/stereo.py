@@ -409,6 +409,41 @@ class Engine:
         _check(self._L.sgm_wls_filter_batch_device(self._h, n, arr(d_disps), arr(d_guides), int(cn), arr(d_confs), H, W, int(invalid),
                                                    float(lambda_), lut.ctypes.data, arr(d_outs), arr(d_out_f32s)))
 
+    # -- the left-right consistency confidence (include/sgm_hip_lrc.h) --
+    def lrc_confidence_host(self, disp_left: np.ndarray, disp_right: np.ndarray, base: np.ndarray | None, invalid: int, thresh: int,
+                            radius: int, var_max: int, want_left: bool = True, want_right: bool = False):
+        """sgm_lrc_confidence: int16 (H, W) left-view and right-view maps, uint8 (H, W) base confidence or None; returns
+        (conf_left, conf_right), uint8 (H, W) each, None for the one that was not asked for."""
+        disp_left = np.ascontiguousarray(disp_left, np.int16)
+        disp_right = np.ascontiguousarray(disp_right, np.int16)
+        base = None if base is None else np.ascontiguousarray(base, np.uint8)
+        H, W = disp_left.shape
+        cl = np.empty((H, W), np.uint8) if want_left else None
+        cr = np.empty((H, W), np.uint8) if want_right else None
+        _check(self._L.sgm_lrc_confidence(self._h, disp_left.ctypes.data, disp_right.ctypes.data,
+                                          None if base is None else base.ctypes.data, H, W, int(invalid), int(thresh), int(radius),
+                                          int(var_max), None if cl is None else cl.ctypes.data, None if cr is None else cr.ctypes.data))
+        return cl, cr
+
+    def lrc_confidence_device(self, d_left: int, d_right: int, d_base: int | None, H: int, W: int, invalid: int, thresh: int,
+                              radius: int, var_max: int, d_conf_left: int | None, d_conf_right: int | None = None) -> None:
+        """sgm_lrc_confidence_device: device addresses, in the order of the engine's stream."""
+        _check(self._L.sgm_lrc_confidence_device(self._h, d_left, d_right, d_base, H, W, int(invalid), int(thresh), int(radius),
+                                                 int(var_max), d_conf_left, d_conf_right))
+
+    def lrc_confidence_batch_device(self, d_lefts, d_rights, d_bases, H: int, W: int, invalid: int, thresh: int, radius: int,
+                                    var_max: int, d_conf_lefts, d_conf_rights=None) -> None:
+        """sgm_lrc_confidence_batch_device: sequences of N device addresses (d_bases / d_conf_lefts / d_conf_rights: such a
+        sequence, or None for none), in the order of the engine's stream."""
+        n = len(d_lefts)
+        arr = lambda xs: (C.c_void_p * len(xs))(*[int(x) if x else None for x in xs]) if xs is not None and len(xs) else None
+        for xs in (d_rights, d_bases, d_conf_lefts, d_conf_rights):
+            if xs is not None and len(xs) != n:
+                raise error(f"lrc_confidence_batch_device: {n} pairs, but a sequence of {len(xs)} addresses")
+        _check(self._L.sgm_lrc_confidence_batch_device(self._h, n, arr(d_lefts), arr(d_rights), arr(d_bases), H, W, int(invalid),
+                                                       int(thresh), int(radius), int(var_max), arr(d_conf_lefts),
+                                                       arr(d_conf_rights)))
+
 
 # The notebook builds a matcher per call and throws it away (main.ipynb:655-668); engines are
 # cached per (parameters, device) so device buffers survive between such calls.
@@ -518,30 +553,44 @@ class StereoSGBM:
         aggregates the paths again on the swapped pair; here they are the left view's."""
         return self._compute(left, right, False, True)
 
-    def computeFiltered(self, left, right, lambda_=8000.0, sigmaColor=1.5):
-        """computeWithConfidence() followed by the edge-aware filter (createDisparityWLSFilter) with `left` as the guide and the
-        confidence map as its weights: int16 (H, W) disparity * 16 with the holes filled from confident neighbours, invalid
-        (minDisparity - 1) * 16 only where no confidence reaches.  Colour pairs guide with all three channels.  numpy in, numpy
-        out; HIP tensors in, a tensor out without leaving the device."""
-        disp, conf = self.computeWithConfidence(left, right)
+    def computeFiltered(self, left, right, lambda_=8000.0, sigmaColor=1.5, confidence="margin"):
+        """A compute followed by the edge-aware filter (createDisparityWLSFilter) with `left` as the guide: int16 (H, W)
+        disparity * 16 with the holes filled from confident neighbours, invalid (minDisparity - 1) * 16 only where no confidence
+        reaches.  Colour pairs guide with all three channels.  numpy in, numpy out; HIP tensors in, a tensor out without leaving
+        the device.  confidence says what weighs the filter:
+          "margin"  (default) computeWithConfidence()'s uniqueness margin;
+          "lrc"     the left-right consistency confidence (lrcConfidence, include/sgm_hip_lrc.h) of computeLeftRight()'s two
+                    maps, with the filter's default threshold, radius and variance: one more pass over the aggregated cost;
+          "both"    the same with the margin as its base: both optional maps of one compute."""
+        _check_confidence_source(confidence)
         f = DisparityWLSFilter(self)
         f.setLambda(lambda_)
         f.setSigmaColor(sigmaColor)
         guide = left if _is_torch(left) else np.asarray(left)
         if len(guide.shape) == 3 and guide.shape[2] == 1:
             guide = guide[:, :, 0]
-        return f.filter(disp, guide, conf)
+        if confidence == "margin":
+            disp, conf = self.computeWithConfidence(left, right)
+            return f.filter(disp, guide, conf)
+        if confidence == "lrc":
+            disp, rmap = self.computeLeftRight(left, right)
+            return f.filter(disp, guide, None, disparity_map_right=rmap)
+        disp, conf, rmap = self._compute(left, right, True, True)
+        return f.filter(disp, guide, conf, disparity_map_right=rmap)
 
-    def computeFilteredBatch(self, lefts, rights, lambda_=8000.0, sigmaColor=1.5):
+    def computeFilteredBatch(self, lefts, rights, lambda_=8000.0, sigmaColor=1.5, confidence="margin"):
         """computeFiltered() over N pairs of one shape: ONE batch compute with the confidence maps delivered per pair (the
         engine's sgm_pipeline_batch_device behind sgm_bind_confidence_device) and ONE batch filter call
-        (sgm_wls_filter_batch_device) with `lefts` as the guides, both on the same engine.  lefts / rights: uint8 stacks
+        (sgm_wls_filter_batch_device) with `lefts` as the guides, both on the same engine.  confidence as in computeFiltered():
+        "lrc" and "both" also bind the right-view maps in the same batch compute (sgm_bind_right_device) and put ONE batch
+        confidence call (sgm_lrc_confidence_batch_device) between the compute and the filter, on the same engine and stream.  lefts / rights: uint8 stacks
         (N, H, W) or (N, H, W, 3), or sequences of N equal-shaped images; numpy (uploaded through torch, a numpy stack comes
         back) or HIP tensors (a tensor (N, H, W) comes back without leaving the device).  Result i equals
         computeFiltered(lefts[i], rights[i]) bit for bit.
         No synchronisation lies between the two calls: the batch compute leaves the engine's stream behind everything its
         internal engines did (run_group joins their streams into it; without a chained group the pairs run on that stream
         itself), and the filter is enqueued on the same stream."""
+        _check_confidence_source(confidence)
         if self._p["mode"] not in (STEREO_SGBM_MODE_SGBM, STEREO_SGBM_MODE_HH, STEREO_SGBM_MODE_HH4):
             raise error("StereoSGBM.compute: MODE_SGBM, MODE_HH and MODE_HH4 are implemented; MODE_SGBM_3WAY is not "
                         "(its result depends on a stripe size upstream derives from the cache size)")
@@ -586,8 +635,22 @@ class StereoSGBM:
             ptrs = lambda ts: [t.data_ptr() for t in ts]
             # the engine runs on its own stream: order it after torch's current stream and wait for it (as _compute_torch does)
             torch.cuda.current_stream(dev).synchronize()
-            with _option_for_this_call(eng, _lib.SGM_OPT_CONFIDENCE):
-                eng.pipeline_batch_device(ptrs(L), ptrs(R), H, W, cn * W, None, ptrs(disp), cn=cn, d_confs=ptrs(conf))
+            if confidence == "margin":
+                with _option_for_this_call(eng, _lib.SGM_OPT_CONFIDENCE):
+                    eng.pipeline_batch_device(ptrs(L), ptrs(R), H, W, cn * W, None, ptrs(disp), cn=cn, d_confs=ptrs(conf))
+            else:
+                # conf receives the LR confidence; with "both" the margin goes to a stack of its own and is the base
+                rmap = torch.empty((N, H, W), dtype=torch.int16, device=dev)
+                base = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if confidence == "both" else None
+                with contextlib.ExitStack() as on:
+                    on.enter_context(_option_for_this_call(eng, _lib.SGM_OPT_RIGHT_VIEW))
+                    if base is not None:
+                        on.enter_context(_option_for_this_call(eng, _lib.SGM_OPT_CONFIDENCE))
+                    eng.pipeline_batch_device(ptrs(L), ptrs(R), H, W, cn * W, None, ptrs(disp), cn=cn,
+                                              d_confs=None if base is None else ptrs(base), d_rmaps=ptrs(rmap))
+                eng.lrc_confidence_batch_device(ptrs(disp), ptrs(rmap), None if base is None else ptrs(base), H, W, f.defaultInvalid(),
+                                                f.getLRCthresh(), f.getDepthDiscontinuityRadius(), f.getDiscontinuityVariance(),
+                                                ptrs(conf))
             eng.wls_filter_batch_device(ptrs(disp), ptrs(L), cn, ptrs(conf), H, W, f.defaultInvalid(), lambda_, wls_weights(sigmaColor),
                                         ptrs(out))
             eng.synchronize()
@@ -624,10 +687,14 @@ class StereoSGBM:
         try:
             if not (with_right or with_conf):
                 return eng.compute_host(left, right)
-            opt, tap = (_lib.SGM_OPT_RIGHT_VIEW, _lib.SGM_TAP_RIGHT) if with_right else (_lib.SGM_OPT_CONFIDENCE, _lib.SGM_TAP_CONF)
-            with _option_for_this_call(eng, opt):
+            # one option: (disp, its map); both (computeFiltered's confidence="both"): (disp, conf, right)
+            sides = ([(_lib.SGM_OPT_CONFIDENCE, _lib.SGM_TAP_CONF)] if with_conf else []) + \
+                    ([(_lib.SGM_OPT_RIGHT_VIEW, _lib.SGM_TAP_RIGHT)] if with_right else [])
+            with contextlib.ExitStack() as on:
+                for opt, _ in sides:
+                    on.enter_context(_option_for_this_call(eng, opt))
                 disp = eng.compute_host(left, right)
-                return disp, eng.tap(tap, *disp.shape)
+                return (disp,) + tuple(eng.tap(tap, *disp.shape) for _, tap in sides)
         finally:
             eng.set_option(_lib.SGM_OPT_COST, STEREO_COST_BT)   # the cached engine goes back as get_engine() hands it out
 
@@ -654,14 +721,21 @@ class StereoSGBM:
                 eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn)
                 eng.synchronize()
                 return out
-            side = torch.empty((H, W), dtype=torch.int16 if with_right else torch.uint8, device=left.device)
-            bound = dict(d_rmap=side.data_ptr()) if with_right else dict(d_conf=side.data_ptr())
-            with _option_for_this_call(eng, _lib.SGM_OPT_RIGHT_VIEW if with_right else _lib.SGM_OPT_CONFIDENCE):
+            sides, bound = [], {}
+            with contextlib.ExitStack() as on:
+                if with_conf:
+                    sides.append(torch.empty((H, W), dtype=torch.uint8, device=left.device))
+                    bound["d_conf"] = sides[-1].data_ptr()
+                    on.enter_context(_option_for_this_call(eng, _lib.SGM_OPT_CONFIDENCE))
+                if with_right:
+                    sides.append(torch.empty((H, W), dtype=torch.int16, device=left.device))
+                    bound["d_rmap"] = sides[-1].data_ptr()
+                    on.enter_context(_option_for_this_call(eng, _lib.SGM_OPT_RIGHT_VIEW))
                 eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, cn * W, out.data_ptr(), cn, **bound)
                 eng.synchronize()
         finally:
             eng.set_option(_lib.SGM_OPT_COST, STEREO_COST_BT)   # (as in _compute)
-        return out, side
+        return (out,) + tuple(sides)
 
 
 def _batch_items(x) -> list:
@@ -692,6 +766,75 @@ def StereoSGBM_create(minDisparity=0, numDisparities=16, blockSize=3, P1=0, P2=0
 
 
 
+_CONFIDENCE_SOURCES = ("margin", "lrc", "both")
+
+
+def _check_confidence_source(confidence) -> None:
+    if not isinstance(confidence, str) or confidence not in _CONFIDENCE_SOURCES:
+        raise error(f"StereoSGBM.computeFiltered: confidence={confidence!r} is none of 'margin', 'lrc', 'both'")
+
+
+LRC_THRESH_DEFAULT, LRC_RADIUS_DEFAULT, LRC_VAR_MAX_DEFAULT = 24, 5, 2304
+LRC_RADIUS_MAX = 16
+
+
+def _lrc_int(who: str, name: str, v, lo: int, hi: int) -> int:
+    """an integer argument of the LR confidence inside its range (include/sgm_hip_lrc.h), or cv.error"""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise error(f"{who}: {name}={v!r} is not an integer in {lo} .. {hi}")
+    return int(v)
+
+
+def _lrc_check_maps(who: str, dl, dr, base, i16, u8) -> None:
+    """the right map (and base) against the left map: dtype, rank, shape"""
+    if dl.dtype != i16 or dr.dtype != i16 or (base is not None and base.dtype != u8):
+        raise error(f"{who}: (-215:Assertion failed) disparity_map_left.type() == CV_16SC1, disparity_map_right.type() == CV_16SC1, "
+                    "confidence.type() == CV_8UC1")
+    if len(dl.shape) != 2:
+        raise error(f"{who}: the maps must be (H, W)")
+    if tuple(dr.shape) != tuple(dl.shape) or (base is not None and tuple(base.shape) != tuple(dl.shape)):
+        raise error(f"{who}: (-215:Assertion failed) the left map, the right map and the confidence must have the same size")
+    if dl.shape[0] == 0 or dl.shape[1] == 0:
+        raise error(f"{who}: empty image")
+
+
+def lrcConfidence(disp_left, disp_right, base=None, invalid=-16, thresh=LRC_THRESH_DEFAULT, radius=LRC_RADIUS_DEFAULT,
+                  var_max=LRC_VAR_MAX_DEFAULT, return_right=False):
+    """The left-right consistency confidence (definition: include/sgm_hip_lrc.h): uint8 (H, W) in 0 .. 100 from the int16 maps of
+    computeLeftRight() -- 0 where the two maps disagree by more than thresh sixteenths, where either is invalid and where the
+    match leaves the image; elsewhere 100 minus the roughness of the maps inside a (2 radius + 1)^2 window against var_max
+    (sixteenths squared), and no more than base (uint8 (H, W), computeWithConfidence's margin) when that is given.  Returns the
+    left-view map, with return_right (left, right).  numpy in, numpy out; HIP tensors in, tensors out on the same device.
+    This package's own definition in integers, NOT cv2's computeConfidenceMap bit for bit; cv2's ROI handling is not built."""
+    who = "lrcConfidence"
+    inv = _lrc_int(who, "invalid", invalid, -32768, 32767)
+    T = _lrc_int(who, "thresh", thresh, 0, 32767)
+    r = _lrc_int(who, "radius", radius, 0, LRC_RADIUS_MAX)
+    V = _lrc_int(who, "var_max", var_max, 1, 1 << 30)
+    maps = [disp_left, disp_right] + ([] if base is None else [base])
+    if any(_is_torch(m) for m in maps):
+        import torch
+        if not all(_is_torch(m) and m.is_cuda for m in maps):
+            raise error(f"{who}: torch inputs must all be CUDA (HIP) tensors")
+        _lrc_check_maps(who, disp_left, disp_right, base, torch.int16, torch.uint8)
+        dl, dr = disp_left.contiguous(), disp_right.contiguous()
+        b = None if base is None else base.contiguous()
+        H, W = int(dl.shape[0]), int(dl.shape[1])
+        eng = get_engine(_DEFAULT, dl.device.index or 0)
+        cl = torch.empty((H, W), dtype=torch.uint8, device=dl.device)
+        cr = torch.empty((H, W), dtype=torch.uint8, device=dl.device) if return_right else None
+        torch.cuda.current_stream(dl.device).synchronize()   # (as _compute_torch does)
+        eng.lrc_confidence_device(dl.data_ptr(), dr.data_ptr(), None if b is None else b.data_ptr(), H, W, inv, T, r, V,
+                                  cl.data_ptr(), None if cr is None else cr.data_ptr())
+        eng.synchronize()
+        return (cl, cr) if return_right else cl
+    dl, dr = np.asarray(disp_left), np.asarray(disp_right)
+    b = None if base is None else np.asarray(base)
+    _lrc_check_maps(who, dl, dr, b, np.int16, np.uint8)
+    cl, cr = get_engine(_DEFAULT).lrc_confidence_host(dl, dr, b, inv, T, r, V, True, bool(return_right))
+    return (cl, cr) if return_right else cl
+
+
 def wls_weights(sigma: float) -> np.ndarray:
     """The filter's default edge weights (sgm_wls_weights): float32 [256], exp(-k / sigma).  Needs no GPU."""
     lut = np.empty(256, np.float32)
@@ -702,12 +845,52 @@ def wls_weights(sigma: float) -> np.ndarray:
 class DisparityWLSFilter:
     """The place cv2.ximgproc.createDisparityWLSFilter takes in cv2 user code: a confidence-weighted, image-guided fast global
     smoother over a disparity map (definition: include/sgm_hip_wls.h).  It is this package's own definition, NOT cv2's filter
-    bit for bit: cv2's ROI handling, its LR-consistency confidence and its depthDiscontinuityRadius are not built."""
+    bit for bit.  With a right-view map (filter(..., disparity_map_right=)) its weights are the left-right consistency
+    confidence of include/sgm_hip_lrc.h, steered by setLRCthresh, setDepthDiscontinuityRadius and setDiscontinuityVariance and
+    handed back by getConfidenceMap: the call shape of cv2's filter, a definition of our own in integers.  What remains
+    unbuilt: cv2's ROI handling, and bit parity with cv2's filter and with its confidence map."""
 
     def __init__(self, matcher_left=None):
         self._matcher = matcher_left
         self._lambda = 8000.0
         self._sigma = 1.5
+        self._lrc_thresh = LRC_THRESH_DEFAULT
+        # cv2's default: ceil(0.5 * blockSize) of the matcher; 5 without one; capped to what the kernel's halo holds
+        self._radius = min(LRC_RADIUS_MAX, (int(matcher_left.getBlockSize()) + 1) // 2) if matcher_left is not None else LRC_RADIUS_DEFAULT
+        self._radius = max(0, self._radius)
+        self._var_max = LRC_VAR_MAX_DEFAULT
+        self._conf_map = None
+
+    def setLRCthresh(self, thresh):
+        """Largest difference of the two maps at a match, in sixteenths of a pixel (cv2: LRCthresh, default 24), 0 .. 32767"""
+        self._lrc_thresh = _lrc_int("DisparityWLSFilter.setLRCthresh", "thresh", thresh, 0, 32767)
+
+    def getLRCthresh(self):
+        return self._lrc_thresh
+
+    def setDepthDiscontinuityRadius(self, radius):
+        """Half width of the window the roughness of the maps is measured in, 0 .. 16 pixels; 0 switches that factor off.
+        Default: ceil(0.5 * blockSize) of the matcher, 5 without one, capped to 16."""
+        self._radius = _lrc_int("DisparityWLSFilter.setDepthDiscontinuityRadius", "radius", radius, 0, LRC_RADIUS_MAX)
+
+    def getDepthDiscontinuityRadius(self):
+        return self._radius
+
+    def setDiscontinuityVariance(self, var_max):
+        """The variance inside the window, in sixteenths squared, at which the confidence reaches 0: 1 .. 2^30, default 2304
+        (a standard deviation of three pixels).  No counterpart in cv2."""
+        self._var_max = _lrc_int("DisparityWLSFilter.setDiscontinuityVariance", "var_max", var_max, 1, 1 << 30)
+
+    def getDiscontinuityVariance(self):
+        return self._var_max
+
+    def getConfidenceMap(self):
+        """The confidence the last filter() / filterBatch() call with a right-view map weighed the filter with: uint8 (H, W) in
+        0 .. 100, a stack (N, H, W) after filterBatch; numpy or a HIP tensor, as that call's inputs were.  Raises before any
+        such call.  (cv2 returns float32 in 0 .. 255, and another definition: include/sgm_hip_lrc.h.)"""
+        if self._conf_map is None:
+            raise error("DisparityWLSFilter.getConfidenceMap: no filter() call with disparity_map_right has been made")
+        return self._conf_map
 
     def setLambda(self, lambda_):
         v = float(lambda_)
@@ -734,16 +917,21 @@ class DisparityWLSFilter:
     def _params(self):
         return self._matcher._p if self._matcher is not None else _DEFAULT
 
-    def filter(self, disparity_map_left, left_view, confidence=None, invalid=None, return_float=False):
+    def filter(self, disparity_map_left, left_view, confidence=None, invalid=None, return_float=False, disparity_map_right=None):
         """disparity_map_left: int16 (H, W), disparity * 16; left_view: the uint8 guide, (H, W) or (H, W, 3); confidence: uint8
         (H, W) in 0 .. 100 (computeWithConfidence's map) or None for full confidence on every valid pixel; invalid: the value
         that marks invalid pixels, by default (matcher_left.minDisparity - 1) * 16, -16 without a matcher.  Returns the filtered
         int16 map, with return_float (map, float32 disparity in pixels, 0 where invalid).  numpy in, numpy out; HIP tensors in,
-        tensors out on the same device."""
+        tensors out on the same device.
+        disparity_map_right: the right-view map of computeLeftRight(), int16 (H, W), or None.  With it the filter is weighed
+        with the left-right consistency confidence of the two maps (lrcConfidence with this object's LRCthresh,
+        depthDiscontinuityRadius and discontinuity variance, `confidence` as its base), which getConfidenceMap() hands back.
+        cv2 spells this call wls.filter(disp_left, left, None, disp_right)."""
         inv = self.defaultInvalid() if invalid is None else int(invalid)
         if not -32768 <= inv <= 32767:
             raise error(f"DisparityWLSFilter.filter: invalid value {inv} outside int16")
-        maps = [disparity_map_left, left_view] + ([] if confidence is None else [confidence])
+        maps = [disparity_map_left, left_view] + ([] if confidence is None else [confidence]) + \
+               ([] if disparity_map_right is None else [disparity_map_right])
         on_device = any(_is_torch(m) for m in maps)
         if on_device:
             import torch
@@ -765,10 +953,18 @@ class DisparityWLSFilter:
         H, W = int(d.shape[0]), int(d.shape[1])
         if H == 0 or W == 0:
             raise error("DisparityWLSFilter.filter: empty image")
+        dr = None
+        if disparity_map_right is not None:
+            dr = disparity_map_right if on_device else np.asarray(disparity_map_right)
+            _lrc_check_maps("DisparityWLSFilter.filter", d, dr, c, i16, u8)
         lut = wls_weights(self._sigma)
         cn = 1 if len(g.shape) == 2 else 3
         if not on_device:
-            return get_engine(self._params()).wls_filter_host(d, g, c, inv, self._lambda, lut, return_float)
+            eng = get_engine(self._params())
+            if dr is not None:
+                c = eng.lrc_confidence_host(d, dr, c, inv, self._lrc_thresh, self._radius, self._var_max)[0]
+                self._conf_map = c
+            return eng.wls_filter_host(d, g, c, inv, self._lambda, lut, return_float)
         import torch
         d, g = d.contiguous(), g.contiguous()
         c = None if c is None else c.contiguous()
@@ -777,24 +973,33 @@ class DisparityWLSFilter:
         outf = torch.empty((H, W), dtype=torch.float32, device=d.device) if return_float else None
         # the engine runs on its own stream: order it after torch's current stream and wait for it (as _compute_torch does)
         torch.cuda.current_stream(d.device).synchronize()
+        if dr is not None:   # (both calls on the engine's stream, in order)
+            dr, base = dr.contiguous(), c
+            c = torch.empty((H, W), dtype=torch.uint8, device=d.device)
+            eng.lrc_confidence_device(d.data_ptr(), dr.data_ptr(), None if base is None else base.data_ptr(), H, W, inv,
+                                      self._lrc_thresh, self._radius, self._var_max, c.data_ptr())
+            self._conf_map = c
         eng.wls_filter_device(d.data_ptr(), g.data_ptr(), cn, None if c is None else c.data_ptr(), H, W, inv, self._lambda, lut,
                               out.data_ptr(), None if outf is None else outf.data_ptr())
         eng.synchronize()
         return (out, outf) if return_float else out
 
 
-    def filterBatch(self, disparity_maps, left_views, confidences=None, invalid=None, return_float=False):
+    def filterBatch(self, disparity_maps, left_views, confidences=None, invalid=None, return_float=False, disparity_maps_right=None):
         """filter() over N maps of one shape in one engine call (sgm_wls_filter_batch): disparity_maps int16 (N, H, W), left_views
         uint8 (N, H, W) or (N, H, W, 3), confidences uint8 (N, H, W) or None -- stacks, or sequences of N equal-shaped maps;
         invalid and return_float as in filter().  numpy in, a numpy stack (N, H, W) out (with return_float: two); HIP tensors in
         (a stacked tensor or a sequence of tensors), a tensor (N, H, W) out without leaving the device.  Map i of the result
-        equals filter() on map i alone, bit for bit."""
+        equals filter() on map i alone, bit for bit.
+        disparity_maps_right: the right-view maps, int16 (N, H, W) or a sequence, or None: as filter()'s disparity_map_right,
+        map by map; getConfidenceMap() then hands back the stack (N, H, W) of the confidences."""
         inv = self.defaultInvalid() if invalid is None else int(invalid)
         if not -32768 <= inv <= 32767:
             raise error(f"DisparityWLSFilter.filter: invalid value {inv} outside int16")
         D, G = _batch_items(disparity_maps), _batch_items(left_views)
         Cf = None if confidences is None else _batch_items(confidences)
-        maps = D + G + (Cf or [])
+        Dr = None if disparity_maps_right is None else _batch_items(disparity_maps_right)
+        maps = D + G + (Cf or []) + (Dr or [])
         on_device = any(_is_torch(m) for m in maps)
         if on_device:
             import torch
@@ -805,6 +1010,7 @@ class DisparityWLSFilter:
             i16, u8 = np.int16, np.uint8
             D, G = [np.asarray(m) for m in D], [np.asarray(m) for m in G]
             Cf = None if Cf is None else [np.asarray(m) for m in Cf]
+            Dr = None if Dr is None else [np.asarray(m) for m in Dr]
         if any(m.dtype != i16 for m in D) or any(m.dtype != u8 for m in G + (Cf or [])):
             raise error("DisparityWLSFilter.filter: (-215:Assertion failed) disparity_map_left.type() == CV_16SC1, "
                         "left_view.depth() == CV_8U, confidence.type() == CV_8UC1")
@@ -819,13 +1025,23 @@ class DisparityWLSFilter:
         N, (H, W) = len(D), shape
         if H == 0 or W == 0:
             raise error("DisparityWLSFilter.filter: empty image")
+        if Dr is not None:
+            if len(Dr) != N:
+                raise error("DisparityWLSFilter.filter: (-215:Assertion failed) the left map, the right map and the confidence must "
+                            "have the same size")
+            for i in range(N):
+                _lrc_check_maps("DisparityWLSFilter.filter", D[i], Dr[i], None, i16, u8)
         lut = wls_weights(self._sigma)
         cn = 1 if len(gshape) == 2 else 3
         if not on_device:
             stack = lambda x, items: np.ascontiguousarray(x) if isinstance(x, np.ndarray) else np.stack(items)
-            return get_engine(self._params()).wls_filter_batch_host(stack(disparity_maps, D), stack(left_views, G),
-                                                                    None if Cf is None else stack(confidences, Cf), inv, self._lambda,
-                                                                    lut, return_float)
+            eng = get_engine(self._params())
+            confs = None if Cf is None else stack(confidences, Cf)
+            if Dr is not None:   # (host maps: the confidence map by map through the host entry, then one batch filter call)
+                confs = np.stack([eng.lrc_confidence_host(D[i], Dr[i], None if Cf is None else Cf[i], inv, self._lrc_thresh,
+                                                          self._radius, self._var_max)[0] for i in range(N)])
+                self._conf_map = confs
+            return eng.wls_filter_batch_host(stack(disparity_maps, D), stack(left_views, G), confs, inv, self._lambda, lut, return_float)
         import torch
         D, G = [m.contiguous() for m in D], [m.contiguous() for m in G]
         Cf = None if Cf is None else [m.contiguous() for m in Cf]
@@ -836,6 +1052,13 @@ class DisparityWLSFilter:
         ptrs = lambda ts: None if ts is None else [t.data_ptr() for t in ts]
         # the engine runs on its own stream: order it after torch's current stream and wait for it (as filter() does)
         torch.cuda.current_stream(dev).synchronize()
+        if Dr is not None:   # (both batch calls on the engine's stream, in order, nothing in between)
+            Dr = [m.contiguous() for m in Dr]
+            confs = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+            eng.lrc_confidence_batch_device(ptrs(D), ptrs(Dr), ptrs(Cf), H, W, inv, self._lrc_thresh, self._radius, self._var_max,
+                                            ptrs(confs))
+            self._conf_map = confs
+            Cf = confs
         eng.wls_filter_batch_device(ptrs(D), ptrs(G), cn, ptrs(Cf), H, W, inv, self._lambda, lut, ptrs(out), ptrs(outf))
         eng.synchronize()
         return (out, outf) if return_float else out
