@@ -24,6 +24,7 @@ SGM_OPT_COST = 12        # the matching cost of every compute on the engine: SGM
 SGM_COST_BT, SGM_COST_CENSUS = 0, 1
 SGM_OPT_DEBUG = 4    # csrc/sgm_debug.h: A/B switches for tools/ and tests/, not part of the public interface
 SGM_OPT_POISON = 9   # csrc/sgm_debug.h: fill every device buffer with a byte (0..255) and arm the same for new ones; -1 disarms (tests only)
+SGM_DBG_VOXEL_TIGHT_TABLE, SGM_DBG_VOXEL_OTHER_REDUCTION = 1 << 22, 1 << 23   # csrc/sgm_debug.h: the two A/B bits of sgm_voxel_downsample
 SGM_MAX_STAGES = 32
 
 # every symbol include/sgm_hip.h declares (checked by tests/test_abi.py)
@@ -47,6 +48,8 @@ WLS_EXPORTS = ("sgm_wls_weights", "sgm_wls_filter", "sgm_wls_filter_device")
 WLS_BATCH_EXPORTS = ("sgm_wls_filter_batch", "sgm_wls_filter_batch_device")
 # include/sgm_hip_lrc.h (likewise): the left-right consistency confidence from a left-view and a right-view map
 LRC_EXPORTS = ("sgm_lrc_confidence", "sgm_lrc_confidence_device", "sgm_lrc_confidence_batch_device")
+# include/sgm_hip_voxel.h (likewise): voxel-grid downsampling of the point cloud
+VOXEL_EXPORTS = ("sgm_voxel_downsample", "sgm_voxel_downsample_device")
 
 
 class SgmParams(C.Structure):
@@ -133,6 +136,8 @@ def load():
     L.sgm_lrc_confidence.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
     L.sgm_lrc_confidence_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
     L.sgm_lrc_confidence_batch_device.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+    L.sgm_voxel_downsample.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float, vp, i32, vp, vp, vp, vp, vp]
+    L.sgm_voxel_downsample_device.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float, vp, i32, vp, vp, vp, vp, vp]
     L.sgm_synchronize.argtypes = [vp]
     L.sgm_get_stage_times.argtypes = [vp, C.POINTER(SgmStageTimes)]
     L.sgm_algorithmic_bytes.argtypes = [pp, i32, i32, i32]
@@ -157,7 +162,7 @@ def load():
     L.sgm_debug_wta_raw_bytes.restype = C.c_longlong
     L.sgm_debug_wta_select_n.argtypes = [i32, i32, vp, i32, vp]
     L.sgm_debug_wta_select_n.restype = i32
-    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS:
+    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS + VOXEL_EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("sgm_abi_version", "sgm_device_count"):
             fn.restype = i32

@@ -34,7 +34,10 @@ enum {
     /* sgm_wls_filter_batch*: the other shapes of the batched line kernels that DESIGN.md 4.16 measured (tools/wls_batch_times.py);
      * two small fields, not flags.  0 in a field is the shape the library uses; the results are the same bits for every value. */
     SGM_DBG_WLS_BATCH_ROWS_SHIFT = 17,     /* 3 bits: k_wls_rows_b<CN, RW, TC>, the index into wls_rows_shapes (sgm_engine.hip) */
-    SGM_DBG_WLS_BATCH_COLS_SHIFT = 20      /* 2 bits: k_wls_cols_b<CN, UNR>, the index into wls_cols_shapes */
+    SGM_DBG_WLS_BATCH_COLS_SHIFT = 20,     /* 2 bits: k_wls_cols_b<CN, UNR>, the index into wls_cols_shapes */
+    /* sgm_voxel_downsample* (tools/voxel_times.py); the results are the same bits under both */
+    SGM_DBG_VOXEL_TIGHT_TABLE = 1 << 22,   /* capacity = the smallest power of two >= the points in range (not twice them): the load can reach 1.0 */
+    SGM_DBG_VOXEL_OTHER_REDUCTION = 1 << 23 /* k_voxel_insert without the wave pre-reduction where it is the default (kernels_voxel.h: VOX_PRE_DEFAULT), with it where not */
 };
 
 /* Plan readout: what normalise + make_plan decide for one compute of a frame of H x W pixels on an engine with these

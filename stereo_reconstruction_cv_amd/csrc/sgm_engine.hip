@@ -30,6 +30,7 @@
 #include "kernels_right.h"
 #include "kernels_wls.h"
 #include "kernels_lrc.h"
+#include "kernels_voxel.h"
 
 using namespace sgm;
 
@@ -261,6 +262,7 @@ struct Plan {
     BUF(ccount) BUF(cpts) BUF(crgb) BUF(crgb_in) /* point compaction */ \
     BUF(wls_u) BUF(wls_v) BUF(wls_c)             /* sgm_wls_filter: float [H][W] planes u, v, c' (kernels_wls.h); sgm_trim releases these three by name */ \
     BUF(lrc_f)                                   /* sgm_lrc_confidence: uint8 [pairs of a chunk][2][H][W], the smoothness factors (kernels_lrc.h); sgm_trim releases it by name */ \
+    BUF(vox_tab) BUF(vox_slot) BUF(vox_ctl) BUF(vox_cnt) /* sgm_voxel_downsample: the hash table (VoxSlot [capacity]), each point's slot (uint32 [n]), the call's control words, the host entry's staged counts (kernels_voxel.h); sgm_trim releases the first two by name */ \
     BUF(headroom)                                /* uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r */ \
     BUF(chain_ctl) BUF(chain_err)                /* chained sweeps: ticket + progress words (zeroed before every launch); sticky give-up flag */ \
     ARR(io, [2][5])                              /* sgm_compute_batch, throughput mode: the transfer slots (sgm_engine says what they hold) */
@@ -2032,7 +2034,8 @@ int sgm_trim(sgm_engine *e)
     e->pin_disp.release();
     for (auto &slot : e->pin_io)
         for (HostBuf &b : slot) b.release();
-    for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f}) (void)b->release();   // the filter's planes and the LR confidence's factors come back on the next call
+    for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f, &e->vox_tab, &e->vox_slot})
+        (void)b->release();   // the filter's planes, the LR confidence's factors and the voxel table come back on the next call
     return check_chain(e);
 }
 
@@ -3285,6 +3288,137 @@ int sgm_lrc_confidence(sgm_engine *e, const int16_t *disp_left, const int16_t *d
     if (conf_left) HIP_TRY(hipMemcpyAsync(conf_left, e->in_right.p, npx, hipMemcpyDeviceToHost, e->stream));
     if (conf_right) HIP_TRY(hipMemcpyAsync(conf_right, e->mask.p, npx, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return SGM_OK;
+}
+
+// ---- voxel-grid downsampling (include/sgm_hip_voxel.h, kernels_voxel.h) ------------------------------------------------------
+static int voxel_check_args(const sgm_engine *e, const void *xyz, const void *colors, int64_t n, float v, const float *origin,
+                            int min_points, const void *out_points, const void *out_colors, const int64_t *n_voxels)
+{
+    if (!e || !xyz || !out_points || !n_voxels) return set_err(SGM_ERR_INVALID_ARG, "sgm_voxel_downsample: null pointer");
+    if (n < 0) return set_err(SGM_ERR_INVALID_ARG, "sgm_voxel_downsample: n=%lld points", (long long)n);
+    if (!std::isfinite(v) || !(v > 0.0f) || !std::isfinite(1.0f / v))
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_voxel_downsample: voxel_size %g is not finite and positive with a finite reciprocal", (double)v);
+    if (!origin || !std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_voxel_downsample: the origin is null or not finite");
+    if (min_points < 1) return set_err(SGM_ERR_INVALID_ARG, "sgm_voxel_downsample: min_points %d < 1", min_points);
+    if (out_colors && !colors) return set_err(SGM_ERR_INVALID_ARG, "sgm_voxel_downsample: out_colors requested without colors");
+    if (n > VOX_MAX_POINTS)
+        return set_err(SGM_ERR_UNSUPPORTED, "sgm_voxel_downsample: %lld points, more than 2^24 - 1 (the widths of a voxel's sums)", (long long)n);
+    return SGM_OK;
+}
+
+int sgm_voxel_downsample_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int64_t n,
+                                float voxel_size, const float origin[3], int min_points, void *d_out_points, void *d_out_colors,
+                                void *d_out_counts, int64_t *n_voxels, int64_t *n_out_of_range)
+{
+    if (int rc = voxel_check_args(e, d_xyz, d_colors_rgb, n, voxel_size, origin, min_points, d_out_points, d_out_colors, n_voxels)) return rc;
+    if (n == 0) {
+        *n_voxels = 0;
+        if (n_out_of_range) *n_out_of_range = 0;
+        return SGM_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const int m = (int)((n + 255) / 256);
+    int rc;
+    if ((rc = e->vox_ctl.ensure(VOX_CTL_WORDS * 4)) || (rc = e->vox_slot.ensure((size_t)n * 4)) || (rc = e->ccount.ensure((size_t)(m + 1) * 4)))
+        return rc;
+    if (e->profile) {   // the stage record is the call's from here on
+        e->nstages = 0;
+        e->nevents = 0;
+        e->last_end_ev = -1;
+    }
+    const VoxGrid G{1.0f / voxel_size, voxel_size, origin[0], origin[1], origin[2]};
+    const float *xyz = (const float *)d_xyz, *disp = (const float *)d_disp_f32;
+    const uint8_t *colors = (const uint8_t *)(d_out_colors ? d_colors_rgb : nullptr);
+    uint32_t *ctl = (uint32_t *)e->vox_ctl.p, *slot_of = (uint32_t *)e->vox_slot.p, *cnt = (uint32_t *)e->ccount.p;
+    hipStream_t st = e->stream;
+    // 1. how many points arrive: the table is sized from them, and a cloud with none is done here
+    HIP_TRY(hipMemsetAsync(ctl, 0, VOX_CTL_WORDS * 4, st));
+    stage_break(e);
+    if ((rc = stage_begin(e, "voxel_count"))) return rc;
+    hipLaunchKernelGGL(k_voxel_count, dim3(std::min(m, VOX_COUNT_BLOCKS)), dim3(256), 0, st, xyz, disp, n, G, ctl);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    uint32_t h_ctl[VOX_CTL_WORDS] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    stage_break(e);
+    const uint32_t n_in = h_ctl[VOX_CTL_IN];
+    if (n_out_of_range) *n_out_of_range = (int64_t)h_ctl[VOX_CTL_OUT];
+    if (n_in == 0) {
+        *n_voxels = 0;
+        return SGM_OK;
+    }
+    // 2. the table: the smallest power of two of at least twice the points in range (debug: of at least the points themselves)
+    const uint64_t want = (e->debug & SGM_DBG_VOXEL_TIGHT_TABLE) ? (uint64_t)n_in : 2 * (uint64_t)n_in;
+    uint32_t cap = 1;
+    while (cap < want) cap <<= 1;   // (n_in < 2^24: at most 2^25)
+    if ((rc = e->vox_tab.ensure((size_t)cap * sizeof(VoxSlot)))) return rc;
+    VoxSlot *tab = (VoxSlot *)e->vox_tab.p;
+    if ((rc = stage_begin(e, "voxel_clear"))) return rc;
+    hipLaunchKernelGGL(k_voxel_clear, dim3((cap + 255) / 256), dim3(256), 0, st, tab, cap);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    // 3. insert and accumulate
+    if ((rc = stage_begin(e, "voxel_insert"))) return rc;
+    const bool pre = VOX_PRE_DEFAULT != !!(e->debug & SGM_DBG_VOXEL_OTHER_REDUCTION);
+    if (pre) hipLaunchKernelGGL(k_voxel_insert<true>, dim3(m), dim3(256), 0, st, xyz, disp, colors, n, G, tab, cap - 1, slot_of, ctl);
+    else hipLaunchKernelGGL(k_voxel_insert<false>, dim3(m), dim3(256), 0, st, xyz, disp, colors, n, G, tab, cap - 1, slot_of, ctl);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    // 4. the heads of the kept voxels through the ordered compaction; the scatter computes the rows
+    if ((rc = stage_begin(e, "voxel_heads"))) return rc;
+    hipLaunchKernelGGL(k_voxel_head_count, dim3(m), dim3(256), 0, st, (const uint32_t *)slot_of, (const VoxSlot *)tab, n, (uint32_t)min_points, cnt);
+    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
+    hipLaunchKernelGGL(k_voxel_scatter, dim3(m), dim3(256), 0, st, (const uint32_t *)slot_of, (const VoxSlot *)tab, n, (uint32_t)min_points,
+                       (const uint32_t *)cnt, G, (float *)d_out_points, (uint8_t *)d_out_colors, (uint32_t *)d_out_counts);
+    KCHECK();
+    if ((rc = stage_end(e, 3))) return rc;
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&total, cnt + m, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_ctl[VOX_CTL_ERR])
+        return set_err(SGM_ERR_HIP, "sgm_voxel_downsample: a point found no slot in a table of %u slots for %u points", cap, n_in);
+    *n_voxels = (int64_t)total;
+    return SGM_OK;
+}
+
+int sgm_voxel_downsample(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int64_t n, float voxel_size,
+                         const float origin[3], int min_points, float *out_points, uint8_t *out_colors, uint32_t *out_counts,
+                         int64_t *n_voxels, int64_t *n_out_of_range)
+{
+    if (int rc = voxel_check_args(e, xyz, colors_rgb, n, voxel_size, origin, min_points, out_points, out_colors, n_voxels)) return rc;
+    if (n == 0) {
+        *n_voxels = 0;
+        if (n_out_of_range) *n_out_of_range = 0;
+        return SGM_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = e->xyz.ensure((size_t)n * 12)) || (rc = e->cpts.ensure((size_t)n * 12)) || (disp && (rc = e->f32.ensure((size_t)n * 4))) ||
+        (out_counts && (rc = e->vox_cnt.ensure((size_t)n * 4))))
+        return rc;
+    if (out_colors && ((rc = e->crgb_in.ensure((size_t)n * 3)) || (rc = e->crgb.ensure((size_t)n * 3)))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, e->stream));
+    if (disp) HIP_TRY(hipMemcpyAsync(e->f32.p, disp, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    if (out_colors) HIP_TRY(hipMemcpyAsync(e->crgb_in.p, colors_rgb, (size_t)n * 3, hipMemcpyHostToDevice, e->stream));
+    int64_t nv = 0, noor = 0;
+    if ((rc = sgm_voxel_downsample_device(e, e->xyz.p, disp ? e->f32.p : nullptr, out_colors ? e->crgb_in.p : nullptr, n, voxel_size, origin,
+                                          min_points, e->cpts.p, out_colors ? e->crgb.p : nullptr, out_counts ? e->vox_cnt.p : nullptr,
+                                          &nv, &noor))) {
+        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
+        return rc;
+    }
+    if (nv > 0) {
+        HIP_TRY(hipMemcpyAsync(out_points, e->cpts.p, (size_t)nv * 12, hipMemcpyDeviceToHost, e->stream));
+        if (out_colors) HIP_TRY(hipMemcpyAsync(out_colors, e->crgb.p, (size_t)nv * 3, hipMemcpyDeviceToHost, e->stream));
+        if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, e->vox_cnt.p, (size_t)nv * 4, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    *n_voxels = nv;
+    if (n_out_of_range) *n_out_of_range = noor;
     return SGM_OK;
 }
 

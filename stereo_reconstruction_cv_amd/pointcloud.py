@@ -3,6 +3,8 @@
     valid_points(points_3D, colors, disparity_map)   main.ipynb:726-737  mask + boolean indexing
                  [, confidence, min_confidence]        ... and confidence >= min_confidence (StereoSGBM.computeWithConfidence)
     write_point_cloud(path, points, colors)           main.ipynb:795-797  o3d.io.write_point_cloud(.ply)
+    voxel_down_sample(points_3D, colors, disparity_map, voxel_size, ...)   what users thin the cloud with before they show or
+                 ship it: one centroid, mean colour and count per voxel, on the GPU (include/sgm_hip_voxel.h; NOT Open3D's values or order)
 
 The compaction runs on the GPU (ordered, so the result equals numpy's `points_3D[mask]`); the
 PLY writer is plain host I/O and replaces the Open3D dependency (absent here) for export only --
@@ -40,6 +42,61 @@ def valid_points(points_3D, colors, disparity_map, confidence=None, min_confiden
         if colors.shape != pts.shape:
             raise _cv.error("valid_points: colors must have the shape of points_3D")
     return _cv.get_engine(_cv._DEFAULT).compact_points_host(pts, disp, colors)
+
+
+VOXEL_MAX_POINTS = (1 << 24) - 1
+
+
+def voxel_down_sample(points_3D, colors, disparity_map, voxel_size, origin=(0, 0, 0), min_points=1, confidence=None,
+                      min_confidence=0, return_counts=False):
+    """Voxel-grid downsampling on the GPU: one centroid, one mean colour and one count per occupied voxel of the grid of cubes of
+    edge voxel_size anchored at origin; voxels with fewer than min_points points are dropped (a cheap outlier filter), and the
+    voxels come in the order of their first points.  The definition is include/sgm_hip_voxel.h, our own and in integers, so the
+    result is the same bits on every run: it is NOT Open3D's voxel_down_sample, neither in its values nor in its order.
+    points_3D (H, W, 3) with disparity_map (H, W) -- a point counts iff X, Y, Z are finite and its disparity > 0, and with a
+    confidence map also confidence >= min_confidence, as in valid_points -- or an (N, 3) list with disparity_map=None (every
+    finite point counts).  colors: uint8 of the shape of points_3D, or None.
+    Returns (points float32 (M, 3), colors uint8 (M, 3) or None[, counts uint32 (M)])."""
+    who = "voxel_down_sample"
+    pts = np.asarray(points_3D)
+    if pts.dtype != np.float32:
+        raise _cv.error(f"{who}: points_3D must be float32, not {pts.dtype}")
+    if disparity_map is None:
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise _cv.error(f"{who}: without a disparity_map points_3D must be an (N, 3) list")
+        if confidence is not None:
+            raise _cv.error(f"{who}: a confidence map needs a disparity_map")
+        disp = None
+    else:
+        disp = np.asarray(disparity_map)
+        if pts.ndim != 3 or pts.shape[2] != 3 or pts.shape[:2] != disp.shape:
+            raise _cv.error(f"{who}: points_3D must be (H, W, 3) and disparity_map (H, W)")
+        if confidence is not None:
+            disp = mask_by_confidence(disp, confidence, min_confidence)
+    if colors is not None:
+        colors = np.asarray(colors)
+        if colors.shape != pts.shape or colors.dtype != np.uint8:
+            raise _cv.error(f"{who}: colors must be uint8 and have the shape of points_3D")
+    with np.errstate(all="ignore"):
+        try:
+            v = np.float32(voxel_size)
+            org = np.asarray(origin, np.float32)
+        except (TypeError, ValueError):
+            raise _cv.error(f"{who}: voxel_size and origin must be numbers") from None
+        if v.shape != () or not np.isfinite(v) or not v > 0 or not np.isfinite(np.float32(1.0) / v):
+            raise _cv.error(f"{who}: voxel_size={voxel_size!r} is not a finite positive float32 with a finite reciprocal")
+    if org.shape != (3,) or not np.isfinite(org).all():
+        raise _cv.error(f"{who}: origin={origin!r} is not three finite numbers")
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= int(min_points) <= 2 ** 31 - 1:
+        raise _cv.error(f"{who}: min_points={min_points!r} is not an integer >= 1")
+    if pts.size // 3 > VOXEL_MAX_POINTS:
+        raise _cv.error(f"{who}: {pts.size // 3} points, more than {VOXEL_MAX_POINTS} (include/sgm_hip_voxel.h)")
+    if pts.size == 0:      # nothing to send to the device
+        none = np.zeros((0, 3), np.float32), None if colors is None else np.zeros((0, 3), np.uint8)
+        return none + (np.zeros(0, np.uint32),) if return_counts else none
+    p, c, k, _ = _cv.get_engine(_cv._DEFAULT).voxel_downsample_host(pts, disp, colors, float(v), org, int(min_points),
+                                                                   bool(return_counts))
+    return (p, c, k) if return_counts else (p, c)
 
 
 def write_point_cloud(filename, points, colors=None, binary=True) -> bool:

@@ -226,6 +226,37 @@ class Engine:
         nothing is synchronised."""
         _check(self._L.sgm_compact_points_device_async(self._h, d_xyz, d_dispf, d_colors, n, d_points, d_out_colors, d_count_i64))
 
+    # -- voxel-grid downsampling (include/sgm_hip_voxel.h) --
+    def voxel_downsample_host(self, xyz: np.ndarray, disp: np.ndarray | None, colors: np.ndarray | None, voxel_size: float,
+                              origin=(0.0, 0.0, 0.0), min_points: int = 1, return_counts: bool = False):
+        """sgm_voxel_downsample: float32 points (n, 3) or (H, W, 3), float32 disparities (n) or (H, W) or None, uint8 colours of
+        the points' shape or None.  Returns (points float32 (M, 3), colors uint8 (M, 3) or None, counts uint32 (M) or None,
+        n_out_of_range), the voxels in the order of their first points."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = xyz.shape[0]
+        disp = None if disp is None else np.ascontiguousarray(disp, np.float32).reshape(-1)
+        colors = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        pts = np.empty((n, 3), np.float32)
+        rgb = None if colors is None else np.empty((n, 3), np.uint8)
+        cnt = np.empty(n, np.uint32) if return_counts else None
+        nv, noor = C.c_int64(0), C.c_int64(0)
+        at = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.sgm_voxel_downsample(self._h, xyz.ctypes.data, at(disp), at(colors), n, float(voxel_size), org.ctypes.data,
+                                            int(min_points), pts.ctypes.data, at(rgb), at(cnt), C.byref(nv), C.byref(noor)))
+        m = nv.value
+        return (pts[:m].copy(), None if rgb is None else rgb[:m].copy(), None if cnt is None else cnt[:m].copy(), int(noor.value))
+
+    def voxel_downsample_device(self, d_xyz: int, d_dispf: int | None, d_colors: int | None, n: int, voxel_size: float, origin,
+                                min_points: int, d_points: int, d_out_colors: int | None = None, d_out_counts: int | None = None):
+        """sgm_voxel_downsample_device: device addresses, outputs with room for n rows; the rows go to the front of the outputs in
+        the order of the voxels' first points.  Returns (n_voxels, n_out_of_range); synchronises the engine's stream."""
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        nv, noor = C.c_int64(0), C.c_int64(0)
+        _check(self._L.sgm_voxel_downsample_device(self._h, d_xyz, d_dispf, d_colors, int(n), float(voxel_size), org.ctypes.data,
+                                                   int(min_points), d_points, d_out_colors, d_out_counts, C.byref(nv), C.byref(noor)))
+        return int(nv.value), int(noor.value)
+
     def median3x3_host(self, img: np.ndarray) -> np.ndarray:
         img = np.ascontiguousarray(img, np.int16)
         out = np.empty_like(img)
