@@ -7,13 +7,13 @@
 //                  (n, s1, s2) of every tile row, halo rows included, then the COLUMN sums of those and the factor.  The window
 //                  sums are separable, so a pixel costs 2 * (2r + 1) LDS reads instead of (2r + 1)^2.
 //   k_lrc_match    the two gathers and the min: one lane per pixel, left and right confidence of a pair in one pass.
-// The maps' own pointers travel as by-value tables (WlsPtrs of kernels_wls.h), as in the batch filter; the factor planes of a
+// The maps' own pointers travel as by-value tables (MapPtrs of sgm_device.h), as in the edge-aware filter; the factor planes of a
 // chunk are one buffer of the engine, uint8 [pairs][2][H][W], addressed with 64-bit offsets.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kernels_wls.h"
+#include "sgm_device.h"
 
 namespace sgm {
 
@@ -44,7 +44,7 @@ __host__ __device__ inline int lrc_factor(int n, int64_t s1, int64_t s2, int64_t
     return 100 - lo;
 }
 
-__global__ __launch_bounds__(LRC_THREADS) void k_lrc_factor(WlsPtrs lefts, WlsPtrs rights, int invalid, int r, int64_t vmax, int H,
+__global__ __launch_bounds__(LRC_THREADS) void k_lrc_factor(MapPtrs lefts, MapPtrs rights, int invalid, int r, int64_t vmax, int H,
                                                             int W, uint8_t *__restrict__ fac)
 {
     extern __shared__ __align__(8) unsigned char lrc_lds[];
@@ -115,8 +115,8 @@ __device__ inline int lrc_one(int d, int xo, int x, const int16_t *__restrict__ 
     return c;
 }
 
-__global__ __launch_bounds__(256) void k_lrc_match(WlsPtrs lefts, WlsPtrs rights, WlsPtrs bases, int invalid, int thresh, int H, int W,
-                                                   const uint8_t *__restrict__ fac, WlsPtrs conf_lefts, WlsPtrs conf_rights)
+__global__ __launch_bounds__(256) void k_lrc_match(MapPtrs lefts, MapPtrs rights, MapPtrs bases, int invalid, int thresh, int H, int W,
+                                                   const uint8_t *__restrict__ fac, MapPtrs conf_lefts, MapPtrs conf_rights)
 {
     const int x = blockIdx.x * 256 + threadIdx.x, m = blockIdx.z;
     if (x >= W) return;

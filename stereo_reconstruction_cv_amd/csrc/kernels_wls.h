@@ -6,25 +6,33 @@
 // arithmetic of a line is the contract of the header -- IEEE binary32, every operation rounded on its own, in the order
 // written there -- so nothing here is reassociated, fused (the library is built with -ffp-contract=off) or split: one lane
 // walks one line from end to end and back.  What the kernels arrange is only where a lane's operands come from:
-//   k_wls_rows   one lane per ROW.  A wave owns 64 rows and walks them in tiles of 64 columns; a tile of u, v and of the edge
-//                weights is brought into LDS with row-major (coalesced) accesses, rows padded to 65 floats so that the 64
-//                lanes of a column step hit 64 banks, and goes back the same way.  Three more waves of the workgroup do
-//                nothing but help with that traffic: 16 tile rows per wave, all in flight at once.
+//   k_wls_rows   one lane per ROW.  Wave 0 of a workgroup owns 64 rows and walks them in tiles of TC columns; a tile of u, v
+//                and of the edge weights is brought into LDS with row-major (coalesced) accesses, rows padded to TC + 1 floats
+//                so that the 64 lanes of a column step hit 64 banks, and goes back the same way.  The other RW - 1 waves do
+//                nothing but help with that traffic, so that a tile's loads are in flight together.
 //   k_wls_cols   one lane per COLUMN: the lanes of a wave touch 64 adjacent floats of a row at every step.  Rows are
-//                fetched WLS_UNR at a time before the dependent chain consumes them.
+//                fetched UNR at a time before the dependent chain consumes them.
 // The edge weights are looked up on the fly, lut[|g_i - g_{i+1}|] (3 channels: the largest of the three differences), from
 // the 256-entry table that travels as a kernel argument and sits in LDS.
+//
+// Every kernel runs over a chunk of up to BATCH_MAPS_MAX maps of one shape: blockIdx.y is the map, and a single map
+// (sgm_wls_filter) is a chunk of one.  The planes u, v, c' of map m are the m-th [H][W] slice of the engine's three buffers
+// (64-bit offsets: 64 planes of a 4K map pass 2^31 bytes); the maps' own pointers -- map, guide, confidence, outputs -- travel as by-value tables
+// in the kernel arguments (MapPtrs, sgm_device.h), each kernel with the tables it reads, so nothing is copied to the device
+// for them and nothing of them outlives the launch.  A map's tail workgroup is cut to its own rows / columns, so it touches
+// no neighbour's plane.
+// How many workgroups share a CU depends on the chunk, so the shape of the row kernel is a template argument -- RW waves per
+// workgroup, tiles of TC columns (LDS: 3 * 64 * (TC + 1) floats + the table) -- and so are the rows in flight of the column
+// kernel; sgm_engine.hip says which are used and DESIGN.md 4.15 / 4.16 what each gave.  Every shape gives the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sgm_device.h"
+
 namespace sgm {
 
-constexpr int WLS_T = 64;       // rows per workgroup of k_wls_rows and columns of a tile; columns (= lanes, one wave) of k_wls_cols
-constexpr int WLS_RW = 4;       // k_wls_rows: waves per workgroup -- one walks the rows, all of them move the tiles
-constexpr int WLS_RT = WLS_T * WLS_RW;
-constexpr int WLS_LD = 65;      // floats per LDS tile row
-constexpr int WLS_UNR = 16;     // k_wls_cols: rows in flight per lane
+constexpr int WLS_T = 64;       // rows per workgroup of k_wls_rows; columns (= lanes, one wave) of k_wls_cols
 
 struct WlsLut { float w[256]; };
 
@@ -67,213 +75,8 @@ __device__ inline void wls_forward(bool first, bool last, float kp, float k, flo
 }
 
 // u = disp * c, v = c with c = 0 where disp is invalid, else the confidence (100 without a map)
-__global__ __launch_bounds__(256) void k_wls_init(const int16_t *__restrict__ disp, const uint8_t *__restrict__ conf, int invalid,
-                                                  int64_t n, float *__restrict__ u, float *__restrict__ v)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int d = disp[i];
-    const bool ok = d != invalid;
-    const float c = ok ? (conf ? (float)conf[i] : 100.f) : 0.f;
-    u[i] = ok ? (float)d * c : 0.f;
-    v[i] = c;
-}
-
-template <int CN>
-__global__ __launch_bounds__(WLS_RT) void k_wls_rows(float *__restrict__ u, float *__restrict__ v, float *__restrict__ cpl,
-                                                     const uint8_t *__restrict__ guide, WlsLut lut, float lam, int H, int W)
-{
-    __shared__ float su[WLS_T * WLS_LD], sv[WLS_T * WLS_LD], sc[WLS_T * WLS_LD], sl[256];
-    wls_lut_to_lds(lut, sl);
-    // wave 0 owns the 64 rows and runs their recurrences; all four waves move the tiles (tile row r: wave r % 4), so that a
-    // tile's loads are in flight together instead of queueing behind one wave
-    const int lane = threadIdx.x & (WLS_T - 1), wv = threadIdx.x / WLS_T, y0 = blockIdx.x * WLS_T;
-    const int rows = min(WLS_T, H - y0), ntile = (W + WLS_T - 1) / WLS_T;
-    const bool walker = wv == 0 && lane < rows;
-    float *const mu = su + lane * WLS_LD, *const mv = sv + lane * WLS_LD, *const mc = sc + lane * WLS_LD;   // the walker's row
-    float kp = 0.f, cp = 0.f, up = 0.f, vp = 0.f;
-    for (int t = 0; t < ntile; t++) {
-        const int x0 = t * WLS_T, x = x0 + lane, nc = min(WLS_T, W - x0);
-        if (x < W) {
-#pragma unroll
-            for (int j = 0; j < WLS_T / WLS_RW; j++) {
-                const int r = wv + WLS_RW * j;
-                if (r < rows) {
-                    const int64_t i = (int64_t)(y0 + r) * W + x;
-                    su[r * WLS_LD + lane] = u[i];
-                    sv[r * WLS_LD + lane] = v[i];
-                    sc[r * WLS_LD + lane] = x < W - 1 ? sl[wls_gdiff<CN>(guide, i, i + 1)] : 0.f;   // the weight w_x
-                }
-            }
-        }
-        __syncthreads();
-        if (walker) {
-            for (int c = 0; c < nc; c++) {
-                const float k = lam * mc[c];
-                wls_forward(x0 + c == 0, x0 + c == W - 1, kp, k, mu[c], mv[c], cp, up, vp);
-                mc[c] = cp;
-                mu[c] = up;
-                mv[c] = vp;
-                kp = k;
-            }
-        }
-        __syncthreads();
-        if (x < W) {
-#pragma unroll
-            for (int j = 0; j < WLS_T / WLS_RW; j++) {
-                const int r = wv + WLS_RW * j;
-                if (r < rows) {
-                    const int64_t i = (int64_t)(y0 + r) * W + x;
-                    u[i] = su[r * WLS_LD + lane];
-                    v[i] = sv[r * WLS_LD + lane];
-                    cpl[i] = sc[r * WLS_LD + lane];
-                }
-            }
-        }
-        __syncthreads();
-    }
-    // back substitution, the tiles in reverse: up / vp now carry x_{i+1}
-    for (int t = ntile - 1; t >= 0; t--) {
-        const int x0 = t * WLS_T, x = x0 + lane, nc = min(WLS_T, W - x0);
-        if (x < W) {
-#pragma unroll
-            for (int j = 0; j < WLS_T / WLS_RW; j++) {
-                const int r = wv + WLS_RW * j;
-                if (r < rows) {
-                    const int64_t i = (int64_t)(y0 + r) * W + x;
-                    su[r * WLS_LD + lane] = u[i];
-                    sv[r * WLS_LD + lane] = v[i];
-                    sc[r * WLS_LD + lane] = cpl[i];
-                }
-            }
-        }
-        __syncthreads();
-        if (walker) {
-            for (int c = nc - 1; c >= 0; c--) {
-                if (x0 + c == W - 1) {
-                    up = mu[c];
-                    vp = mv[c];
-                } else {
-                    const float cc = mc[c];
-                    up = mu[c] - cc * up;
-                    vp = mv[c] - cc * vp;
-                }
-                mu[c] = up;
-                mv[c] = vp;
-            }
-        }
-        __syncthreads();
-        if (x < W) {
-#pragma unroll
-            for (int j = 0; j < WLS_T / WLS_RW; j++) {
-                const int r = wv + WLS_RW * j;
-                if (r < rows) {
-                    const int64_t i = (int64_t)(y0 + r) * W + x;
-                    u[i] = su[r * WLS_LD + lane];
-                    v[i] = sv[r * WLS_LD + lane];
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-template <int CN>
-__global__ __launch_bounds__(WLS_T) void k_wls_cols(float *__restrict__ u, float *__restrict__ v, float *__restrict__ cpl,
-                                                    const uint8_t *__restrict__ guide, WlsLut lut, float lam, int H, int W)
-{
-    __shared__ float sl[256];
-    wls_lut_to_lds(lut, sl);
-    const int x = blockIdx.x * WLS_T + threadIdx.x;
-    if (x >= W) return;
-    float kp = 0.f, cp = 0.f, up = 0.f, vp = 0.f;
-    for (int y0 = 0; y0 < H; y0 += WLS_UNR) {
-        float uu[WLS_UNR], vv[WLS_UNR], ww[WLS_UNR];
-#pragma unroll
-        for (int j = 0; j < WLS_UNR; j++) {
-            const int y = y0 + j;
-            if (y < H) {
-                const int64_t i = (int64_t)y * W + x;
-                uu[j] = u[i];
-                vv[j] = v[i];
-                ww[j] = y < H - 1 ? sl[wls_gdiff<CN>(guide, i, i + W)] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < WLS_UNR; j++) {
-            const int y = y0 + j;
-            if (y < H) {
-                const int64_t i = (int64_t)y * W + x;
-                const float k = lam * ww[j];
-                wls_forward(y == 0, y == H - 1, kp, k, uu[j], vv[j], cp, up, vp);
-                cpl[i] = cp;
-                u[i] = up;
-                v[i] = vp;
-                kp = k;
-            }
-        }
-    }
-    for (int y0 = (H - 1) / WLS_UNR * WLS_UNR; y0 >= 0; y0 -= WLS_UNR) {
-        float uu[WLS_UNR], vv[WLS_UNR], cc[WLS_UNR];
-#pragma unroll
-        for (int j = WLS_UNR - 1; j >= 0; j--) {
-            const int y = y0 + j;
-            if (y < H) {
-                const int64_t i = (int64_t)y * W + x;
-                uu[j] = u[i];
-                vv[j] = v[i];
-                cc[j] = cpl[i];
-            }
-        }
-#pragma unroll
-        for (int j = WLS_UNR - 1; j >= 0; j--) {
-            const int y = y0 + j;
-            if (y < H) {
-                const int64_t i = (int64_t)y * W + x;
-                if (y == H - 1) {
-                    up = uu[j];
-                    vp = vv[j];
-                } else {
-                    up = uu[j] - cc[j] * up;
-                    vp = vv[j] - cc[j] * vp;
-                }
-                u[i] = up;
-                v[i] = vp;
-            }
-        }
-    }
-}
-
-// valid iff v >= 1 (one percent of full confidence reached the pixel): out = rint(u / v), out_f32 = (u / v) / 16
-__global__ __launch_bounds__(256) void k_wls_final(const float *__restrict__ u, const float *__restrict__ v, int invalid, int64_t n,
-                                                   int16_t *__restrict__ out, float *__restrict__ out_f32)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float vi = v[i];
-    const bool ok = vi >= 1.f;
-    const float q = ok ? u[i] / vi : 0.f;
-    out[i] = ok ? (int16_t)fminf(fmaxf(rintf(q), -32768.f), 32767.f) : (int16_t)invalid;
-    if (out_f32) out_f32[i] = ok ? q * 0.0625f : 0.f;
-}
-
-// ---- the batch form (include/sgm_hip_wls_batch.h: sgm_wls_filter_batch) -----------------------------------------------------------
-// The same four kernels over a chunk of up to WLS_BATCH_MAX maps of one shape: blockIdx.y is the map.  The planes u, v, c' of map m
-// are the m-th [H][W] slice of the engine's three buffers (64-bit offsets: 64 planes of a 4K map pass 2^31 bytes); the maps'
-// own pointers -- map, guide, confidence, outputs -- travel as by-value tables in the kernel arguments, each kernel with the
-// tables it reads (512 bytes each), so nothing is copied to the device for them and nothing of them outlives the launch.  The
-// arithmetic of a line is wls_forward / wls_gdiff and the order of the single-map kernels: one lane, one line, end to end; a
-// map's tail workgroup is cut to its own rows / columns exactly as there, so it touches no neighbour's plane.
-// What a batch changes is who shares a CU: the single map has one workgroup per CU at most and pays for its own waiting; here
-// several workgroups of different maps sit on a CU and walk while the others move their tiles.  So the shape of the row
-// kernel is a template argument -- RW waves per workgroup (wave 0 walks, all move tiles), tiles of TC columns (LDS:
-// 3 * 64 * (TC + 1) floats + the table) -- and so are the rows in flight of the column kernel; sgm_engine.hip says which are
-// used and DESIGN.md 4.16 what each gave.
-constexpr int WLS_BATCH_MAX = 64;
-struct WlsPtrs { void *p[WLS_BATCH_MAX]; };
-
-__global__ __launch_bounds__(256) void k_wls_init_b(WlsPtrs disps, WlsPtrs confs, int invalid, int64_t n, float *__restrict__ u,
-                                                    float *__restrict__ v)
+__global__ __launch_bounds__(256) void k_wls_init(MapPtrs disps, MapPtrs confs, int invalid, int64_t n, float *__restrict__ u,
+                                                  float *__restrict__ v)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -288,8 +91,8 @@ __global__ __launch_bounds__(256) void k_wls_init_b(WlsPtrs disps, WlsPtrs confs
 }
 
 template <int CN, int RW, int TC>
-__global__ __launch_bounds__(RW * WLS_T) void k_wls_rows_b(float *__restrict__ u, float *__restrict__ v, float *__restrict__ cpl,
-                                                           WlsPtrs guides, WlsLut lut, float lam, int H, int W)
+__global__ __launch_bounds__(RW * WLS_T) void k_wls_rows(float *__restrict__ u, float *__restrict__ v, float *__restrict__ cpl,
+                                                         MapPtrs guides, WlsLut lut, float lam, int H, int W)
 {
     constexpr int LD = TC + 1;                  // floats per LDS tile row: odd, so the 64 lanes of a column step hit 64 banks
     constexpr int RS = RW * WLS_T / TC;         // tile rows the workgroup's threads cover at once
@@ -394,8 +197,8 @@ __global__ __launch_bounds__(RW * WLS_T) void k_wls_rows_b(float *__restrict__ u
 }
 
 template <int CN, int UNR>
-__global__ __launch_bounds__(WLS_T) void k_wls_cols_b(float *__restrict__ u, float *__restrict__ v, float *__restrict__ cpl,
-                                                      WlsPtrs guides, WlsLut lut, float lam, int H, int W)
+__global__ __launch_bounds__(WLS_T) void k_wls_cols(float *__restrict__ u, float *__restrict__ v, float *__restrict__ cpl,
+                                                    MapPtrs guides, WlsLut lut, float lam, int H, int W)
 {
     __shared__ float sl[256];
     wls_lut_to_lds(lut, sl);
@@ -464,8 +267,9 @@ __global__ __launch_bounds__(WLS_T) void k_wls_cols_b(float *__restrict__ u, flo
     }
 }
 
-__global__ __launch_bounds__(256) void k_wls_final_b(const float *__restrict__ u, const float *__restrict__ v, int invalid, int64_t n,
-                                                     WlsPtrs outs, WlsPtrs outfs)
+// valid iff v >= 1 (one percent of full confidence reached the pixel): out = rint(u / v), out_f32 = (u / v) / 16
+__global__ __launch_bounds__(256) void k_wls_final(const float *__restrict__ u, const float *__restrict__ v, int invalid, int64_t n,
+                                                   MapPtrs outs, MapPtrs outfs)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;

@@ -31,10 +31,12 @@ enum {
     SGM_DBG_SMALL_D_RECORD = 8192,       /* D <= 64, MODE_SGBM: per-row record + element-wise vertical kernel (k_prepass3_g + k_vert3_g) instead of k_lines3_g's volumes */
     SGM_DBG_IN_ROW_ON_MAIN_STREAM = 4096, /* D <= 64, MODE_SGBM: the left-to-right in-row path after the vertical kernel (S +=) instead of beside it */
     SGM_DBG_FIFTH_PATH_AFTER_SWEEP = 65536, /* MODE_SGBM, D <= 128: the fifth path after the sweep (S +=) instead of beside it */
-    /* sgm_wls_filter_batch*: the other shapes of the batched line kernels that DESIGN.md 4.16 measured (tools/wls_batch_times.py);
-     * two small fields, not flags.  0 in a field is the shape the library uses; the results are the same bits for every value. */
-    SGM_DBG_WLS_BATCH_ROWS_SHIFT = 17,     /* 3 bits: k_wls_rows_b<CN, RW, TC>, the index into wls_rows_shapes (sgm_engine.hip) */
-    SGM_DBG_WLS_BATCH_COLS_SHIFT = 20,     /* 2 bits: k_wls_cols_b<CN, UNR>, the index into wls_cols_shapes */
+    /* sgm_wls_filter* and sgm_wls_filter_batch* (a single map is a batch of one): the other shapes of the line kernels that
+     * DESIGN.md 4.15 / 4.16 measured (tools/wls_batch_times.py); two small fields, not flags.  0 in a field leaves the choice
+     * to the library (index 0 for a chunk of several maps; rows 3, columns 1 for a chunk of one), any other value selects that
+     * shape for every chunk; the results are the same bits for every value (tests/test_gpu_wls.py runs them all). */
+    SGM_DBG_WLS_BATCH_ROWS_SHIFT = 17,     /* 3 bits: k_wls_rows<CN, RW, TC>, the index into wls_rows_shapes (sgm_engine.hip) */
+    SGM_DBG_WLS_BATCH_COLS_SHIFT = 20,     /* 2 bits: k_wls_cols<CN, UNR>, the index into wls_cols_shapes */
     /* sgm_voxel_downsample* (tools/voxel_times.py); the results are the same bits under both */
     SGM_DBG_VOXEL_TIGHT_TABLE = 1 << 22,   /* capacity = the smallest power of two >= the points in range (not twice them): the load can reach 1.0 */
     SGM_DBG_VOXEL_OTHER_REDUCTION = 1 << 23 /* k_voxel_insert without the wave pre-reduction where it is the default (kernels_voxel.h: VOX_PRE_DEFAULT), with it where not */

@@ -470,6 +470,12 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void *base,
                                              0x00020000);
 }
 
+// The batched add-on entries (the edge-aware filter, the left-right confidence) run a chunk of up to BATCH_MAPS_MAX maps per
+// launch; the maps' own device pointers travel by value in the kernel arguments, one table (512 bytes) per role, and a
+// workgroup reads the entry of its map.  Entries past the chunk are null and never read.
+constexpr int BATCH_MAPS_MAX = 64;
+struct MapPtrs { void *p[BATCH_MAPS_MAX]; };
+
 #define SGM_MAX_COST 32767
 #define SGM_SENT 0x7fff7fffu  // packed pair of MAX_COST
 

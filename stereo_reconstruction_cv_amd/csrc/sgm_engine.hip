@@ -472,6 +472,13 @@ static int stage_end(sgm_engine *e, int launches, hipStream_t on = nullptr)
 }
 // something other than a stage was enqueued (a wait for another stream, a memset ...): the next stage needs a begin event of its own
 static void stage_break(sgm_engine *e) { e->last_end_ev = -1; }
+// a call takes the stage record over: stage_times reports this call's stages from here on
+static void stage_reset(sgm_engine *e)
+{
+    e->nstages = 0;
+    e->nevents = 0;
+    e->last_end_ev = -1;
+}
 
 #define KCHECK() HIP_TRY(hipGetLastError())
 
@@ -1609,9 +1616,7 @@ static int run_compute(sgm_engine *e, const PairIO &io, int H, int W, int64_t st
     if ((rc = ensure_plan_buffers(e, p, H, W))) return rc;
     const bool do_pre = (phases & PH_PRE) != 0, do_mid = (phases & PH_MID) != 0, do_post = (phases & PH_POST) != 0;
     if (do_pre) {
-        e->nstages = 0;
-        e->nevents = 0;
-        e->last_end_ev = -1;
+        stage_reset(e);
         e->plan = p;
         e->conf.last = e->right.last = 0;
     } else {
@@ -2876,7 +2881,43 @@ int sgm_median3x3(sgm_engine *e, const int16_t *src, int H, int W, int16_t *dst)
     return SGM_OK;
 }
 
-// ---- the edge-aware disparity filter (include/sgm_hip_wls.h, kernels_wls.h) -----------------------------------------------
+// ---- what the batched add-on entries share (the edge-aware filter and the left-right confidence) ------------------------------
+// Maps (the confidence: pairs) per chunk, and the buffers of the call sized for it.  C = min(N, BATCH_MAPS_MAX, SGM_OPT_GROUP_MAX
+// if set), cut to what free device memory allows beside the reserve of prepare_group (4 GiB or 5 %) when a buffer has to grow;
+// at least 1.  All allocations of the call happen here, before anything is enqueued.
+struct BatchNeed { DevBuf *b; size_t per_map; };
+static int batch_reserve(sgm_engine *e, int N, std::initializer_list<BatchNeed> needs, int *C_out)
+{
+    int C = std::min(N, BATCH_MAPS_MAX);
+    if (e->group_max > 0) C = std::min(C, e->group_max);
+    size_t per_map = 0, freed = 0;   // of the buffers that grow: bytes per map, and what they give back first (DevBuf::ensure)
+    for (const BatchNeed &n : needs)
+        if (n.b->cap < n.per_map * (size_t)C) {
+            per_map += n.per_map;
+            freed += n.b->cap;
+        }
+    size_t fr = 0, tot = 0;
+    if (per_map && hipMemGetInfo(&fr, &tot) == hipSuccess) {
+        const size_t reserve = std::max<size_t>((size_t)4 << 30, tot / 20), have = fr + freed;
+        const size_t room = have > reserve ? have - reserve : 0;
+        C = (int)std::max<size_t>(1, std::min<size_t>((size_t)C, room / per_map));
+    }
+    for (const BatchNeed &n : needs)
+        if (int rc = n.b->ensure(n.per_map * (size_t)C)) return rc;
+    *C_out = C;
+    return SGM_OK;
+}
+
+// the by-value table of a chunk's n device pointers from the caller's array (null: the chunk has no such map, every entry null)
+static MapPtrs map_ptrs(const void *const *a, int n)
+{
+    MapPtrs t{};
+    for (int i = 0; a && i < n; i++) t.p[i] = (void *)a[i];
+    return t;
+}
+
+// ---- the edge-aware disparity filter (include/sgm_hip_wls.h, sgm_hip_wls_batch.h; kernels_wls.h) ------------------------------
+// One map is a batch of one: the single entries and the batch entries run the same four kernels.
 int sgm_wls_weights(double sigma, float lut[256])
 {
     if (!lut || !std::isfinite(sigma) || sigma <= 0.0) return set_err(SGM_ERR_INVALID_ARG, "sgm_wls_weights: null table or sigma %g not a positive finite number", sigma);
@@ -2895,113 +2936,35 @@ static int wls_check_args(const sgm_engine *e, const void *disp, const void *gui
     return SGM_OK;
 }
 
-// arguments checked; everything a device pointer but lut.  Enqueues init, three times (rows, columns), final.
-static int run_wls(sgm_engine *e, const int16_t *d_disp, const uint8_t *d_guide, int cn, const uint8_t *d_conf, int H, int W, int invalid,
-                   double lambda, const float *lut, int16_t *d_out, float *d_out_f32)
-{
-    const int64_t npx = (int64_t)H * W;
-    int rc;
-    if ((rc = e->wls_u.ensure((size_t)npx * 4)) || (rc = e->wls_v.ensure((size_t)npx * 4)) || (rc = e->wls_c.ensure((size_t)npx * 4))) return rc;
-    float *u = (float *)e->wls_u.p, *v = (float *)e->wls_v.p, *c = (float *)e->wls_c.p;
-    WlsLut t;
-    memcpy(t.w, lut, sizeof(t.w));
-    const dim3 px((unsigned)((npx + 255) / 256));
-    if (e->profile) {   // the stage record is the filter's from here on (one stage name per kernel)
-        e->nstages = 0;
-        e->nevents = 0;
-        e->last_end_ev = -1;
-    }
-    if ((rc = stage_begin(e, "wls_init"))) return rc;
-    hipLaunchKernelGGL(k_wls_init, px, dim3(256), 0, e->stream, d_disp, d_conf, invalid, npx, u, v);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
-    const int T = 3;
-    for (int it = 1; it <= T; it++) {
-        const float lam = (float)(1.5 * lambda * (double)(1 << (2 * (T - it))) / (double)((1 << (2 * T)) - 1));
-        if (W > 1) {   // (a line of one element is the identity)
-            const dim3 grid((H + WLS_T - 1) / WLS_T);
-            if ((rc = stage_begin(e, "wls_rows"))) return rc;
-            if (cn == 3) hipLaunchKernelGGL(k_wls_rows<3>, grid, dim3(WLS_RT), 0, e->stream, u, v, c, d_guide, t, lam, H, W);
-            else hipLaunchKernelGGL(k_wls_rows<1>, grid, dim3(WLS_RT), 0, e->stream, u, v, c, d_guide, t, lam, H, W);
-            KCHECK();
-            if ((rc = stage_end(e, 1))) return rc;
-        }
-        if (H > 1) {
-            const dim3 grid((W + WLS_T - 1) / WLS_T);
-            if ((rc = stage_begin(e, "wls_cols"))) return rc;
-            if (cn == 3) hipLaunchKernelGGL(k_wls_cols<3>, grid, dim3(WLS_T), 0, e->stream, u, v, c, d_guide, t, lam, H, W);
-            else hipLaunchKernelGGL(k_wls_cols<1>, grid, dim3(WLS_T), 0, e->stream, u, v, c, d_guide, t, lam, H, W);
-            KCHECK();
-            if ((rc = stage_end(e, 1))) return rc;
-        }
-    }
-    if ((rc = stage_begin(e, "wls_final"))) return rc;
-    hipLaunchKernelGGL(k_wls_final, px, dim3(256), 0, e->stream, (const float *)u, (const float *)v, invalid, npx, d_out, d_out_f32);
-    KCHECK();
-    return stage_end(e, 1);
-}
-
-int sgm_wls_filter_device(sgm_engine *e, const void *d_disp_i16, const void *d_guide_u8, int cn, const void *d_conf_u8, int H, int W,
-                          int invalid, double lambda, const float lut[256], void *d_out_i16, void *d_out_f32)
-{
-    if (int rc = wls_check_args(e, d_disp_i16, d_guide_u8, cn, H, W, invalid, lambda, lut, d_out_i16)) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    return run_wls(e, (const int16_t *)d_disp_i16, (const uint8_t *)d_guide_u8, cn, (const uint8_t *)d_conf_u8, H, W, invalid, lambda, lut,
-                   (int16_t *)d_out_i16, (float *)d_out_f32);
-}
-
-int sgm_wls_filter(sgm_engine *e, const int16_t *disp, const uint8_t *guide, int cn, const uint8_t *conf, int H, int W, int invalid,
-                   double lambda, const float lut[256], int16_t *out, float *out_f32)
-{
-    if (int rc = wls_check_args(e, disp, guide, cn, H, W, invalid, lambda, lut, out)) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t npx = (size_t)H * W;
-    int rc;
-    // staging: the map in disp_out (filtered in place), the guide in in_left, the confidence in in_right, the float map in f32
-    if ((rc = e->disp_out.ensure(npx * 2)) || (rc = e->in_left.ensure(npx * cn)) || (conf && (rc = e->in_right.ensure(npx))) ||
-        (out_f32 && (rc = e->f32.ensure(npx * 4))))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(e->disp_out.p, disp, npx * 2, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->in_left.p, guide, npx * cn, hipMemcpyHostToDevice, e->stream));
-    if (conf) HIP_TRY(hipMemcpyAsync(e->in_right.p, conf, npx, hipMemcpyHostToDevice, e->stream));
-    if ((rc = run_wls(e, (const int16_t *)e->disp_out.p, (const uint8_t *)e->in_left.p, cn, conf ? (const uint8_t *)e->in_right.p : nullptr, H, W,
-                      invalid, lambda, lut, (int16_t *)e->disp_out.p, out_f32 ? (float *)e->f32.p : nullptr)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(out, e->disp_out.p, npx * 2, hipMemcpyDeviceToHost, e->stream));
-    if (out_f32) HIP_TRY(hipMemcpyAsync(out_f32, e->f32.p, npx * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return SGM_OK;
-}
-
-// ---- the batch form of the filter (include/sgm_hip_wls_batch.h; kernels_wls.h: k_wls_*_b) ------------------------------------------
-// The shapes of the batched line kernels.  Entry 0 is the one the library uses; the others are what DESIGN.md 4.16 measured
-// against it and stay reachable through SGM_OPT_DEBUG (sgm_debug.h) for tools/wls_batch_times.py.  Every shape gives the same bits.
-struct WlsRowsShape { int rw, tc; };   // k_wls_rows_b<CN, RW, TC>: waves per workgroup, columns per tile
+// The shapes of the line kernels.  Entry 0 is the one the library uses for a chunk of several maps, entries 3 (rows) and 1
+// (columns) for a chunk of one (run_wls_batch); the others are what DESIGN.md 4.15 / 4.16 measured against them and stay
+// reachable through SGM_OPT_DEBUG (sgm_debug.h) for tools/wls_batch_times.py.  Every shape gives the same bits.
+struct WlsRowsShape { int rw, tc; };   // k_wls_rows<CN, RW, TC>: waves per workgroup, columns per tile
 static const WlsRowsShape wls_rows_shapes[] = {{4, 32}, {2, 64}, {1, 64}, {4, 64}, {2, 32}};
-static const int wls_cols_shapes[] = {8, 16, 32, 4};   // k_wls_cols_b<CN, UNR>: rows in flight per lane
+static const int wls_cols_shapes[] = {8, 16, 32, 4};   // k_wls_cols<CN, UNR>: rows in flight per lane
 
 extern "C++" {   // (templates: this part of the file has C linkage)
 template <int CN>
-static void launch_wls_rows_b(int shape, dim3 grid, hipStream_t st, float *u, float *v, float *c, const WlsPtrs &g, const WlsLut &t,
-                              float lam, int H, int W)
+static void launch_wls_rows(int shape, dim3 grid, hipStream_t st, float *u, float *v, float *c, const MapPtrs &g, const WlsLut &t,
+                            float lam, int H, int W)
 {
     switch (shape) {
-    case 1: hipLaunchKernelGGL((k_wls_rows_b<CN, 2, 64>), grid, dim3(2 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
-    case 2: hipLaunchKernelGGL((k_wls_rows_b<CN, 1, 64>), grid, dim3(1 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
-    case 3: hipLaunchKernelGGL((k_wls_rows_b<CN, 4, 64>), grid, dim3(4 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
-    case 4: hipLaunchKernelGGL((k_wls_rows_b<CN, 2, 32>), grid, dim3(2 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
-    default: hipLaunchKernelGGL((k_wls_rows_b<CN, 4, 32>), grid, dim3(4 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    case 1: hipLaunchKernelGGL((k_wls_rows<CN, 2, 64>), grid, dim3(2 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    case 2: hipLaunchKernelGGL((k_wls_rows<CN, 1, 64>), grid, dim3(1 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    case 3: hipLaunchKernelGGL((k_wls_rows<CN, 4, 64>), grid, dim3(4 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    case 4: hipLaunchKernelGGL((k_wls_rows<CN, 2, 32>), grid, dim3(2 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    default: hipLaunchKernelGGL((k_wls_rows<CN, 4, 32>), grid, dim3(4 * WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
     }
 }
 template <int CN>
-static void launch_wls_cols_b(int shape, dim3 grid, hipStream_t st, float *u, float *v, float *c, const WlsPtrs &g, const WlsLut &t,
-                              float lam, int H, int W)
+static void launch_wls_cols(int shape, dim3 grid, hipStream_t st, float *u, float *v, float *c, const MapPtrs &g, const WlsLut &t,
+                            float lam, int H, int W)
 {
     switch (shape) {
-    case 1: hipLaunchKernelGGL((k_wls_cols_b<CN, 16>), grid, dim3(WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
-    case 2: hipLaunchKernelGGL((k_wls_cols_b<CN, 32>), grid, dim3(WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
-    case 3: hipLaunchKernelGGL((k_wls_cols_b<CN, 4>), grid, dim3(WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
-    default: hipLaunchKernelGGL((k_wls_cols_b<CN, 8>), grid, dim3(WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    case 1: hipLaunchKernelGGL((k_wls_cols<CN, 16>), grid, dim3(WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    case 2: hipLaunchKernelGGL((k_wls_cols<CN, 32>), grid, dim3(WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    case 3: hipLaunchKernelGGL((k_wls_cols<CN, 4>), grid, dim3(WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
+    default: hipLaunchKernelGGL((k_wls_cols<CN, 8>), grid, dim3(WLS_T), 0, st, u, v, c, g, t, lam, H, W); break;
     }
 }
 }  // extern "C++"
@@ -3019,34 +2982,8 @@ static int wls_batch_check_args(const sgm_engine *e, int N, const void *const *d
     return SGM_OK;
 }
 
-// Maps per chunk, and the buffers of the call sized for it.  C = min(N, WLS_BATCH_MAX, SGM_OPT_GROUP_MAX if set), cut to what
-// free device memory allows beside the reserve of prepare_group (4 GiB or 5 %) when a buffer has to grow; at least 1.  All
-// allocations of the call happen here, before anything is enqueued.
-struct WlsNeed { DevBuf *b; size_t per_map; };
-static int wls_batch_reserve(sgm_engine *e, int N, std::initializer_list<WlsNeed> needs, int *C_out)
-{
-    int C = std::min(N, WLS_BATCH_MAX);
-    if (e->group_max > 0) C = std::min(C, e->group_max);
-    size_t per_map = 0, freed = 0;   // of the buffers that grow: bytes per map, and what they give back first (DevBuf::ensure)
-    for (const WlsNeed &n : needs)
-        if (n.b->cap < n.per_map * (size_t)C) {
-            per_map += n.per_map;
-            freed += n.b->cap;
-        }
-    size_t fr = 0, tot = 0;
-    if (per_map && hipMemGetInfo(&fr, &tot) == hipSuccess) {
-        const size_t reserve = std::max<size_t>((size_t)4 << 30, tot / 20), have = fr + freed;
-        const size_t room = have > reserve ? have - reserve : 0;
-        C = (int)std::max<size_t>(1, std::min<size_t>((size_t)C, room / per_map));
-    }
-    for (const WlsNeed &n : needs)
-        if (int rc = n.b->ensure(n.per_map * (size_t)C)) return rc;
-    *C_out = C;
-    return SGM_OK;
-}
-
-// One chunk of n <= WLS_BATCH_MAX maps: init, three times (rows, columns), final, every launch over all n maps.  conf / outf: null
-// for none.  The planes hold n maps (wls_batch_reserve).
+// One chunk of n <= BATCH_MAPS_MAX maps: init, three times (rows, columns), final, every launch over all n maps.  conf / outf: null
+// for none.  The planes hold n maps (batch_reserve).
 static int run_wls_batch(sgm_engine *e, int n, const void *const *d_disp, const void *const *d_guide, int cn, const void *const *d_conf,
                          int H, int W, int invalid, double lambda, const float *lut, void *const *d_out, void *const *d_outf)
 {
@@ -3054,22 +2991,18 @@ static int run_wls_batch(sgm_engine *e, int n, const void *const *d_disp, const 
     float *u = (float *)e->wls_u.p, *v = (float *)e->wls_v.p, *c = (float *)e->wls_c.p;
     WlsLut t;
     memcpy(t.w, lut, sizeof(t.w));
-    WlsPtrs disps{}, guides{}, confs{}, outs{}, outfs{};
-    for (int i = 0; i < n; i++) {
-        disps.p[i] = (void *)d_disp[i];
-        guides.p[i] = (void *)d_guide[i];
-        confs.p[i] = d_conf ? (void *)d_conf[i] : nullptr;
-        outs.p[i] = d_out[i];
-        outfs.p[i] = d_outf ? d_outf[i] : nullptr;
-    }
+    const MapPtrs disps = map_ptrs(d_disp, n), guides = map_ptrs(d_guide, n), confs = map_ptrs(d_conf, n), outs = map_ptrs(d_out, n),
+                  outfs = map_ptrs(d_outf, n);
     const unsigned rsh = ((unsigned)e->debug >> SGM_DBG_WLS_BATCH_ROWS_SHIFT) & 7, csh = ((unsigned)e->debug >> SGM_DBG_WLS_BATCH_COLS_SHIFT) & 3;
-    const int rshape = rsh < sizeof(wls_rows_shapes) / sizeof(wls_rows_shapes[0]) ? (int)rsh : 0;
-    const int cshape = csh < sizeof(wls_cols_shapes) / sizeof(wls_cols_shapes[0]) ? (int)csh : 0;
+    // a chunk of one map has the CUs to itself, one workgroup each at most: there 64-column tiles and 16 rows in flight are the
+    // faster shapes (entries 3 and 1).  A non-zero debug field overrides that.
+    const int rshape = !rsh ? (n == 1 ? 3 : 0) : rsh < sizeof(wls_rows_shapes) / sizeof(wls_rows_shapes[0]) ? (int)rsh : 0;
+    const int cshape = !csh ? (n == 1 ? 1 : 0) : csh < sizeof(wls_cols_shapes) / sizeof(wls_cols_shapes[0]) ? (int)csh : 0;
     const dim3 px((unsigned)((npx + 255) / 256), n);
     int rc;
     stage_break(e);   // (the host entry's copies lie between the chunks)
     if ((rc = stage_begin(e, "wls_init"))) return rc;
-    hipLaunchKernelGGL(k_wls_init_b, px, dim3(256), 0, e->stream, disps, confs, invalid, npx, u, v);
+    hipLaunchKernelGGL(k_wls_init, px, dim3(256), 0, e->stream, disps, confs, invalid, npx, u, v);
     KCHECK();
     if ((rc = stage_end(e, 1))) return rc;
     const int T = 3;
@@ -3078,22 +3011,22 @@ static int run_wls_batch(sgm_engine *e, int n, const void *const *d_disp, const 
         if (W > 1) {   // (a line of one element is the identity)
             const dim3 grid((H + WLS_T - 1) / WLS_T, n);
             if ((rc = stage_begin(e, "wls_rows"))) return rc;
-            if (cn == 3) launch_wls_rows_b<3>(rshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
-            else launch_wls_rows_b<1>(rshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
+            if (cn == 3) launch_wls_rows<3>(rshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
+            else launch_wls_rows<1>(rshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
             KCHECK();
             if ((rc = stage_end(e, 1))) return rc;
         }
         if (H > 1) {
             const dim3 grid((W + WLS_T - 1) / WLS_T, n);
             if ((rc = stage_begin(e, "wls_cols"))) return rc;
-            if (cn == 3) launch_wls_cols_b<3>(cshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
-            else launch_wls_cols_b<1>(cshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
+            if (cn == 3) launch_wls_cols<3>(cshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
+            else launch_wls_cols<1>(cshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
             KCHECK();
             if ((rc = stage_end(e, 1))) return rc;
         }
     }
     if ((rc = stage_begin(e, "wls_final"))) return rc;
-    hipLaunchKernelGGL(k_wls_final_b, px, dim3(256), 0, e->stream, (const float *)u, (const float *)v, invalid, npx, outs, outfs);
+    hipLaunchKernelGGL(k_wls_final, px, dim3(256), 0, e->stream, (const float *)u, (const float *)v, invalid, npx, outs, outfs);
     KCHECK();
     return stage_end(e, 1);
 }
@@ -3107,12 +3040,8 @@ int sgm_wls_filter_batch_device(sgm_engine *e, int N, const void *const *d_disp_
     HIP_TRY(hipSetDevice(e->device));
     const size_t pb = (size_t)H * W * 4;
     int rc, C = 1;
-    if ((rc = wls_batch_reserve(e, N, {{&e->wls_u, pb}, {&e->wls_v, pb}, {&e->wls_c, pb}}, &C))) return rc;
-    if (e->profile) {   // the stage record is the call's from here on
-        e->nstages = 0;
-        e->nevents = 0;
-        e->last_end_ev = -1;
-    }
+    if ((rc = batch_reserve(e, N, {{&e->wls_u, pb}, {&e->wls_v, pb}, {&e->wls_c, pb}}, &C))) return rc;
+    if (e->profile) stage_reset(e);   // the stage record is the call's from here on
     for (int i0 = 0; i0 < N; i0 += C)
         if ((rc = run_wls_batch(e, std::min(C, N - i0), d_disp_i16 + i0, d_guide_u8 + i0, cn, d_conf_u8 ? d_conf_u8 + i0 : nullptr, H, W,
                                 invalid, lambda, lut, d_out_i16 + i0, d_out_f32 ? d_out_f32 + i0 : nullptr)))
@@ -3131,14 +3060,10 @@ int sgm_wls_filter_batch(sgm_engine *e, int N, const int16_t *disp, const uint8_
     // staging, [C] of each: the maps in disp_out (filtered in place), the guides in in_left, the confidence maps in in_right, the
     // float maps in f32
     int rc, C = 1;
-    if ((rc = wls_batch_reserve(e, N, {{&e->wls_u, pb}, {&e->wls_v, pb}, {&e->wls_c, pb}, {&e->disp_out, npx * 2}, {&e->in_left, npx * cn},
-                                       {&e->in_right, conf ? npx : 0}, {&e->f32, out_f32 ? pb : 0}}, &C)))
+    if ((rc = batch_reserve(e, N, {{&e->wls_u, pb}, {&e->wls_v, pb}, {&e->wls_c, pb}, {&e->disp_out, npx * 2}, {&e->in_left, npx * cn},
+                                   {&e->in_right, conf ? npx : 0}, {&e->f32, out_f32 ? pb : 0}}, &C)))
         return rc;
-    if (e->profile) {
-        e->nstages = 0;
-        e->nevents = 0;
-        e->last_end_ev = -1;
-    }
+    if (e->profile) stage_reset(e);   // the stage record is the call's from here on
     std::vector<void *> pd(C), pg(C), pc(C), pf(C);
     for (int k = 0; k < C; k++) {
         pd[k] = (char *)e->disp_out.p + (size_t)k * npx * 2;
@@ -3161,6 +3086,22 @@ int sgm_wls_filter_batch(sgm_engine *e, int N, const int16_t *disp, const uint8_
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     return SGM_OK;
+}
+
+// the single entries: their own refusals (sgm_wls_filter: ...), then a batch of one
+int sgm_wls_filter_device(sgm_engine *e, const void *d_disp_i16, const void *d_guide_u8, int cn, const void *d_conf_u8, int H, int W,
+                          int invalid, double lambda, const float lut[256], void *d_out_i16, void *d_out_f32)
+{
+    if (int rc = wls_check_args(e, d_disp_i16, d_guide_u8, cn, H, W, invalid, lambda, lut, d_out_i16)) return rc;
+    return sgm_wls_filter_batch_device(e, 1, &d_disp_i16, &d_guide_u8, cn, d_conf_u8 ? &d_conf_u8 : nullptr, H, W, invalid, lambda, lut,
+                                       &d_out_i16, d_out_f32 ? &d_out_f32 : nullptr);
+}
+
+int sgm_wls_filter(sgm_engine *e, const int16_t *disp, const uint8_t *guide, int cn, const uint8_t *conf, int H, int W, int invalid,
+                   double lambda, const float lut[256], int16_t *out, float *out_f32)
+{
+    if (int rc = wls_check_args(e, disp, guide, cn, H, W, invalid, lambda, lut, out)) return rc;
+    return sgm_wls_filter_batch(e, 1, disp, guide, cn, conf, H, W, invalid, lambda, lut, out, out_f32);
 }
 
 // ---- the left-right consistency confidence (include/sgm_hip_lrc.h, kernels_lrc.h) ---------------------------------------------
@@ -3198,18 +3139,12 @@ static int lrc_check_overlap(int N, const void *const *left, const void *const *
     return SGM_OK;
 }
 
-// One chunk of n <= WLS_BATCH_MAX pairs, arguments checked, lrc_f holding n pairs of planes: factor, match.
+// One chunk of n <= BATCH_MAPS_MAX pairs, arguments checked, lrc_f holding n pairs of planes: factor, match.
 static int run_lrc_batch(sgm_engine *e, int n, const void *const *d_left, const void *const *d_right, const void *const *d_base, int H,
                          int W, int invalid, int thresh, int radius, int var_max, void *const *d_cl, void *const *d_cr)
 {
-    WlsPtrs lefts{}, rights{}, bases{}, cls{}, crs{};
-    for (int i = 0; i < n; i++) {
-        lefts.p[i] = (void *)d_left[i];
-        rights.p[i] = (void *)d_right[i];
-        bases.p[i] = d_base ? (void *)d_base[i] : nullptr;
-        cls.p[i] = d_cl ? d_cl[i] : nullptr;
-        crs.p[i] = d_cr ? d_cr[i] : nullptr;
-    }
+    const MapPtrs lefts = map_ptrs(d_left, n), rights = map_ptrs(d_right, n), bases = map_ptrs(d_base, n), cls = map_ptrs(d_cl, n),
+                  crs = map_ptrs(d_cr, n);
     uint8_t *fac = (uint8_t *)e->lrc_f.p;
     int rc;
     stage_break(e);
@@ -3238,12 +3173,8 @@ int sgm_lrc_confidence_batch_device(sgm_engine *e, int N, const void *const *d_l
     if (int rc = lrc_check_overlap(N, d_lefts, d_rights, d_bases, d_conf_lefts, d_conf_rights)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     int rc, C = 1;
-    if ((rc = wls_batch_reserve(e, N, {{&e->lrc_f, (size_t)H * W * 2}}, &C))) return rc;
-    if (e->profile) {   // the stage record is the call's from here on
-        e->nstages = 0;
-        e->nevents = 0;
-        e->last_end_ev = -1;
-    }
+    if ((rc = batch_reserve(e, N, {{&e->lrc_f, (size_t)H * W * 2}}, &C))) return rc;
+    if (e->profile) stage_reset(e);   // the stage record is the call's from here on
     for (int i0 = 0; i0 < N; i0 += C)
         if ((rc = run_lrc_batch(e, std::min(C, N - i0), d_lefts + i0, d_rights + i0, d_bases ? d_bases + i0 : nullptr, H, W, invalid,
                                 thresh, radius, var_max, d_conf_lefts ? d_conf_lefts + i0 : nullptr,
@@ -3323,11 +3254,7 @@ int sgm_voxel_downsample_device(sgm_engine *e, const void *d_xyz, const void *d_
     int rc;
     if ((rc = e->vox_ctl.ensure(VOX_CTL_WORDS * 4)) || (rc = e->vox_slot.ensure((size_t)n * 4)) || (rc = e->ccount.ensure((size_t)(m + 1) * 4)))
         return rc;
-    if (e->profile) {   // the stage record is the call's from here on
-        e->nstages = 0;
-        e->nevents = 0;
-        e->last_end_ev = -1;
-    }
+    if (e->profile) stage_reset(e);   // the stage record is the call's from here on
     const VoxGrid G{1.0f / voxel_size, voxel_size, origin[0], origin[1], origin[2]};
     const float *xyz = (const float *)d_xyz, *disp = (const float *)d_disp_f32;
     const uint8_t *colors = (const uint8_t *)(d_out_colors ? d_colors_rgb : nullptr);

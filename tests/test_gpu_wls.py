@@ -65,6 +65,46 @@ def test_shapes_through_the_host_entry(eng, H, W, cn, with_conf, lam, sigma, inv
         assert 0 < want["valid"].sum() and (want["out"] != s["disp"]).any()     # the case does something
 
 
+# Every shape of the line kernels gives the same bits (csrc/sgm_debug.h): the five of wls_rows_shapes beside the default column
+# shape, the four of wls_cols_shapes beside the default row shape.  A single map is a chunk of one, so a shape picked for such
+# chunks is what every single call runs; a non-zero field selects its shape for every chunk, 0 leaves the choice to the library
+# (one pair of shapes for the single calls below, another for the batches of three).
+ROWS_SHIFT, COLS_SHIFT = 17, 20       # SGM_DBG_WLS_BATCH_ROWS_SHIFT, SGM_DBG_WLS_BATCH_COLS_SHIFT
+LINE_SHAPES = [("rows", i, i << ROWS_SHIFT) for i in range(5)] + [("cols", i, i << COLS_SHIFT) for i in range(4)]
+
+
+@pytest.mark.parametrize("debug", [d for _, _, d in LINE_SHAPES], ids=[f"{k}{i}" for k, i, _ in LINE_SHAPES])
+def test_every_line_kernel_shape_gives_the_same_bits(debug):
+    import torch
+    e = Engine(P16)
+    e.set_option(_lib.SGM_OPT_DEBUG, debug)
+    dev = torch.device("cuda", e.device)
+    up = lambda a: None if a is None else torch.from_numpy(a.copy()).to(dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    for case in WR.SHAPE_CASES:
+        H, W, cn, with_conf, lam, sigma, invalid = case
+        s, want = _case(*case)
+        d, g, c = up(s["disp"]), up(s["guide"]), up(s["conf"])
+        out = torch.full((H, W), 77, dtype=torch.int16, device=dev)
+        outf = torch.full((H, W), 7.0, dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        e.wls_filter_device(ptr(d), ptr(g), cn, ptr(c), H, W, invalid, lam, _weights(sigma), ptr(out), ptr(outf))
+        e.synchronize()
+        _same(out.cpu().numpy(), outf.cpu().numpy(), want, ("single", debug, H, W, cn))
+    for case in (WR.SHAPE_CASES[6], WR.SHAPE_CASES[7]):       # 65 x 129 gray with confidence, 130 x 67 colour without
+        H, W, cn, with_conf, lam, sigma, invalid = case
+        maps = [_case(*case, seed=2000 + i) for i in range(3)]
+        d, g, c = ([up(s[k]) for s, _ in maps] for k in ("disp", "guide", "conf"))
+        out = [torch.full((H, W), 77, dtype=torch.int16, device=dev) for _ in maps]
+        outf = [torch.full((H, W), 7.0, dtype=torch.float32, device=dev) for _ in maps]
+        ptrs = lambda ts: None if ts[0] is None else [t.data_ptr() for t in ts]
+        torch.cuda.synchronize()
+        e.wls_filter_batch_device(ptrs(d), ptrs(g), cn, ptrs(c), H, W, invalid, lam, _weights(sigma), ptrs(out), ptrs(outf))
+        e.synchronize()
+        for i, (_, want) in enumerate(maps):
+            _same(out[i].cpu().numpy(), outf[i].cpu().numpy(), want, ("batch", debug, H, W, cn, i))
+
+
 # ---- 2. lambda / sigma, channels, confidence ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("lam,sigma", [(0.0, 1.5), (100.0, 10.0), (8000.0, 1.5), (8000.0, 0.5), (1e6, 1.5)])
 @pytest.mark.parametrize("H,W,cn,with_conf,invalid", [(65, 129, 1, False, -160), (130, 67, 3, True, -16)])

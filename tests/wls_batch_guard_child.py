@@ -1,7 +1,7 @@
 """Child process of tests/test_gpu_wls_batch.py: batches of the edge-aware disparity filter under the engine's GUARDED allocation
 mode (SGM_DEBUG_ALLOC=1, sgm_engine.hip: DevBuf::ensure_guarded; why: tests/guard_child.py), through the host entry.  The three
 float planes [C][H][W] and the staged maps, guides and confidence maps of a chunk end where their mappings end, so the LAST map
-of a chunk is the one whose neighbour reads (guide[i + 1] in k_wls_rows_b, guide[i + W] in k_wls_cols_b) or tile rows past its
+of a chunk is the one whose neighbour reads (guide[i + 1] in k_wls_rows, guide[i + W] in k_wls_cols) or tile rows past its
 last pixel would die here with a memory access fault, which ends THIS process, not the test session; a map in the middle that
 strays into its neighbour's plane shows as a wrong result instead.  Ragged tails in both directions, degenerate lines, a batch
 cut into chunks.  An engine per case (the regrow finding): every buffer then has exactly the case's size.

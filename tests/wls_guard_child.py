@@ -2,7 +2,8 @@
 allocation mode (SGM_DEBUG_ALLOC=1, sgm_engine.hip: DevBuf::ensure_guarded; why: tests/guard_child.py).  The three float planes
 and the staged map, guide and confidence end where their mappings end, so a neighbour read past the last pixel of a line
 (guide[i + 1] in k_wls_rows, guide[i + W] in k_wls_cols) or a tile row stored past a plane dies here with a memory access fault,
-which ends THIS process, not the test session.  An engine per case, as in the other guard children: every buffer then has exactly
+which ends THIS process, not the test session.  A single map is a chunk of one of the same kernels the batch entries run
+(csrc/kernels_wls.h), in the shape the library picks for such a chunk.  An engine per case, as in the other guard children: every buffer then has exactly
 the case's size.  Prints one line `WLS_GUARD_OK <cases>` when everything ran and matched."""
 import os
 import sys
