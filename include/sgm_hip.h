@@ -55,7 +55,8 @@ extern "C" {
                              * SGM_TAP_CONF, sgm_bind_confidence_device (sgm_hip_confidence.h); SGM_OPT_RIGHT_VIEW, SGM_TAP_RIGHT_RAW,
                              * SGM_TAP_RIGHT, sgm_bind_right_device (sgm_hip_right.h); SGM_OPT_COST, SGM_COST_BT, SGM_COST_CENSUS;
                              * the disparity post-filter of sgm_hip_wls.h and sgm_hip_wls_batch.h; the left-right
-                             * consistency confidence of sgm_hip_lrc.h; the voxel-grid downsampling of sgm_hip_voxel.h */
+                             * consistency confidence of sgm_hip_lrc.h; the voxel-grid downsampling of sgm_hip_voxel.h; the grid
+                             * triangulation of sgm_hip_mesh.h */
 
 typedef enum {
     SGM_OK = 0,
@@ -314,4 +315,6 @@ int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_r
 #include "sgm_hip_lrc.h"
 /* voxel-grid downsampling of the point cloud: one centroid, mean colour and count per occupied voxel */
 #include "sgm_hip_voxel.h"
+/* a triangle mesh from the organised cloud: two triangles per pixel quad wherever the disparity is continuous */
+#include "sgm_hip_mesh.h"
 #endif

@@ -9,7 +9,8 @@ from .stereo import (CV_32F, STEREO_COST_BT, STEREO_COST_CENSUS, STEREO_SGBM_MOD
                      INTER_LINEAR, BORDER_CONSTANT, DisparityWLSFilter, createDisparityWLSFilter, wls_weights,
                      lrcConfidence)
 from .pipeline import compute_disparity_map, reconstruct_3D, rectify_pair, run_disparity, valid_point_mask
-from .pointcloud import mask_by_confidence, read_point_cloud, valid_points, voxel_down_sample, write_point_cloud
+from .pointcloud import (mask_by_confidence, read_point_cloud, read_triangle_mesh, triangulate_points, valid_points,
+                         voxel_down_sample, write_point_cloud, write_triangle_mesh)
 from ._lib import SGM_OPT_CONFIDENCE, SGM_TAP_CONF, SGM_TAP_CONF_RAW
 from ._lib import SGM_OPT_RIGHT_VIEW, SGM_TAP_RIGHT, SGM_TAP_RIGHT_RAW
 
@@ -21,5 +22,5 @@ __all__ = [
     "mask_by_confidence", "SGM_OPT_CONFIDENCE", "SGM_TAP_CONF_RAW", "SGM_TAP_CONF",
     "SGM_OPT_RIGHT_VIEW", "SGM_TAP_RIGHT_RAW", "SGM_TAP_RIGHT", "STEREO_COST_BT", "STEREO_COST_CENSUS",
     "DisparityWLSFilter", "createDisparityWLSFilter", "wls_weights", "lrcConfidence",
-    "voxel_down_sample",
+    "voxel_down_sample", "triangulate_points", "write_triangle_mesh", "read_triangle_mesh",
 ]

@@ -31,6 +31,7 @@
 #include "kernels_wls.h"
 #include "kernels_lrc.h"
 #include "kernels_voxel.h"
+#include "kernels_mesh.h"
 
 using namespace sgm;
 
@@ -263,6 +264,7 @@ struct Plan {
     BUF(wls_u) BUF(wls_v) BUF(wls_c)             /* sgm_wls_filter: float [H][W] planes u, v, c' (kernels_wls.h); sgm_trim releases these three by name */ \
     BUF(lrc_f)                                   /* sgm_lrc_confidence: uint8 [pairs of a chunk][2][H][W], the smoothness factors (kernels_lrc.h); sgm_trim releases it by name */ \
     BUF(vox_tab) BUF(vox_slot) BUF(vox_ctl) BUF(vox_cnt) /* sgm_voxel_downsample: the hash table (VoxSlot [capacity]), each point's slot (uint32 [n]), the call's control words, the host entry's staged counts (kernels_voxel.h); sgm_trim releases the first two by name */ \
+    BUF(mesh_code) BUF(mesh_num) BUF(mesh_fcnt) BUF(mesh_vcnt) BUF(mesh_faces) /* sgm_mesh_grid: a code byte per quad (uint8 [H][W]), the pixel -> vertex number map (uint32 [H][W]), the blocks' numbers of faces and of vertices (uint32 [blocks + 1] each), the host entry's staged faces (kernels_mesh.h); sgm_trim releases the first two and the last by name */ \
     BUF(headroom)                                /* uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r */ \
     BUF(chain_ctl) BUF(chain_err)                /* chained sweeps: ticket + progress words (zeroed before every launch); sticky give-up flag */ \
     ARR(io, [2][5])                              /* sgm_compute_batch, throughput mode: the transfer slots (sgm_engine says what they hold) */
@@ -2039,8 +2041,8 @@ int sgm_trim(sgm_engine *e)
     e->pin_disp.release();
     for (auto &slot : e->pin_io)
         for (HostBuf &b : slot) b.release();
-    for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f, &e->vox_tab, &e->vox_slot})
-        (void)b->release();   // the filter's planes, the LR confidence's factors and the voxel table come back on the next call
+    for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f, &e->vox_tab, &e->vox_slot, &e->mesh_code, &e->mesh_num, &e->mesh_faces})
+        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table and the mesh's maps come back on the next call
     return check_chain(e);
 }
 
@@ -3346,6 +3348,119 @@ int sgm_voxel_downsample(sgm_engine *e, const float *xyz, const float *disp, con
     HIP_TRY(hipStreamSynchronize(e->stream));
     *n_voxels = nv;
     if (n_out_of_range) *n_out_of_range = noor;
+    return SGM_OK;
+}
+
+// ---- triangle mesh from the organised cloud (include/sgm_hip_mesh.h, kernels_mesh.h) -------------------------------------------
+static int mesh_check_args(const sgm_engine *e, const void *xyz, const void *disp, const void *colors, int H, int W, float max_diff,
+                           const void *out_vertices, const void *out_colors, const void *out_faces, const int64_t *n_vertices,
+                           const int64_t *n_faces)
+{
+    if (!e || !xyz || !disp || !out_vertices || !out_faces || !n_vertices || !n_faces)
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_mesh_grid: null pointer");
+    if (H < 1 || W < 1) return set_err(SGM_ERR_INVALID_ARG, "sgm_mesh_grid: a frame of %d x %d pixels", H, W);
+    if (!std::isfinite(max_diff) || !(max_diff >= 0.0f))
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_mesh_grid: max_diff %g is not finite and >= 0", (double)max_diff);
+    if (out_colors && !colors) return set_err(SGM_ERR_INVALID_ARG, "sgm_mesh_grid: out_colors requested without colors");
+    if ((int64_t)H * W > MESH_MAX_PIXELS)
+        return set_err(SGM_ERR_UNSUPPORTED, "sgm_mesh_grid: %d x %d pixels, more than 2^26", H, W);
+    return SGM_OK;
+}
+
+int sgm_mesh_grid_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int H, int W, float max_diff,
+                         void *d_out_vertices, void *d_out_colors, void *d_out_faces, int64_t *n_vertices, int64_t *n_faces)
+{
+    if (int rc = mesh_check_args(e, d_xyz, d_disp_f32, d_colors_rgb, H, W, max_diff, d_out_vertices, d_out_colors, d_out_faces, n_vertices,
+                                 n_faces))
+        return rc;
+    if (H < 2 || W < 2) {   // no quad
+        *n_vertices = 0;
+        *n_faces = 0;
+        return SGM_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const int64_t n = (int64_t)H * W;
+    const int m = (int)((n + MESH_BLOCK - 1) / MESH_BLOCK);   // (n <= 2^26: at most 2^16 blocks)
+    int rc;
+    if ((rc = e->mesh_code.ensure((size_t)n)) || (rc = e->mesh_num.ensure((size_t)n * 4)) || (rc = e->mesh_fcnt.ensure((size_t)(m + 1) * 4)) ||
+        (rc = e->mesh_vcnt.ensure((size_t)(m + 1) * 4)))
+        return rc;
+    if (e->profile) stage_reset(e);   // the stage record is the call's from here on
+    const float *xyz = (const float *)d_xyz, *disp = (const float *)d_disp_f32;
+    const uint8_t *colors = (const uint8_t *)(d_out_colors ? d_colors_rgb : nullptr);
+    uint8_t *code = (uint8_t *)e->mesh_code.p;
+    uint32_t *number = (uint32_t *)e->mesh_num.p, *fcnt = (uint32_t *)e->mesh_fcnt.p, *vcnt = (uint32_t *)e->mesh_vcnt.p;
+    hipStream_t st = e->stream;
+    // 1. every quad's code and the blocks' numbers of triangles; 2. from the codes, the blocks' numbers of vertices
+    if ((rc = stage_begin(e, "mesh_quads"))) return rc;
+    // (16-byte loads where every group of four pixels, and the four below it, starts on a 16-byte boundary)
+    const bool wide = W % 4 == 0 && (uintptr_t)xyz % 16 == 0 && (uintptr_t)disp % 16 == 0;
+    if (wide) hipLaunchKernelGGL(k_mesh_quads<true>, dim3(m), dim3(MESH_BLOCK / 4), 0, st, xyz, disp, H, W, max_diff, code, fcnt);
+    else hipLaunchKernelGGL(k_mesh_quads<false>, dim3(m), dim3(MESH_BLOCK / 4), 0, st, xyz, disp, H, W, max_diff, code, fcnt);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    if ((rc = stage_begin(e, "mesh_used"))) return rc;
+    hipLaunchKernelGGL(k_mesh_used, dim3(m), dim3(MESH_BLOCK), 0, st, (const uint8_t *)code, H, W, vcnt);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    // 3. both lists of counts become offsets, the totals behind them
+    if ((rc = stage_begin(e, "mesh_scan"))) return rc;
+    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, vcnt, m);
+    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, fcnt, m);
+    KCHECK();
+    if ((rc = stage_end(e, 2))) return rc;
+    // 4. the vertices and each used pixel's number; 5. the faces, in those numbers
+    if ((rc = stage_begin(e, "mesh_vertices"))) return rc;
+    hipLaunchKernelGGL(k_mesh_vertices, dim3(m), dim3(MESH_BLOCK), 0, st, xyz, colors, (const uint8_t *)code, H, W, (const uint32_t *)vcnt,
+                       (float *)d_out_vertices, (uint8_t *)d_out_colors, number);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    if ((rc = stage_begin(e, "mesh_faces"))) return rc;
+    hipLaunchKernelGGL(k_mesh_faces, dim3(m), dim3(MESH_BLOCK), 0, st, (const uint8_t *)code, (const uint32_t *)number, H, W, (const uint32_t *)fcnt,
+                       (int32_t *)d_out_faces);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    uint32_t nv = 0, nf = 0;
+    HIP_TRY(hipMemcpyAsync(&nv, vcnt + m, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&nf, fcnt + m, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_vertices = (int64_t)nv;
+    *n_faces = (int64_t)nf;
+    return SGM_OK;
+}
+
+int sgm_mesh_grid(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int H, int W, float max_diff,
+                  float *out_vertices, uint8_t *out_colors, int32_t *out_faces, int64_t *n_vertices, int64_t *n_faces)
+{
+    if (int rc = mesh_check_args(e, xyz, disp, colors_rgb, H, W, max_diff, out_vertices, out_colors, out_faces, n_vertices, n_faces)) return rc;
+    if (H < 2 || W < 2) {
+        *n_vertices = 0;
+        *n_faces = 0;
+        return SGM_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = (size_t)H * W, fmax = 2 * (size_t)(H - 1) * (W - 1);
+    int rc;
+    if ((rc = e->xyz.ensure(n * 12)) || (rc = e->f32.ensure(n * 4)) || (rc = e->cpts.ensure(n * 12)) || (rc = e->mesh_faces.ensure(fmax * 12)))
+        return rc;
+    if (out_colors && ((rc = e->crgb_in.ensure(n * 3)) || (rc = e->crgb.ensure(n * 3)))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, n * 12, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->f32.p, disp, n * 4, hipMemcpyHostToDevice, e->stream));
+    if (out_colors) HIP_TRY(hipMemcpyAsync(e->crgb_in.p, colors_rgb, n * 3, hipMemcpyHostToDevice, e->stream));
+    int64_t nv = 0, nf = 0;
+    if ((rc = sgm_mesh_grid_device(e, e->xyz.p, e->f32.p, out_colors ? e->crgb_in.p : nullptr, H, W, max_diff, e->cpts.p,
+                                   out_colors ? e->crgb.p : nullptr, e->mesh_faces.p, &nv, &nf))) {
+        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
+        return rc;
+    }
+    if (nv > 0) {
+        HIP_TRY(hipMemcpyAsync(out_vertices, e->cpts.p, (size_t)nv * 12, hipMemcpyDeviceToHost, e->stream));
+        if (out_colors) HIP_TRY(hipMemcpyAsync(out_colors, e->crgb.p, (size_t)nv * 3, hipMemcpyDeviceToHost, e->stream));
+    }
+    if (nf > 0) HIP_TRY(hipMemcpyAsync(out_faces, e->mesh_faces.p, (size_t)nf * 12, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    *n_vertices = nv;
+    *n_faces = nf;
     return SGM_OK;
 }
 

@@ -257,6 +257,33 @@ class Engine:
                                                    int(min_points), d_points, d_out_colors, d_out_counts, C.byref(nv), C.byref(noor)))
         return int(nv.value), int(noor.value)
 
+    # -- triangle mesh from the organised cloud (include/sgm_hip_mesh.h) --
+    def mesh_grid_host(self, xyz: np.ndarray, disp: np.ndarray, colors: np.ndarray | None, max_diff: float = 1.0):
+        """sgm_mesh_grid: float32 points (H, W, 3), float32 disparities (H, W), uint8 colours (H, W, 3) or None.  Returns
+        (vertices float32 (V, 3), colors uint8 (V, 3) or None, faces int32 (F, 3)): the vertices in row-major order of their
+        pixels, the faces in row-major order of their quads."""
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        H, W = xyz.shape[:2]
+        disp = np.ascontiguousarray(disp, np.float32).reshape(H, W)
+        colors = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(H, W, 3)
+        vert = np.empty((H * W, 3), np.float32)
+        rgb = None if colors is None else np.empty((H * W, 3), np.uint8)
+        faces = np.empty((2 * max(H - 1, 0) * max(W - 1, 0), 3), np.int32)
+        nv, nf = C.c_int64(0), C.c_int64(0)
+        at = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.sgm_mesh_grid(self._h, xyz.ctypes.data, disp.ctypes.data, at(colors), H, W, float(max_diff), vert.ctypes.data,
+                                     at(rgb), faces.ctypes.data, C.byref(nv), C.byref(nf)))
+        return vert[:nv.value].copy(), None if rgb is None else rgb[:nv.value].copy(), faces[:nf.value].copy()
+
+    def mesh_grid_device(self, d_xyz: int, d_dispf: int, d_colors: int | None, H: int, W: int, max_diff: float, d_vertices: int,
+                         d_out_colors: int | None, d_faces: int):
+        """sgm_mesh_grid_device: device addresses, outputs with room for H * W vertex rows and 2 (H - 1)(W - 1) face rows; the rows
+        go to the front of the outputs.  Returns (n_vertices, n_faces); synchronises the engine's stream."""
+        nv, nf = C.c_int64(0), C.c_int64(0)
+        _check(self._L.sgm_mesh_grid_device(self._h, d_xyz, d_dispf, d_colors, int(H), int(W), float(max_diff), d_vertices, d_out_colors,
+                                            d_faces, C.byref(nv), C.byref(nf)))
+        return int(nv.value), int(nf.value)
+
     def median3x3_host(self, img: np.ndarray) -> np.ndarray:
         img = np.ascontiguousarray(img, np.int16)
         out = np.empty_like(img)
