@@ -64,7 +64,24 @@ template <int GW> __device__ __forceinline__ uint32_t group_from_upper(uint32_t 
 {
     return max(dpp_view<DPP_WAVE_SHL1>(v), ge.last);
 }
-template <int NP, bool PARTIAL, int GW = 64>
+// path_elem<.., BIAS = true> (the chained sweeps): the state is held CLAMPED AND BIASED.  With B = 0x7fff - P2 per int16 half (path_bias) the
+// wave carries Lb(d) = min(Lq'(d), P2) + B, in [B, 0x7fff], and Cp is C - B.  A state enters the recurrence only through
+// min(Lq'(d), Lq'(d+-1) + P1, P2), for which the clamped state does as well as the state itself, and
+//     pk_adds_s(min(Lb(d-1), Lb(d+1)), P1) = min(Lq'(d-1) + P1, Lq'(d+1) + P1, P2) + B
+// because the add saturates at 0x7fff = P2 + B: the clamp to P2 comes with the add that is there anyway, and the minimum
+// with Lb(d) <= P2 + B leaves t + B exactly (P2 + P1 > P2: the clamp of a neighbour never wins against the P2 term it
+// stands for).  (C - B) + (t + B) is the same L_r(p,.) as the plain form returns, bit for bit (wrapping 16-bit adds:
+// C - B may be negative, the sum is not), so S, the minimum and the headroom record do not change; path_normalise_bias
+// makes the next state with the one saturating add the normalisation costs anyway.  The sentinel 0x7fff is "P2 or more"
+// in the biased domain as it is "MAX_COST" in the plain one.  P2s is unused.
+__host__ __device__ inline uint32_t path_bias(int P2)
+{
+    // P2 > 32767 is outside the int16 regime whatever the state's form (hr[0] + P2 > 32767: sgm_get_headroom says so);
+    // the bias only has to stay a non-negative int16 there
+    const uint32_t B = P2 < 0x7fff ? 0x7fffu - (uint32_t)(P2 > 0 ? P2 : 0) : 0u;
+    return B | (B << 16);
+}
+template <int NP, bool PARTIAL, int GW = 64, bool BIAS = false>
 __device__ __forceinline__ void path_elem(const Pack<NP> &Cp, const Pack<NP> &Lq, uint32_t P1s, uint32_t P2s,
                                           bool active, Pack<NP> &Ln, uint32_t &rmin, ShiftRegs &sr,
                                           GroupEdge ge = GroupEdge())
@@ -84,10 +101,20 @@ __device__ __forceinline__ void path_elem(const Pack<NP> &Cp, const Pack<NP> &Lq
     for (int i = 0; i < NP; i++) {
         const uint32_t prevp = i == 0 ? up : Lq.r[i - 1];
         const uint32_t nextp = i == NP - 1 ? dn : Lq.r[i + 1];
-        const uint32_t lm1 = __builtin_amdgcn_alignbit(Lq.r[i], prevp, 16);
-        const uint32_t lp1 = __builtin_amdgcn_alignbit(nextp, Lq.r[i], 16);
-        uint32_t t = pk_adds_s(pk_min_s(lm1, lp1), P1s);
-        t = pk_min_s(pk_min_s(t, Lq.r[i]), P2s);
+        uint32_t nb;  // min(L(d-1), L(d+1)) per half
+        if constexpr (BIAS) {
+            // the two neighbours a register does not hold itself, in ONE word: {L(d_lo - 1), L(d_hi + 1)} = the previous
+            // register's high half and the next one's low half; the other two are the register's own halves, swapped,
+            // which the packed minimum takes through its operand selects -- NP alignbit per direction instead of NP + 1
+            const uint32_t w = __builtin_amdgcn_alignbit(nextp, prevp, 16);
+            nb = pk_min_s_swap0(Lq.r[i], w);
+        } else {
+            const uint32_t lm1 = __builtin_amdgcn_alignbit(Lq.r[i], prevp, 16);
+            const uint32_t lp1 = __builtin_amdgcn_alignbit(nextp, Lq.r[i], 16);
+            nb = pk_min_s(lm1, lp1);
+        }
+        uint32_t t = pk_min_s(pk_adds_s(nb, P1s), Lq.r[i]);
+        if (!BIAS) t = pk_min_s(t, P2s);
         uint32_t v = pk_add(Cp.r[i], t);
         if (PARTIAL) v = active ? v : SGM_SENT;
         Ln.r[i] = v;
@@ -147,6 +174,18 @@ __device__ __forceinline__ void path_normalise_splat(const Pack<NP> &Ln, uint32_
 #pragma unroll
     for (int i = 0; i < NP; i++) {
         uint32_t v = pk_sub(Ln.r[i], ms);
+        if (PARTIAL) v = active ? v : SGM_SENT;
+        out.r[i] = v;
+    }
+}
+// The biased state min(Ln - m, P2) + B from bms = {B - m, B - m} (wave_min4_bias_splat): Ln - m >= 0 and B >= 0, so the
+// signed saturating add only ever saturates upwards, at 0x7fff = P2 + B -- normalise, clamp and bias in one instruction
+template <int NP, bool PARTIAL>
+__device__ __forceinline__ void path_normalise_bias(const Pack<NP> &Ln, uint32_t bms, bool active, Pack<NP> &out)
+{
+#pragma unroll
+    for (int i = 0; i < NP; i++) {
+        uint32_t v = pk_adds_s(Ln.r[i], bms);
         if (PARTIAL) v = active ? v : SGM_SENT;
         out.r[i] = v;
     }

@@ -35,7 +35,7 @@ struct SweepArgs {
     int R;           // rows per band = compute waves per workgroup
     const int16_t *C;
     int16_t *S;
-    const int16_t *bndL;  // [band][x][3 roles][D], normalised (axis-only sweeps: [band][x][1][D])
+    const int16_t *bndL;  // [band][x][3 roles][D], normalised (axis-only sweeps: [band][x][1][D]); chained: clamped and biased
     uint2 *wta;      // SWEEP_LAST: the records [H][W]; SWEEP_REDUCE: the raw records [H][W] uint4 (ChainFrames::raw)
     int keepS;
     int dbg;  // timing experiments only (results become wrong): 64 = loader wave skips its HBM loads
@@ -197,11 +197,18 @@ __device__ __forceinline__ void sweep_loader_wave(const Geom &g, const SweepArgs
     constexpr int SLOT = sweep_slot_dwords(NP, NR);
     constexpr int ROLE = 64 * NP;  // dwords per role inside a slot
     const int R = a.R;
-    const int W1 = g.W1, D = g.D;
+    int W1 = g.W1;
+    const int D = g.D;
+    // Chained kernels are persistent: this function runs inside the ticket loop, and every "does pixel k exist" condition of the
+    // guarded blocks below depends only on W1.  Left alone, hipcc hoists those conditions out of the ticket loop and holds
+    // them across the whole kernel -- as 0 / 1 values in VGPRs, which a kernel at its 128-register cap then spills to
+    // scratch.  Opaque per band, they are a few scalar compares where they are used and nothing is held.
+    if (CHAIN) asm volatile("" : "+s"(W1));
     const int T = (W1 + PPS - 1) / PPS + 2 * (R - 1);  // lockstep steps
     const bool active = !PARTIAL || (2 * NP * lane < D);
     const int lane_off = active ? 2 * NP * lane : 0;
-    const uint32_t init = active ? 0u : SGM_SENT;
+    // the start state: zero, in the form the band's compute waves hold state in (chained: biased, kernels_path.h)
+    const uint32_t init = active ? (CHAIN ? path_bias(g.P2) : 0u) : SGM_SENT;
     uint32_t *const ring0 = lds + lane * NP;
 
     const bool has_prev = band > 0 && !(a.dbg & 64);
@@ -362,7 +369,9 @@ struct ReduceRow<true> {
 // ==== compute wave: one image row ======================================================================
 // NR = 1 (axis-only form, MODE_HH4): per pixel the in-row path and role B only -- two recurrences, their minima reduced
 // together (wave_min2_splat), one role handed to the row below; same path_elem / path_normalise_splat, same lockstep.
-template <int NP, bool PARTIAL, int MODE, bool POSW, int NR = 3>
+// BIAS (the chained kernels): every path state -- L0, what the rings hold, what the publisher copies to the band's hand-off
+// record -- is the clamped and biased one of path_elem<.., BIAS>; C, S, the minima and the headroom record are as ever.
+template <int NP, bool PARTIAL, int MODE, bool POSW, int NR = 3, bool BIAS = false>
 __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArgs &a, int band, int wave, int lane, uint32_t *lds)
 {
     constexpr int LDAUX = SGM_NT_SWEEP_LOADS ? 2 : 0;  // "nt": every byte the sweep loads is used once
@@ -376,7 +385,8 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
     const int T = (W1 + PPS - 1) / PPS + 2 * (R - 1);
     const bool active = !PARTIAL || (2 * NP * lane < D);
     const int lane_off = active ? 2 * NP * lane : 0;
-    const uint32_t init = active ? 0u : SGM_SENT;
+    const uint32_t Bs = BIAS ? path_bias(g.P2) : 0u;  // {B, B}: the zero state of the biased form
+    const uint32_t init = active ? Bs : SGM_SENT;
     // ring 0 is fed by the loader (row above the band), ring r+1 by compute wave r
     uint32_t *const ring0 = lds + lane * NP;
 
@@ -399,7 +409,7 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
 
     for (int i = 0; i < 2 * wave; i++) wg_barrier();  // start two steps behind the row above
 
-    Pack<NP> L0;  // normalised state of the in-row path
+    Pack<NP> L0;  // state of the in-row path: normalised, or (BIAS) clamped and biased
     L0.fill(init);
     ShiftRegs sr0, srA, srB, srC;
     // headroom record (sgm_get_headroom): largest min_d L_r(p, d) of the row, all four directions.
@@ -461,25 +471,46 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
             }
         }
     };
+    // the cost as the recurrence takes it: C, or C - B once per pixel for the four directions of the biased form
+    auto cost_in = [&](const Pack<NP> &Cp) {
+        Pack<NP> c = Cp;
+        if constexpr (BIAS) {
+#pragma unroll
+            for (int i = 0; i < NP; i++) c.r[i] = pk_sub(Cp.r[i], Bs);
+        }
+        return c;
+    };
     // one pixel: four recurrences (minima reduced two directions at a time), hand-off, S, WTA
     // (vo, so): where this pixel's S goes -- per-lane offset (+ immediate) and scalar offset
     auto pixel = [&](const Pack<NP> &Cp, const Pack<NP> &Sp, const Pack<NP> &QA, const Pack<NP> &QB,
                      const Pack<NP> &QC, int u, int vo, int so) {
         Pack<NP> N0, NA, NB, NC;
         uint32_t r0, rA, rB, rC;
-        path_elem<NP, PARTIAL>(Cp, L0, P1s, P2s, active, N0, r0, sr0);
-        path_elem<NP, PARTIAL>(Cp, QA, P1s, P2s, active, NA, rA, srA);
-        path_elem<NP, PARTIAL>(Cp, QB, P1s, P2s, active, NB, rB, srB);
-        path_elem<NP, PARTIAL>(Cp, QC, P1s, P2s, active, NC, rC, srC);
-        uint32_t ms[4];  // {m, m} of the directions 0, A, B, C
+        const Pack<NP> Cb = cost_in(Cp);
+        path_elem<NP, PARTIAL, 64, BIAS>(Cb, L0, P1s, P2s, active, N0, r0, sr0);
+        path_elem<NP, PARTIAL, 64, BIAS>(Cb, QA, P1s, P2s, active, NA, rA, srA);
+        path_elem<NP, PARTIAL, 64, BIAS>(Cb, QB, P1s, P2s, active, NB, rB, srB);
+        path_elem<NP, PARTIAL, 64, BIAS>(Cb, QC, P1s, P2s, active, NC, rC, srC);
+        uint32_t ms[4];  // {m, m} of the directions 0, A, B, C (BIAS: {B - m, B - m})
         uint32_t rows;
-        wave_min4_splat(r0, rA, rB, rC, ms, rows);
-        hm = max(hm, rows);
         Pack<NP> LA, LB, LC;
-        path_normalise_splat<NP, PARTIAL>(N0, ms[0], active, L0);
-        path_normalise_splat<NP, PARTIAL>(NA, ms[1], active, LA);
-        path_normalise_splat<NP, PARTIAL>(NB, ms[2], active, LB);
-        path_normalise_splat<NP, PARTIAL>(NC, ms[3], active, LC);
+        if constexpr (BIAS) {
+            // one register per lane: the lane's partial minimum IS its register of path costs, so the reduction takes those
+            // registers themselves (whatever path_elem hands back as rmin) and returns them in place (fold32_pair_keep)
+            if constexpr (NP == 1) wave_min4_bias_splat<true>(N0.r[0], NA.r[0], NB.r[0], NC.r[0], Bs, ms, rows);
+            else wave_min4_bias_splat(r0, rA, rB, rC, Bs, ms, rows);
+            path_normalise_bias<NP, PARTIAL>(N0, ms[0], active, L0);
+            path_normalise_bias<NP, PARTIAL>(NA, ms[1], active, LA);
+            path_normalise_bias<NP, PARTIAL>(NB, ms[2], active, LB);
+            path_normalise_bias<NP, PARTIAL>(NC, ms[3], active, LC);
+        } else {
+            wave_min4_splat(r0, rA, rB, rC, ms, rows);
+            path_normalise_splat<NP, PARTIAL>(N0, ms[0], active, L0);
+            path_normalise_splat<NP, PARTIAL>(NA, ms[1], active, LA);
+            path_normalise_splat<NP, PARTIAL>(NB, ms[2], active, LB);
+            path_normalise_splat<NP, PARTIAL>(NC, ms[3], active, LC);
+        }
+        hm = max(hm, rows);
         uint32_t *s = mine + u * SLOT;
         lds_store<NP>(LA, s + 0 * ROLE);
         lds_store<NP>(LB, s + 1 * ROLE);
@@ -499,15 +530,22 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
     auto pixel_axis = [&](const Pack<NP> &Cp, const Pack<NP> &Sp, const Pack<NP> &QB, int u, int vo, int so) {
         Pack<NP> N0, NB;
         uint32_t r0, rB;
-        path_elem<NP, PARTIAL>(Cp, L0, P1s, P2s, active, N0, r0, sr0);
-        path_elem<NP, PARTIAL>(Cp, QB, P1s, P2s, active, NB, rB, srB);
-        uint32_t ms[2];  // {m, m} of the directions 0, B
+        const Pack<NP> Cb = cost_in(Cp);
+        path_elem<NP, PARTIAL, 64, BIAS>(Cb, L0, P1s, P2s, active, N0, r0, sr0);
+        path_elem<NP, PARTIAL, 64, BIAS>(Cb, QB, P1s, P2s, active, NB, rB, srB);
+        uint32_t ms[2];  // {m, m} of the directions 0, B (BIAS: {B - m, B - m})
         uint32_t rows;
-        wave_min2_splat(r0, rB, ms, rows);
-        hm = max(hm, rows);
         Pack<NP> LB;
-        path_normalise_splat<NP, PARTIAL>(N0, ms[0], active, L0);
-        path_normalise_splat<NP, PARTIAL>(NB, ms[1], active, LB);
+        if constexpr (BIAS) {
+            wave_min2_bias_splat(r0, rB, Bs, ms, rows);
+            path_normalise_bias<NP, PARTIAL>(N0, ms[0], active, L0);
+            path_normalise_bias<NP, PARTIAL>(NB, ms[1], active, LB);
+        } else {
+            wave_min2_splat(r0, rB, ms, rows);
+            path_normalise_splat<NP, PARTIAL>(N0, ms[0], active, L0);
+            path_normalise_splat<NP, PARTIAL>(NB, ms[1], active, LB);
+        }
+        hm = max(hm, rows);
         lds_store<NP>(LB, mine + u * SLOT);
         Pack<NP> Sn;
 #pragma unroll
@@ -528,7 +566,7 @@ __device__ __forceinline__ void sweep_compute_wave(const Geom &g, const SweepArg
 #pragma unroll
         for (int u0 = 0; u0 < PB; u0 += PPS) {
             if (FULL || k0 + u0 < W1) {
-                // normalised state of the row above for the PPS pixels of this step (LDS)
+                // state of the row above for the PPS pixels of this step (LDS): normalised, or (BIAS) clamped and biased
                 Pack<NP> QA[PPS], QB[PPS], QC[PPS], Sn[PPS];
 #pragma unroll
                 for (int p = 0; p < PPS; p++) {
@@ -653,7 +691,11 @@ __global__ __launch_bounds__(SWEEP_MAX_ROWS * 64 + 64) void k_sweep(Geom g, Swee
 // (3 / R of a volume, written and read once) instead of the pre-pass's second and third read of C.
 //
 // Workgroup = R compute waves + loader wave (wave R) + publisher wave (wave R + 1).  The compute waves are
-// those of k_sweep, unchanged.  The publisher reads what compute wave R - 1 leaves in its LDS ring (in
+// those of k_sweep with the path state held clamped and biased (sweep_compute_wave<.., BIAS>; kernels_path.h: path_elem):
+// min(L - min, P2) + (0x7fff - P2) instead of L - min, in registers, in the LDS rings and therefore in the hand-off record
+// [band][x][3][D], which only the loader of the band below ever reads; the start state (band 0's row above, the virtual
+// pixels -1 and W1) is the splat of that bias instead of zero.  The pre-pass's records and k_sweep stay unbiased.
+// The publisher reads what compute wave R - 1 leaves in its LDS ring (in
 // k_sweep nobody reads that ring) one step later and stores it to the record of band + 1 with write-through
 // ("sc1") stores; it then advances the band's progress word to the pixels whose stores are known complete:
 // a counted s_waitcnt -- every lockstep step issues the same number of stores (those of pixels that do not
@@ -688,7 +730,9 @@ __device__ __forceinline__ void chain_publisher_wave(const Geom &g, const SweepA
     constexpr int STORES_PER_STEP = NR * PPS * (NP == 4 ? 2 : 1) + 1;  // buf_store<4> = two 64-bit stores; + the progress word
     static_assert(CHAIN_KD * STORES_PER_STEP <= 63, "vmcnt is a 6-bit counter");
     const int R = a.R;
-    const int W1 = g.W1, D = g.D;
+    int W1 = g.W1;
+    const int D = g.D;
+    asm volatile("" : "+s"(W1));  // (per band, as in sweep_loader_wave: nothing derived from it is held across the ticket loop)
     const int NS = (W1 + PPS - 1) / PPS;
     const int T = NS + 2 * (R - 1);
     const bool active = !PARTIAL || (2 * NP * lane < D);
@@ -772,7 +816,7 @@ __global__ __launch_bounds__(CHAIN_MAX_ROWS * 64 + 128) void k_sweep_chain(Geom 
         if constexpr (MODE == SWEEP_REDUCE) a.wta = reinterpret_cast<uint2 *>(fr.raw[f]);
         if (wave == a.R) sweep_loader_wave<NP, PARTIAL, true>(g, a, band, lane, lds);
         else if (wave == a.R + 1) chain_publisher_wave<NP, PARTIAL>(g, a, band, lane, lds);
-        else sweep_compute_wave<NP, PARTIAL, MODE, true>(g, a, band, wave, lane, lds);
+        else sweep_compute_wave<NP, PARTIAL, MODE, true, 3, true>(g, a, band, wave, lane, lds);
     }
 }
 
@@ -815,7 +859,7 @@ __global__ __launch_bounds__(CHAIN_MAX_ROWS * 64 + 128) void k_axis_chain(Geom g
         g.hr = fr.hr[f];
         if (wave == a.R) sweep_loader_wave<NP, PARTIAL, true, 1>(g, a, band, lane, lds);
         else if (wave == a.R + 1) chain_publisher_wave<NP, PARTIAL, 1>(g, a, band, lane, lds);
-        else sweep_compute_wave<NP, PARTIAL, MODE, true, 1>(g, a, band, wave, lane, lds);
+        else sweep_compute_wave<NP, PARTIAL, MODE, true, 1, true>(g, a, band, wave, lane, lds);
     }
 }
 

@@ -30,6 +30,15 @@ __device__ __forceinline__ uint32_t pk_adds_s(uint32_t a, uint32_t b) { return b
 __device__ __forceinline__ uint32_t pk_subs_u(uint32_t a, uint32_t b) { return bits(__builtin_elementwise_sub_sat(as_u(a), as_u(b))); }  // max(0, a-b)
 __device__ __forceinline__ uint32_t pk_max_u(uint32_t a, uint32_t b) { return bits(__builtin_elementwise_max(as_u(a), as_u(b))); }
 __device__ __forceinline__ uint32_t pk_min_u(uint32_t a, uint32_t b) { return bits(__builtin_elementwise_min(as_u(a), as_u(b))); }
+// {min(a.hi, b.lo), min(a.lo, b.hi)}: the packed minimum with a's halves swapped by the instruction's operand selects.
+// (Written as a shuffle in front of pk_min_s, hipcc folds the swap into op_sel for five registers of eight and spends a
+// v_alignbit_b32 on each of the others.)
+__device__ __forceinline__ uint32_t pk_min_s_swap0(uint32_t a, uint32_t b)
+{
+    uint32_t r;
+    asm("v_pk_min_i16 %0, %1, %2 op_sel:[1,0] op_sel_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
 __device__ __forceinline__ uint32_t pk_shr_u(uint32_t a, int s) { return bits(as_u(a) >> (unsigned short)s); }
 
 // DPP controls (GFX9 encodings)
@@ -139,6 +148,46 @@ __device__ __forceinline__ void wave_min2_splat(uint32_t r0, uint32_t r1, uint32
     rows = x;
     ms[0] = __builtin_amdgcn_readlane(x, 0);
     ms[1] = __builtin_amdgcn_readlane(x, 32);
+}
+// The same two reductions for the biased path state of the chained sweeps (kernels_path.h: path_elem<.., BIAS>): what
+// the next state adds is B - m, so the splats handed back are {B - m, B - m}, Bs = {B, B} -- ONE packed subtraction on
+// the register the splats are read from, in front of the v_readlane, instead of one per direction behind them.  `rows`
+// stays the register of the minima themselves (the headroom record's running maximum).
+// KEEP (one register per lane: the operands are the path costs themselves, which S and the next state still need): the half
+// swap exchanges its two registers in place, so keeping them costs a copy of each; a second swap of the same pair puts
+// both back in one instruction.  The operands come back in the registers of that second swap.
+template <bool KEEP>
+__device__ __forceinline__ uint32_t fold32_pair_keep(uint32_t &a, uint32_t &b)
+{
+    if constexpr (!KEEP) return fold32_pair(a, b);
+    const auto s = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+    const uint32_t m = pk_min_s(s[0], s[1]);
+    const auto t = __builtin_amdgcn_permlane32_swap(s[0], s[1], false, false);
+    a = t[0];
+    b = t[1];
+    return m;
+}
+template <bool KEEP = false>
+__device__ __forceinline__ void wave_min4_bias_splat(uint32_t &r0, uint32_t &r1, uint32_t &r2, uint32_t &r3, uint32_t Bs, uint32_t (&bm)[4],
+                                                     uint32_t &rows)
+{
+    const uint32_t f01 = fold32_pair_keep<KEEP>(r0, r1), f23 = fold32_pair_keep<KEEP>(r2, r3);
+    const uint32_t x = row_min_eq(fold_halves(fold16_pair(f01, f23)));
+    rows = x;
+    const uint32_t y = pk_sub(Bs, x);
+    bm[0] = __builtin_amdgcn_readlane(y, 0);
+    bm[2] = __builtin_amdgcn_readlane(y, 16);
+    bm[1] = __builtin_amdgcn_readlane(y, 32);
+    bm[3] = __builtin_amdgcn_readlane(y, 48);
+}
+__device__ __forceinline__ void wave_min2_bias_splat(uint32_t r0, uint32_t r1, uint32_t Bs, uint32_t (&bm)[2], uint32_t &rows)
+{
+    const uint32_t z = fold32_pair(r0, r1);
+    const uint32_t x = row_min_eq(fold_halves(fold16_pair(z, z)));
+    rows = x;
+    const uint32_t y = pk_sub(Bs, x);
+    bm[0] = __builtin_amdgcn_readlane(y, 0);
+    bm[1] = __builtin_amdgcn_readlane(y, 32);
 }
 __device__ __forceinline__ void wave_min3_splat(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t (&ms)[3])
 {
