@@ -9,8 +9,9 @@ from .stereo import (CV_32F, STEREO_COST_BT, STEREO_COST_CENSUS, STEREO_SGBM_MOD
                      INTER_LINEAR, BORDER_CONSTANT, DisparityWLSFilter, createDisparityWLSFilter, wls_weights,
                      lrcConfidence)
 from .pipeline import compute_disparity_map, reconstruct_3D, rectify_pair, run_disparity, valid_point_mask
-from .pointcloud import (mask_by_confidence, read_point_cloud, read_triangle_mesh, triangulate_points, valid_points,
-                         voxel_down_sample, write_point_cloud, write_triangle_mesh)
+from .pointcloud import (estimate_normals, mask_by_confidence, read_ply, read_point_cloud, read_triangle_mesh, triangulate_points,
+                         triangulate_points_with_normals, valid_points, voxel_down_sample, write_ply, write_point_cloud,
+                         write_triangle_mesh)
 from ._lib import SGM_OPT_CONFIDENCE, SGM_TAP_CONF, SGM_TAP_CONF_RAW
 from ._lib import SGM_OPT_RIGHT_VIEW, SGM_TAP_RIGHT, SGM_TAP_RIGHT_RAW
 
@@ -23,4 +24,5 @@ __all__ = [
     "SGM_OPT_RIGHT_VIEW", "SGM_TAP_RIGHT_RAW", "SGM_TAP_RIGHT", "STEREO_COST_BT", "STEREO_COST_CENSUS",
     "DisparityWLSFilter", "createDisparityWLSFilter", "wls_weights", "lrcConfidence",
     "voxel_down_sample", "triangulate_points", "write_triangle_mesh", "read_triangle_mesh",
+    "estimate_normals", "triangulate_points_with_normals", "write_ply", "read_ply",
 ]

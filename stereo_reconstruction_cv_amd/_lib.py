@@ -52,6 +52,8 @@ LRC_EXPORTS = ("sgm_lrc_confidence", "sgm_lrc_confidence_device", "sgm_lrc_confi
 VOXEL_EXPORTS = ("sgm_voxel_downsample", "sgm_voxel_downsample_device")
 # include/sgm_hip_mesh.h (likewise): the triangle mesh from the organised cloud
 MESH_EXPORTS = ("sgm_mesh_grid", "sgm_mesh_grid_device")
+# include/sgm_hip_normals.h (likewise): the vertex normals of that mesh and the normal image of the organised cloud
+NORMALS_EXPORTS = ("sgm_normals_grid", "sgm_normals_grid_device", "sgm_mesh_grid_normals", "sgm_mesh_grid_normals_device")
 
 
 class SgmParams(C.Structure):
@@ -142,6 +144,10 @@ def load():
     L.sgm_voxel_downsample_device.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float, vp, i32, vp, vp, vp, vp, vp]
     L.sgm_mesh_grid.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, vp, vp]
     L.sgm_mesh_grid_device.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, vp, vp]
+    L.sgm_normals_grid.argtypes = [vp, vp, vp, i32, i32, C.c_float, i32, vp]
+    L.sgm_normals_grid_device.argtypes = [vp, vp, vp, i32, i32, C.c_float, i32, vp]
+    L.sgm_mesh_grid_normals.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, i32, vp, vp, vp, vp, vp, vp]
+    L.sgm_mesh_grid_normals_device.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, i32, vp, vp, vp, vp, vp, vp]
     L.sgm_synchronize.argtypes = [vp]
     L.sgm_get_stage_times.argtypes = [vp, C.POINTER(SgmStageTimes)]
     L.sgm_algorithmic_bytes.argtypes = [pp, i32, i32, i32]
@@ -166,7 +172,7 @@ def load():
     L.sgm_debug_wta_raw_bytes.restype = C.c_longlong
     L.sgm_debug_wta_select_n.argtypes = [i32, i32, vp, i32, vp]
     L.sgm_debug_wta_select_n.restype = i32
-    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS + VOXEL_EXPORTS + MESH_EXPORTS:
+    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS + VOXEL_EXPORTS + MESH_EXPORTS + NORMALS_EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("sgm_abi_version", "sgm_device_count"):
             fn.restype = i32

@@ -32,6 +32,7 @@
 #include "kernels_lrc.h"
 #include "kernels_voxel.h"
 #include "kernels_mesh.h"
+#include "kernels_normals.h"
 
 using namespace sgm;
 
@@ -265,6 +266,7 @@ struct Plan {
     BUF(lrc_f)                                   /* sgm_lrc_confidence: uint8 [pairs of a chunk][2][H][W], the smoothness factors (kernels_lrc.h); sgm_trim releases it by name */ \
     BUF(vox_tab) BUF(vox_slot) BUF(vox_ctl) BUF(vox_cnt) /* sgm_voxel_downsample: the hash table (VoxSlot [capacity]), each point's slot (uint32 [n]), the call's control words, the host entry's staged counts (kernels_voxel.h); sgm_trim releases the first two by name */ \
     BUF(mesh_code) BUF(mesh_num) BUF(mesh_fcnt) BUF(mesh_vcnt) BUF(mesh_faces) /* sgm_mesh_grid: a code byte per quad (uint8 [H][W]), the pixel -> vertex number map (uint32 [H][W]), the blocks' numbers of faces and of vertices (uint32 [blocks + 1] each), the host entry's staged faces (kernels_mesh.h); sgm_trim releases the first two and the last by name */ \
+    BUF(mesh_nrm)                                /* sgm_normals_grid, sgm_mesh_grid_normals: the host entries' staged normals (float32 [H][W][3]; kernels_normals.h); sgm_trim releases it by name */ \
     BUF(headroom)                                /* uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r */ \
     BUF(chain_ctl) BUF(chain_err)                /* chained sweeps: ticket + progress words (zeroed before every launch); sticky give-up flag */ \
     ARR(io, [2][5])                              /* sgm_compute_batch, throughput mode: the transfer slots (sgm_engine says what they hold) */
@@ -2041,8 +2043,8 @@ int sgm_trim(sgm_engine *e)
     e->pin_disp.release();
     for (auto &slot : e->pin_io)
         for (HostBuf &b : slot) b.release();
-    for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f, &e->vox_tab, &e->vox_slot, &e->mesh_code, &e->mesh_num, &e->mesh_faces})
-        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table and the mesh's maps come back on the next call
+    for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f, &e->vox_tab, &e->vox_slot, &e->mesh_code, &e->mesh_num, &e->mesh_faces, &e->mesh_nrm})
+        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps and the staged normals come back on the next call
     return check_chain(e);
 }
 
@@ -3351,28 +3353,43 @@ int sgm_voxel_downsample(sgm_engine *e, const float *xyz, const float *disp, con
     return SGM_OK;
 }
 
-// ---- triangle mesh from the organised cloud (include/sgm_hip_mesh.h, kernels_mesh.h) -------------------------------------------
-static int mesh_check_args(const sgm_engine *e, const void *xyz, const void *disp, const void *colors, int H, int W, float max_diff,
-                           const void *out_vertices, const void *out_colors, const void *out_faces, const int64_t *n_vertices,
-                           const int64_t *n_faces)
+// ---- triangle mesh from the organised cloud (include/sgm_hip_mesh.h, kernels_mesh.h) and its normals (include/sgm_hip_normals.h,
+// kernels_normals.h) -----------------------------------------------------------------------------------------------------------------
+// What every entry of the two headers refuses, under the entry's name.  null: one of its required pointers is.
+static int mesh_check_args(const char *who, bool null, int H, int W, float max_diff, int orient, bool out_colors_without_colors)
 {
-    if (!e || !xyz || !disp || !out_vertices || !out_faces || !n_vertices || !n_faces)
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_mesh_grid: null pointer");
-    if (H < 1 || W < 1) return set_err(SGM_ERR_INVALID_ARG, "sgm_mesh_grid: a frame of %d x %d pixels", H, W);
+    if (null) return set_err(SGM_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (H < 1 || W < 1) return set_err(SGM_ERR_INVALID_ARG, "%s: a frame of %d x %d pixels", who, H, W);
     if (!std::isfinite(max_diff) || !(max_diff >= 0.0f))
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_mesh_grid: max_diff %g is not finite and >= 0", (double)max_diff);
-    if (out_colors && !colors) return set_err(SGM_ERR_INVALID_ARG, "sgm_mesh_grid: out_colors requested without colors");
-    if ((int64_t)H * W > MESH_MAX_PIXELS)
-        return set_err(SGM_ERR_UNSUPPORTED, "sgm_mesh_grid: %d x %d pixels, more than 2^26", H, W);
+        return set_err(SGM_ERR_INVALID_ARG, "%s: max_diff %g is not finite and >= 0", who, (double)max_diff);
+    if (orient != 0 && orient != 1) return set_err(SGM_ERR_INVALID_ARG, "%s: orient %d is not 0 or 1", who, orient);
+    if (out_colors_without_colors) return set_err(SGM_ERR_INVALID_ARG, "%s: out_colors requested without colors", who);
+    if ((int64_t)H * W > MESH_MAX_PIXELS) return set_err(SGM_ERR_UNSUPPORTED, "%s: %d x %d pixels, more than 2^26", who, H, W);
     return SGM_OK;
 }
 
-int sgm_mesh_grid_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int H, int W, float max_diff,
-                         void *d_out_vertices, void *d_out_colors, void *d_out_faces, int64_t *n_vertices, int64_t *n_faces)
+// steps 1 - 3: every quad's code and the blocks' numbers of triangles, into the engine's mesh_code and mesh_fcnt (m blocks)
+static int mesh_stage_quads(sgm_engine *e, const float *xyz, const float *disp, int H, int W, float max_diff, int m)
 {
-    if (int rc = mesh_check_args(e, d_xyz, d_disp_f32, d_colors_rgb, H, W, max_diff, d_out_vertices, d_out_colors, d_out_faces, n_vertices,
-                                 n_faces))
-        return rc;
+    uint8_t *code = (uint8_t *)e->mesh_code.p;
+    uint32_t *fcnt = (uint32_t *)e->mesh_fcnt.p;
+    hipStream_t st = e->stream;
+    int rc;
+    if ((rc = stage_begin(e, "mesh_quads"))) return rc;
+    // (16-byte loads where every group of four pixels, and the four below it, starts on a 16-byte boundary)
+    const bool wide = W % 4 == 0 && (uintptr_t)xyz % 16 == 0 && (uintptr_t)disp % 16 == 0;
+    if (wide) hipLaunchKernelGGL(k_mesh_quads<true>, dim3(m), dim3(MESH_BLOCK / 4), 0, st, xyz, disp, H, W, max_diff, code, fcnt);
+    else hipLaunchKernelGGL(k_mesh_quads<false>, dim3(m), dim3(MESH_BLOCK / 4), 0, st, xyz, disp, H, W, max_diff, code, fcnt);
+    KCHECK();
+    return stage_end(e, 1);
+}
+
+// The mesh on the engine's stream from device pointers, for sgm_mesh_grid_device and sgm_mesh_grid_normals_device: with
+// d_out_normals also one normal per vertex.  Arguments checked; blocks once, at the end, for the two counts.
+static int mesh_run(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int H, int W, float max_diff,
+                    int orient, void *d_out_vertices, void *d_out_colors, void *d_out_faces, void *d_out_normals, int64_t *n_vertices,
+                    int64_t *n_faces)
+{
     if (H < 2 || W < 2) {   // no quad
         *n_vertices = 0;
         *n_faces = 0;
@@ -3392,13 +3409,7 @@ int sgm_mesh_grid_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f3
     uint32_t *number = (uint32_t *)e->mesh_num.p, *fcnt = (uint32_t *)e->mesh_fcnt.p, *vcnt = (uint32_t *)e->mesh_vcnt.p;
     hipStream_t st = e->stream;
     // 1. every quad's code and the blocks' numbers of triangles; 2. from the codes, the blocks' numbers of vertices
-    if ((rc = stage_begin(e, "mesh_quads"))) return rc;
-    // (16-byte loads where every group of four pixels, and the four below it, starts on a 16-byte boundary)
-    const bool wide = W % 4 == 0 && (uintptr_t)xyz % 16 == 0 && (uintptr_t)disp % 16 == 0;
-    if (wide) hipLaunchKernelGGL(k_mesh_quads<true>, dim3(m), dim3(MESH_BLOCK / 4), 0, st, xyz, disp, H, W, max_diff, code, fcnt);
-    else hipLaunchKernelGGL(k_mesh_quads<false>, dim3(m), dim3(MESH_BLOCK / 4), 0, st, xyz, disp, H, W, max_diff, code, fcnt);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    if ((rc = mesh_stage_quads(e, xyz, disp, H, W, max_diff, m))) return rc;
     if ((rc = stage_begin(e, "mesh_used"))) return rc;
     hipLaunchKernelGGL(k_mesh_used, dim3(m), dim3(MESH_BLOCK), 0, st, (const uint8_t *)code, H, W, vcnt);
     KCHECK();
@@ -3420,6 +3431,14 @@ int sgm_mesh_grid_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f3
                        (int32_t *)d_out_faces);
     KCHECK();
     if ((rc = stage_end(e, 1))) return rc;
+    // 6 - 9. the vertices' normals, to the rows step 4 numbered the pixels with
+    if (d_out_normals) {
+        if ((rc = stage_begin(e, "mesh_normals"))) return rc;
+        hipLaunchKernelGGL(k_normals<true>, dim3(m), dim3(MESH_BLOCK), 0, st, xyz, (const uint8_t *)code, (const uint32_t *)number, H, W, orient,
+                           (float *)d_out_normals);
+        KCHECK();
+        if ((rc = stage_end(e, 1))) return rc;
+    }
     uint32_t nv = 0, nf = 0;
     HIP_TRY(hipMemcpyAsync(&nv, vcnt + m, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&nf, fcnt + m, 4, hipMemcpyDeviceToHost, st));
@@ -3429,10 +3448,11 @@ int sgm_mesh_grid_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f3
     return SGM_OK;
 }
 
-int sgm_mesh_grid(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int H, int W, float max_diff,
-                  float *out_vertices, uint8_t *out_colors, int32_t *out_faces, int64_t *n_vertices, int64_t *n_faces)
+// The same from host pointers through the engine's staging buffers, for sgm_mesh_grid and sgm_mesh_grid_normals
+static int mesh_run_host(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int H, int W, float max_diff,
+                         int orient, float *out_vertices, uint8_t *out_colors, int32_t *out_faces, float *out_normals, int64_t *n_vertices,
+                         int64_t *n_faces)
 {
-    if (int rc = mesh_check_args(e, xyz, disp, colors_rgb, H, W, max_diff, out_vertices, out_colors, out_faces, n_vertices, n_faces)) return rc;
     if (H < 2 || W < 2) {
         *n_vertices = 0;
         *n_faces = 0;
@@ -3444,23 +3464,110 @@ int sgm_mesh_grid(sgm_engine *e, const float *xyz, const float *disp, const uint
     if ((rc = e->xyz.ensure(n * 12)) || (rc = e->f32.ensure(n * 4)) || (rc = e->cpts.ensure(n * 12)) || (rc = e->mesh_faces.ensure(fmax * 12)))
         return rc;
     if (out_colors && ((rc = e->crgb_in.ensure(n * 3)) || (rc = e->crgb.ensure(n * 3)))) return rc;
+    if (out_normals && (rc = e->mesh_nrm.ensure(n * 12))) return rc;
     HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, n * 12, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(e->f32.p, disp, n * 4, hipMemcpyHostToDevice, e->stream));
     if (out_colors) HIP_TRY(hipMemcpyAsync(e->crgb_in.p, colors_rgb, n * 3, hipMemcpyHostToDevice, e->stream));
     int64_t nv = 0, nf = 0;
-    if ((rc = sgm_mesh_grid_device(e, e->xyz.p, e->f32.p, out_colors ? e->crgb_in.p : nullptr, H, W, max_diff, e->cpts.p,
-                                   out_colors ? e->crgb.p : nullptr, e->mesh_faces.p, &nv, &nf))) {
+    if ((rc = mesh_run(e, e->xyz.p, e->f32.p, out_colors ? e->crgb_in.p : nullptr, H, W, max_diff, orient, e->cpts.p,
+                       out_colors ? e->crgb.p : nullptr, e->mesh_faces.p, out_normals ? e->mesh_nrm.p : nullptr, &nv, &nf))) {
         (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
         return rc;
     }
     if (nv > 0) {
         HIP_TRY(hipMemcpyAsync(out_vertices, e->cpts.p, (size_t)nv * 12, hipMemcpyDeviceToHost, e->stream));
         if (out_colors) HIP_TRY(hipMemcpyAsync(out_colors, e->crgb.p, (size_t)nv * 3, hipMemcpyDeviceToHost, e->stream));
+        if (out_normals) HIP_TRY(hipMemcpyAsync(out_normals, e->mesh_nrm.p, (size_t)nv * 12, hipMemcpyDeviceToHost, e->stream));
     }
     if (nf > 0) HIP_TRY(hipMemcpyAsync(out_faces, e->mesh_faces.p, (size_t)nf * 12, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     *n_vertices = nv;
     *n_faces = nf;
+    return SGM_OK;
+}
+
+int sgm_mesh_grid_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int H, int W, float max_diff,
+                         void *d_out_vertices, void *d_out_colors, void *d_out_faces, int64_t *n_vertices, int64_t *n_faces)
+{
+    if (int rc = mesh_check_args("sgm_mesh_grid", !e || !d_xyz || !d_disp_f32 || !d_out_vertices || !d_out_faces || !n_vertices || !n_faces, H, W,
+                                 max_diff, 0, d_out_colors && !d_colors_rgb))
+        return rc;
+    return mesh_run(e, d_xyz, d_disp_f32, d_colors_rgb, H, W, max_diff, 0, d_out_vertices, d_out_colors, d_out_faces, nullptr, n_vertices, n_faces);
+}
+
+int sgm_mesh_grid(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int H, int W, float max_diff,
+                  float *out_vertices, uint8_t *out_colors, int32_t *out_faces, int64_t *n_vertices, int64_t *n_faces)
+{
+    if (int rc = mesh_check_args("sgm_mesh_grid", !e || !xyz || !disp || !out_vertices || !out_faces || !n_vertices || !n_faces, H, W, max_diff, 0,
+                                 out_colors && !colors_rgb))
+        return rc;
+    return mesh_run_host(e, xyz, disp, colors_rgb, H, W, max_diff, 0, out_vertices, out_colors, out_faces, nullptr, n_vertices, n_faces);
+}
+
+int sgm_mesh_grid_normals_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int H, int W,
+                                 float max_diff, int orient, void *d_out_vertices, void *d_out_colors, void *d_out_faces,
+                                 void *d_out_normals, int64_t *n_vertices, int64_t *n_faces)
+{
+    if (int rc = mesh_check_args("sgm_mesh_grid_normals",
+                                 !e || !d_xyz || !d_disp_f32 || !d_out_vertices || !d_out_faces || !d_out_normals || !n_vertices || !n_faces, H, W,
+                                 max_diff, orient, d_out_colors && !d_colors_rgb))
+        return rc;
+    return mesh_run(e, d_xyz, d_disp_f32, d_colors_rgb, H, W, max_diff, orient, d_out_vertices, d_out_colors, d_out_faces, d_out_normals,
+                    n_vertices, n_faces);
+}
+
+int sgm_mesh_grid_normals(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int H, int W, float max_diff,
+                          int orient, float *out_vertices, uint8_t *out_colors, int32_t *out_faces, float *out_normals,
+                          int64_t *n_vertices, int64_t *n_faces)
+{
+    if (int rc = mesh_check_args("sgm_mesh_grid_normals", !e || !xyz || !disp || !out_vertices || !out_faces || !out_normals || !n_vertices || !n_faces,
+                                 H, W, max_diff, orient, out_colors && !colors_rgb))
+        return rc;
+    return mesh_run_host(e, xyz, disp, colors_rgb, H, W, max_diff, orient, out_vertices, out_colors, out_faces, out_normals, n_vertices, n_faces);
+}
+
+// The normal image: the quads' codes, then one pass over the pixels.  Nothing is counted, so nothing waits.
+int sgm_normals_grid_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, int H, int W, float max_diff, int orient,
+                            void *d_out_normals)
+{
+    if (int rc = mesh_check_args("sgm_normals_grid", !e || !d_xyz || !d_disp_f32 || !d_out_normals, H, W, max_diff, orient, false)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const int64_t n = (int64_t)H * W;
+    if (e->profile) stage_reset(e);   // the stage record is the call's from here on
+    if (H < 2 || W < 2) {             // no quad, no vertex, no stage
+        HIP_TRY(hipMemsetAsync(d_out_normals, 0, (size_t)n * 12, e->stream));
+        return SGM_OK;
+    }
+    const int m = (int)((n + MESH_BLOCK - 1) / MESH_BLOCK);
+    int rc;
+    if ((rc = e->mesh_code.ensure((size_t)n)) || (rc = e->mesh_fcnt.ensure((size_t)(m + 1) * 4))) return rc;
+    if ((rc = mesh_stage_quads(e, (const float *)d_xyz, (const float *)d_disp_f32, H, W, max_diff, m))) return rc;
+    if ((rc = stage_begin(e, "normals_grid"))) return rc;
+    hipLaunchKernelGGL(k_normals<false>, dim3(m), dim3(MESH_BLOCK), 0, e->stream, (const float *)d_xyz, (const uint8_t *)e->mesh_code.p,
+                       (const uint32_t *)nullptr, H, W, orient, (float *)d_out_normals);
+    KCHECK();
+    return stage_end(e, 1);
+}
+
+int sgm_normals_grid(sgm_engine *e, const float *xyz, const float *disp, int H, int W, float max_diff, int orient, float *out_normals)
+{
+    if (int rc = mesh_check_args("sgm_normals_grid", !e || !xyz || !disp || !out_normals, H, W, max_diff, orient, false)) return rc;
+    const size_t n = (size_t)H * W;
+    if (H < 2 || W < 2) {
+        memset(out_normals, 0, n * 12);
+        return SGM_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = e->xyz.ensure(n * 12)) || (rc = e->f32.ensure(n * 4)) || (rc = e->mesh_nrm.ensure(n * 12))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, n * 12, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->f32.p, disp, n * 4, hipMemcpyHostToDevice, e->stream));
+    if ((rc = sgm_normals_grid_device(e, e->xyz.p, e->f32.p, H, W, max_diff, orient, e->mesh_nrm.p))) {
+        (void)hipStreamSynchronize(e->stream);
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out_normals, e->mesh_nrm.p, n * 12, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return SGM_OK;
 }
 

@@ -8,6 +8,10 @@
     triangulate_points(points_3D, colors, disparity_map, max_diff, ...)    the surface over the organised cloud: two triangles per
                  pixel quad wherever the disparity is continuous, on the GPU (include/sgm_hip_mesh.h; NOT Open3D's meshing)
     write_triangle_mesh(path, vertices, triangles, colors)                 its PLY export, in the layout of Open3D's mesh writer
+    estimate_normals(points_3D, disparity_map, max_diff, ...)              one unit normal per pixel of the organised cloud, and
+    triangulate_points_with_normals(points_3D, colors, disparity_map, ...) the mesh with one per vertex: the area-weighted sum of the
+                 triangles around it, on the GPU (include/sgm_hip_normals.h; NOT Open3D's estimate_normals / compute_vertex_normals)
+    write_ply(path, points, colors, normals, triangles) / read_ply(path)   one PLY writer for a cloud or a mesh, with or without normals
 
 The compaction runs on the GPU (ordered, so the result equals numpy's `points_3D[mask]`); the
 PLY writer is plain host I/O and replaces the Open3D dependency (absent here) for export only --
@@ -105,17 +109,9 @@ def voxel_down_sample(points_3D, colors, disparity_map, voxel_size, origin=(0, 0
 MESH_MAX_PIXELS = 1 << 26
 
 
-def triangulate_points(points_3D, colors, disparity_map, max_diff=1.0, confidence=None, min_confidence=0):
-    """A triangle mesh over the organised cloud, on the GPU: two triangles per pixel quad wherever the disparity is continuous --
-    a pixel counts iff X, Y, Z are finite and its disparity > 0 (with a confidence map also confidence >= min_confidence, as in
-    valid_points), two pixels are connected iff their disparities differ by max_diff at most, each quad is cut along the diagonal
-    with the smaller disparity difference, and a triangle is kept iff its three edges are connected.  The vertices are the pixels
-    that a triangle uses, in row-major order; the triangles come in row-major order of their quads and face the camera.  The
-    definition is include/sgm_hip_mesh.h, our own, and the result is the same bits on every run: it is NOT Open3D's meshing nor
-    any other library's.
-    points_3D float32 (H, W, 3), disparity_map float32 (H, W) in pixels, colors uint8 (H, W, 3) or None.
-    Returns (vertices float32 (V, 3), colors uint8 (V, 3) or None, triangles int32 (F, 3))."""
-    who = "triangulate_points"
+def _grid_args(who, points_3D, colors, disparity_map, max_diff, confidence, min_confidence):
+    """the argument checks the functions over the organised cloud share, raised before any engine exists: (points, colors,
+    disparity with the confidence mask applied, max_diff as float32)"""
     pts = np.asarray(points_3D)
     if pts.dtype != np.float32:
         raise _cv.error(f"{who}: points_3D must be float32, not {pts.dtype}")
@@ -142,9 +138,50 @@ def triangulate_points(points_3D, colors, disparity_map, max_diff=1.0, confidenc
     H, W = disp.shape
     if H * W > MESH_MAX_PIXELS:
         raise _cv.error(f"{who}: {H} x {W} pixels, more than {MESH_MAX_PIXELS} (include/sgm_hip_mesh.h)")
+    return pts, colors, disp, md
+
+
+def triangulate_points(points_3D, colors, disparity_map, max_diff=1.0, confidence=None, min_confidence=0):
+    """A triangle mesh over the organised cloud, on the GPU: two triangles per pixel quad wherever the disparity is continuous --
+    a pixel counts iff X, Y, Z are finite and its disparity > 0 (with a confidence map also confidence >= min_confidence, as in
+    valid_points), two pixels are connected iff their disparities differ by max_diff at most, each quad is cut along the diagonal
+    with the smaller disparity difference, and a triangle is kept iff its three edges are connected.  The vertices are the pixels
+    that a triangle uses, in row-major order; the triangles come in row-major order of their quads and face the camera.  The
+    definition is include/sgm_hip_mesh.h, our own, and the result is the same bits on every run: it is NOT Open3D's meshing nor
+    any other library's.
+    points_3D float32 (H, W, 3), disparity_map float32 (H, W) in pixels, colors uint8 (H, W, 3) or None.
+    Returns (vertices float32 (V, 3), colors uint8 (V, 3) or None, triangles int32 (F, 3))."""
+    pts, colors, disp, md = _grid_args("triangulate_points", points_3D, colors, disparity_map, max_diff, confidence, min_confidence)
+    H, W = disp.shape
     if H < 2 or W < 2:     # no quad: nothing to send to the device
         return np.zeros((0, 3), np.float32), None if colors is None else np.zeros((0, 3), np.uint8), np.zeros((0, 3), np.int32)
     return _cv.get_engine(_cv._DEFAULT).mesh_grid_host(pts, disp, colors, float(md))
+
+
+def estimate_normals(points_3D, disparity_map, max_diff=1.0, confidence=None, min_confidence=0, orient=True):
+    """One unit normal per pixel of the organised cloud, on the GPU: the sum of the (area-weighted) normals of the triangles of
+    triangulate_points around the pixel -- same validity, same max_diff, same confidence mask --, normalised, and with orient
+    turned so that it points towards the camera at the origin.  Pixels that no triangle uses get (0, 0, 0).  The definition is
+    include/sgm_hip_normals.h, our own, every operation and its order written out, and the result is the same bits on every run:
+    it is NOT Open3D's estimate_normals (no neighbour search, no covariance) nor any other library's.
+    points_3D float32 (H, W, 3), disparity_map float32 (H, W) in pixels.  Returns float32 (H, W, 3)."""
+    pts, _, disp, md = _grid_args("estimate_normals", points_3D, None, disparity_map, max_diff, confidence, min_confidence)
+    if disp.shape[0] < 2 or disp.shape[1] < 2:     # no quad, no vertex: nothing to send to the device
+        return np.zeros(disp.shape + (3,), np.float32)
+    return _cv.get_engine(_cv._DEFAULT).normals_grid_host(pts, disp, float(md), bool(orient))
+
+
+def triangulate_points_with_normals(points_3D, colors, disparity_map, max_diff=1.0, confidence=None, min_confidence=0, orient=True):
+    """triangulate_points and one unit normal per vertex: the rows of estimate_normals at the vertices' pixels, computed in the same
+    call.  The faces keep their winding whatever orient turns.  The definition is include/sgm_hip_normals.h, our own: it is NOT
+    Open3D's compute_vertex_normals nor any other library's.
+    Returns (vertices float32 (V, 3), colors uint8 (V, 3) or None, triangles int32 (F, 3), normals float32 (V, 3))."""
+    pts, colors, disp, md = _grid_args("triangulate_points_with_normals", points_3D, colors, disparity_map, max_diff, confidence,
+                                       min_confidence)
+    if disp.shape[0] < 2 or disp.shape[1] < 2:     # no quad: nothing to send to the device
+        return (np.zeros((0, 3), np.float32), None if colors is None else np.zeros((0, 3), np.uint8), np.zeros((0, 3), np.int32),
+                np.zeros((0, 3), np.float32))
+    return _cv.get_engine(_cv._DEFAULT).mesh_grid_normals_host(pts, disp, colors, float(md), bool(orient))
 
 
 def write_triangle_mesh(filename, vertices, triangles, colors=None, binary=True) -> bool:
@@ -282,3 +319,101 @@ def read_point_cloud(filename):
         pts = np.array([[float(v) for v in r[:3]] for r in rows], np.float64).reshape(n, 3)
         col = np.array([[int(v) for v in r[3:6]] for r in rows], np.uint8).reshape(n, 3) if has_col else None
         return pts, col
+
+
+def write_ply(filename, points, colors=None, normals=None, triangles=None, binary=True) -> bool:
+    """One PLY writer for a cloud or a mesh, with or without normals and colours: vertex properties double x/y/z, then double
+    nx/ny/nz, then uchar red/green/blue, then with triangles the face list of write_triangle_mesh -- the order Open3D writes.
+    Without normals the file equals write_point_cloud's (triangles None) or write_triangle_mesh's byte for byte."""
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    n = pts.shape[0]
+    cols = [("p", pts)]
+    if normals is not None:
+        nrm = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+        if nrm.shape[0] != n:
+            raise _cv.error("write_ply: normals and points differ in length")
+        cols.append(("n", nrm))
+    if colors is not None:
+        col = np.asarray(colors).reshape(-1, 3)
+        if col.shape[0] != n:
+            raise _cv.error("write_ply: colors and points differ in length")
+        if col.dtype != np.uint8:  # as write_point_cloud: colours in [0, 1] or [0, 255]
+            col = np.clip(np.rint(np.asarray(col, np.float64) * (255.0 if col.max(initial=0) <= 1.0 else 1.0)), 0, 255).astype(np.uint8)
+        cols.append(("c", col))
+    tri = None
+    if triangles is not None:
+        tri = np.asarray(triangles)
+        if tri.dtype.kind not in "iu" or tri.ndim != 2 or tri.shape[1] != 3:
+            raise _cv.error("write_ply: triangles must be an integer (F, 3) array")
+        if tri.size and (int(tri.min()) < 0 or int(tri.max()) >= n):
+            raise _cv.error(f"write_ply: a triangle indexes outside the {n} vertices")
+    names = dict(p=["double x", "double y", "double z"], n=["double nx", "double ny", "double nz"],
+                 c=["uchar red", "uchar green", "uchar blue"])
+    head = ["ply", "format binary_little_endian 1.0" if binary else "format ascii 1.0",
+            "comment stereo_reconstruction_cv_amd", f"element vertex {n}"]
+    head += ["property " + prop for k, _ in cols for prop in names[k]]
+    if tri is not None:
+        head += [f"element face {tri.shape[0]}", "property list uchar uint vertex_indices"]
+    head.append("end_header")
+    with open(filename, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii"))
+        if binary:
+            rec = np.empty(n, dtype=[(k, "u1" if k == "c" else "<f8", 3) for k, _ in cols])
+            for k, a in cols:
+                rec[k] = a
+            rec.tofile(f)
+            if tri is not None:
+                frec = np.empty(tri.shape[0], dtype=[("k", "u1"), ("v", "<u4", 3)])
+                frec["k"], frec["v"] = 3, tri
+                frec.tofile(f)
+        else:
+            for i in range(n):
+                line = " ".join(" ".join(str(int(v)) if k == "c" else repr(float(v)) for v in a[i]) for k, a in cols)
+                f.write((line + "\n").encode("ascii"))
+            for t in (tri if tri is not None else ()):
+                f.write(("3 " + " ".join(str(int(v)) for v in t) + "\n").encode("ascii"))
+    return True
+
+
+def read_ply(filename):
+    """Minimal reader for files written by write_ply, write_point_cloud and write_triangle_mesh (used by the tests): (points
+    float64 (N, 3), colors uint8 (N, 3) or None, normals float64 (N, 3) or None, triangles int32 (F, 3) or None)."""
+    with open(filename, "rb") as f:
+        header = []
+        while True:
+            line = f.readline().decode("ascii").strip()
+            header.append(line)
+            if line == "end_header":
+                break
+        n = int([h for h in header if h.startswith("element vertex")][0].split()[-1])
+        face = [h for h in header if h.startswith("element face")]
+        nf = int(face[0].split()[-1]) if face else None
+        if face and "property list uchar uint vertex_indices" not in header:
+            raise _cv.error("read_ply: not a face list of uchar counts and uint indices")
+        has_nrm, has_col = "property double nx" in header, "property uchar red" in header
+        if "format binary_little_endian 1.0" in header:
+            dt = [("p", "<f8", 3)] + ([("n", "<f8", 3)] if has_nrm else []) + ([("c", "u1", 3)] if has_col else [])
+            rec = np.fromfile(f, dtype=dt, count=n)
+            tri = None
+            if face:
+                frec = np.fromfile(f, dtype=[("k", "u1"), ("v", "<u4", 3)], count=nf)
+                if frec.shape[0] != nf or (frec["k"] != 3).any():
+                    raise _cv.error("read_ply: the file is cut short or a face is no triangle")
+                tri = frec["v"].astype(np.int32)
+            if rec.shape[0] != n:
+                raise _cv.error("read_ply: the file is cut short")
+            return rec["p"].copy(), (rec["c"].copy() if has_col else None), (rec["n"].copy() if has_nrm else None), tri
+        rows = [f.readline().decode("ascii").split() for _ in range(n)]
+        k = 6 if has_nrm else 3
+        if any(len(r) != k + 3 * has_col for r in rows):
+            raise _cv.error("read_ply: the file is cut short")
+        pts = np.array([[float(v) for v in r[:3]] for r in rows], np.float64).reshape(n, 3)
+        nrm = np.array([[float(v) for v in r[3:6]] for r in rows], np.float64).reshape(n, 3) if has_nrm else None
+        col = np.array([[int(v) for v in r[k:k + 3]] for r in rows], np.uint8).reshape(n, 3) if has_col else None
+        tri = None
+        if face:
+            frows = [f.readline().decode("ascii").split() for _ in range(nf)]
+            if any(len(r) != 4 or r[0] != "3" for r in frows):
+                raise _cv.error("read_ply: the file is cut short or a face is no triangle")
+            tri = np.array([[int(v) for v in r[1:]] for r in frows], np.int32).reshape(nf, 3)
+        return pts, col, nrm, tri

@@ -284,6 +284,48 @@ class Engine:
                                             d_faces, C.byref(nv), C.byref(nf)))
         return int(nv.value), int(nf.value)
 
+    # -- vertex normals of that mesh, and the normal image (include/sgm_hip_normals.h) --
+    def normals_grid_host(self, xyz: np.ndarray, disp: np.ndarray, max_diff: float = 1.0, orient: bool = True) -> np.ndarray:
+        """sgm_normals_grid: float32 points (H, W, 3) and disparities (H, W).  Returns the normal image float32 (H, W, 3): unit
+        normals at the pixels that are vertices of the grid mesh, (0, 0, 0) elsewhere; with orient turned towards the camera."""
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        H, W = xyz.shape[:2]
+        disp = np.ascontiguousarray(disp, np.float32).reshape(H, W)
+        out = np.empty((H, W, 3), np.float32)
+        _check(self._L.sgm_normals_grid(self._h, xyz.ctypes.data, disp.ctypes.data, H, W, float(max_diff), int(orient), out.ctypes.data))
+        return out
+
+    def normals_grid_device(self, d_xyz: int, d_dispf: int, H: int, W: int, max_diff: float, orient: bool, d_normals: int) -> None:
+        """sgm_normals_grid_device: device addresses, d_normals with room for H * W rows; in stream order, nothing is
+        synchronised."""
+        _check(self._L.sgm_normals_grid_device(self._h, d_xyz, d_dispf, int(H), int(W), float(max_diff), int(orient), d_normals))
+
+    def mesh_grid_normals_host(self, xyz: np.ndarray, disp: np.ndarray, colors: np.ndarray | None, max_diff: float = 1.0,
+                               orient: bool = True):
+        """sgm_mesh_grid_normals: mesh_grid_host and one normal per vertex.  Returns (vertices float32 (V, 3), colors uint8 (V, 3)
+        or None, faces int32 (F, 3), normals float32 (V, 3))."""
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        H, W = xyz.shape[:2]
+        disp = np.ascontiguousarray(disp, np.float32).reshape(H, W)
+        colors = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(H, W, 3)
+        vert, nrm = np.empty((H * W, 3), np.float32), np.empty((H * W, 3), np.float32)
+        rgb = None if colors is None else np.empty((H * W, 3), np.uint8)
+        faces = np.empty((2 * max(H - 1, 0) * max(W - 1, 0), 3), np.int32)
+        nv, nf = C.c_int64(0), C.c_int64(0)
+        at = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.sgm_mesh_grid_normals(self._h, xyz.ctypes.data, disp.ctypes.data, at(colors), H, W, float(max_diff), int(orient),
+                                             vert.ctypes.data, at(rgb), faces.ctypes.data, nrm.ctypes.data, C.byref(nv), C.byref(nf)))
+        return vert[:nv.value].copy(), None if rgb is None else rgb[:nv.value].copy(), faces[:nf.value].copy(), nrm[:nv.value].copy()
+
+    def mesh_grid_normals_device(self, d_xyz: int, d_dispf: int, d_colors: int | None, H: int, W: int, max_diff: float, orient: bool,
+                                 d_vertices: int, d_out_colors: int | None, d_faces: int, d_normals: int):
+        """sgm_mesh_grid_normals_device: mesh_grid_device with d_normals, room for H * W rows like d_vertices.  Returns
+        (n_vertices, n_faces); synchronises the engine's stream."""
+        nv, nf = C.c_int64(0), C.c_int64(0)
+        _check(self._L.sgm_mesh_grid_normals_device(self._h, d_xyz, d_dispf, d_colors, int(H), int(W), float(max_diff), int(orient),
+                                                    d_vertices, d_out_colors, d_faces, d_normals, C.byref(nv), C.byref(nf)))
+        return int(nv.value), int(nf.value)
+
     def median3x3_host(self, img: np.ndarray) -> np.ndarray:
         img = np.ascontiguousarray(img, np.int16)
         out = np.empty_like(img)
