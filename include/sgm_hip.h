@@ -56,7 +56,8 @@ extern "C" {
                              * SGM_TAP_RIGHT, sgm_bind_right_device (sgm_hip_right.h); SGM_OPT_COST, SGM_COST_BT, SGM_COST_CENSUS;
                              * the disparity post-filter of sgm_hip_wls.h and sgm_hip_wls_batch.h; the left-right
                              * consistency confidence of sgm_hip_lrc.h; the voxel-grid downsampling of sgm_hip_voxel.h; the grid
-                             * triangulation of sgm_hip_mesh.h; its vertex normals and the normal image of sgm_hip_normals.h */
+                             * triangulation of sgm_hip_mesh.h; its vertex normals and the normal image of sgm_hip_normals.h; the
+                             * radius outlier removal of sgm_hip_radius.h */
 
 typedef enum {
     SGM_OK = 0,
@@ -319,4 +320,6 @@ int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_r
 #include "sgm_hip_mesh.h"
 /* one normal per vertex of that mesh, and the same as a normal image over the organised cloud */
 #include "sgm_hip_normals.h"
+/* radius outlier removal for the point cloud: the number of neighbours within a radius, and the points that have enough */
+#include "sgm_hip_radius.h"
 #endif

@@ -39,7 +39,10 @@ enum {
     SGM_DBG_WLS_BATCH_COLS_SHIFT = 20,     /* 2 bits: k_wls_cols<CN, UNR>, the index into wls_cols_shapes */
     /* sgm_voxel_downsample* (tools/voxel_times.py); the results are the same bits under both */
     SGM_DBG_VOXEL_TIGHT_TABLE = 1 << 22,   /* capacity = the smallest power of two >= the points in range (not twice them): the load can reach 1.0 */
-    SGM_DBG_VOXEL_OTHER_REDUCTION = 1 << 23 /* k_voxel_insert without the wave pre-reduction where it is the default (kernels_voxel.h: VOX_PRE_DEFAULT), with it where not */
+    SGM_DBG_VOXEL_OTHER_REDUCTION = 1 << 23, /* k_voxel_insert without the wave pre-reduction where it is the default (kernels_voxel.h: VOX_PRE_DEFAULT), with it where not */
+    /* sgm_radius_outlier* (tools/radius_times.py); the results are the same bits under both */
+    SGM_DBG_RADIUS_TIGHT_TABLE = 1 << 24,   /* capacity = the smallest power of two >= the points in range (not twice them): the load can reach 1.0 */
+    SGM_DBG_RADIUS_SOURCE_ORDER = 1 << 25   /* k_radius_query over the points in source order instead of sorted by cell */
 };
 
 /* Plan readout: what normalise + make_plan decide for one compute of a frame of H x W pixels on an engine with these

@@ -31,6 +31,7 @@
 #include "kernels_wls.h"
 #include "kernels_lrc.h"
 #include "kernels_voxel.h"
+#include "kernels_radius.h"
 #include "kernels_mesh.h"
 #include "kernels_normals.h"
 
@@ -265,6 +266,7 @@ struct Plan {
     BUF(wls_u) BUF(wls_v) BUF(wls_c)             /* sgm_wls_filter: float [H][W] planes u, v, c' (kernels_wls.h); sgm_trim releases these three by name */ \
     BUF(lrc_f)                                   /* sgm_lrc_confidence: uint8 [pairs of a chunk][2][H][W], the smoothness factors (kernels_lrc.h); sgm_trim releases it by name */ \
     BUF(vox_tab) BUF(vox_slot) BUF(vox_ctl) BUF(vox_cnt) /* sgm_voxel_downsample: the hash table (VoxSlot [capacity]), each point's slot (uint32 [n]), the call's control words, the host entry's staged counts (kernels_voxel.h); sgm_trim releases the first two by name */ \
+    BUF(rad_tab) BUF(rad_sorted) BUF(rad_pt) BUF(rad_ctl) BUF(rad_keep) BUF(rad_cnt) BUF(rad_idx) /* sgm_radius_outlier: the hash table of cells (RadSlot [capacity]), the records sorted by cell (float4 [points in range]), each point's slot and rank (uint2 [n]), the call's control words, the keep bytes where the caller asks for none and the host entry's staged ones (uint8 [n]), its staged counts and indices (uint32 [n] each; kernels_radius.h); sgm_trim releases all but the control words by name */ \
     BUF(mesh_code) BUF(mesh_num) BUF(mesh_fcnt) BUF(mesh_vcnt) BUF(mesh_faces) /* sgm_mesh_grid: a code byte per quad (uint8 [H][W]), the pixel -> vertex number map (uint32 [H][W]), the blocks' numbers of faces and of vertices (uint32 [blocks + 1] each), the host entry's staged faces (kernels_mesh.h); sgm_trim releases the first two and the last by name */ \
     BUF(mesh_nrm)                                /* sgm_normals_grid, sgm_mesh_grid_normals: the host entries' staged normals (float32 [H][W][3]; kernels_normals.h); sgm_trim releases it by name */ \
     BUF(headroom)                                /* uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r */ \
@@ -2043,8 +2045,9 @@ int sgm_trim(sgm_engine *e)
     e->pin_disp.release();
     for (auto &slot : e->pin_io)
         for (HostBuf &b : slot) b.release();
-    for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f, &e->vox_tab, &e->vox_slot, &e->mesh_code, &e->mesh_num, &e->mesh_faces, &e->mesh_nrm})
-        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps and the staged normals come back on the next call
+    for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f, &e->vox_tab, &e->vox_slot, &e->mesh_code, &e->mesh_num, &e->mesh_faces, &e->mesh_nrm,
+                      &e->rad_tab, &e->rad_sorted, &e->rad_pt, &e->rad_keep, &e->rad_cnt, &e->rad_idx})
+        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps, the staged normals and the radius search's table, records and staging come back on the next call
     return check_chain(e);
 }
 
@@ -3349,6 +3352,168 @@ int sgm_voxel_downsample(sgm_engine *e, const float *xyz, const float *disp, con
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     *n_voxels = nv;
+    if (n_out_of_range) *n_out_of_range = noor;
+    return SGM_OK;
+}
+
+// ---- radius outlier removal (include/sgm_hip_radius.h, kernels_radius.h) -------------------------------------------------------
+static int radius_check_args(const sgm_engine *e, const void *xyz, const void *colors, int64_t n, float r, const float *origin,
+                             int nb_points, int max_count, const void *out_colors, const int64_t *n_kept)
+{
+    if (!e || !xyz || !n_kept) return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: null pointer");
+    if (n < 0) return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: n=%lld points", (long long)n);
+    const float r2 = r * r, v = r * 1.03125f;
+    if (!std::isfinite(r) || !(r > 0.0f) || !std::isnormal(r2) || !std::isfinite(1.0f / v))
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: radius %g is not finite and positive with a finite normal square", (double)r);
+    if (!origin || !std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: the origin is null or not finite");
+    if (nb_points < 1) return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: nb_points %d < 1", nb_points);
+    if (max_count < nb_points) return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: max_count %d < nb_points %d", max_count, nb_points);
+    if (out_colors && !colors) return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: out_colors requested without colors");
+    if (n > RAD_MAX_POINTS)
+        return set_err(SGM_ERR_UNSUPPORTED, "sgm_radius_outlier: %lld points, more than 2^24 - 1 (a source index shares a record with its point)", (long long)n);
+    return SGM_OK;
+}
+
+int sgm_radius_outlier_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int64_t n, float radius,
+                              const float origin[3], int nb_points, int max_count, void *d_out_keep, void *d_out_counts,
+                              void *d_out_points, void *d_out_colors, void *d_out_index, int64_t *n_kept, int64_t *n_out_of_range)
+{
+    if (int rc = radius_check_args(e, d_xyz, d_colors_rgb, n, radius, origin, nb_points, max_count, d_out_colors, n_kept)) return rc;
+    if (n == 0) {
+        *n_kept = 0;
+        if (n_out_of_range) *n_out_of_range = 0;
+        return SGM_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const int m = (int)((n + 255) / 256);
+    int rc;
+    if ((rc = e->rad_ctl.ensure(RAD_CTL_WORDS * 4)) || (rc = e->rad_pt.ensure((size_t)n * 8)) || (rc = e->ccount.ensure((size_t)(m + 1) * 4)) ||
+        (!d_out_keep && (rc = e->rad_keep.ensure((size_t)n))))
+        return rc;
+    if (e->profile) stage_reset(e);   // the stage record is the call's from here on
+    const float v = radius * 1.03125f;
+    const RadGrid G{1.0f / v, radius * radius, origin[0], origin[1], origin[2]};
+    const float *xyz = (const float *)d_xyz, *disp = (const float *)d_disp_f32;
+    const uint8_t *colors = (const uint8_t *)(d_out_colors ? d_colors_rgb : nullptr);
+    uint32_t *ctl = (uint32_t *)e->rad_ctl.p, *cnt = (uint32_t *)e->ccount.p, *counts = (uint32_t *)d_out_counts;
+    uint2 *slot_rank = (uint2 *)e->rad_pt.p;
+    uint8_t *keep = (uint8_t *)(d_out_keep ? d_out_keep : e->rad_keep.p);
+    hipStream_t st = e->stream;
+    // 1. how many points arrive: the table and the sorted records are sized from them, and a cloud with none is done here
+    HIP_TRY(hipMemsetAsync(ctl, 0, RAD_CTL_WORDS * 4, st));
+    stage_break(e);
+    if ((rc = stage_begin(e, "radius_count"))) return rc;
+    hipLaunchKernelGGL(k_radius_count, dim3(std::min(m, RAD_COUNT_BLOCKS)), dim3(256), 0, st, xyz, disp, n, G, ctl);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    uint32_t h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    stage_break(e);
+    const uint32_t n_in = h_ctl[RAD_CTL_IN];
+    if (n_in == 0) {   // nobody has a neighbour
+        if (d_out_keep) HIP_TRY(hipMemsetAsync(d_out_keep, 0, (size_t)n, st));
+        if (counts) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n * 4, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *n_kept = 0;
+        if (n_out_of_range) *n_out_of_range = (int64_t)h_ctl[RAD_CTL_OUT];
+        return SGM_OK;
+    }
+    // 2. the table: the smallest power of two of at least twice the points in range (debug: of at least the points themselves)
+    const uint64_t want = (e->debug & SGM_DBG_RADIUS_TIGHT_TABLE) ? (uint64_t)n_in : 2 * (uint64_t)n_in;
+    uint32_t cap = 1;
+    while (cap < want) cap <<= 1;   // (n_in < 2^24: at most 2^25)
+    if ((rc = e->rad_tab.ensure((size_t)cap * sizeof(RadSlot))) || (rc = e->rad_sorted.ensure((size_t)n_in * 16))) return rc;
+    RadSlot *tab = (RadSlot *)e->rad_tab.p;
+    float4 *sorted = (float4 *)e->rad_sorted.p;
+    if ((rc = stage_begin(e, "radius_clear"))) return rc;
+    hipLaunchKernelGGL(k_radius_clear, dim3((cap + 255) / 256), dim3(256), 0, st, tab, cap);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    // 3. insert: each point's cell and its rank there
+    if ((rc = stage_begin(e, "radius_insert"))) return rc;
+    hipLaunchKernelGGL(k_radius_insert, dim3(m), dim3(256), 0, st, xyz, disp, n, G, tab, cap - 1, slot_rank, ctl);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    // 4. where each cell's run begins
+    if ((rc = stage_begin(e, "radius_starts"))) return rc;
+    hipLaunchKernelGGL(k_radius_starts, dim3((cap + RAD_STARTS_PER_BLOCK - 1) / RAD_STARTS_PER_BLOCK), dim3(256), 0, st, tab, cap, ctl);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    // 5. the records sorted by cell; the points in no cell get their zeros
+    if ((rc = stage_begin(e, "radius_sort"))) return rc;
+    hipLaunchKernelGGL(k_radius_sort, dim3(m), dim3(256), 0, st, xyz, n, (const RadSlot *)tab, (const uint2 *)slot_rank, sorted, keep, counts);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    // 6. the counts
+    if ((rc = stage_begin(e, "radius_query"))) return rc;
+    if (e->debug & SGM_DBG_RADIUS_SOURCE_ORDER)
+        hipLaunchKernelGGL(k_radius_query<false>, dim3(m), dim3(256), 0, st, (const float4 *)sorted, n_in, xyz, (const uint2 *)slot_rank, n, G,
+                           (const RadSlot *)tab, cap - 1, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
+    else
+        hipLaunchKernelGGL(k_radius_query<true>, dim3((n_in + 255) / 256), dim3(256), 0, st, (const float4 *)sorted, n_in, xyz,
+                           (const uint2 *)slot_rank, n, G, (const RadSlot *)tab, cap - 1, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    // 7. the kept points through the ordered compaction
+    if ((rc = stage_begin(e, "radius_compact"))) return rc;
+    hipLaunchKernelGGL(k_radius_keep_count, dim3(m), dim3(256), 0, st, (const uint8_t *)keep, n, cnt);
+    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
+    const bool rows = d_out_points || d_out_colors || d_out_index;
+    if (rows)
+        hipLaunchKernelGGL(k_radius_scatter, dim3(m), dim3(256), 0, st, (const uint8_t *)keep, xyz, colors, n, (const uint32_t *)cnt,
+                           (float *)d_out_points, (uint8_t *)d_out_colors, (uint32_t *)d_out_index);
+    KCHECK();
+    if ((rc = stage_end(e, rows ? 3 : 2))) return rc;
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&total, cnt + m, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_ctl[RAD_CTL_ERR])
+        return set_err(SGM_ERR_HIP, "sgm_radius_outlier: a point found no slot in a table of %u slots for %u points", cap, n_in);
+    *n_kept = (int64_t)total;
+    if (n_out_of_range) *n_out_of_range = (int64_t)h_ctl[RAD_CTL_OUT];
+    return SGM_OK;
+}
+
+int sgm_radius_outlier(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int64_t n, float radius,
+                       const float origin[3], int nb_points, int max_count, uint8_t *out_keep, uint32_t *out_counts, float *out_points,
+                       uint8_t *out_colors, uint32_t *out_index, int64_t *n_kept, int64_t *n_out_of_range)
+{
+    if (int rc = radius_check_args(e, xyz, colors_rgb, n, radius, origin, nb_points, max_count, out_colors, n_kept)) return rc;
+    if (n == 0) {
+        *n_kept = 0;
+        if (n_out_of_range) *n_out_of_range = 0;
+        return SGM_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = e->xyz.ensure((size_t)n * 12)) || (disp && (rc = e->f32.ensure((size_t)n * 4))) || (rc = e->rad_keep.ensure((size_t)n)) ||
+        (out_counts && (rc = e->rad_cnt.ensure((size_t)n * 4))) || (out_points && (rc = e->cpts.ensure((size_t)n * 12))) ||
+        (out_index && (rc = e->rad_idx.ensure((size_t)n * 4))))
+        return rc;
+    if (out_colors && ((rc = e->crgb_in.ensure((size_t)n * 3)) || (rc = e->crgb.ensure((size_t)n * 3)))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, e->stream));
+    if (disp) HIP_TRY(hipMemcpyAsync(e->f32.p, disp, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    if (out_colors) HIP_TRY(hipMemcpyAsync(e->crgb_in.p, colors_rgb, (size_t)n * 3, hipMemcpyHostToDevice, e->stream));
+    int64_t nk = 0, noor = 0;
+    if ((rc = sgm_radius_outlier_device(e, e->xyz.p, disp ? e->f32.p : nullptr, out_colors ? e->crgb_in.p : nullptr, n, radius, origin,
+                                        nb_points, max_count, e->rad_keep.p, out_counts ? e->rad_cnt.p : nullptr,
+                                        out_points ? e->cpts.p : nullptr, out_colors ? e->crgb.p : nullptr,
+                                        out_index ? e->rad_idx.p : nullptr, &nk, &noor))) {
+        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
+        return rc;
+    }
+    if (out_keep) HIP_TRY(hipMemcpyAsync(out_keep, e->rad_keep.p, (size_t)n, hipMemcpyDeviceToHost, e->stream));
+    if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, e->rad_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+    if (nk > 0) {
+        if (out_points) HIP_TRY(hipMemcpyAsync(out_points, e->cpts.p, (size_t)nk * 12, hipMemcpyDeviceToHost, e->stream));
+        if (out_colors) HIP_TRY(hipMemcpyAsync(out_colors, e->crgb.p, (size_t)nk * 3, hipMemcpyDeviceToHost, e->stream));
+        if (out_index) HIP_TRY(hipMemcpyAsync(out_index, e->rad_idx.p, (size_t)nk * 4, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    *n_kept = nk;
     if (n_out_of_range) *n_out_of_range = noor;
     return SGM_OK;
 }

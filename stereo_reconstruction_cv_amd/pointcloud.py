@@ -5,6 +5,8 @@
     write_point_cloud(path, points, colors)           main.ipynb:795-797  o3d.io.write_point_cloud(.ply)
     voxel_down_sample(points_3D, colors, disparity_map, voxel_size, ...)   what users thin the cloud with before they show or
                  ship it: one centroid, mean colour and count per voxel, on the GPU (include/sgm_hip_voxel.h; NOT Open3D's values or order)
+    remove_radius_outlier(points_3D, colors, disparity_map, nb_points, radius, ...)   the first thing users do to a stereo cloud:
+                 drop the points with fewer than nb_points others within radius, on the GPU (include/sgm_hip_radius.h; NOT Open3D's)
     triangulate_points(points_3D, colors, disparity_map, max_diff, ...)    the surface over the organised cloud: two triangles per
                  pixel quad wherever the disparity is continuous, on the GPU (include/sgm_hip_mesh.h; NOT Open3D's meshing)
     write_triangle_mesh(path, vertices, triangles, colors)                 its PLY export, in the layout of Open3D's mesh writer
@@ -104,6 +106,81 @@ def voxel_down_sample(points_3D, colors, disparity_map, voxel_size, origin=(0, 0
     p, c, k, _ = _cv.get_engine(_cv._DEFAULT).voxel_downsample_host(pts, disp, colors, float(v), org, int(min_points),
                                                                    bool(return_counts))
     return (p, c, k) if return_counts else (p, c)
+
+
+RADIUS_MAX_POINTS = (1 << 24) - 1
+
+
+def remove_radius_outlier(points_3D, colors, disparity_map, nb_points, radius, origin=(0, 0, 0), max_count=None, confidence=None,
+                          min_confidence=0, return_mask=False, return_counts=False, return_index=False):
+    """Radius outlier removal on the GPU: keeps the points that have at least nb_points OTHER points within radius, in source
+    order.  The definition is include/sgm_hip_radius.h, our own, and the result is the same bits on every run: it is NOT Open3D's
+    remove_radius_outlier -- a point does not count itself, points whose cell index (cells of edge radius * 1.03125 anchored at
+    origin) leaves -2^16 .. 2^16 - 1 are dropped, and the counts saturate at max_count (None: nb_points), where a point's search
+    stops.  A fixed metric radius thins the far range of a stereo cloud, whose point spacing grows with depth.
+    points_3D (H, W, 3) with disparity_map (H, W) -- a point takes part iff X, Y, Z are finite and its disparity > 0, and with a
+    confidence map also confidence >= min_confidence, as in valid_points -- or an (N, 3) list with disparity_map=None (every
+    finite point takes part).  colors: uint8 of the shape of points_3D, or None.
+    Returns (points float32 (M, 3), colors uint8 (M, 3) or None[, mask][, counts][, index]): mask uint8, 1 where the point is
+    kept -- usable as the `confidence` of valid_points, triangulate_points and estimate_normals with min_confidence=1 -- and
+    counts uint32, min(neighbours, max_count), both of the shape of disparity_map (of (N,) for a list); index uint32 (M), the
+    source index of each kept point."""
+    who = "remove_radius_outlier"
+    pts = np.asarray(points_3D)
+    if pts.dtype != np.float32:
+        raise _cv.error(f"{who}: points_3D must be float32, not {pts.dtype}")
+    if disparity_map is None:
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise _cv.error(f"{who}: without a disparity_map points_3D must be an (N, 3) list")
+        if confidence is not None:
+            raise _cv.error(f"{who}: a confidence map needs a disparity_map")
+        disp = None
+    else:
+        disp = np.asarray(disparity_map)
+        if pts.ndim != 3 or pts.shape[2] != 3 or pts.shape[:2] != disp.shape:
+            raise _cv.error(f"{who}: points_3D must be (H, W, 3) and disparity_map (H, W)")
+        if confidence is not None:
+            disp = mask_by_confidence(disp, confidence, min_confidence)
+    if colors is not None:
+        colors = np.asarray(colors)
+        if colors.shape != pts.shape or colors.dtype != np.uint8:
+            raise _cv.error(f"{who}: colors must be uint8 and have the shape of points_3D")
+    with np.errstate(all="ignore"):
+        try:
+            r = np.float32(radius)
+            org = np.asarray(origin, np.float32)
+        except (TypeError, ValueError):
+            raise _cv.error(f"{who}: radius and origin must be numbers") from None
+        r2 = r * r
+        if (r.shape != () or not np.isfinite(r) or not r > 0 or not np.isfinite(r2) or r2 < np.finfo(np.float32).tiny
+                or not np.isfinite(np.float32(1.0) / (r * np.float32(1.03125)))):
+            raise _cv.error(f"{who}: radius={radius!r} is not a finite positive float32 with a finite normal square")
+    if org.shape != (3,) or not np.isfinite(org).all():
+        raise _cv.error(f"{who}: origin={origin!r} is not three finite numbers")
+    if isinstance(nb_points, bool) or not isinstance(nb_points, (int, np.integer)) or not 1 <= int(nb_points) <= 2 ** 31 - 1:
+        raise _cv.error(f"{who}: nb_points={nb_points!r} is not an integer >= 1")
+    if max_count is not None and (isinstance(max_count, bool) or not isinstance(max_count, (int, np.integer))
+                                  or not int(nb_points) <= int(max_count) <= 2 ** 31 - 1):
+        raise _cv.error(f"{who}: max_count={max_count!r} is not an integer >= nb_points")
+    n = pts.size // 3
+    if n > RADIUS_MAX_POINTS:
+        raise _cv.error(f"{who}: {n} points, more than {RADIUS_MAX_POINTS} (include/sgm_hip_radius.h)")
+    shape = pts.shape[:-1]
+    if n == 0:      # nothing to send to the device
+        p, c, keep, cnt, idx = (np.zeros((0, 3), np.float32), None if colors is None else np.zeros((0, 3), np.uint8),
+                                np.zeros(0, np.uint8), np.zeros(0, np.uint32), np.zeros(0, np.uint32))
+    else:
+        p, c, keep, cnt, idx, _ = _cv.get_engine(_cv._DEFAULT).radius_outlier_host(
+            pts, disp, colors, float(r), int(nb_points), None if max_count is None else int(max_count), org, bool(return_counts),
+            bool(return_index))
+    out = (p, c)
+    if return_mask:
+        out += (keep.reshape(shape),)
+    if return_counts:
+        out += (cnt.reshape(shape),)
+    if return_index:
+        out += (idx,)
+    return out
 
 
 MESH_MAX_PIXELS = 1 << 26

@@ -257,6 +257,46 @@ class Engine:
                                                    int(min_points), d_points, d_out_colors, d_out_counts, C.byref(nv), C.byref(noor)))
         return int(nv.value), int(noor.value)
 
+    # -- radius outlier removal (include/sgm_hip_radius.h) --
+    def radius_outlier_host(self, xyz: np.ndarray, disp: np.ndarray | None, colors: np.ndarray | None, radius: float, nb_points: int,
+                            max_count: int | None = None, origin=(0.0, 0.0, 0.0), return_counts: bool = False,
+                            return_index: bool = False):
+        """sgm_radius_outlier: float32 points (n, 3) or (H, W, 3), float32 disparities (n) or (H, W) or None, uint8 colours of the
+        points' shape or None; max_count None means nb_points.  Returns (points float32 (M, 3), colors uint8 (M, 3) or None,
+        keep uint8 (n), counts uint32 (n) or None, index uint32 (M) or None, n_out_of_range): the kept points in source order."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = xyz.shape[0]
+        disp = None if disp is None else np.ascontiguousarray(disp, np.float32).reshape(-1)
+        colors = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        keep = np.zeros(n, np.uint8)
+        cnt = np.zeros(n, np.uint32) if return_counts else None
+        pts = np.empty((n, 3), np.float32)
+        rgb = None if colors is None else np.empty((n, 3), np.uint8)
+        idx = np.empty(n, np.uint32) if return_index else None
+        nk, noor = C.c_int64(0), C.c_int64(0)
+        at = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.sgm_radius_outlier(self._h, xyz.ctypes.data, at(disp), at(colors), n, float(radius), org.ctypes.data,
+                                          int(nb_points), int(nb_points if max_count is None else max_count), keep.ctypes.data,
+                                          at(cnt), pts.ctypes.data, at(rgb), at(idx), C.byref(nk), C.byref(noor)))
+        m = nk.value
+        return (pts[:m].copy(), None if rgb is None else rgb[:m].copy(), keep, cnt, None if idx is None else idx[:m].copy(),
+                int(noor.value))
+
+    def radius_outlier_device(self, d_xyz: int, d_dispf: int | None, d_colors: int | None, n: int, radius: float, nb_points: int,
+                              max_count: int | None = None, origin=(0.0, 0.0, 0.0), d_keep: int | None = None,
+                              d_counts: int | None = None, d_points: int | None = None, d_out_colors: int | None = None,
+                              d_index: int | None = None):
+        """sgm_radius_outlier_device: device addresses; d_keep (uint8) and d_counts (uint32) have n entries, d_points, d_out_colors
+        and d_index (uint32) room for n rows, and the kept points go to their front in source order.  Returns (n_kept,
+        n_out_of_range); synchronises the engine's stream."""
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        nk, noor = C.c_int64(0), C.c_int64(0)
+        _check(self._L.sgm_radius_outlier_device(self._h, d_xyz, d_dispf, d_colors, int(n), float(radius), org.ctypes.data,
+                                                 int(nb_points), int(nb_points if max_count is None else max_count), d_keep, d_counts,
+                                                 d_points, d_out_colors, d_index, C.byref(nk), C.byref(noor)))
+        return int(nk.value), int(noor.value)
+
     # -- triangle mesh from the organised cloud (include/sgm_hip_mesh.h) --
     def mesh_grid_host(self, xyz: np.ndarray, disp: np.ndarray, colors: np.ndarray | None, max_diff: float = 1.0):
         """sgm_mesh_grid: float32 points (H, W, 3), float32 disparities (H, W), uint8 colours (H, W, 3) or None.  Returns
