@@ -57,7 +57,8 @@ extern "C" {
                              * the disparity post-filter of sgm_hip_wls.h and sgm_hip_wls_batch.h; the left-right
                              * consistency confidence of sgm_hip_lrc.h; the voxel-grid downsampling of sgm_hip_voxel.h; the grid
                              * triangulation of sgm_hip_mesh.h; its vertex normals and the normal image of sgm_hip_normals.h; the
-                             * radius outlier removal of sgm_hip_radius.h */
+                             * radius outlier removal of sgm_hip_radius.h; the statistical outlier removal of
+                             * sgm_hip_statistical.h */
 
 typedef enum {
     SGM_OK = 0,
@@ -322,4 +323,6 @@ int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_r
 #include "sgm_hip_normals.h"
 /* radius outlier removal for the point cloud: the number of neighbours within a radius, and the points that have enough */
 #include "sgm_hip_radius.h"
+/* statistical outlier removal: the mean distance to the k nearest neighbours against the cloud's own statistic of it */
+#include "sgm_hip_statistical.h"
 #endif

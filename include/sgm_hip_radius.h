@@ -59,7 +59,8 @@
  * Cost.  The work of a call is the number of candidates in the 27 cells around each point, cut short per point once its count
  * has reached max_count.  A radius that puts the whole cloud into a few cells, with a large max_count, is quadratic in n; nothing
  * bounds that except max_count.  A fixed metric radius also thins the far range of a stereo cloud, whose point spacing grows with
- * depth; a radius scaled by depth, and statistical outlier removal, are not offered.
+ * depth; a radius scaled by depth is not offered.  Statistical outlier removal, which asks for the mean distance to the k nearest
+ * neighbours instead of a count and takes its threshold from the cloud, is sgm_hip_statistical.h; it runs on this grid.
  */
 #ifndef SGM_HIP_RADIUS_H
 #define SGM_HIP_RADIUS_H

@@ -42,7 +42,9 @@ enum {
     SGM_DBG_VOXEL_OTHER_REDUCTION = 1 << 23, /* k_voxel_insert without the wave pre-reduction where it is the default (kernels_voxel.h: VOX_PRE_DEFAULT), with it where not */
     /* sgm_radius_outlier* (tools/radius_times.py); the results are the same bits under both */
     SGM_DBG_RADIUS_TIGHT_TABLE = 1 << 24,   /* capacity = the smallest power of two >= the points in range (not twice them): the load can reach 1.0 */
-    SGM_DBG_RADIUS_SOURCE_ORDER = 1 << 25   /* k_radius_query over the points in source order instead of sorted by cell */
+    SGM_DBG_RADIUS_SOURCE_ORDER = 1 << 25,  /* k_radius_query over the points in source order instead of sorted by cell */
+    /* sgm_statistical_outlier* (tools/statistical_times.py); SGM_DBG_RADIUS_TIGHT_TABLE acts on its table too; the same bits under all */
+    SGM_DBG_STAT_WIDE_LIST = 1 << 26        /* k_stat_query<64> whatever nb_neighbors is: the cost of the list's capacity apart from that of k */
 };
 
 /* Plan readout: what normalise + make_plan decide for one compute of a frame of H x W pixels on an engine with these

@@ -32,6 +32,7 @@
 #include "kernels_lrc.h"
 #include "kernels_voxel.h"
 #include "kernels_radius.h"
+#include "kernels_statistical.h"
 #include "kernels_mesh.h"
 #include "kernels_normals.h"
 
@@ -267,6 +268,7 @@ struct Plan {
     BUF(lrc_f)                                   /* sgm_lrc_confidence: uint8 [pairs of a chunk][2][H][W], the smoothness factors (kernels_lrc.h); sgm_trim releases it by name */ \
     BUF(vox_tab) BUF(vox_slot) BUF(vox_ctl) BUF(vox_cnt) /* sgm_voxel_downsample: the hash table (VoxSlot [capacity]), each point's slot (uint32 [n]), the call's control words, the host entry's staged counts (kernels_voxel.h); sgm_trim releases the first two by name */ \
     BUF(rad_tab) BUF(rad_sorted) BUF(rad_pt) BUF(rad_ctl) BUF(rad_keep) BUF(rad_cnt) BUF(rad_idx) /* sgm_radius_outlier: the hash table of cells (RadSlot [capacity]), the records sorted by cell (float4 [points in range]), each point's slot and rank (uint2 [n]), the call's control words, the keep bytes where the caller asks for none and the host entry's staged ones (uint8 [n]), its staged counts and indices (uint32 [n] each; kernels_radius.h); sgm_trim releases all but the control words by name */ \
+    BUF(stat_mean) BUF(stat_sums)                /* sgm_statistical_outlier, beside the radius search's buffers it reuses: the host entry's staged means (float32 [n]) and the call's 64-bit sums m, A, B (kernels_statistical.h); sgm_trim releases the first by name */ \
     BUF(mesh_code) BUF(mesh_num) BUF(mesh_fcnt) BUF(mesh_vcnt) BUF(mesh_faces) /* sgm_mesh_grid: a code byte per quad (uint8 [H][W]), the pixel -> vertex number map (uint32 [H][W]), the blocks' numbers of faces and of vertices (uint32 [blocks + 1] each), the host entry's staged faces (kernels_mesh.h); sgm_trim releases the first two and the last by name */ \
     BUF(mesh_nrm)                                /* sgm_normals_grid, sgm_mesh_grid_normals: the host entries' staged normals (float32 [H][W][3]; kernels_normals.h); sgm_trim releases it by name */ \
     BUF(headroom)                                /* uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r */ \
@@ -2046,8 +2048,8 @@ int sgm_trim(sgm_engine *e)
     for (auto &slot : e->pin_io)
         for (HostBuf &b : slot) b.release();
     for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f, &e->vox_tab, &e->vox_slot, &e->mesh_code, &e->mesh_num, &e->mesh_faces, &e->mesh_nrm,
-                      &e->rad_tab, &e->rad_sorted, &e->rad_pt, &e->rad_keep, &e->rad_cnt, &e->rad_idx})
-        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps, the staged normals and the radius search's table, records and staging come back on the next call
+                      &e->rad_tab, &e->rad_sorted, &e->rad_pt, &e->rad_keep, &e->rad_cnt, &e->rad_idx, &e->stat_mean})
+        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps, the staged normals, the radius search's table, records and staging and the staged means of the statistical one come back on the next call
     return check_chain(e);
 }
 
@@ -3375,6 +3377,86 @@ static int radius_check_args(const sgm_engine *e, const void *xyz, const void *c
     return SGM_OK;
 }
 
+// The grid of cells both searches run on, steps 1 to 5 of the device entries: the control words, the count of the points that
+// arrive (read back: *n_in, *n_out; with none the call is done and nothing else is built), then the table (*cap slots in rad_tab),
+// each point's slot and rank (rad_pt), the cells' starts and the records sorted by cell (rad_sorted).  keep and counts are what
+// k_radius_sort zeroes for the points in no cell (counts may be null).  names: the five stage names of the caller's record.
+static int radius_build_grid(sgm_engine *e, const float *xyz, const float *disp, int64_t n, const RadGrid &G, uint8_t *keep, uint32_t *counts,
+                             const char *const names[5], uint32_t *n_in_out, uint32_t *n_out, uint32_t *cap_out)
+{
+    const int m = (int)((n + 255) / 256);
+    int rc;
+    uint32_t *ctl = (uint32_t *)e->rad_ctl.p;
+    uint2 *slot_rank = (uint2 *)e->rad_pt.p;
+    hipStream_t st = e->stream;
+    // 1. how many points arrive: the table and the sorted records are sized from them, and a cloud with none is done here
+    HIP_TRY(hipMemsetAsync(ctl, 0, RAD_CTL_WORDS * 4, st));
+    stage_break(e);
+    if ((rc = stage_begin(e, names[0]))) return rc;
+    hipLaunchKernelGGL(k_radius_count, dim3(std::min(m, RAD_COUNT_BLOCKS)), dim3(256), 0, st, xyz, disp, n, G, ctl);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    uint32_t h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    stage_break(e);
+    const uint32_t n_in = h_ctl[RAD_CTL_IN];
+    *n_in_out = n_in;
+    *n_out = h_ctl[RAD_CTL_OUT];
+    *cap_out = 0;
+    if (n_in == 0) return SGM_OK;
+    // 2. the table: the smallest power of two of at least twice the points in range (debug: of at least the points themselves)
+    const uint64_t want = (e->debug & SGM_DBG_RADIUS_TIGHT_TABLE) ? (uint64_t)n_in : 2 * (uint64_t)n_in;
+    uint32_t cap = 1;
+    while (cap < want) cap <<= 1;   // (n_in < 2^24: at most 2^25)
+    *cap_out = cap;
+    if ((rc = e->rad_tab.ensure((size_t)cap * sizeof(RadSlot))) || (rc = e->rad_sorted.ensure((size_t)n_in * 16))) return rc;
+    RadSlot *tab = (RadSlot *)e->rad_tab.p;
+    float4 *sorted = (float4 *)e->rad_sorted.p;
+    if ((rc = stage_begin(e, names[1]))) return rc;
+    hipLaunchKernelGGL(k_radius_clear, dim3((cap + 255) / 256), dim3(256), 0, st, tab, cap);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    // 3. insert: each point's cell and its rank there
+    if ((rc = stage_begin(e, names[2]))) return rc;
+    hipLaunchKernelGGL(k_radius_insert, dim3(m), dim3(256), 0, st, xyz, disp, n, G, tab, cap - 1, slot_rank, ctl);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    // 4. where each cell's run begins
+    if ((rc = stage_begin(e, names[3]))) return rc;
+    hipLaunchKernelGGL(k_radius_starts, dim3((cap + RAD_STARTS_PER_BLOCK - 1) / RAD_STARTS_PER_BLOCK), dim3(256), 0, st, tab, cap, ctl);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    // 5. the records sorted by cell; the points in no cell get their zeros
+    if ((rc = stage_begin(e, names[4]))) return rc;
+    hipLaunchKernelGGL(k_radius_sort, dim3(m), dim3(256), 0, st, xyz, n, (const RadSlot *)tab, (const uint2 *)slot_rank, sorted, keep, counts);
+    KCHECK();
+    return stage_end(e, 1);
+}
+
+// step 7 of both: the kept points through the ordered compaction; *total and the call's control words come back (blocks)
+static int radius_compact_kept(sgm_engine *e, const char *stage, const uint8_t *keep, const float *xyz, const uint8_t *colors, int64_t n,
+                               void *d_out_points, void *d_out_colors, void *d_out_index, uint32_t *total, uint32_t h_ctl[RAD_CTL_WORDS])
+{
+    const int m = (int)((n + 255) / 256);
+    int rc;
+    uint32_t *cnt = (uint32_t *)e->ccount.p;
+    hipStream_t st = e->stream;
+    if ((rc = stage_begin(e, stage))) return rc;
+    hipLaunchKernelGGL(k_radius_keep_count, dim3(m), dim3(256), 0, st, keep, n, cnt);
+    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
+    const bool rows = d_out_points || d_out_colors || d_out_index;
+    if (rows)
+        hipLaunchKernelGGL(k_radius_scatter, dim3(m), dim3(256), 0, st, keep, xyz, colors, n, (const uint32_t *)cnt,
+                           (float *)d_out_points, (uint8_t *)d_out_colors, (uint32_t *)d_out_index);
+    KCHECK();
+    if ((rc = stage_end(e, rows ? 3 : 2))) return rc;
+    HIP_TRY(hipMemcpyAsync(h_ctl, e->rad_ctl.p, RAD_CTL_WORDS * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(total, cnt + m, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return SGM_OK;
+}
+
 int sgm_radius_outlier_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int64_t n, float radius,
                               const float origin[3], int nb_points, int max_count, void *d_out_keep, void *d_out_counts,
                               void *d_out_points, void *d_out_colors, void *d_out_index, int64_t *n_kept, int64_t *n_out_of_range)
@@ -3396,84 +3478,40 @@ int sgm_radius_outlier_device(sgm_engine *e, const void *d_xyz, const void *d_di
     const RadGrid G{1.0f / v, radius * radius, origin[0], origin[1], origin[2]};
     const float *xyz = (const float *)d_xyz, *disp = (const float *)d_disp_f32;
     const uint8_t *colors = (const uint8_t *)(d_out_colors ? d_colors_rgb : nullptr);
-    uint32_t *ctl = (uint32_t *)e->rad_ctl.p, *cnt = (uint32_t *)e->ccount.p, *counts = (uint32_t *)d_out_counts;
+    uint32_t *counts = (uint32_t *)d_out_counts;
     uint2 *slot_rank = (uint2 *)e->rad_pt.p;
     uint8_t *keep = (uint8_t *)(d_out_keep ? d_out_keep : e->rad_keep.p);
     hipStream_t st = e->stream;
-    // 1. how many points arrive: the table and the sorted records are sized from them, and a cloud with none is done here
-    HIP_TRY(hipMemsetAsync(ctl, 0, RAD_CTL_WORDS * 4, st));
-    stage_break(e);
-    if ((rc = stage_begin(e, "radius_count"))) return rc;
-    hipLaunchKernelGGL(k_radius_count, dim3(std::min(m, RAD_COUNT_BLOCKS)), dim3(256), 0, st, xyz, disp, n, G, ctl);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
-    uint32_t h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    stage_break(e);
-    const uint32_t n_in = h_ctl[RAD_CTL_IN];
+    static const char *const names[5] = {"radius_count", "radius_clear", "radius_insert", "radius_starts", "radius_sort"};
+    uint32_t n_in = 0, n_out = 0, cap = 0;
+    if ((rc = radius_build_grid(e, xyz, disp, n, G, keep, counts, names, &n_in, &n_out, &cap))) return rc;
     if (n_in == 0) {   // nobody has a neighbour
         if (d_out_keep) HIP_TRY(hipMemsetAsync(d_out_keep, 0, (size_t)n, st));
         if (counts) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n * 4, st));
         HIP_TRY(hipStreamSynchronize(st));
         *n_kept = 0;
-        if (n_out_of_range) *n_out_of_range = (int64_t)h_ctl[RAD_CTL_OUT];
+        if (n_out_of_range) *n_out_of_range = (int64_t)n_out;
         return SGM_OK;
     }
-    // 2. the table: the smallest power of two of at least twice the points in range (debug: of at least the points themselves)
-    const uint64_t want = (e->debug & SGM_DBG_RADIUS_TIGHT_TABLE) ? (uint64_t)n_in : 2 * (uint64_t)n_in;
-    uint32_t cap = 1;
-    while (cap < want) cap <<= 1;   // (n_in < 2^24: at most 2^25)
-    if ((rc = e->rad_tab.ensure((size_t)cap * sizeof(RadSlot))) || (rc = e->rad_sorted.ensure((size_t)n_in * 16))) return rc;
-    RadSlot *tab = (RadSlot *)e->rad_tab.p;
-    float4 *sorted = (float4 *)e->rad_sorted.p;
-    if ((rc = stage_begin(e, "radius_clear"))) return rc;
-    hipLaunchKernelGGL(k_radius_clear, dim3((cap + 255) / 256), dim3(256), 0, st, tab, cap);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
-    // 3. insert: each point's cell and its rank there
-    if ((rc = stage_begin(e, "radius_insert"))) return rc;
-    hipLaunchKernelGGL(k_radius_insert, dim3(m), dim3(256), 0, st, xyz, disp, n, G, tab, cap - 1, slot_rank, ctl);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
-    // 4. where each cell's run begins
-    if ((rc = stage_begin(e, "radius_starts"))) return rc;
-    hipLaunchKernelGGL(k_radius_starts, dim3((cap + RAD_STARTS_PER_BLOCK - 1) / RAD_STARTS_PER_BLOCK), dim3(256), 0, st, tab, cap, ctl);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
-    // 5. the records sorted by cell; the points in no cell get their zeros
-    if ((rc = stage_begin(e, "radius_sort"))) return rc;
-    hipLaunchKernelGGL(k_radius_sort, dim3(m), dim3(256), 0, st, xyz, n, (const RadSlot *)tab, (const uint2 *)slot_rank, sorted, keep, counts);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    const RadSlot *tab = (const RadSlot *)e->rad_tab.p;
+    const float4 *sorted = (const float4 *)e->rad_sorted.p;
     // 6. the counts
     if ((rc = stage_begin(e, "radius_query"))) return rc;
     if (e->debug & SGM_DBG_RADIUS_SOURCE_ORDER)
-        hipLaunchKernelGGL(k_radius_query<false>, dim3(m), dim3(256), 0, st, (const float4 *)sorted, n_in, xyz, (const uint2 *)slot_rank, n, G,
-                           (const RadSlot *)tab, cap - 1, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
+        hipLaunchKernelGGL(k_radius_query<false>, dim3(m), dim3(256), 0, st, sorted, n_in, xyz, (const uint2 *)slot_rank, n, G,
+                           tab, cap - 1, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
     else
-        hipLaunchKernelGGL(k_radius_query<true>, dim3((n_in + 255) / 256), dim3(256), 0, st, (const float4 *)sorted, n_in, xyz,
-                           (const uint2 *)slot_rank, n, G, (const RadSlot *)tab, cap - 1, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
+        hipLaunchKernelGGL(k_radius_query<true>, dim3((n_in + 255) / 256), dim3(256), 0, st, sorted, n_in, xyz,
+                           (const uint2 *)slot_rank, n, G, tab, cap - 1, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
     KCHECK();
     if ((rc = stage_end(e, 1))) return rc;
     // 7. the kept points through the ordered compaction
-    if ((rc = stage_begin(e, "radius_compact"))) return rc;
-    hipLaunchKernelGGL(k_radius_keep_count, dim3(m), dim3(256), 0, st, (const uint8_t *)keep, n, cnt);
-    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
-    const bool rows = d_out_points || d_out_colors || d_out_index;
-    if (rows)
-        hipLaunchKernelGGL(k_radius_scatter, dim3(m), dim3(256), 0, st, (const uint8_t *)keep, xyz, colors, n, (const uint32_t *)cnt,
-                           (float *)d_out_points, (uint8_t *)d_out_colors, (uint32_t *)d_out_index);
-    KCHECK();
-    if ((rc = stage_end(e, rows ? 3 : 2))) return rc;
-    uint32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&total, cnt + m, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    uint32_t total = 0, h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0};
+    if ((rc = radius_compact_kept(e, "radius_compact", keep, xyz, colors, n, d_out_points, d_out_colors, d_out_index, &total, h_ctl))) return rc;
     if (h_ctl[RAD_CTL_ERR])
         return set_err(SGM_ERR_HIP, "sgm_radius_outlier: a point found no slot in a table of %u slots for %u points", cap, n_in);
     *n_kept = (int64_t)total;
-    if (n_out_of_range) *n_out_of_range = (int64_t)h_ctl[RAD_CTL_OUT];
+    if (n_out_of_range) *n_out_of_range = (int64_t)n_out;
     return SGM_OK;
 }
 
@@ -3515,6 +3553,171 @@ int sgm_radius_outlier(sgm_engine *e, const float *xyz, const float *disp, const
     HIP_TRY(hipStreamSynchronize(e->stream));
     *n_kept = nk;
     if (n_out_of_range) *n_out_of_range = noor;
+    return SGM_OK;
+}
+
+// ---- statistical outlier removal (include/sgm_hip_statistical.h, kernels_statistical.h) ------------------------------------------
+static int stat_check_args(const sgm_engine *e, const void *xyz, const void *colors, int64_t n, int k, float ratio, float r, const float *origin,
+                           const void *out_colors, const int64_t *n_kept)
+{
+    if (!e || !xyz || !n_kept) return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: null pointer");
+    if (n < 0) return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: n=%lld points", (long long)n);
+    if (k < 1 || k > STAT_MAX_K) return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: nb_neighbors %d outside 1 .. %d", k, STAT_MAX_K);
+    if (!std::isfinite(ratio) || !(ratio >= 0.0f))
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: std_ratio %g is not finite and >= 0", (double)ratio);
+    const float r2 = r * r, v = r * 1.03125f;
+    if (!std::isfinite(r) || !(r > 0.0f) || !std::isnormal(r2) || !std::isfinite(1.0f / v) || !std::isfinite(524288.0f / r))
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: max_radius %g is not finite and positive with a finite normal square", (double)r);
+    if (!origin || !std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: the origin is null or not finite");
+    if (out_colors && !colors) return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: out_colors requested without colors");
+    if (n > RAD_MAX_POINTS)
+        return set_err(SGM_ERR_UNSUPPORTED, "sgm_statistical_outlier: %lld points, more than 2^24 - 1 (a source index shares a record with its point)", (long long)n);
+    return SGM_OK;
+}
+
+// step 8 of the definition: T from m, A, B in binary64, every operation on its own (the build has -ffp-contract=off)
+static uint32_t stat_threshold(uint64_t m, uint64_t A, uint64_t B, float ratio)
+{
+    if (m == 0) return 0;
+    const double mu = (double)A / (double)m;
+    double var = 0.0;
+    if (m >= 2) {
+        const double prod = (double)A * mu;
+        const double diff = (double)B - prod;
+        var = diff / (double)(m - 1);
+    }
+    if (var < 0.0) var = 0.0;
+    const double dev = (double)ratio * std::sqrt(var);
+    const double thr = std::floor(mu + dev);
+    return thr >= 4294967295.0 ? 4294967294u : (uint32_t)thr;
+}
+
+int sgm_statistical_outlier_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int64_t n,
+                                   int nb_neighbors, float std_ratio, float max_radius, const float origin[3], void *d_out_keep,
+                                   void *d_out_mean, void *d_out_points, void *d_out_colors, void *d_out_index, int64_t *n_kept,
+                                   uint64_t *out_stats)
+{
+    if (int rc = stat_check_args(e, d_xyz, d_colors_rgb, n, nb_neighbors, std_ratio, max_radius, origin, d_out_colors, n_kept)) return rc;
+    if (n == 0) {
+        *n_kept = 0;
+        if (out_stats) std::fill(out_stats, out_stats + 8, (uint64_t)0);
+        return SGM_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const int m = (int)((n + 255) / 256);
+    int rc;
+    if ((rc = e->rad_ctl.ensure(RAD_CTL_WORDS * 4)) || (rc = e->stat_sums.ensure(STAT_SUM_WORDS * 8)) || (rc = e->rad_pt.ensure((size_t)n * 8)) ||
+        (rc = e->ccount.ensure((size_t)(m + 1) * 4)) || (!d_out_keep && (rc = e->rad_keep.ensure((size_t)n))))
+        return rc;
+    if (e->profile) stage_reset(e);   // the stage record is the call's from here on
+    const float v = max_radius * 1.03125f, qscale = 524288.0f / max_radius;
+    const RadGrid G{1.0f / v, max_radius * max_radius, origin[0], origin[1], origin[2]};
+    const float *xyz = (const float *)d_xyz, *disp = (const float *)d_disp_f32;
+    const uint8_t *colors = (const uint8_t *)(d_out_colors ? d_colors_rgb : nullptr);
+    float *mean = (float *)d_out_mean;
+    uint2 *pt = (uint2 *)e->rad_pt.p;
+    unsigned long long *sums = (unsigned long long *)e->stat_sums.p;
+    uint8_t *keep = (uint8_t *)(d_out_keep ? d_out_keep : e->rad_keep.p);
+    hipStream_t st = e->stream;
+    static const char *const names[5] = {"stat_count", "stat_clear", "stat_insert", "stat_starts", "stat_sort"};
+    uint32_t n_in = 0, n_out = 0, cap = 0;
+    if ((rc = radius_build_grid(e, xyz, disp, n, G, keep, nullptr, names, &n_in, &n_out, &cap))) return rc;
+    if (n_in == 0) {   // nobody has a neighbour
+        if (d_out_keep) HIP_TRY(hipMemsetAsync(d_out_keep, 0, (size_t)n, st));
+        if (mean) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)mean, (int)0xBF800000u, (size_t)n, st));   // -1.0f
+        HIP_TRY(hipStreamSynchronize(st));
+        *n_kept = 0;
+        if (out_stats) {
+            std::fill(out_stats, out_stats + 8, (uint64_t)0);
+            out_stats[1] = n_out;
+        }
+        return SGM_OK;
+    }
+    const RadSlot *tab = (const RadSlot *)e->rad_tab.p;
+    const float4 *sorted = (const float4 *)e->rad_sorted.p;
+    // 6. per point the k nearest, their mean distance and q: the list of a lane has the smallest capacity that holds k
+    HIP_TRY(hipMemsetAsync(sums, 0, STAT_SUM_WORDS * 8, st));
+    stage_break(e);
+    if ((rc = stage_begin(e, "stat_query"))) return rc;
+    const dim3 qgrid((n_in + 255) / 256);
+    const uint32_t k = (uint32_t)nb_neighbors;
+#define SGM_STAT_QUERY(CAP) \
+    hipLaunchKernelGGL(k_stat_query<CAP>, qgrid, dim3(256), 0, st, sorted, n_in, G, tab, cap - 1, k, qscale, (uint32_t *)pt, mean)
+    if (e->debug & SGM_DBG_STAT_WIDE_LIST) SGM_STAT_QUERY(64);
+    else if (k <= 8) SGM_STAT_QUERY(8);
+    else if (k <= 16) SGM_STAT_QUERY(16);
+    else if (k <= 32) SGM_STAT_QUERY(32);
+    else SGM_STAT_QUERY(64);
+#undef SGM_STAT_QUERY
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    // 7. m, A, B over the dense points; the host forms T from them
+    if ((rc = stage_begin(e, "stat_reduce"))) return rc;
+    hipLaunchKernelGGL(k_stat_reduce, dim3(std::min(m, RAD_COUNT_BLOCKS)), dim3(256), 0, st, (const uint2 *)pt, n, sums);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    unsigned long long h_sums[STAT_SUM_WORDS] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_sums, sums, sizeof(h_sums), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    stage_break(e);
+    const uint32_t T = stat_threshold(h_sums[STAT_SUM_M], h_sums[STAT_SUM_A], h_sums[STAT_SUM_B], std_ratio);
+    // 8. keep, then the kept points through the ordered compaction
+    if ((rc = stage_begin(e, "stat_keep"))) return rc;
+    hipLaunchKernelGGL(k_stat_keep, dim3(m), dim3(256), 0, st, (const uint2 *)pt, n, T, keep, mean);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    uint32_t total = 0, h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0};
+    if ((rc = radius_compact_kept(e, "stat_compact", keep, xyz, colors, n, d_out_points, d_out_colors, d_out_index, &total, h_ctl))) return rc;
+    if (h_ctl[RAD_CTL_ERR])
+        return set_err(SGM_ERR_HIP, "sgm_statistical_outlier: a point found no slot in a table of %u slots for %u points", cap, n_in);
+    *n_kept = (int64_t)total;
+    if (out_stats) {
+        const uint64_t s[8] = {n_in, n_out, h_sums[STAT_SUM_M], n_in - h_sums[STAT_SUM_M], h_sums[STAT_SUM_A], h_sums[STAT_SUM_B], T, 0};
+        std::copy(s, s + 8, out_stats);
+    }
+    return SGM_OK;
+}
+
+int sgm_statistical_outlier(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int64_t n, int nb_neighbors,
+                            float std_ratio, float max_radius, const float origin[3], uint8_t *out_keep, float *out_mean, float *out_points,
+                            uint8_t *out_colors, uint32_t *out_index, int64_t *n_kept, uint64_t *out_stats)
+{
+    if (int rc = stat_check_args(e, xyz, colors_rgb, n, nb_neighbors, std_ratio, max_radius, origin, out_colors, n_kept)) return rc;
+    if (n == 0) {
+        *n_kept = 0;
+        if (out_stats) std::fill(out_stats, out_stats + 8, (uint64_t)0);
+        return SGM_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = e->xyz.ensure((size_t)n * 12)) || (disp && (rc = e->f32.ensure((size_t)n * 4))) || (rc = e->rad_keep.ensure((size_t)n)) ||
+        (out_mean && (rc = e->stat_mean.ensure((size_t)n * 4))) || (out_points && (rc = e->cpts.ensure((size_t)n * 12))) ||
+        (out_index && (rc = e->rad_idx.ensure((size_t)n * 4))))
+        return rc;
+    if (out_colors && ((rc = e->crgb_in.ensure((size_t)n * 3)) || (rc = e->crgb.ensure((size_t)n * 3)))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, e->stream));
+    if (disp) HIP_TRY(hipMemcpyAsync(e->f32.p, disp, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    if (out_colors) HIP_TRY(hipMemcpyAsync(e->crgb_in.p, colors_rgb, (size_t)n * 3, hipMemcpyHostToDevice, e->stream));
+    int64_t nk = 0;
+    uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if ((rc = sgm_statistical_outlier_device(e, e->xyz.p, disp ? e->f32.p : nullptr, out_colors ? e->crgb_in.p : nullptr, n, nb_neighbors,
+                                             std_ratio, max_radius, origin, e->rad_keep.p, out_mean ? e->stat_mean.p : nullptr,
+                                             out_points ? e->cpts.p : nullptr, out_colors ? e->crgb.p : nullptr,
+                                             out_index ? e->rad_idx.p : nullptr, &nk, stats))) {
+        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
+        return rc;
+    }
+    if (out_keep) HIP_TRY(hipMemcpyAsync(out_keep, e->rad_keep.p, (size_t)n, hipMemcpyDeviceToHost, e->stream));
+    if (out_mean) HIP_TRY(hipMemcpyAsync(out_mean, e->stat_mean.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+    if (nk > 0) {
+        if (out_points) HIP_TRY(hipMemcpyAsync(out_points, e->cpts.p, (size_t)nk * 12, hipMemcpyDeviceToHost, e->stream));
+        if (out_colors) HIP_TRY(hipMemcpyAsync(out_colors, e->crgb.p, (size_t)nk * 3, hipMemcpyDeviceToHost, e->stream));
+        if (out_index) HIP_TRY(hipMemcpyAsync(out_index, e->rad_idx.p, (size_t)nk * 4, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    *n_kept = nk;
+    if (out_stats) std::copy(stats, stats + 8, out_stats);
     return SGM_OK;
 }
 

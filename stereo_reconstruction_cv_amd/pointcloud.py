@@ -7,6 +7,9 @@
                  ship it: one centroid, mean colour and count per voxel, on the GPU (include/sgm_hip_voxel.h; NOT Open3D's values or order)
     remove_radius_outlier(points_3D, colors, disparity_map, nb_points, radius, ...)   the first thing users do to a stereo cloud:
                  drop the points with fewer than nb_points others within radius, on the GPU (include/sgm_hip_radius.h; NOT Open3D's)
+    remove_statistical_outlier(points_3D, colors, disparity_map, nb_neighbors, std_ratio, max_radius, ...)   its companion: drop the
+                 points whose mean distance to their nb_neighbors nearest others within max_radius is above the cloud's own mean of
+                 it plus std_ratio deviations, on the GPU (include/sgm_hip_statistical.h; NOT Open3D's)
     triangulate_points(points_3D, colors, disparity_map, max_diff, ...)    the surface over the organised cloud: two triangles per
                  pixel quad wherever the disparity is continuous, on the GPU (include/sgm_hip_mesh.h; NOT Open3D's meshing)
     write_triangle_mesh(path, vertices, triangles, colors)                 its PLY export, in the layout of Open3D's mesh writer
@@ -111,21 +114,8 @@ def voxel_down_sample(points_3D, colors, disparity_map, voxel_size, origin=(0, 0
 RADIUS_MAX_POINTS = (1 << 24) - 1
 
 
-def remove_radius_outlier(points_3D, colors, disparity_map, nb_points, radius, origin=(0, 0, 0), max_count=None, confidence=None,
-                          min_confidence=0, return_mask=False, return_counts=False, return_index=False):
-    """Radius outlier removal on the GPU: keeps the points that have at least nb_points OTHER points within radius, in source
-    order.  The definition is include/sgm_hip_radius.h, our own, and the result is the same bits on every run: it is NOT Open3D's
-    remove_radius_outlier -- a point does not count itself, points whose cell index (cells of edge radius * 1.03125 anchored at
-    origin) leaves -2^16 .. 2^16 - 1 are dropped, and the counts saturate at max_count (None: nb_points), where a point's search
-    stops.  A fixed metric radius thins the far range of a stereo cloud, whose point spacing grows with depth.
-    points_3D (H, W, 3) with disparity_map (H, W) -- a point takes part iff X, Y, Z are finite and its disparity > 0, and with a
-    confidence map also confidence >= min_confidence, as in valid_points -- or an (N, 3) list with disparity_map=None (every
-    finite point takes part).  colors: uint8 of the shape of points_3D, or None.
-    Returns (points float32 (M, 3), colors uint8 (M, 3) or None[, mask][, counts][, index]): mask uint8, 1 where the point is
-    kept -- usable as the `confidence` of valid_points, triangulate_points and estimate_normals with min_confidence=1 -- and
-    counts uint32, min(neighbours, max_count), both of the shape of disparity_map (of (N,) for a list); index uint32 (M), the
-    source index of each kept point."""
-    who = "remove_radius_outlier"
+def _outlier_cloud(who, points_3D, colors, disparity_map, confidence, min_confidence):
+    """what the two outlier removals accept as a cloud: (points, disparities or None, colours or None), checked"""
     pts = np.asarray(points_3D)
     if pts.dtype != np.float32:
         raise _cv.error(f"{who}: points_3D must be float32, not {pts.dtype}")
@@ -145,6 +135,25 @@ def remove_radius_outlier(points_3D, colors, disparity_map, nb_points, radius, o
         colors = np.asarray(colors)
         if colors.shape != pts.shape or colors.dtype != np.uint8:
             raise _cv.error(f"{who}: colors must be uint8 and have the shape of points_3D")
+    return pts, disp, colors
+
+
+def remove_radius_outlier(points_3D, colors, disparity_map, nb_points, radius, origin=(0, 0, 0), max_count=None, confidence=None,
+                          min_confidence=0, return_mask=False, return_counts=False, return_index=False):
+    """Radius outlier removal on the GPU: keeps the points that have at least nb_points OTHER points within radius, in source
+    order.  The definition is include/sgm_hip_radius.h, our own, and the result is the same bits on every run: it is NOT Open3D's
+    remove_radius_outlier -- a point does not count itself, points whose cell index (cells of edge radius * 1.03125 anchored at
+    origin) leaves -2^16 .. 2^16 - 1 are dropped, and the counts saturate at max_count (None: nb_points), where a point's search
+    stops.  A fixed metric radius thins the far range of a stereo cloud, whose point spacing grows with depth.
+    points_3D (H, W, 3) with disparity_map (H, W) -- a point takes part iff X, Y, Z are finite and its disparity > 0, and with a
+    confidence map also confidence >= min_confidence, as in valid_points -- or an (N, 3) list with disparity_map=None (every
+    finite point takes part).  colors: uint8 of the shape of points_3D, or None.
+    Returns (points float32 (M, 3), colors uint8 (M, 3) or None[, mask][, counts][, index]): mask uint8, 1 where the point is
+    kept -- usable as the `confidence` of valid_points, triangulate_points and estimate_normals with min_confidence=1 -- and
+    counts uint32, min(neighbours, max_count), both of the shape of disparity_map (of (N,) for a list); index uint32 (M), the
+    source index of each kept point."""
+    who = "remove_radius_outlier"
+    pts, disp, colors = _outlier_cloud(who, points_3D, colors, disparity_map, confidence, min_confidence)
     with np.errstate(all="ignore"):
         try:
             r = np.float32(radius)
@@ -180,6 +189,72 @@ def remove_radius_outlier(points_3D, colors, disparity_map, nb_points, radius, o
         out += (cnt.reshape(shape),)
     if return_index:
         out += (idx,)
+    return out
+
+
+STATISTICAL_MAX_NEIGHBORS = 64
+
+
+def remove_statistical_outlier(points_3D, colors, disparity_map, nb_neighbors, std_ratio, max_radius, origin=(0, 0, 0), confidence=None,
+                               min_confidence=0, return_mask=False, return_distances=False, return_index=False, return_stats=False):
+    """Statistical outlier removal on the GPU: per point the mean distance to its nb_neighbors nearest OTHER points within
+    max_radius, and the points whose mean is not above the cloud's mean of these means plus std_ratio standard deviations, in
+    source order.  The definition is include/sgm_hip_statistical.h, our own, and the result is the same bits on every run: it is
+    NOT Open3D's remove_statistical_outlier -- the search is bounded by max_radius and a point with fewer than nb_neighbors
+    (1 .. 64) neighbours there is an outlier outright and stays out of the statistic, a point does not count itself, points whose
+    cell index (cells of edge max_radius * 1.03125 anchored at origin) leaves -2^16 .. 2^16 - 1 are dropped, and the statistic is
+    formed in integers (the means scaled by 2^19 / max_radius).  max_radius should hold a few times nb_neighbors neighbours; the
+    work grows with every candidate in the 27 cells around a point.  A fixed metric max_radius thins the far range of a stereo
+    cloud, whose point spacing grows with depth.
+    points_3D (H, W, 3) with disparity_map (H, W) -- a point takes part iff X, Y, Z are finite and its disparity > 0, and with a
+    confidence map also confidence >= min_confidence, as in valid_points -- or an (N, 3) list with disparity_map=None (every
+    finite point takes part).  colors: uint8 of the shape of points_3D, or None.
+    Returns (points float32 (M, 3), colors uint8 (M, 3) or None[, mask][, distances][, index][, stats]): mask uint8, 1 where the
+    point is kept -- usable as the `confidence` of valid_points, triangulate_points and estimate_normals with min_confidence=1 --
+    and distances float32, the mean distance of a point with nb_neighbors neighbours and -1 for every other point, both of the
+    shape of disparity_map (of (N,) for a list); index uint32 (M), the source index of each kept point; stats a dict: in_range,
+    out_of_range, dense, sparse, A, B, T."""
+    who = "remove_statistical_outlier"
+    pts, disp, colors = _outlier_cloud(who, points_3D, colors, disparity_map, confidence, min_confidence)
+    if isinstance(nb_neighbors, bool) or not isinstance(nb_neighbors, (int, np.integer)) or not 1 <= int(nb_neighbors) <= STATISTICAL_MAX_NEIGHBORS:
+        raise _cv.error(f"{who}: nb_neighbors={nb_neighbors!r} is not an integer in 1 .. {STATISTICAL_MAX_NEIGHBORS}")
+    with np.errstate(all="ignore"):
+        try:
+            ratio = np.float32(std_ratio)
+        except (TypeError, ValueError):
+            raise _cv.error(f"{who}: std_ratio={std_ratio!r} is not a number") from None
+        if isinstance(std_ratio, bool) or ratio.shape != () or not np.isfinite(ratio) or not ratio >= 0:
+            raise _cv.error(f"{who}: std_ratio={std_ratio!r} is not a finite float32 >= 0")
+        try:
+            r = np.float32(max_radius)
+            org = np.asarray(origin, np.float32)
+        except (TypeError, ValueError):
+            raise _cv.error(f"{who}: max_radius and origin must be numbers") from None
+        r2 = r * r
+        if (r.shape != () or not np.isfinite(r) or not r > 0 or not np.isfinite(r2) or r2 < np.finfo(np.float32).tiny
+                or not np.isfinite(np.float32(1.0) / (r * np.float32(1.03125))) or not np.isfinite(np.float32(524288.0) / r)):
+            raise _cv.error(f"{who}: max_radius={max_radius!r} is not a finite positive float32 with a finite normal square")
+    if org.shape != (3,) or not np.isfinite(org).all():
+        raise _cv.error(f"{who}: origin={origin!r} is not three finite numbers")
+    n = pts.size // 3
+    if n > RADIUS_MAX_POINTS:
+        raise _cv.error(f"{who}: {n} points, more than {RADIUS_MAX_POINTS} (include/sgm_hip_statistical.h)")
+    shape = pts.shape[:-1]
+    if n == 0:      # nothing to send to the device
+        p, c, keep, mean, idx, st = (np.zeros((0, 3), np.float32), None if colors is None else np.zeros((0, 3), np.uint8),
+                                     np.zeros(0, np.uint8), np.zeros(0, np.float32), np.zeros(0, np.uint32), np.zeros(8, np.uint64))
+    else:
+        p, c, keep, mean, idx, st = _cv.get_engine(_cv._DEFAULT).statistical_outlier_host(
+            pts, disp, colors, int(nb_neighbors), float(ratio), float(r), org, bool(return_distances), bool(return_index))
+    out = (p, c)
+    if return_mask:
+        out += (keep.reshape(shape),)
+    if return_distances:
+        out += (mean.reshape(shape),)
+    if return_index:
+        out += (idx,)
+    if return_stats:
+        out += (dict(zip(("in_range", "out_of_range", "dense", "sparse", "A", "B", "T"), (int(x) for x in st[:7]))),)
     return out
 
 

@@ -297,6 +297,46 @@ class Engine:
                                                  d_points, d_out_colors, d_index, C.byref(nk), C.byref(noor)))
         return int(nk.value), int(noor.value)
 
+    # -- statistical outlier removal (include/sgm_hip_statistical.h) --
+    def statistical_outlier_host(self, xyz: np.ndarray, disp: np.ndarray | None, colors: np.ndarray | None, nb_neighbors: int,
+                                 std_ratio: float, max_radius: float, origin=(0.0, 0.0, 0.0), return_distances: bool = False,
+                                 return_index: bool = False):
+        """sgm_statistical_outlier: float32 points (n, 3) or (H, W, 3), float32 disparities (n) or (H, W) or None, uint8 colours of
+        the points' shape or None.  Returns (points float32 (M, 3), colors uint8 (M, 3) or None, keep uint8 (n), mean float32 (n)
+        or None, index uint32 (M) or None, stats uint64 (8)): the kept points in source order; stats is points in range, valid
+        points out of range, dense, sparse, A, B, T, 0."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = xyz.shape[0]
+        disp = None if disp is None else np.ascontiguousarray(disp, np.float32).reshape(-1)
+        colors = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        keep = np.zeros(n, np.uint8)
+        mean = np.full(n, -1, np.float32) if return_distances else None
+        pts = np.empty((n, 3), np.float32)
+        rgb = None if colors is None else np.empty((n, 3), np.uint8)
+        idx = np.empty(n, np.uint32) if return_index else None
+        nk, stats = C.c_int64(0), np.zeros(8, np.uint64)
+        at = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.sgm_statistical_outlier(self._h, xyz.ctypes.data, at(disp), at(colors), n, int(nb_neighbors), float(std_ratio),
+                                               float(max_radius), org.ctypes.data, keep.ctypes.data, at(mean), pts.ctypes.data, at(rgb),
+                                               at(idx), C.byref(nk), stats.ctypes.data))
+        m = nk.value
+        return (pts[:m].copy(), None if rgb is None else rgb[:m].copy(), keep, mean, None if idx is None else idx[:m].copy(), stats)
+
+    def statistical_outlier_device(self, d_xyz: int, d_dispf: int | None, d_colors: int | None, n: int, nb_neighbors: int,
+                                   std_ratio: float, max_radius: float, origin=(0.0, 0.0, 0.0), d_keep: int | None = None,
+                                   d_mean: int | None = None, d_points: int | None = None, d_out_colors: int | None = None,
+                                   d_index: int | None = None):
+        """sgm_statistical_outlier_device: device addresses; d_keep (uint8) and d_mean (float32) have n entries, d_points,
+        d_out_colors and d_index (uint32) room for n rows, and the kept points go to their front in source order.  Returns
+        (n_kept, stats uint64 (8)); synchronises the engine's stream."""
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        nk, stats = C.c_int64(0), np.zeros(8, np.uint64)
+        _check(self._L.sgm_statistical_outlier_device(self._h, d_xyz, d_dispf, d_colors, int(n), int(nb_neighbors), float(std_ratio),
+                                                      float(max_radius), org.ctypes.data, d_keep, d_mean, d_points, d_out_colors, d_index,
+                                                      C.byref(nk), stats.ctypes.data))
+        return int(nk.value), stats
+
     # -- triangle mesh from the organised cloud (include/sgm_hip_mesh.h) --
     def mesh_grid_host(self, xyz: np.ndarray, disp: np.ndarray, colors: np.ndarray | None, max_diff: float = 1.0):
         """sgm_mesh_grid: float32 points (H, W, 3), float32 disparities (H, W), uint8 colours (H, W, 3) or None.  Returns
