@@ -58,7 +58,7 @@ extern "C" {
                              * consistency confidence of sgm_hip_lrc.h; the voxel-grid downsampling of sgm_hip_voxel.h; the grid
                              * triangulation of sgm_hip_mesh.h; its vertex normals and the normal image of sgm_hip_normals.h; the
                              * radius outlier removal of sgm_hip_radius.h; the statistical outlier removal of
-                             * sgm_hip_statistical.h */
+                             * sgm_hip_statistical.h; the covariance normals of sgm_hip_covariance.h */
 
 typedef enum {
     SGM_OK = 0,
@@ -325,4 +325,6 @@ int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_r
 #include "sgm_hip_radius.h"
 /* statistical outlier removal: the mean distance to the k nearest neighbours against the cloud's own statistic of it */
 #include "sgm_hip_statistical.h"
+/* covariance normals for a point list: the plane fitted to the neighbours within a radius, on the same grid of cells */
+#include "sgm_hip_covariance.h"
 #endif

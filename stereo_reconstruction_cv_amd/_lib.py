@@ -27,6 +27,7 @@ SGM_OPT_POISON = 9   # csrc/sgm_debug.h: fill every device buffer with a byte (0
 SGM_DBG_VOXEL_TIGHT_TABLE, SGM_DBG_VOXEL_OTHER_REDUCTION = 1 << 22, 1 << 23   # csrc/sgm_debug.h: the two A/B bits of sgm_voxel_downsample
 SGM_DBG_RADIUS_TIGHT_TABLE, SGM_DBG_RADIUS_SOURCE_ORDER = 1 << 24, 1 << 25   # csrc/sgm_debug.h: the two A/B bits of sgm_radius_outlier
 SGM_DBG_STAT_WIDE_LIST = 1 << 26   # csrc/sgm_debug.h: the A/B bit of sgm_statistical_outlier (the 64-word list at every nb_neighbors)
+SGM_DBG_COV_SEPARATE_SOLVE, SGM_DBG_COV_SELECT_ACCUM = 1 << 27, 1 << 28   # csrc/sgm_debug.h: the two A/B bits of sgm_covariance_normals
 SGM_MAX_STAGES = 32
 
 # every symbol include/sgm_hip.h declares (checked by tests/test_abi.py)
@@ -60,6 +61,10 @@ NORMALS_EXPORTS = ("sgm_normals_grid", "sgm_normals_grid_device", "sgm_mesh_grid
 RADIUS_EXPORTS = ("sgm_radius_outlier", "sgm_radius_outlier_device")
 # include/sgm_hip_statistical.h (likewise): statistical outlier removal for the point cloud
 STATISTICAL_EXPORTS = ("sgm_statistical_outlier", "sgm_statistical_outlier_device")
+# include/sgm_hip_covariance.h (likewise): covariance normals for a point list
+COVARIANCE_EXPORTS = ("sgm_covariance_normals", "sgm_covariance_normals_device")
+# the stage record of one sgm_covariance_normals call with SGM_OPT_PROFILE (cov_solve only with SGM_DBG_COV_SEPARATE_SOLVE)
+COVARIANCE_STAGES = ("cov_count", "cov_clear", "cov_insert", "cov_starts", "cov_sort", "cov_query", "cov_solve")
 
 
 class SgmParams(C.Structure):
@@ -158,6 +163,8 @@ def load():
     L.sgm_radius_outlier_device.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.sgm_statistical_outlier.argtypes = [vp, vp, vp, vp, C.c_int64, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp]
     L.sgm_statistical_outlier_device.argtypes = [vp, vp, vp, vp, C.c_int64, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sgm_covariance_normals.argtypes = [vp, vp, vp, C.c_int64, C.c_float, i32, vp, vp, i32, vp, vp, vp, vp]
+    L.sgm_covariance_normals_device.argtypes = [vp, vp, vp, C.c_int64, C.c_float, i32, vp, vp, i32, vp, vp, vp, vp]
     L.sgm_synchronize.argtypes = [vp]
     L.sgm_get_stage_times.argtypes = [vp, C.POINTER(SgmStageTimes)]
     L.sgm_algorithmic_bytes.argtypes = [pp, i32, i32, i32]
@@ -182,7 +189,7 @@ def load():
     L.sgm_debug_wta_raw_bytes.restype = C.c_longlong
     L.sgm_debug_wta_select_n.argtypes = [i32, i32, vp, i32, vp]
     L.sgm_debug_wta_select_n.restype = i32
-    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS + VOXEL_EXPORTS + MESH_EXPORTS + NORMALS_EXPORTS + RADIUS_EXPORTS + STATISTICAL_EXPORTS:
+    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS + VOXEL_EXPORTS + MESH_EXPORTS + NORMALS_EXPORTS + RADIUS_EXPORTS + STATISTICAL_EXPORTS + COVARIANCE_EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("sgm_abi_version", "sgm_device_count"):
             fn.restype = i32

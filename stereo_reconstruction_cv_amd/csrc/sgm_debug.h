@@ -44,7 +44,10 @@ enum {
     SGM_DBG_RADIUS_TIGHT_TABLE = 1 << 24,   /* capacity = the smallest power of two >= the points in range (not twice them): the load can reach 1.0 */
     SGM_DBG_RADIUS_SOURCE_ORDER = 1 << 25,  /* k_radius_query over the points in source order instead of sorted by cell */
     /* sgm_statistical_outlier* (tools/statistical_times.py); SGM_DBG_RADIUS_TIGHT_TABLE acts on its table too; the same bits under all */
-    SGM_DBG_STAT_WIDE_LIST = 1 << 26        /* k_stat_query<64> whatever nb_neighbors is: the cost of the list's capacity apart from that of k */
+    SGM_DBG_STAT_WIDE_LIST = 1 << 26,       /* k_stat_query<64> whatever nb_neighbors is: the cost of the list's capacity apart from that of k */
+    /* sgm_covariance_normals* (tools/covariance_times.py); SGM_DBG_RADIUS_TIGHT_TABLE acts on its table too; the same bits under all */
+    SGM_DBG_COV_SEPARATE_SOLVE = 1 << 27,   /* steps 7 to 10 in a kernel of their own (k_cov_solve) over ten staged words per point instead of at the end of k_cov_query's lane */
+    SGM_DBG_COV_SELECT_ACCUM = 1 << 28      /* k_cov_query adds zeros for a candidate that is no neighbour instead of branching over the accumulation */
 };
 
 /* Plan readout: what normalise + make_plan decide for one compute of a frame of H x W pixels on an engine with these

@@ -33,6 +33,7 @@
 #include "kernels_voxel.h"
 #include "kernels_radius.h"
 #include "kernels_statistical.h"
+#include "kernels_covariance.h"
 #include "kernels_mesh.h"
 #include "kernels_normals.h"
 
@@ -269,6 +270,7 @@ struct Plan {
     BUF(vox_tab) BUF(vox_slot) BUF(vox_ctl) BUF(vox_cnt) /* sgm_voxel_downsample: the hash table (VoxSlot [capacity]), each point's slot (uint32 [n]), the call's control words, the host entry's staged counts (kernels_voxel.h); sgm_trim releases the first two by name */ \
     BUF(rad_tab) BUF(rad_sorted) BUF(rad_pt) BUF(rad_ctl) BUF(rad_keep) BUF(rad_cnt) BUF(rad_idx) /* sgm_radius_outlier: the hash table of cells (RadSlot [capacity]), the records sorted by cell (float4 [points in range]), each point's slot and rank (uint2 [n]), the call's control words, the keep bytes where the caller asks for none and the host entry's staged ones (uint8 [n]), its staged counts and indices (uint32 [n] each; kernels_radius.h); sgm_trim releases all but the control words by name */ \
     BUF(stat_mean) BUF(stat_sums)                /* sgm_statistical_outlier, beside the radius search's buffers it reuses: the host entry's staged means (float32 [n]) and the call's 64-bit sums m, A, B (kernels_statistical.h); sgm_trim releases the first by name */ \
+    BUF(cov_nrm) BUF(cov_curv) BUF(cov_mom) BUF(cov_ctl) /* sgm_covariance_normals, beside the radius search's buffers it reuses: the host entry's staged normals (float32 [n][3]) and curvatures (float32 [n]), the staged moments where the solve is a kernel of its own (int64 [points in range][10]) and the call's two counts (kernels_covariance.h); sgm_trim releases the first three by name */ \
     BUF(mesh_code) BUF(mesh_num) BUF(mesh_fcnt) BUF(mesh_vcnt) BUF(mesh_faces) /* sgm_mesh_grid: a code byte per quad (uint8 [H][W]), the pixel -> vertex number map (uint32 [H][W]), the blocks' numbers of faces and of vertices (uint32 [blocks + 1] each), the host entry's staged faces (kernels_mesh.h); sgm_trim releases the first two and the last by name */ \
     BUF(mesh_nrm)                                /* sgm_normals_grid, sgm_mesh_grid_normals: the host entries' staged normals (float32 [H][W][3]; kernels_normals.h); sgm_trim releases it by name */ \
     BUF(headroom)                                /* uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r */ \
@@ -2048,8 +2050,8 @@ int sgm_trim(sgm_engine *e)
     for (auto &slot : e->pin_io)
         for (HostBuf &b : slot) b.release();
     for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f, &e->vox_tab, &e->vox_slot, &e->mesh_code, &e->mesh_num, &e->mesh_faces, &e->mesh_nrm,
-                      &e->rad_tab, &e->rad_sorted, &e->rad_pt, &e->rad_keep, &e->rad_cnt, &e->rad_idx, &e->stat_mean})
-        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps, the staged normals, the radius search's table, records and staging and the staged means of the statistical one come back on the next call
+                      &e->rad_tab, &e->rad_sorted, &e->rad_pt, &e->rad_keep, &e->rad_cnt, &e->rad_idx, &e->stat_mean, &e->cov_nrm, &e->cov_curv, &e->cov_mom})
+        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps, the staged normals, the radius search's table, records and staging, the staged means of the statistical one and the staged normals, curvatures and moments of the covariance normals come back on the next call
     return check_chain(e);
 }
 
@@ -3718,6 +3720,137 @@ int sgm_statistical_outlier(sgm_engine *e, const float *xyz, const float *disp, 
     HIP_TRY(hipStreamSynchronize(e->stream));
     *n_kept = nk;
     if (out_stats) std::copy(stats, stats + 8, out_stats);
+    return SGM_OK;
+}
+
+// ---- covariance normals of a point list (include/sgm_hip_covariance.h, kernels_covariance.h) --------------------------------------
+static int cov_check_args(const sgm_engine *e, const void *xyz, int64_t n, float r, int k, const float *origin, const float *viewpoint,
+                          int orient)
+{
+    if (!e || !xyz) return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: null pointer");
+    if (n < 0) return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: n=%lld points", (long long)n);
+    const float r2 = r * r, v = r * 1.03125f;
+    if (!std::isfinite(r) || !(r > 0.0f) || !std::isnormal(r2) || !std::isfinite(1.0f / v) || !std::isfinite(32768.0f / r))
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: radius %g is not finite and positive with a finite normal square", (double)r);
+    if (k < COV_MIN_K || (int64_t)k > RAD_MAX_POINTS)
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: min_neighbors %d outside %d .. 2^24 - 1", k, COV_MIN_K);
+    if (!origin || !std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: the origin is null or not finite");
+    if (!viewpoint || !std::isfinite(viewpoint[0]) || !std::isfinite(viewpoint[1]) || !std::isfinite(viewpoint[2]))
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: the viewpoint is null or not finite");
+    if (orient != 0 && orient != 1) return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: orient %d is neither 0 nor 1", orient);
+    if (n > RAD_MAX_POINTS)
+        return set_err(SGM_ERR_UNSUPPORTED, "sgm_covariance_normals: %lld points, more than 2^24 - 1 (a source index shares a record with its point)", (long long)n);
+    return SGM_OK;
+}
+
+int sgm_covariance_normals_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, int64_t n, float radius, int min_neighbors,
+                                  const float origin[3], const float viewpoint[3], int orient, void *d_out_normals,
+                                  void *d_out_curvature, void *d_out_counts, uint64_t *out_stats)
+{
+    if (int rc = cov_check_args(e, d_xyz, n, radius, min_neighbors, origin, viewpoint, orient)) return rc;
+    if (n == 0) {
+        if (out_stats) std::fill(out_stats, out_stats + 4, (uint64_t)0);
+        return SGM_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const int m = (int)((n + 255) / 256);
+    int rc;
+    if ((rc = e->rad_ctl.ensure(RAD_CTL_WORDS * 4)) || (rc = e->cov_ctl.ensure(COV_CTL_WORDS * 4)) || (rc = e->rad_pt.ensure((size_t)n * 8)) ||
+        (rc = e->rad_keep.ensure((size_t)n)))
+        return rc;
+    if (e->profile) stage_reset(e);   // the stage record is the call's from here on
+    const float v = radius * 1.03125f;
+    const RadGrid G{1.0f / v, radius * radius, origin[0], origin[1], origin[2]};
+    const CovView V{32768.0f / radius, viewpoint[0], viewpoint[1], viewpoint[2], (uint32_t)min_neighbors, (uint32_t)orient};
+    const float *xyz = (const float *)d_xyz, *disp = (const float *)d_disp_f32;
+    float *normals = (float *)d_out_normals, *curv = (float *)d_out_curvature;
+    uint32_t *counts = (uint32_t *)d_out_counts;
+    uint32_t *ctl = (uint32_t *)e->cov_ctl.p;
+    hipStream_t st = e->stream;
+    static const char *const names[5] = {"cov_count", "cov_clear", "cov_insert", "cov_starts", "cov_sort"};
+    uint32_t n_in = 0, n_out = 0, cap = 0;
+    // (the keep bytes k_radius_sort zeroes for the points in no cell are nobody's here: they go to the engine's own)
+    if ((rc = radius_build_grid(e, xyz, disp, n, G, (uint8_t *)e->rad_keep.p, counts, names, &n_in, &n_out, &cap))) return rc;
+    if (n_in == 0) {   // nobody has a neighbour
+        if (normals) HIP_TRY(hipMemsetAsync(normals, 0, (size_t)n * 12, st));
+        if (curv) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)curv, (int)0xBF800000u, (size_t)n, st));   // -1.0f
+        if (counts) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n * 4, st));
+        if (out_stats) {
+            HIP_TRY(hipStreamSynchronize(st));
+            std::fill(out_stats, out_stats + 4, (uint64_t)0);
+            out_stats[1] = n_out;
+        }
+        return SGM_OK;
+    }
+    const bool separate = (e->debug & SGM_DBG_COV_SEPARATE_SOLVE) != 0, select = (e->debug & SGM_DBG_COV_SELECT_ACCUM) != 0;
+    if (separate && (rc = e->cov_mom.ensure((size_t)n_in * COV_WORDS * 8))) return rc;
+    const RadSlot *tab = (const RadSlot *)e->rad_tab.p;
+    const float4 *sorted = (const float4 *)e->rad_sorted.p;
+    long long *staged = (long long *)(separate ? e->cov_mom.p : nullptr);
+    // 6. per point the moments of its neighbours and (fused) the normal; the points in no cell get their zeros and -1 first
+    HIP_TRY(hipMemsetAsync(ctl, 0, COV_CTL_WORDS * 4, st));
+    stage_break(e);
+    if ((rc = stage_begin(e, "cov_query"))) return rc;
+    const bool fill = n_in < (uint64_t)n && (normals || curv);
+    if (fill) hipLaunchKernelGGL(k_cov_fill, dim3(m), dim3(256), 0, st, (const uint2 *)e->rad_pt.p, n, normals, curv);
+    const dim3 qgrid((n_in + 255) / 256);
+#define SGM_COV_QUERY(SEP, SEL) \
+    hipLaunchKernelGGL((k_cov_query<SEP, SEL>), qgrid, dim3(256), 0, st, sorted, n_in, G, tab, cap - 1, V, staged, normals, curv, counts, ctl)
+    if (separate && select) SGM_COV_QUERY(true, true);
+    else if (separate) SGM_COV_QUERY(true, false);
+    else if (select) SGM_COV_QUERY(false, true);
+    else SGM_COV_QUERY(false, false);
+#undef SGM_COV_QUERY
+    KCHECK();
+    if ((rc = stage_end(e, fill ? 2 : 1))) return rc;
+    if (separate) {   // 7. the solve as a kernel of its own
+        if ((rc = stage_begin(e, "cov_solve"))) return rc;
+        hipLaunchKernelGGL(k_cov_solve, qgrid, dim3(256), 0, st, sorted, n_in, V, (const long long *)staged, normals, curv, counts, ctl);
+        KCHECK();
+        if ((rc = stage_end(e, 1))) return rc;
+    }
+    if (!out_stats) return SGM_OK;
+    uint32_t h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0}, h_cov[COV_CTL_WORDS] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_ctl, e->rad_ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_cov, ctl, sizeof(h_cov), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_ctl[RAD_CTL_ERR])
+        return set_err(SGM_ERR_HIP, "sgm_covariance_normals: a point found no slot in a table of %u slots for %u points", cap, n_in);
+    const uint64_t s[4] = {n_in, n_out, h_cov[COV_CTL_NORMAL], h_cov[COV_CTL_DEGENERATE]};
+    std::copy(s, s + 4, out_stats);
+    return SGM_OK;
+}
+
+int sgm_covariance_normals(sgm_engine *e, const float *xyz, const float *disp, int64_t n, float radius, int min_neighbors,
+                           const float origin[3], const float viewpoint[3], int orient, float *out_normals, float *out_curvature,
+                           uint32_t *out_counts, uint64_t *out_stats)
+{
+    if (int rc = cov_check_args(e, xyz, n, radius, min_neighbors, origin, viewpoint, orient)) return rc;
+    if (n == 0) {
+        if (out_stats) std::fill(out_stats, out_stats + 4, (uint64_t)0);
+        return SGM_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = e->xyz.ensure((size_t)n * 12)) || (disp && (rc = e->f32.ensure((size_t)n * 4))) ||
+        (out_normals && (rc = e->cov_nrm.ensure((size_t)n * 12))) || (out_curvature && (rc = e->cov_curv.ensure((size_t)n * 4))) ||
+        (out_counts && (rc = e->rad_cnt.ensure((size_t)n * 4))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, e->stream));
+    if (disp) HIP_TRY(hipMemcpyAsync(e->f32.p, disp, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    uint64_t stats[4] = {0, 0, 0, 0};   // (always asked for: the host entry reports a full table whatever the caller wants)
+    if ((rc = sgm_covariance_normals_device(e, e->xyz.p, disp ? e->f32.p : nullptr, n, radius, min_neighbors, origin, viewpoint, orient,
+                                            out_normals ? e->cov_nrm.p : nullptr, out_curvature ? e->cov_curv.p : nullptr,
+                                            out_counts ? e->rad_cnt.p : nullptr, stats))) {
+        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
+        return rc;
+    }
+    if (out_normals) HIP_TRY(hipMemcpyAsync(out_normals, e->cov_nrm.p, (size_t)n * 12, hipMemcpyDeviceToHost, e->stream));
+    if (out_curvature) HIP_TRY(hipMemcpyAsync(out_curvature, e->cov_curv.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+    if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, e->rad_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (out_stats) std::copy(stats, stats + 4, out_stats);
     return SGM_OK;
 }
 

@@ -16,6 +16,9 @@
     estimate_normals(points_3D, disparity_map, max_diff, ...)              one unit normal per pixel of the organised cloud, and
     triangulate_points_with_normals(points_3D, colors, disparity_map, ...) the mesh with one per vertex: the area-weighted sum of the
                  triangles around it, on the GPU (include/sgm_hip_normals.h; NOT Open3D's estimate_normals / compute_vertex_normals)
+    estimate_normals_radius(points_3D, disparity_map, radius, ...)         one unit normal per point of a point LIST (voxel centroids,
+                 a cleaned list, a cloud read back): the plane fitted to the neighbours within radius, on the GPU
+                 (include/sgm_hip_covariance.h; NOT Open3D's estimate_normals)
     write_ply(path, points, colors, normals, triangles) / read_ply(path)   one PLY writer for a cloud or a mesh, with or without normals
 
 The compaction runs on the GPU (ordered, so the result equals numpy's `points_3D[mask]`); the
@@ -256,6 +259,125 @@ def remove_statistical_outlier(points_3D, colors, disparity_map, nb_neighbors, s
     if return_stats:
         out += (dict(zip(("in_range", "out_of_range", "dense", "sparse", "A", "B", "T"), (int(x) for x in st[:7]))),)
     return out
+
+
+COVARIANCE_MIN_NEIGHBORS = 2
+COVARIANCE_STATS = ("in_range", "out_of_range", "with_normal", "degenerate")
+
+
+def estimate_normals_radius(points_3D, disparity_map, radius, min_neighbors=3, origin=(0, 0, 0), viewpoint=(0, 0, 0), orient=True,
+                            confidence=None, min_confidence=0, return_curvature=False, return_counts=False, return_stats=False):
+    """Covariance (PCA) normals for a point LIST, on the GPU: per point the unit normal of the plane fitted to its OTHER points
+    within radius -- the eigenvector of the smallest eigenvalue of their covariance --, and with orient turned towards viewpoint.
+    A point with fewer than min_neighbors (>= 2) neighbours, or whose neighbours all sit on it, gets (0, 0, 0).  Where
+    estimate_normals needs the pixel grid, this needs points only: the centroids of voxel_down_sample, a list cleaned by
+    remove_radius_outlier or remove_statistical_outlier, a cloud from read_ply, two clouds concatenated.  The definition is
+    include/sgm_hip_covariance.h, our own, and the result is the same bits on every run: it is NOT Open3D's estimate_normals --
+    a point is not its own neighbour, points whose cell index (cells of edge radius * 1.03125 anchored at origin) leaves
+    -2^16 .. 2^16 - 1 get no normal, the neighbours' offsets are quantised to radius / 32768 and summed in integers, and the 3 x 3
+    eigenproblem is solved by six fixed Jacobi sweeps in binary64.  The radius should hold ten to a few tens of neighbours; the
+    work grows with every candidate in the 27 cells around a point.
+    points_3D (H, W, 3) with disparity_map (H, W) -- a point takes part iff X, Y, Z are finite and its disparity > 0, and with a
+    confidence map also confidence >= min_confidence, as in valid_points -- or an (N, 3) list with disparity_map=None (every
+    finite point takes part); numpy arrays, or HIP tensors (float32, on the GPU), which stay on the device.
+    Returns normals float32 of the shape of points_3D, or with any of the return_ flags a tuple (normals[, curvature][, counts]
+    [, stats]): curvature float32, the surface variation l_min / (l_0 + l_1 + l_2) in 0 .. 1/3 and -1 where there is no normal;
+    counts uint32 (int32 for tensors), the number of neighbours; both of the shape of disparity_map (of (N,) for a list); stats a
+    dict: in_range, out_of_range, with_normal, degenerate.
+
+    The chain this exists for:
+
+        centroids, colors = voxel_down_sample(points_3D, colors, disparity_map, voxel_size)
+        normals = estimate_normals_radius(centroids, None, radius=2 * voxel_size)
+        write_ply(path, centroids, colors, normals)
+    """
+    who = "estimate_normals_radius"
+    on_device = _cv._is_torch(points_3D)
+    if on_device:
+        pts, disp = _device_cloud(who, points_3D, disparity_map, confidence, min_confidence)
+        shape = tuple(pts.shape[:-1])
+        n = pts.numel() // 3
+    else:
+        pts, disp, _ = _outlier_cloud(who, points_3D, None, disparity_map, confidence, min_confidence)
+        shape = pts.shape[:-1]
+        n = pts.size // 3
+    with np.errstate(all="ignore"):
+        try:
+            r = np.float32(radius)
+            org = np.asarray(origin, np.float32)
+            view = np.asarray(viewpoint, np.float32)
+        except (TypeError, ValueError):
+            raise _cv.error(f"{who}: radius, origin and viewpoint must be numbers") from None
+        r2 = r * r
+        if (r.shape != () or not np.isfinite(r) or not r > 0 or not np.isfinite(r2) or r2 < np.finfo(np.float32).tiny
+                or not np.isfinite(np.float32(1.0) / (r * np.float32(1.03125))) or not np.isfinite(np.float32(32768.0) / r)):
+            raise _cv.error(f"{who}: radius={radius!r} is not a finite positive float32 with a finite normal square")
+    if org.shape != (3,) or not np.isfinite(org).all():
+        raise _cv.error(f"{who}: origin={origin!r} is not three finite numbers")
+    if view.shape != (3,) or not np.isfinite(view).all():
+        raise _cv.error(f"{who}: viewpoint={viewpoint!r} is not three finite numbers")
+    if (isinstance(min_neighbors, bool) or not isinstance(min_neighbors, (int, np.integer))
+            or not COVARIANCE_MIN_NEIGHBORS <= int(min_neighbors) <= RADIUS_MAX_POINTS):
+        raise _cv.error(f"{who}: min_neighbors={min_neighbors!r} is not an integer in {COVARIANCE_MIN_NEIGHBORS} .. {RADIUS_MAX_POINTS}")
+    if not isinstance(orient, (bool, np.bool_)):
+        raise _cv.error(f"{who}: orient={orient!r} is not a bool")
+    if n > RADIUS_MAX_POINTS:
+        raise _cv.error(f"{who}: {n} points, more than {RADIUS_MAX_POINTS} (include/sgm_hip_covariance.h)")
+    if on_device:
+        import torch
+        nrm = torch.zeros(shape + (3,), dtype=torch.float32, device=pts.device)
+        curv = torch.full(shape, -1.0, dtype=torch.float32, device=pts.device) if return_curvature else None
+        cnt = torch.zeros(shape, dtype=torch.int32, device=pts.device) if return_counts else None     # (the bits of uint32 counts < 2^24)
+        st = np.zeros(4, np.uint64)
+        if n:
+            e = _cv.get_engine(_cv._DEFAULT, pts.device.index)
+            torch.cuda.synchronize(pts.device)      # the inputs were made on torch's stream, the call runs on the engine's
+            ptr = lambda t: None if t is None else t.data_ptr()
+            st = e.covariance_normals_device(pts.data_ptr(), ptr(disp), n, float(r), int(min_neighbors), org, view, bool(orient),
+                                             nrm.data_ptr(), ptr(curv), ptr(cnt))
+    elif n == 0:      # nothing to send to the device
+        nrm, curv, cnt, st = (np.zeros(shape + (3,), np.float32), np.zeros(shape, np.float32), np.zeros(shape, np.uint32),
+                              np.zeros(4, np.uint64))
+    else:
+        nrm, curv, cnt, st = _cv.get_engine(_cv._DEFAULT).covariance_normals_host(
+            pts, disp, float(r), int(min_neighbors), org, view, bool(orient), bool(return_curvature), bool(return_counts))
+        nrm = nrm.reshape(shape + (3,))
+        curv = None if curv is None else curv.reshape(shape)
+        cnt = None if cnt is None else cnt.reshape(shape)
+    out = (nrm,)
+    if return_curvature:
+        out += (curv,)
+    if return_counts:
+        out += (cnt,)
+    if return_stats:
+        out += (dict(zip(COVARIANCE_STATS, (int(x) for x in st))),)
+    return out if len(out) > 1 else nrm
+
+
+def _device_cloud(who, points_3D, disparity_map, confidence, min_confidence):
+    """what estimate_normals_radius accepts as a cloud on the device: (points, disparities or None) as contiguous float32 HIP
+    tensors, the confidence mask applied to a copy of the disparities"""
+    import torch
+    pts = points_3D
+    if not pts.is_cuda or pts.dtype != torch.float32:
+        raise _cv.error(f"{who}: a tensor points_3D must be float32 and on the GPU")
+    if disparity_map is None:
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise _cv.error(f"{who}: without a disparity_map points_3D must be an (N, 3) list")
+        if confidence is not None:
+            raise _cv.error(f"{who}: a confidence map needs a disparity_map")
+        return pts.contiguous(), None
+    disp = disparity_map
+    if not _cv._is_torch(disp) or disp.device != pts.device or disp.dtype != torch.float32:
+        raise _cv.error(f"{who}: with a tensor points_3D the disparity_map must be a float32 tensor on the same GPU")
+    if pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[:2] != disp.shape:
+        raise _cv.error(f"{who}: points_3D must be (H, W, 3) and disparity_map (H, W)")
+    if confidence is not None:
+        conf = confidence if _cv._is_torch(confidence) else torch.from_numpy(np.ascontiguousarray(confidence))
+        if tuple(conf.shape) != tuple(disp.shape):
+            raise _cv.error(f"{who}: confidence must have the shape of disparity_map")
+        disp = torch.where(conf.to(pts.device) >= min_confidence, disp, torch.zeros_like(disp))
+    return pts.contiguous(), disp.contiguous()
 
 
 MESH_MAX_PIXELS = 1 << 26

@@ -337,6 +337,42 @@ class Engine:
                                                       C.byref(nk), stats.ctypes.data))
         return int(nk.value), stats
 
+    # -- covariance normals of a point list (include/sgm_hip_covariance.h) --
+    def covariance_normals_host(self, xyz: np.ndarray, disp: np.ndarray | None, radius: float, min_neighbors: int = 3,
+                                origin=(0.0, 0.0, 0.0), viewpoint=(0.0, 0.0, 0.0), orient: bool = True,
+                                return_curvature: bool = False, return_counts: bool = False):
+        """sgm_covariance_normals: float32 points (n, 3) or (H, W, 3), float32 disparities (n) or (H, W) or None.  Returns (normals
+        float32 (n, 3), curvature float32 (n) or None, counts uint32 (n) or None, stats uint64 (4)), all at the source index: a
+        point without a normal has (0, 0, 0) and -1; stats is points in range, valid points out of range, points with a normal,
+        degenerate points."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = xyz.shape[0]
+        disp = None if disp is None else np.ascontiguousarray(disp, np.float32).reshape(-1)
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        view = np.ascontiguousarray(viewpoint, np.float32).reshape(3)
+        nrm = np.zeros((n, 3), np.float32)
+        curv = np.full(n, -1, np.float32) if return_curvature else None
+        cnt = np.zeros(n, np.uint32) if return_counts else None
+        stats = np.zeros(4, np.uint64)
+        at = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.sgm_covariance_normals(self._h, xyz.ctypes.data, at(disp), n, float(radius), int(min_neighbors), org.ctypes.data,
+                                              view.ctypes.data, int(bool(orient)), nrm.ctypes.data, at(curv), at(cnt), stats.ctypes.data))
+        return nrm, curv, cnt, stats
+
+    def covariance_normals_device(self, d_xyz: int, d_dispf: int | None, n: int, radius: float, min_neighbors: int = 3,
+                                  origin=(0.0, 0.0, 0.0), viewpoint=(0.0, 0.0, 0.0), orient: bool = True, d_normals: int | None = None,
+                                  d_curvature: int | None = None, d_counts: int | None = None, return_stats: bool = True):
+        """sgm_covariance_normals_device: device addresses; d_normals (float32) has n rows of 3, d_curvature (float32) and d_counts
+        (uint32) n entries.  Returns stats uint64 (4) after synchronising the engine's stream, or with return_stats=False None
+        with the outputs complete once the stream has run (synchronize())."""
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        view = np.ascontiguousarray(viewpoint, np.float32).reshape(3)
+        stats = np.zeros(4, np.uint64) if return_stats else None
+        _check(self._L.sgm_covariance_normals_device(self._h, d_xyz, d_dispf, int(n), float(radius), int(min_neighbors), org.ctypes.data,
+                                                     view.ctypes.data, int(bool(orient)), d_normals, d_curvature, d_counts,
+                                                     None if stats is None else stats.ctypes.data))
+        return stats
+
     # -- triangle mesh from the organised cloud (include/sgm_hip_mesh.h) --
     def mesh_grid_host(self, xyz: np.ndarray, disp: np.ndarray, colors: np.ndarray | None, max_diff: float = 1.0):
         """sgm_mesh_grid: float32 points (H, W, 3), float32 disparities (H, W), uint8 colours (H, W, 3) or None.  Returns
