@@ -58,7 +58,8 @@ extern "C" {
                              * consistency confidence of sgm_hip_lrc.h; the voxel-grid downsampling of sgm_hip_voxel.h; the grid
                              * triangulation of sgm_hip_mesh.h; its vertex normals and the normal image of sgm_hip_normals.h; the
                              * radius outlier removal of sgm_hip_radius.h; the statistical outlier removal of
-                             * sgm_hip_statistical.h; the covariance normals of sgm_hip_covariance.h */
+                             * sgm_hip_statistical.h; the covariance normals of sgm_hip_covariance.h; the density clustering of
+                             * sgm_hip_dbscan.h */
 
 typedef enum {
     SGM_OK = 0,
@@ -327,4 +328,6 @@ int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_r
 #include "sgm_hip_statistical.h"
 /* covariance normals for a point list: the plane fitted to the neighbours within a radius, on the same grid of cells */
 #include "sgm_hip_covariance.h"
+/* density clustering of the cloud: core points, their connected components and the border points, on the same grid of cells */
+#include "sgm_hip_dbscan.h"
 #endif

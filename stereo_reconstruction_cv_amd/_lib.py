@@ -28,6 +28,7 @@ SGM_DBG_VOXEL_TIGHT_TABLE, SGM_DBG_VOXEL_OTHER_REDUCTION = 1 << 22, 1 << 23   # 
 SGM_DBG_RADIUS_TIGHT_TABLE, SGM_DBG_RADIUS_SOURCE_ORDER = 1 << 24, 1 << 25   # csrc/sgm_debug.h: the two A/B bits of sgm_radius_outlier
 SGM_DBG_STAT_WIDE_LIST = 1 << 26   # csrc/sgm_debug.h: the A/B bit of sgm_statistical_outlier (the 64-word list at every nb_neighbors)
 SGM_DBG_COV_SEPARATE_SOLVE, SGM_DBG_COV_SELECT_ACCUM = 1 << 27, 1 << 28   # csrc/sgm_debug.h: the two A/B bits of sgm_covariance_normals
+SGM_DBG_DBSCAN_GATHER_CORE = 1 << 29   # csrc/sgm_debug.h: the A/B bit of sgm_cluster_dbscan (the core bit gathered by source index)
 SGM_MAX_STAGES = 32
 
 # every symbol include/sgm_hip.h declares (checked by tests/test_abi.py)
@@ -65,6 +66,11 @@ STATISTICAL_EXPORTS = ("sgm_statistical_outlier", "sgm_statistical_outlier_devic
 COVARIANCE_EXPORTS = ("sgm_covariance_normals", "sgm_covariance_normals_device")
 # the stage record of one sgm_covariance_normals call with SGM_OPT_PROFILE (cov_solve only with SGM_DBG_COV_SEPARATE_SOLVE)
 COVARIANCE_STAGES = ("cov_count", "cov_clear", "cov_insert", "cov_starts", "cov_sort", "cov_query", "cov_solve")
+# include/sgm_hip_dbscan.h (likewise): density clustering of the point cloud
+DBSCAN_EXPORTS = ("sgm_cluster_dbscan", "sgm_cluster_dbscan_device")
+# the stage record of one sgm_cluster_dbscan call with SGM_OPT_PROFILE
+DBSCAN_STAGES = ("dbscan_count", "dbscan_clear", "dbscan_insert", "dbscan_starts", "dbscan_sort", "dbscan_core", "dbscan_link",
+                 "dbscan_number", "dbscan_label")
 
 
 class SgmParams(C.Structure):
@@ -165,6 +171,8 @@ def load():
     L.sgm_statistical_outlier_device.argtypes = [vp, vp, vp, vp, C.c_int64, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp]
     L.sgm_covariance_normals.argtypes = [vp, vp, vp, C.c_int64, C.c_float, i32, vp, vp, i32, vp, vp, vp, vp]
     L.sgm_covariance_normals_device.argtypes = [vp, vp, vp, C.c_int64, C.c_float, i32, vp, vp, i32, vp, vp, vp, vp]
+    L.sgm_cluster_dbscan.argtypes = [vp, vp, vp, C.c_int64, C.c_float, i32, vp, vp, vp, vp, vp, vp]
+    L.sgm_cluster_dbscan_device.argtypes = [vp, vp, vp, C.c_int64, C.c_float, i32, vp, vp, vp, vp, vp, vp]
     L.sgm_synchronize.argtypes = [vp]
     L.sgm_get_stage_times.argtypes = [vp, C.POINTER(SgmStageTimes)]
     L.sgm_algorithmic_bytes.argtypes = [pp, i32, i32, i32]
@@ -189,7 +197,7 @@ def load():
     L.sgm_debug_wta_raw_bytes.restype = C.c_longlong
     L.sgm_debug_wta_select_n.argtypes = [i32, i32, vp, i32, vp]
     L.sgm_debug_wta_select_n.restype = i32
-    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS + VOXEL_EXPORTS + MESH_EXPORTS + NORMALS_EXPORTS + RADIUS_EXPORTS + STATISTICAL_EXPORTS + COVARIANCE_EXPORTS:
+    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS + VOXEL_EXPORTS + MESH_EXPORTS + NORMALS_EXPORTS + RADIUS_EXPORTS + STATISTICAL_EXPORTS + COVARIANCE_EXPORTS + DBSCAN_EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("sgm_abi_version", "sgm_device_count"):
             fn.restype = i32

@@ -34,6 +34,7 @@
 #include "kernels_radius.h"
 #include "kernels_statistical.h"
 #include "kernels_covariance.h"
+#include "kernels_dbscan.h"
 #include "kernels_mesh.h"
 #include "kernels_normals.h"
 
@@ -271,6 +272,7 @@ struct Plan {
     BUF(rad_tab) BUF(rad_sorted) BUF(rad_pt) BUF(rad_ctl) BUF(rad_keep) BUF(rad_cnt) BUF(rad_idx) /* sgm_radius_outlier: the hash table of cells (RadSlot [capacity]), the records sorted by cell (float4 [points in range]), each point's slot and rank (uint2 [n]), the call's control words, the keep bytes where the caller asks for none and the host entry's staged ones (uint8 [n]), its staged counts and indices (uint32 [n] each; kernels_radius.h); sgm_trim releases all but the control words by name */ \
     BUF(stat_mean) BUF(stat_sums)                /* sgm_statistical_outlier, beside the radius search's buffers it reuses: the host entry's staged means (float32 [n]) and the call's 64-bit sums m, A, B (kernels_statistical.h); sgm_trim releases the first by name */ \
     BUF(cov_nrm) BUF(cov_curv) BUF(cov_mom) BUF(cov_ctl) /* sgm_covariance_normals, beside the radius search's buffers it reuses: the host entry's staged normals (float32 [n][3]) and curvatures (float32 [n]), the staged moments where the solve is a kernel of its own (int64 [points in range][10]) and the call's two counts (kernels_covariance.h); sgm_trim releases the first three by name */ \
+    BUF(db_parent) BUF(db_near) BUF(db_rank) BUF(db_ctl) BUF(db_lab) BUF(db_sizes) /* sgm_cluster_dbscan, beside the radius search's buffers it reuses: per point the union-find link (int32 [n]), the nearest core point (uint32 [n]) and the root's rank (uint32 [n]), the call's three counts, and the host entry's staged labels (int32 [n]) and sizes (uint32 [n]; kernels_dbscan.h); sgm_trim releases all but the counts by name */ \
     BUF(mesh_code) BUF(mesh_num) BUF(mesh_fcnt) BUF(mesh_vcnt) BUF(mesh_faces) /* sgm_mesh_grid: a code byte per quad (uint8 [H][W]), the pixel -> vertex number map (uint32 [H][W]), the blocks' numbers of faces and of vertices (uint32 [blocks + 1] each), the host entry's staged faces (kernels_mesh.h); sgm_trim releases the first two and the last by name */ \
     BUF(mesh_nrm)                                /* sgm_normals_grid, sgm_mesh_grid_normals: the host entries' staged normals (float32 [H][W][3]; kernels_normals.h); sgm_trim releases it by name */ \
     BUF(headroom)                                /* uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r */ \
@@ -2050,8 +2052,9 @@ int sgm_trim(sgm_engine *e)
     for (auto &slot : e->pin_io)
         for (HostBuf &b : slot) b.release();
     for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f, &e->vox_tab, &e->vox_slot, &e->mesh_code, &e->mesh_num, &e->mesh_faces, &e->mesh_nrm,
-                      &e->rad_tab, &e->rad_sorted, &e->rad_pt, &e->rad_keep, &e->rad_cnt, &e->rad_idx, &e->stat_mean, &e->cov_nrm, &e->cov_curv, &e->cov_mom})
-        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps, the staged normals, the radius search's table, records and staging, the staged means of the statistical one and the staged normals, curvatures and moments of the covariance normals come back on the next call
+                      &e->rad_tab, &e->rad_sorted, &e->rad_pt, &e->rad_keep, &e->rad_cnt, &e->rad_idx, &e->stat_mean, &e->cov_nrm, &e->cov_curv, &e->cov_mom,
+                      &e->db_parent, &e->db_near, &e->db_rank, &e->db_lab, &e->db_sizes})
+        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps, the staged normals, the radius search's table, records and staging, the staged means of the statistical one and the staged normals, curvatures and moments of the covariance normals and the links, ranks and staging of the clustering come back on the next call
     return check_chain(e);
 }
 
@@ -3851,6 +3854,145 @@ int sgm_covariance_normals(sgm_engine *e, const float *xyz, const float *disp, i
     if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, e->rad_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (out_stats) std::copy(stats, stats + 4, out_stats);
+    return SGM_OK;
+}
+
+// ---- density clustering of the point cloud (include/sgm_hip_dbscan.h, kernels_dbscan.h) -------------------------------------------
+static int dbscan_check_args(const sgm_engine *e, const void *xyz, int64_t n, float r, int k, const float *origin, const int64_t *n_clusters)
+{
+    if (!e || !xyz || !n_clusters) return set_err(SGM_ERR_INVALID_ARG, "sgm_cluster_dbscan: null pointer");
+    if (n < 0) return set_err(SGM_ERR_INVALID_ARG, "sgm_cluster_dbscan: n=%lld points", (long long)n);
+    const float r2 = r * r, v = r * 1.03125f;
+    if (!std::isfinite(r) || !(r > 0.0f) || !std::isnormal(r2) || !std::isfinite(1.0f / v))
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_cluster_dbscan: eps %g is not finite and positive with a finite normal square", (double)r);
+    if (k < 1 || (int64_t)k > RAD_MAX_POINTS) return set_err(SGM_ERR_INVALID_ARG, "sgm_cluster_dbscan: min_points %d outside 1 .. 2^24 - 1", k);
+    if (!origin || !std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+        return set_err(SGM_ERR_INVALID_ARG, "sgm_cluster_dbscan: the origin is null or not finite");
+    if (n > RAD_MAX_POINTS)
+        return set_err(SGM_ERR_UNSUPPORTED, "sgm_cluster_dbscan: %lld points, more than 2^24 - 1 (a source index shares a record with its point)", (long long)n);
+    return SGM_OK;
+}
+
+int sgm_cluster_dbscan_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, int64_t n, float eps, int min_points,
+                              const float origin[3], void *d_out_labels, void *d_out_core, void *d_out_sizes, uint64_t *out_stats,
+                              int64_t *n_clusters)
+{
+    if (int rc = dbscan_check_args(e, d_xyz, n, eps, min_points, origin, n_clusters)) return rc;
+    if (n == 0) {
+        *n_clusters = 0;
+        if (out_stats) std::fill(out_stats, out_stats + 6, (uint64_t)0);
+        return SGM_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const int m = (int)((n + 255) / 256);
+    int rc;
+    if ((rc = e->rad_ctl.ensure(RAD_CTL_WORDS * 4)) || (rc = e->db_ctl.ensure(DB_CTL_WORDS * 4)) || (rc = e->rad_pt.ensure((size_t)n * 8)) ||
+        (rc = e->ccount.ensure((size_t)(m + 1) * 4)) || (!d_out_core && (rc = e->rad_keep.ensure((size_t)n))) ||
+        (rc = e->db_parent.ensure((size_t)n * 4)) || (rc = e->db_near.ensure((size_t)n * 4)) || (rc = e->db_rank.ensure((size_t)n * 4)))
+        return rc;
+    if (e->profile) stage_reset(e);   // the stage record is the call's from here on
+    const float v = eps * 1.03125f;
+    const RadGrid G{1.0f / v, eps * eps, origin[0], origin[1], origin[2]};
+    const float *xyz = (const float *)d_xyz, *disp = (const float *)d_disp_f32;
+    uint8_t *core = (uint8_t *)(d_out_core ? d_out_core : e->rad_keep.p);
+    int *labels = (int *)d_out_labels;
+    uint32_t *sizes = (uint32_t *)d_out_sizes;
+    hipStream_t st = e->stream;
+    static const char *const names[5] = {"dbscan_count", "dbscan_clear", "dbscan_insert", "dbscan_starts", "dbscan_sort"};
+    uint32_t n_in = 0, n_out = 0, cap = 0;
+    if ((rc = radius_build_grid(e, xyz, disp, n, G, core, nullptr, names, &n_in, &n_out, &cap))) return rc;
+    if (n_in == 0) {   // nobody has a neighbour: everything is noise
+        if (labels) HIP_TRY(hipMemsetAsync(labels, 0xFF, (size_t)n * 4, st));   // -1
+        if (d_out_core) HIP_TRY(hipMemsetAsync(d_out_core, 0, (size_t)n, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *n_clusters = 0;
+        if (out_stats) {
+            std::fill(out_stats, out_stats + 6, (uint64_t)0);
+            out_stats[1] = n_out;
+        }
+        return SGM_OK;
+    }
+    const RadSlot *tab = (const RadSlot *)e->rad_tab.p;
+    float4 *sorted = (float4 *)e->rad_sorted.p;
+    const uint2 *slot_rank = (const uint2 *)e->rad_pt.p;
+    int *parent = (int *)e->db_parent.p;
+    uint32_t *nearest = (uint32_t *)e->db_near.p, *rank = (uint32_t *)e->db_rank.p, *ctl = (uint32_t *)e->db_ctl.p, *cnt = (uint32_t *)e->ccount.p;
+    const bool gather = (e->debug & SGM_DBG_DBSCAN_GATHER_CORE) != 0;
+    const dim3 qgrid((n_in + 255) / 256);
+    // 5. the core points: the radius filter's count, cut short at min_points; then the core bit beside the sorted records and the
+    // links set to identity
+    HIP_TRY(hipMemsetAsync(ctl, 0, DB_CTL_WORDS * 4, st));
+    stage_break(e);
+    if ((rc = stage_begin(e, "dbscan_core"))) return rc;
+    hipLaunchKernelGGL(k_radius_query<true>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, xyz, slot_rank, n, G, tab, cap - 1,
+                       (uint32_t)min_points, (uint32_t)min_points, core, (uint32_t *)nullptr);
+    if (gather) hipLaunchKernelGGL(k_dbscan_mark<false>, qgrid, dim3(256), 0, st, sorted, n_in, (const uint8_t *)core, parent, nearest);
+    else hipLaunchKernelGGL(k_dbscan_mark<true>, qgrid, dim3(256), 0, st, sorted, n_in, (const uint8_t *)core, parent, nearest);
+    KCHECK();
+    if ((rc = stage_end(e, 2))) return rc;
+    // 6, 7. the links between core points and each other point's nearest core point
+    if ((rc = stage_begin(e, "dbscan_link"))) return rc;
+    if (gather) hipLaunchKernelGGL(k_dbscan_link<true>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, G, tab, cap - 1, (const uint8_t *)core, parent, nearest);
+    else hipLaunchKernelGGL(k_dbscan_link<false>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, G, tab, cap - 1, (const uint8_t *)core, parent, nearest);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    // 9. the roots in source order are the clusters in the order of their numbers
+    if ((rc = stage_begin(e, "dbscan_number"))) return rc;
+    hipLaunchKernelGGL(k_dbscan_roots, dim3(m), dim3(256), 0, st, (const uint8_t *)core, (const int *)parent, n, cnt);
+    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
+    hipLaunchKernelGGL(k_dbscan_rank, dim3(m), dim3(256), 0, st, (const uint8_t *)core, (const int *)parent, n, (const uint32_t *)cnt, m, rank, sizes);
+    KCHECK();
+    if ((rc = stage_end(e, 3))) return rc;
+    // 8, 10. labels, sizes, statistics
+    if ((rc = stage_begin(e, "dbscan_label"))) return rc;
+    hipLaunchKernelGGL(k_dbscan_label, dim3(m), dim3(256), 0, st, slot_rank, (const uint8_t *)core, parent, (const uint32_t *)nearest,
+                       (const uint32_t *)rank, n, labels, sizes, ctl);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    uint32_t h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0}, h_db[DB_CTL_WORDS] = {0, 0, 0, 0}, total = 0;
+    HIP_TRY(hipMemcpyAsync(h_ctl, e->rad_ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_db, ctl, sizeof(h_db), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&total, cnt + m, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_ctl[RAD_CTL_ERR])
+        return set_err(SGM_ERR_HIP, "sgm_cluster_dbscan: a point found no slot in a table of %u slots for %u points", cap, n_in);
+    *n_clusters = (int64_t)total;
+    if (out_stats) {
+        const uint64_t s[6] = {n_in, n_out, h_db[DB_CTL_CORE], h_db[DB_CTL_BORDER], h_db[DB_CTL_NOISE], total};
+        std::copy(s, s + 6, out_stats);
+    }
+    return SGM_OK;
+}
+
+int sgm_cluster_dbscan(sgm_engine *e, const float *xyz, const float *disp, int64_t n, float eps, int min_points, const float origin[3],
+                       int32_t *out_labels, uint8_t *out_core, uint32_t *out_sizes, uint64_t *out_stats, int64_t *n_clusters)
+{
+    if (int rc = dbscan_check_args(e, xyz, n, eps, min_points, origin, n_clusters)) return rc;
+    if (n == 0) {
+        *n_clusters = 0;
+        if (out_stats) std::fill(out_stats, out_stats + 6, (uint64_t)0);
+        return SGM_OK;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = e->xyz.ensure((size_t)n * 12)) || (disp && (rc = e->f32.ensure((size_t)n * 4))) || (rc = e->rad_keep.ensure((size_t)n)) ||
+        (out_labels && (rc = e->db_lab.ensure((size_t)n * 4))) || (out_sizes && (rc = e->db_sizes.ensure((size_t)n * 4))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, e->stream));
+    if (disp) HIP_TRY(hipMemcpyAsync(e->f32.p, disp, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    int64_t nc = 0;
+    uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
+    if ((rc = sgm_cluster_dbscan_device(e, e->xyz.p, disp ? e->f32.p : nullptr, n, eps, min_points, origin, out_labels ? e->db_lab.p : nullptr,
+                                        e->rad_keep.p, out_sizes ? e->db_sizes.p : nullptr, stats, &nc))) {
+        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
+        return rc;
+    }
+    if (out_labels) HIP_TRY(hipMemcpyAsync(out_labels, e->db_lab.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+    if (out_core) HIP_TRY(hipMemcpyAsync(out_core, e->rad_keep.p, (size_t)n, hipMemcpyDeviceToHost, e->stream));
+    if (out_sizes && nc > 0) HIP_TRY(hipMemcpyAsync(out_sizes, e->db_sizes.p, (size_t)nc * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    *n_clusters = nc;
+    if (out_stats) std::copy(stats, stats + 6, out_stats);
     return SGM_OK;
 }
 

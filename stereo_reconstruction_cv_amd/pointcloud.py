@@ -19,6 +19,9 @@
     estimate_normals_radius(points_3D, disparity_map, radius, ...)         one unit normal per point of a point LIST (voxel centroids,
                  a cleaned list, a cloud read back): the plane fitted to the neighbours within radius, on the GPU
                  (include/sgm_hip_covariance.h; NOT Open3D's estimate_normals)
+    cluster_dbscan(points_3D, disparity_map, eps, min_points, ...)         the cloud split into the objects it holds: a cluster number
+                 per point or -1 for noise, on the GPU (include/sgm_hip_dbscan.h; NOT Open3D's cluster_dbscan), and
+    largest_clusters(labels, sizes, count, min_size)                       the mask of the largest of them, usable as a confidence map
     write_ply(path, points, colors, normals, triangles) / read_ply(path)   one PLY writer for a cloud or a mesh, with or without normals
 
 The compaction runs on the GPU (ordered, so the result equals numpy's `points_3D[mask]`); the
@@ -378,6 +381,131 @@ def _device_cloud(who, points_3D, disparity_map, confidence, min_confidence):
             raise _cv.error(f"{who}: confidence must have the shape of disparity_map")
         disp = torch.where(conf.to(pts.device) >= min_confidence, disp, torch.zeros_like(disp))
     return pts.contiguous(), disp.contiguous()
+
+
+DBSCAN_STATS = ("in_range", "out_of_range", "core", "border", "noise", "clusters")
+
+
+def cluster_dbscan(points_3D, disparity_map, eps, min_points, origin=(0, 0, 0), confidence=None, min_confidence=0, return_core=False,
+                   return_sizes=False, return_stats=False):
+    """Density clustering of the cloud, on the GPU: per point the number of the cluster it belongs to, or -1 for noise.  A point
+    with at least min_points OTHER points within eps is a core point; core points within eps of each other are one cluster; a
+    point that is not core but has a core point within eps is a border point and joins the cluster of its nearest core point (ties
+    in the binary32 squared distance go to the lowest index); everything else is noise.  The clusters are numbered 0, 1, ... by
+    the smallest index among their core points.  The definition is include/sgm_hip_dbscan.h, our own, and the result is the same
+    bits on every run and does not depend on the order of the points beyond the numbering: it is NOT Open3D's cluster_dbscan
+    (nor scikit-learn's DBSCAN) -- a point does not count itself, so Open3D's min_points is ours plus one; points whose cell index
+    (cells of edge eps * 1.03125 anchored at origin) leaves -2^16 .. 2^16 - 1 are noise; and a border point goes to its nearest
+    core point, not to whichever cluster reaches it first.  The work grows with every candidate in the 27 cells around a point: thin
+    the cloud first and cluster at about twice the voxel size.
+    points_3D (H, W, 3) with disparity_map (H, W) -- a point takes part iff X, Y, Z are finite and its disparity > 0, and with a
+    confidence map also confidence >= min_confidence, as in valid_points -- or an (N, 3) list with disparity_map=None (every
+    finite point takes part); numpy arrays, or HIP tensors (float32, on the GPU), which stay on the device.
+    Returns labels int32 of the shape of disparity_map (of (N,) for a list), or with any of the return_ flags a tuple (labels[,
+    core][, sizes][, stats]): core uint8 of the same shape, 1 for a core point; sizes uint32 (int32 for tensors) (clusters,), the
+    core and border points of each cluster; stats a dict: in_range, out_of_range, core, border, noise (in range), clusters.
+
+    The chain this exists for:
+
+        centroids, colors = voxel_down_sample(points_3D, colors, disparity_map, voxel_size)
+        labels, sizes = cluster_dbscan(centroids, None, eps=2 * voxel_size, min_points=4, return_sizes=True)
+        mask = largest_clusters(labels, sizes)
+        statue, statue_colors = centroids[mask > 0], colors[mask > 0]
+
+    In short voxel_down_sample -> cluster_dbscan -> largest_clusters -> valid_points: on the organised cloud itself the labels
+    of cluster_dbscan(points_3D, disparity_map, eps, min_points) have the shape of the disparity map, and the mask goes into
+    valid_points(points_3D, colors, disparity_map, confidence=mask, min_confidence=1).
+    """
+    who = "cluster_dbscan"
+    on_device = _cv._is_torch(points_3D)
+    if on_device:
+        pts, disp = _device_cloud(who, points_3D, disparity_map, confidence, min_confidence)
+        shape = tuple(pts.shape[:-1])
+        n = pts.numel() // 3
+    else:
+        pts, disp, _ = _outlier_cloud(who, points_3D, None, disparity_map, confidence, min_confidence)
+        shape = pts.shape[:-1]
+        n = pts.size // 3
+    with np.errstate(all="ignore"):
+        try:
+            r = np.float32(eps)
+            org = np.asarray(origin, np.float32)
+        except (TypeError, ValueError):
+            raise _cv.error(f"{who}: eps and origin must be numbers") from None
+        r2 = r * r
+        if (r.shape != () or not np.isfinite(r) or not r > 0 or not np.isfinite(r2) or r2 < np.finfo(np.float32).tiny
+                or not np.isfinite(np.float32(1.0) / (r * np.float32(1.03125)))):
+            raise _cv.error(f"{who}: eps={eps!r} is not a finite positive float32 with a finite normal square")
+    if org.shape != (3,) or not np.isfinite(org).all():
+        raise _cv.error(f"{who}: origin={origin!r} is not three finite numbers")
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= int(min_points) <= RADIUS_MAX_POINTS:
+        raise _cv.error(f"{who}: min_points={min_points!r} is not an integer in 1 .. {RADIUS_MAX_POINTS}")
+    if n > RADIUS_MAX_POINTS:
+        raise _cv.error(f"{who}: {n} points, more than {RADIUS_MAX_POINTS} (include/sgm_hip_dbscan.h)")
+    if on_device:
+        import torch
+        labels = torch.full(shape, -1, dtype=torch.int32, device=pts.device)
+        core = torch.zeros(shape, dtype=torch.uint8, device=pts.device) if return_core else None
+        sizes = torch.zeros(n, dtype=torch.int32, device=pts.device) if return_sizes else None      # (the bits of uint32 sizes < 2^24)
+        nc, st = 0, np.zeros(6, np.uint64)
+        if n:
+            e = _cv.get_engine(_cv._DEFAULT, pts.device.index)
+            torch.cuda.synchronize(pts.device)      # the inputs were made on torch's stream, the call runs on the engine's
+            ptr = lambda t: None if t is None else t.data_ptr()
+            nc, st = e.cluster_dbscan_device(pts.data_ptr(), ptr(disp), n, float(r), int(min_points), org, labels.data_ptr(), ptr(core),
+                                             ptr(sizes))
+        sizes = None if sizes is None else sizes[:nc].clone()
+    elif n == 0:      # nothing to send to the device
+        labels, core, sizes, st = np.zeros(shape, np.int32), np.zeros(shape, np.uint8), np.zeros(0, np.uint32), np.zeros(6, np.uint64)
+    else:
+        labels, core, sizes, st = _cv.get_engine(_cv._DEFAULT).cluster_dbscan_host(pts, disp, float(r), int(min_points), org,
+                                                                                   bool(return_core), bool(return_sizes))
+        labels = labels.reshape(shape)
+        core = None if core is None else core.reshape(shape)
+    out = (labels,)
+    if return_core:
+        out += (core,)
+    if return_sizes:
+        out += (sizes,)
+    if return_stats:
+        out += (dict(zip(DBSCAN_STATS, (int(x) for x in st))),)
+    return out if len(out) > 1 else labels
+
+
+def largest_clusters(labels, sizes, count=1, min_size=1):
+    """The points of the `count` largest clusters of cluster_dbscan that have at least min_size points, as a uint8 mask of the shape
+    of labels: 1 where the point's label is one of them, 0 elsewhere (noise included).  Among clusters of the same size the lower
+    label is the larger.  The mask is usable as the `confidence` of valid_points, triangulate_points, estimate_normals and the
+    outlier removals with min_confidence=1.  Plain numpy, or plain torch for tensors: no kernel."""
+    who = "largest_clusters"
+    for name, v in (("count", count), ("min_size", min_size)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < (0 if name == "count" else 1):
+            raise _cv.error(f"{who}: {name}={v!r} is not an integer >= {0 if name == 'count' else 1}")
+    if _cv._is_torch(labels):
+        import torch
+        sz = sizes if _cv._is_torch(sizes) else torch.from_numpy(np.asarray(sizes).astype(np.int64))
+        sz = sz.to(labels.device).to(torch.int64).reshape(-1)
+        if labels.dtype != torch.int32:
+            raise _cv.error(f"{who}: labels must be int32")
+        if labels.numel() and int(labels.max()) >= sz.numel():
+            raise _cv.error(f"{who}: a label is not below the {sz.numel()} sizes")
+        order = torch.argsort(-sz, stable=True)[:int(count)]      # descending size, ties in ascending label
+        order = order[sz[order] >= int(min_size)]
+        chosen = torch.zeros(sz.numel() + 1, dtype=torch.uint8, device=labels.device)      # (the last row is noise's)
+        chosen[order] = 1
+        lab = labels.to(torch.int64)
+        return chosen[torch.where(lab >= 0, lab, torch.full_like(lab, sz.numel()))]
+    lab = np.asarray(labels)
+    sz = np.asarray(sizes).astype(np.int64).reshape(-1)
+    if lab.dtype != np.int32:
+        raise _cv.error(f"{who}: labels must be int32, not {lab.dtype}")
+    if lab.size and int(lab.max()) >= sz.size:
+        raise _cv.error(f"{who}: a label is not below the {sz.size} sizes")
+    order = np.argsort(-sz, kind="stable")[:int(count)]
+    order = order[sz[order] >= int(min_size)]
+    chosen = np.zeros(sz.size + 1, np.uint8)
+    chosen[order] = 1
+    return chosen[np.where(lab >= 0, lab, sz.size)]
 
 
 MESH_MAX_PIXELS = 1 << 26

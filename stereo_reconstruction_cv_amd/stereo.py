@@ -373,6 +373,37 @@ class Engine:
                                                      None if stats is None else stats.ctypes.data))
         return stats
 
+    # -- density clustering of the point cloud (include/sgm_hip_dbscan.h) --
+    def cluster_dbscan_host(self, xyz: np.ndarray, disp: np.ndarray | None, eps: float, min_points: int, origin=(0.0, 0.0, 0.0),
+                            return_core: bool = False, return_sizes: bool = False):
+        """sgm_cluster_dbscan: float32 points (n, 3) or (H, W, 3), float32 disparities (n) or (H, W) or None.  Returns (labels int32
+        (n): the cluster's number or -1, core uint8 (n) or None, sizes uint32 (clusters) or None, stats uint64 (6)), the first two at
+        the source index; stats is points in range, valid points out of range, core, border, in-range noise, clusters."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = xyz.shape[0]
+        disp = None if disp is None else np.ascontiguousarray(disp, np.float32).reshape(-1)
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        labels = np.full(n, -1, np.int32)
+        core = np.zeros(n, np.uint8) if return_core else None
+        sizes = np.zeros(n, np.uint32) if return_sizes else None
+        stats = np.zeros(6, np.uint64)
+        nc = C.c_int64(0)
+        at = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.sgm_cluster_dbscan(self._h, xyz.ctypes.data, at(disp), n, float(eps), int(min_points), org.ctypes.data,
+                                          labels.ctypes.data, at(core), at(sizes), stats.ctypes.data, C.byref(nc)))
+        return labels, core, None if sizes is None else sizes[:int(nc.value)].copy(), stats
+
+    def cluster_dbscan_device(self, d_xyz: int, d_dispf: int | None, n: int, eps: float, min_points: int, origin=(0.0, 0.0, 0.0),
+                              d_labels: int | None = None, d_core: int | None = None, d_sizes: int | None = None):
+        """sgm_cluster_dbscan_device: device addresses; d_labels (int32) and d_core (uint8) have n entries, d_sizes (uint32) room for
+        n of which the first `clusters` are written.  Returns (clusters, stats uint64 (6)) after synchronising the engine's stream."""
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        stats = np.zeros(6, np.uint64)
+        nc = C.c_int64(0)
+        _check(self._L.sgm_cluster_dbscan_device(self._h, d_xyz, d_dispf, int(n), float(eps), int(min_points), org.ctypes.data,
+                                                 d_labels, d_core, d_sizes, stats.ctypes.data, C.byref(nc)))
+        return int(nc.value), stats
+
     # -- triangle mesh from the organised cloud (include/sgm_hip_mesh.h) --
     def mesh_grid_host(self, xyz: np.ndarray, disp: np.ndarray, colors: np.ndarray | None, max_diff: float = 1.0):
         """sgm_mesh_grid: float32 points (H, W, 3), float32 disparities (H, W), uint8 colours (H, W, 3) or None.  Returns
