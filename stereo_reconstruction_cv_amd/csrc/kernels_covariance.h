@@ -3,14 +3,13 @@
 // sweeps, the normal and the surface variation.  The grid of cells is that of kernels_radius.h, built by the same kernels (count,
 // clear, insert, starts, sort); the header's definition is the contract.
 //
-//   k_cov_query<SEPARATE, SELECT>  THE HOT KERNEL.  One lane per point in the order of the sorted records, the 27 cells one after
-//                     the other: a read-only probe, then the cell's run, RAD_RUN_LOADS records in flight, as in k_radius_query and
-//                     k_stat_query -- nothing ends a point's search early.  Per candidate the distance test of step 4, the three
+//   k_cov_query<SEPARATE, SELECT>  THE HOT KERNEL.  One lane per point in the order of the sorted records, over its 27 cells by
+//                     rad_walk (kernels_radius.h) -- nothing ends a point's search early.  The visitor: per neighbour the three
 //                     offsets quantised by one product and one v_rndne each, and nine signed 64-bit sums in registers (eighteen
 //                     VGPRs, every index a constant): three 64-bit adds and six 32 x 32 + 64 multiply-adds (v_mad_i64_i32).
-//                     SELECT = false: the accumulation sits under `if (near)`, so a wave none of whose lanes has a neighbour in
-//                     the candidate branches over it; true: the offsets of a candidate that is no neighbour are made 0 and the
-//                     accumulation runs for all.  SEPARATE = false: steps 7 to 10 at the end of the same lane (cov_solve), the
+//                     SELECT = false: the accumulation is left out for a candidate that is no neighbour, so a wave none of whose
+//                     lanes has a neighbour in the candidate branches over it; true: the offsets of a candidate that is no
+//                     neighbour are made 0 and the accumulation runs for all.  SEPARATE = false: steps 7 to 10 at the end of the same lane (cov_solve), the
 //                     outputs to the source index, the two counts of out_stats by a ballot per wave and one atomicAdd per block
 //                     and word; true: the nine sums and the count go to ten staged 64-bit words per point and k_cov_solve does
 //                     the rest.
@@ -151,43 +150,23 @@ __global__ __launch_bounds__(256) void k_cov_query(const float4 *__restrict__ so
     const float4 me = sorted[live ? t : (int64_t)n_in - 1];   // (n_in >= 1; a lane past the end does nothing with it)
     const float x = me.x, y = me.y, z = me.z;
     const uint32_t self = __float_as_uint(me.w);
-    uint32_t gx = 0, gy = 0, gz = 0;   // the point's own cell, by the arithmetic that put it there
-    radius_axis(x, G.ox, G.inv, gx);
-    radius_axis(y, G.oy, G.inv, gy);
-    radius_axis(z, G.oz, G.inv, gz);
     long long s0 = 0, s1 = 0, s2 = 0, s00 = 0, s01 = 0, s02 = 0, s11 = 0, s12 = 0, s22 = 0;
     uint32_t c = 0;
-    for (int cell = 0; live && cell < 27; cell++) {
-        const uint32_t nx = gx + (uint32_t)(cell / 9) - 1u, ny = gy + (uint32_t)(cell / 3 % 3) - 1u, nz = gz + (uint32_t)(cell % 3) - 1u;
-        if (nx >= 2u * RAD_GBIAS || ny >= 2u * RAD_GBIAS || nz >= 2u * RAD_GBIAS) continue;   // (0 - 1 wraps to a large number)
-        uint32_t cnt = 0, start = 0;
-        if (rad_find(tab, mask, radius_key(nx, ny, nz), cnt, start) == VOX_NONE || !cnt) continue;
-        const uint32_t end = start + cnt;
-        for (uint32_t j = start; j < end; j += RAD_RUN_LOADS) {
-            float4 q[RAD_RUN_LOADS];
-#pragma unroll
-            for (int u = 0; u < RAD_RUN_LOADS; u++) q[u] = sorted[min(j + (uint32_t)u, end - 1u)];
-#pragma unroll
-            for (int u = 0; u < RAD_RUN_LOADS; u++) {
-                const float dx = q[u].x - x, dy = q[u].y - y, dz = q[u].z - z;
-                const float d2 = (dx * dx + dy * dy) + dz * dz;
-                const bool near = j + (uint32_t)u < end && d2 <= G.r2 && __float_as_uint(q[u].w) != self;
-                c += near ? 1u : 0u;
-                if (SELECT) {   // a candidate that is no neighbour adds zeros (its products may be anything: they are not converted)
-                    const int qx = (int)rintf(near ? dx * V.qscale : 0.0f), qy = (int)rintf(near ? dy * V.qscale : 0.0f);
-                    const int qz = (int)rintf(near ? dz * V.qscale : 0.0f);
-                    s0 += qx, s1 += qy, s2 += qz;
-                    s00 += (long long)qx * qx, s01 += (long long)qx * qy, s02 += (long long)qx * qz;
-                    s11 += (long long)qy * qy, s12 += (long long)qy * qz, s22 += (long long)qz * qz;
-                } else if (near) {
-                    const int qx = (int)rintf(dx * V.qscale), qy = (int)rintf(dy * V.qscale), qz = (int)rintf(dz * V.qscale);
-                    s0 += qx, s1 += qy, s2 += qz;
-                    s00 += (long long)qx * qx, s01 += (long long)qx * qy, s02 += (long long)qx * qz;
-                    s11 += (long long)qy * qy, s12 += (long long)qy * qz, s22 += (long long)qz * qz;
-                }
-            }
-        }
-    }
+    // (a lane past the end walks nothing and stays: cov_finish is wave-wide)
+    rad_walk(sorted, tab, mask, G, x, y, z, [&] { return live; }, [&](bool inside, uint32_t w, float dx, float dy, float dz, float) {
+        // (& and not &&: w is read whether or not the candidate is inside, so its record stays one 16-byte load.  With && the
+        // compiler loads the index word of a step's first record under the distance test, a dependent load with a full wait in
+        // the loop: 2 to 8 % of cov_query, measured)
+        const bool near = inside & (w != self);
+        c += near ? 1u : 0u;
+        // SELECT: a candidate that is no neighbour adds zeros (its products may be anything: they are not converted)
+        if (!SELECT && !near) return;
+        const auto quant = [&](float d) { return (int)rintf(near ? d * V.qscale : 0.0f); };
+        const int qx = quant(dx), qy = quant(dy), qz = quant(dz);
+        s0 += qx, s1 += qy, s2 += qz;
+        s00 += (long long)qx * qx, s01 += (long long)qx * qy, s02 += (long long)qx * qz;
+        s11 += (long long)qy * qy, s12 += (long long)qy * qz, s22 += (long long)qz * qz;
+    });
     if (SEPARATE) {
         if (!live) return;
         long long *w = staged + (size_t)t * COV_WORDS;

@@ -8,8 +8,8 @@
 //                     the link kernel reads it with the run.  A kernel of its own: no lane of it reads another lane's word.
 //                     MARK = false (SGM_DBG_DBSCAN_GATHER_CORE) leaves the records alone; the link kernel then gathers
 //                     core[source index] per candidate.
-//   k_dbscan_link     THE HOT KERNEL.  One lane per point in sorted order over its 27 cells, the runs RAD_RUN_LOADS records at a
-//                     time as in k_radius_query, and nothing stops it early.  A core lane unites itself (uf_union of kernels_post.h,
+//   k_dbscan_link     THE HOT KERNEL.  One lane per point in sorted order over its 27 cells by rad_walk (kernels_radius.h), and
+//                     nothing stops it early.  The visitor: a core lane unites itself (uf_union of kernels_post.h,
 //                     on links indexed by source index) with every core candidate within r2 whose source index is smaller than its
 //                     own -- every linked pair is met twice and handled once --, after a look at the two current links, which
 //                     are equal for most pairs once a neighbourhood has grown together.  A lane that is not core keeps the
@@ -67,43 +67,18 @@ __global__ __launch_bounds__(256) void k_dbscan_link(const float4 *__restrict__ 
     const float x = me.x, y = me.y, z = me.z;
     const uint32_t mw = __float_as_uint(me.w), self = mw & DB_INDEX_MASK;
     const bool me_core = GATHER ? core[self] != 0 : (mw & DB_CORE_BIT) != 0;
-    uint32_t gx = 0, gy = 0, gz = 0;   // the point's own cell, by the arithmetic that put it there
-    radius_axis(x, G.ox, G.inv, gx);
-    radius_axis(y, G.oy, G.inv, gy);
-    radius_axis(z, G.oz, G.inv, gz);
     unsigned long long best = ~0ull;
-    for (int k = 0; k < 27; k++) {
-        const uint32_t nx = gx + (uint32_t)(k / 9) - 1u, ny = gy + (uint32_t)(k / 3 % 3) - 1u, nz = gz + (uint32_t)(k % 3) - 1u;
-        if (nx >= 2u * RAD_GBIAS || ny >= 2u * RAD_GBIAS || nz >= 2u * RAD_GBIAS) continue;   // (0 - 1 wraps to a large number)
-        uint32_t cnt = 0, start = 0;
-        if (rad_find(tab, mask, radius_key(nx, ny, nz), cnt, start) == VOX_NONE || !cnt) continue;
-        const uint32_t end = start + cnt;
-        for (uint32_t j = start; j < end; j += RAD_RUN_LOADS) {
-            float4 q[RAD_RUN_LOADS];
-            bool qc[RAD_RUN_LOADS];
-#pragma unroll
-            for (int u = 0; u < RAD_RUN_LOADS; u++) q[u] = sorted[min(j + (uint32_t)u, end - 1u)];
-#pragma unroll
-            for (int u = 0; u < RAD_RUN_LOADS; u++) {
-                const uint32_t w = __float_as_uint(q[u].w);
-                qc[u] = GATHER ? core[w & DB_INDEX_MASK] != 0 : (w & DB_CORE_BIT) != 0;
-            }
-#pragma unroll
-            for (int u = 0; u < RAD_RUN_LOADS; u++) {
-                const float dx = q[u].x - x, dy = q[u].y - y, dz = q[u].z - z;
-                const float d2 = (dx * dx + dy * dy) + dz * dz;
-                const uint32_t other = __float_as_uint(q[u].w) & DB_INDEX_MASK;
-                if (!(j + (uint32_t)u < end && d2 <= G.r2 && qc[u])) continue;
-                if (me_core) {
-                    // each linked pair once, from its larger index; equal links: the two are in one tree already
-                    if (other < self && uf_load(parent, (int)self) != uf_load(parent, (int)other)) uf_union(parent, (int)self, (int)other);
-                } else {
-                    const unsigned long long key = (unsigned long long)__float_as_uint(d2) << 32 | other;   // d2 >= 0: its bits order as its value
-                    best = key < best ? key : best;
-                }
-            }
+    rad_walk(sorted, tab, mask, G, x, y, z, [] { return true; }, [&](bool inside, uint32_t w, float, float, float, float d2) {
+        const uint32_t other = w & DB_INDEX_MASK;
+        if (!(inside && (GATHER ? core[other] != 0 : (w & DB_CORE_BIT) != 0))) return;
+        if (me_core) {
+            // each linked pair once, from its larger index; equal links: the two are in one tree already
+            if (other < self && uf_load(parent, (int)self) != uf_load(parent, (int)other)) uf_union(parent, (int)self, (int)other);
+        } else {
+            const unsigned long long key = (unsigned long long)__float_as_uint(d2) << 32 | other;   // d2 >= 0: its bits order as its value
+            best = key < best ? key : best;
         }
-    }
+    });
     if (!me_core && best != ~0ull) nearest[self] = (uint32_t)best;
 }
 

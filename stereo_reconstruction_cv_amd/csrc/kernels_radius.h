@@ -15,9 +15,9 @@
 //                     no cell get count 0 and keep 0 here.
 //   k_radius_query    THE HOT KERNEL.  One lane per point in sorted order (SORTED = true, the default: the lanes of a wave are
 //                     neighbours in one or two cells and share most of their 27 cells, so the slot loads and the run loads of a wave
-//                     are mostly one address) or in source order (false: behind SGM_DBG_RADIUS_SOURCE_ORDER).  Per neighbour cell
-//                     a read-only probe of the table, then 16-byte loads of the cell's run, four in flight; the count lives in a
-//                     register and the lane stops once it has reached max_count, which is what bounds the work in a dense cloud.
+//                     are mostly one address) or in source order (false: behind SGM_DBG_RADIUS_SOURCE_ORDER).  The walk over the
+//                     27 cells is rad_walk below, which every search on this grid shares; the count lives in a register and the
+//                     lane stops once it has reached max_count, which is what bounds the work in a dense cloud.
 //   k_radius_keep_count / k_radius_scatter   the ordered compaction of kernels_post.h (count -> k_compact_scan -> scatter) with
 //                     the predicate keep[i]; the scatter also writes the source index.
 // All atomics are the ordinary vector global atomics atomicAdd / atomicCAS / atomicOr compile to, at device scope; no lane waits
@@ -142,6 +142,44 @@ __device__ __forceinline__ uint32_t rad_find(const RadSlot *__restrict__ tab, ui
     return VOX_NONE;
 }
 
+// THE WALK of every search on this grid (k_radius_query, k_stat_query, k_cov_query, k_dbscan_link), and the one place where its
+// shape is decided.  The own cell of (x, y, z) by the arithmetic that put the point there (an in-range point: the
+// three calls succeed), then the 27 cells around it, one after the other: a read-only probe, then the cell's run, RAD_RUN_LOADS
+// records at a time -- the loads of one step do not depend on each other, so a lane waits for memory once per step and not once
+// per record; the indices past the run's end are clamped to its last record and come with inside = false.  (Nine first probes in
+// flight per plane of cells were measured and lost.)  go() is asked before every cell and before every step, so a search that
+// stops early passes that by less than RAD_RUN_LOADS candidates.  visit(inside, w, dx, dy, dz, d2) gets every candidate in the
+// order of the cells and of the runs: inside = a record of the run within r2 (the point itself among them: leaving it out is the
+// visitor's), w its index word.  The walk never returns from the kernel: a lane whose go() is false from the start walks nothing
+// and is still there afterwards (k_cov_query ends wave-wide).
+template <class Go, class Visit>
+__device__ __forceinline__ void rad_walk(const float4 *__restrict__ sorted, const RadSlot *__restrict__ tab, uint32_t mask, const RadGrid &G,
+                                         float x, float y, float z, Go go, Visit visit)
+{
+    uint32_t gx = 0, gy = 0, gz = 0;
+    radius_axis(x, G.ox, G.inv, gx);
+    radius_axis(y, G.oy, G.inv, gy);
+    radius_axis(z, G.oz, G.inv, gz);
+    for (int k = 0; k < 27 && go(); k++) {
+        const uint32_t nx = gx + (uint32_t)(k / 9) - 1u, ny = gy + (uint32_t)(k / 3 % 3) - 1u, nz = gz + (uint32_t)(k % 3) - 1u;
+        if (nx >= 2u * RAD_GBIAS || ny >= 2u * RAD_GBIAS || nz >= 2u * RAD_GBIAS) continue;   // (0 - 1 wraps to a large number)
+        uint32_t cnt = 0, start = 0;
+        if (rad_find(tab, mask, radius_key(nx, ny, nz), cnt, start) == VOX_NONE || !cnt) continue;
+        const uint32_t end = start + cnt;
+        for (uint32_t j = start; j < end && go(); j += RAD_RUN_LOADS) {
+            float4 q[RAD_RUN_LOADS];
+#pragma unroll
+            for (int u = 0; u < RAD_RUN_LOADS; u++) q[u] = sorted[min(j + (uint32_t)u, end - 1u)];
+#pragma unroll
+            for (int u = 0; u < RAD_RUN_LOADS; u++) {
+                const float dx = q[u].x - x, dy = q[u].y - y, dz = q[u].z - z;
+                const float d2 = (dx * dx + dy * dy) + dz * dz;
+                visit(j + (uint32_t)u < end && d2 <= G.r2, __float_as_uint(q[u].w), dx, dy, dz, d2);
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_radius_insert(const float *__restrict__ xyz, const float *__restrict__ disp, int64_t n, RadGrid G,
                                                        RadSlot *tab, uint32_t mask, uint2 *__restrict__ slot_rank, uint32_t *ctl)
 {
@@ -225,34 +263,10 @@ __global__ __launch_bounds__(256) void k_radius_query(const float4 *__restrict__
         x = xyz[t * 3], y = xyz[t * 3 + 1], z = xyz[t * 3 + 2];
         self = (uint32_t)t;
     }
-    // the point's own cell, by the arithmetic that put it there (an in-range point: the three calls succeed)
-    uint32_t gx = 0, gy = 0, gz = 0;
-    radius_axis(x, G.ox, G.inv, gx);
-    radius_axis(y, G.oy, G.inv, gy);
-    radius_axis(z, G.oz, G.inv, gz);
-    // The 27 cells, one after the other: a read-only probe, then the cell's run, RAD_RUN_LOADS records at a time -- the loads of
-    // one step do not depend on each other, so a lane waits for memory once per step and not once per record; the indices past
-    // the run's end are clamped to its last record and their results left out.  c can pass max_count by less than RAD_RUN_LOADS,
-    // which the min below takes back.  (Nine first probes in flight per plane of cells were measured and lost: DESIGN.md 4.21.)
+    // c can pass max_count by less than RAD_RUN_LOADS, which the min below takes back
     uint32_t c = 0;
-    for (int k = 0; k < 27 && c < max_count; k++) {
-        const uint32_t nx = gx + (uint32_t)(k / 9) - 1u, ny = gy + (uint32_t)(k / 3 % 3) - 1u, nz = gz + (uint32_t)(k % 3) - 1u;
-        if (nx >= 2u * RAD_GBIAS || ny >= 2u * RAD_GBIAS || nz >= 2u * RAD_GBIAS) continue;   // (0 - 1 wraps to a large number)
-        uint32_t cnt = 0, start = 0;
-        if (rad_find(tab, mask, radius_key(nx, ny, nz), cnt, start) == VOX_NONE || !cnt) continue;
-        const uint32_t end = start + cnt;
-        for (uint32_t j = start; j < end && c < max_count; j += RAD_RUN_LOADS) {
-            float4 q[RAD_RUN_LOADS];
-#pragma unroll
-            for (int u = 0; u < RAD_RUN_LOADS; u++) q[u] = sorted[min(j + (uint32_t)u, end - 1u)];
-#pragma unroll
-            for (int u = 0; u < RAD_RUN_LOADS; u++) {
-                const float dx = q[u].x - x, dy = q[u].y - y, dz = q[u].z - z;
-                const float d2 = (dx * dx + dy * dy) + dz * dz;
-                c += (j + (uint32_t)u < end && d2 <= G.r2 && __float_as_uint(q[u].w) != self) ? 1u : 0u;
-            }
-        }
-    }
+    rad_walk(sorted, tab, mask, G, x, y, z, [&] { return c < max_count; },
+             [&](bool inside, uint32_t w, float, float, float, float) { c += (inside && w != self) ? 1u : 0u; });
     keep[self] = c >= nb_points ? 1 : 0;
     if (counts) counts[self] = min(c, max_count);
 }

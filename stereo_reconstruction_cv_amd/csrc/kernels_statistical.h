@@ -3,10 +3,9 @@
 // points at or under the threshold the host forms from it.  The grid of cells is that of kernels_radius.h, built by the same
 // kernels (count, clear, insert, starts, sort); the header's definition is the contract.
 //
-//   k_stat_query<CAP> THE HOT KERNEL.  One lane per point in the order of the sorted records, the 27 cells one after the other: a
-//                     read-only probe, then the cell's run, RAD_RUN_LOADS records in flight, as in k_radius_query -- but nothing
-//                     ends a point's search early, and the lane keeps the k smallest d2 it has seen.  Non-negative binary32
-//                     values order as their bit patterns, so the list is one of unsigned words, ascending, in CAP registers
+//   k_stat_query<CAP> THE HOT KERNEL.  One lane per point in the order of the sorted records, over its 27 cells by rad_walk
+//                     (kernels_radius.h) -- nothing ends a point's search early --, and the visitor keeps the k smallest d2 the
+//                     lane has seen.  Non-negative binary32 values order as their bit patterns, so the list is one of unsigned words, ascending, in CAP registers
 //                     (CAP = 8, 16, 32, 64: the smallest that holds k): the first CAP - k words are 0 for good and pass every
 //                     candidate on, the last k start at STAT_FAR, and a candidate goes in by CAP fully unrolled compare-exchanges
 //                     (min stays, max moves on; the largest falls off the end).  Every index is a constant: the list never
@@ -44,42 +43,23 @@ __global__ __launch_bounds__(256) void k_stat_query(const float4 *__restrict__ s
     const float4 me = sorted[t];
     const float x = me.x, y = me.y, z = me.z;
     const uint32_t self = __float_as_uint(me.w);
-    uint32_t gx = 0, gy = 0, gz = 0;   // the point's own cell, by the arithmetic that put it there
-    radius_axis(x, G.ox, G.inv, gx);
-    radius_axis(y, G.oy, G.inv, gy);
-    radius_axis(z, G.oz, G.inv, gz);
     uint32_t e[CAP];
 #pragma unroll
     for (int m = 0; m < CAP; m++) e[m] = (uint32_t)m + k < (uint32_t)CAP ? 0u : STAT_FAR;
     uint32_t c = 0;
-    for (int cell = 0; cell < 27; cell++) {
-        const uint32_t nx = gx + (uint32_t)(cell / 9) - 1u, ny = gy + (uint32_t)(cell / 3 % 3) - 1u, nz = gz + (uint32_t)(cell % 3) - 1u;
-        if (nx >= 2u * RAD_GBIAS || ny >= 2u * RAD_GBIAS || nz >= 2u * RAD_GBIAS) continue;   // (0 - 1 wraps to a large number)
-        uint32_t cnt = 0, start = 0;
-        if (rad_find(tab, mask, radius_key(nx, ny, nz), cnt, start) == VOX_NONE || !cnt) continue;
-        const uint32_t end = start + cnt;
-        for (uint32_t j = start; j < end; j += RAD_RUN_LOADS) {
-            float4 q[RAD_RUN_LOADS];
+    rad_walk(sorted, tab, mask, G, x, y, z, [] { return true; }, [&](bool inside, uint32_t w, float, float, float, float d2) {
+        const bool near = inside && w != self;
+        c += near ? 1u : 0u;
+        uint32_t v = near ? __float_as_uint(d2) : STAT_FAR;
+        if (v < e[CAP - 1]) {
 #pragma unroll
-            for (int u = 0; u < RAD_RUN_LOADS; u++) q[u] = sorted[min(j + (uint32_t)u, end - 1u)];
-#pragma unroll
-            for (int u = 0; u < RAD_RUN_LOADS; u++) {
-                const float dx = q[u].x - x, dy = q[u].y - y, dz = q[u].z - z;
-                const float d2 = (dx * dx + dy * dy) + dz * dz;
-                const bool near = j + (uint32_t)u < end && d2 <= G.r2 && __float_as_uint(q[u].w) != self;
-                c += near ? 1u : 0u;
-                uint32_t v = near ? __float_as_uint(d2) : STAT_FAR;
-                if (v < e[CAP - 1]) {
-#pragma unroll
-                    for (int m = 0; m < CAP; m++) {
-                        const uint32_t lo = min(e[m], v);
-                        v = max(e[m], v);
-                        e[m] = lo;
-                    }
-                }
+            for (int m = 0; m < CAP; m++) {
+                const uint32_t lo = min(e[m], v);
+                v = max(e[m], v);
+                e[m] = lo;
             }
         }
-    }
+    });
     float mean = -1.0f;
     uint32_t qi = STAT_SPARSE;
     if (c >= k) {

@@ -2856,27 +2856,54 @@ int sgm_compact_points_device_async(sgm_engine *e, const void *d_xyz, const void
     return SGM_OK;
 }
 
+// One output of a point-list call's host entry: `host` (null: not asked for) gets rows of `row` bytes from the engine's `dev`,
+// which is made to hold n of them -- as many as *rows says once the device entry has run, or n with rows null
+struct HostOut {
+    void *host;
+    DevBuf *dev;
+    size_t row;
+    const int64_t *rows;
+    void *d() const { return host ? dev->p : nullptr; }   // what the device entry gets (after the buffers have been made)
+};
+
+// What the host entries of the point-list calls share: the buffers, the cloud up (xyz to e->xyz; disp, colors: to e->f32, e->crgb_in,
+// or null), run(d_disp, d_colors) -- the device entry on these --, then the outputs down and one synchronise.
+extern "C++" {   // (a template: this part of the file has C linkage)
+template <class Run>
+static int cloud_host_call(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors, int64_t n,
+                           std::initializer_list<HostOut> outs, Run run)
+{
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    if ((rc = e->xyz.ensure((size_t)n * 12)) || (disp && (rc = e->f32.ensure((size_t)n * 4))) || (colors && (rc = e->crgb_in.ensure((size_t)n * 3))))
+        return rc;
+    for (const HostOut &o : outs)
+        if (o.host && (rc = o.dev->ensure((size_t)n * o.row))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, e->stream));
+    if (disp) HIP_TRY(hipMemcpyAsync(e->f32.p, disp, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    if (colors) HIP_TRY(hipMemcpyAsync(e->crgb_in.p, colors, (size_t)n * 3, hipMemcpyHostToDevice, e->stream));
+    if ((rc = run(disp ? e->f32.p : nullptr, colors ? e->crgb_in.p : nullptr))) {
+        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
+        return rc;
+    }
+    for (const HostOut &o : outs) {
+        const int64_t rows = o.rows ? *o.rows : n;
+        if (o.host && rows > 0) HIP_TRY(hipMemcpyAsync(o.host, o.dev->p, (size_t)rows * o.row, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SGM_OK;
+}
+}  // extern "C++"
+
 int sgm_compact_points(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int64_t n,
                        float *out_points, uint8_t *out_colors, int64_t *n_valid)
 {
     if (!e || !xyz || !disp || !out_points || !n_valid || n <= 0) return set_err(SGM_ERR_INVALID_ARG, "bad argument");
     if (out_colors && !colors_rgb) return set_err(SGM_ERR_INVALID_ARG, "out_colors requested without colors");
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = e->f32.ensure((size_t)n * 4)) || (rc = e->xyz.ensure((size_t)n * 12)) || (rc = e->cpts.ensure((size_t)n * 12))) return rc;
-    if (out_colors && ((rc = e->crgb_in.ensure((size_t)n * 3)) || (rc = e->crgb.ensure((size_t)n * 3)))) return rc;
-    HIP_TRY(hipMemcpyAsync(e->f32.p, disp, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, e->stream));
-    if (out_colors) HIP_TRY(hipMemcpyAsync(e->crgb_in.p, colors_rgb, (size_t)n * 3, hipMemcpyHostToDevice, e->stream));
-    if ((rc = sgm_compact_points_device(e, e->xyz.p, e->f32.p, out_colors ? e->crgb_in.p : nullptr, n, e->cpts.p,
-                                        out_colors ? e->crgb.p : nullptr, n_valid)))
-        return rc;
-    if (*n_valid > 0) {
-        HIP_TRY(hipMemcpyAsync(out_points, e->cpts.p, (size_t)*n_valid * 12, hipMemcpyDeviceToHost, e->stream));
-        if (out_colors) HIP_TRY(hipMemcpyAsync(out_colors, e->crgb.p, (size_t)*n_valid * 3, hipMemcpyDeviceToHost, e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return SGM_OK;
+    const HostOut pts{out_points, &e->cpts, 12, n_valid}, rgb{out_colors, &e->crgb, 3, n_valid};
+    return cloud_host_call(e, xyz, disp, out_colors ? colors_rgb : nullptr, n, {pts, rgb}, [&](void *d_disp, void *d_colors) {
+        return sgm_compact_points_device(e, e->xyz.p, d_disp, d_colors, n, pts.d(), rgb.d(), n_valid);
+    });
 }
 
 int sgm_median3x3(sgm_engine *e, const int16_t *src, int H, int W, int16_t *dst)
@@ -3336,64 +3363,84 @@ int sgm_voxel_downsample(sgm_engine *e, const float *xyz, const float *disp, con
         if (n_out_of_range) *n_out_of_range = 0;
         return SGM_OK;
     }
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = e->xyz.ensure((size_t)n * 12)) || (rc = e->cpts.ensure((size_t)n * 12)) || (disp && (rc = e->f32.ensure((size_t)n * 4))) ||
-        (out_counts && (rc = e->vox_cnt.ensure((size_t)n * 4))))
-        return rc;
-    if (out_colors && ((rc = e->crgb_in.ensure((size_t)n * 3)) || (rc = e->crgb.ensure((size_t)n * 3)))) return rc;
-    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, e->stream));
-    if (disp) HIP_TRY(hipMemcpyAsync(e->f32.p, disp, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    if (out_colors) HIP_TRY(hipMemcpyAsync(e->crgb_in.p, colors_rgb, (size_t)n * 3, hipMemcpyHostToDevice, e->stream));
     int64_t nv = 0, noor = 0;
-    if ((rc = sgm_voxel_downsample_device(e, e->xyz.p, disp ? e->f32.p : nullptr, out_colors ? e->crgb_in.p : nullptr, n, voxel_size, origin,
-                                          min_points, e->cpts.p, out_colors ? e->crgb.p : nullptr, out_counts ? e->vox_cnt.p : nullptr,
-                                          &nv, &noor))) {
-        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
+    const HostOut pts{out_points, &e->cpts, 12, &nv}, rgb{out_colors, &e->crgb, 3, &nv}, cnt{out_counts, &e->vox_cnt, 4, &nv};
+    if (int rc = cloud_host_call(e, xyz, disp, out_colors ? colors_rgb : nullptr, n, {pts, rgb, cnt}, [&](void *d_disp, void *d_colors) {
+            return sgm_voxel_downsample_device(e, e->xyz.p, d_disp, d_colors, n, voxel_size, origin, min_points, pts.d(), rgb.d(), cnt.d(), &nv,
+                                               &noor);
+        }))
         return rc;
-    }
-    if (nv > 0) {
-        HIP_TRY(hipMemcpyAsync(out_points, e->cpts.p, (size_t)nv * 12, hipMemcpyDeviceToHost, e->stream));
-        if (out_colors) HIP_TRY(hipMemcpyAsync(out_colors, e->crgb.p, (size_t)nv * 3, hipMemcpyDeviceToHost, e->stream));
-        if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, e->vox_cnt.p, (size_t)nv * 4, hipMemcpyDeviceToHost, e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
     *n_voxels = nv;
     if (n_out_of_range) *n_out_of_range = noor;
     return SGM_OK;
 }
 
 // ---- radius outlier removal (include/sgm_hip_radius.h, kernels_radius.h) -------------------------------------------------------
+// What the four calls on the grid of cells check alike, in the order they check it: null pointers, n, the radius under the entry's
+// word for it (scale: a further quotient scale / r that must stay finite, or 0), the origin, the number of points.  own(after)
+// makes the entry's own checks that stand behind the check on n (after = 0), the radius (1) and the origin (2).
+extern "C++" {   // (a template: this part of the file has C linkage)
+template <class Own>
+static int cloud_check_args(const char *who, bool null, int64_t n, const char *rname, float r, float scale, const float *origin, Own own)
+{
+    int rc;
+    if (null) return set_err(SGM_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (n < 0) return set_err(SGM_ERR_INVALID_ARG, "%s: n=%lld points", who, (long long)n);
+    if ((rc = own(0))) return rc;
+    const float r2 = r * r, v = r * 1.03125f;
+    if (!std::isfinite(r) || !(r > 0.0f) || !std::isnormal(r2) || !std::isfinite(1.0f / v) || !std::isfinite(scale / r))
+        return set_err(SGM_ERR_INVALID_ARG, "%s: %s %g is not finite and positive with a finite normal square", who, rname, (double)r);
+    if ((rc = own(1))) return rc;
+    if (!origin || !std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+        return set_err(SGM_ERR_INVALID_ARG, "%s: the origin is null or not finite", who);
+    if ((rc = own(2))) return rc;
+    if (n > RAD_MAX_POINTS)
+        return set_err(SGM_ERR_UNSUPPORTED, "%s: %lld points, more than 2^24 - 1 (a source index shares a record with its point)", who, (long long)n);
+    return SGM_OK;
+}
+}  // extern "C++"
+
 static int radius_check_args(const sgm_engine *e, const void *xyz, const void *colors, int64_t n, float r, const float *origin,
                              int nb_points, int max_count, const void *out_colors, const int64_t *n_kept)
 {
-    if (!e || !xyz || !n_kept) return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: null pointer");
-    if (n < 0) return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: n=%lld points", (long long)n);
-    const float r2 = r * r, v = r * 1.03125f;
-    if (!std::isfinite(r) || !(r > 0.0f) || !std::isnormal(r2) || !std::isfinite(1.0f / v))
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: radius %g is not finite and positive with a finite normal square", (double)r);
-    if (!origin || !std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: the origin is null or not finite");
-    if (nb_points < 1) return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: nb_points %d < 1", nb_points);
-    if (max_count < nb_points) return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: max_count %d < nb_points %d", max_count, nb_points);
-    if (out_colors && !colors) return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: out_colors requested without colors");
-    if (n > RAD_MAX_POINTS)
-        return set_err(SGM_ERR_UNSUPPORTED, "sgm_radius_outlier: %lld points, more than 2^24 - 1 (a source index shares a record with its point)", (long long)n);
-    return SGM_OK;
+    return cloud_check_args("sgm_radius_outlier", !e || !xyz || !n_kept, n, "radius", r, 0.0f, origin, [&](int after) -> int {
+        if (after != 2) return SGM_OK;
+        if (nb_points < 1) return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: nb_points %d < 1", nb_points);
+        if (max_count < nb_points) return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: max_count %d < nb_points %d", max_count, nb_points);
+        if (out_colors && !colors) return set_err(SGM_ERR_INVALID_ARG, "sgm_radius_outlier: out_colors requested without colors");
+        return SGM_OK;
+    });
 }
 
-// The grid of cells both searches run on, steps 1 to 5 of the device entries: the control words, the count of the points that
-// arrive (read back: *n_in, *n_out; with none the call is done and nothing else is built), then the table (*cap slots in rad_tab),
+// The grid of cells of one call, as radius_build_grid leaves it
+struct CloudGrid {
+    RadGrid G;
+    uint32_t n_in, n_out, cap, mask;   // points in range, valid points out of range, the table's slots (0 with no point in range)
+    const RadSlot *tab;                // rad_tab
+    float4 *sorted;                    // rad_sorted: n_in records
+    uint2 *slot_rank;                  // rad_pt: n pairs
+    int m;                             // blocks of 256 over the n points
+};
+
+static int cloud_no_slot(const char *who, const CloudGrid &g)
+{
+    return set_err(SGM_ERR_HIP, "%s: a point found no slot in a table of %u slots for %u points", who, g.cap, g.n_in);
+}
+
+// The grid of cells every search runs on, steps 1 to 5 of the device entries: the control words, the count of the points that
+// arrive (read back: n_in, n_out; with none the call is done and nothing else is built), then the table (cap slots in rad_tab),
 // each point's slot and rank (rad_pt), the cells' starts and the records sorted by cell (rad_sorted).  keep and counts are what
 // k_radius_sort zeroes for the points in no cell (counts may be null).  names: the five stage names of the caller's record.
-static int radius_build_grid(sgm_engine *e, const float *xyz, const float *disp, int64_t n, const RadGrid &G, uint8_t *keep, uint32_t *counts,
-                             const char *const names[5], uint32_t *n_in_out, uint32_t *n_out, uint32_t *cap_out)
+static int radius_build_grid(sgm_engine *e, const float *xyz, const float *disp, int64_t n, float r, const float origin[3], uint8_t *keep,
+                             uint32_t *counts, const char *const names[5], CloudGrid *g)
 {
     const int m = (int)((n + 255) / 256);
     int rc;
     uint32_t *ctl = (uint32_t *)e->rad_ctl.p;
     uint2 *slot_rank = (uint2 *)e->rad_pt.p;
     hipStream_t st = e->stream;
+    const RadGrid G{1.0f / (r * 1.03125f), r * r, origin[0], origin[1], origin[2]};
+    *g = CloudGrid{G, 0, 0, 0, 0, nullptr, nullptr, slot_rank, m};
     // 1. how many points arrive: the table and the sorted records are sized from them, and a cloud with none is done here
     HIP_TRY(hipMemsetAsync(ctl, 0, RAD_CTL_WORDS * 4, st));
     stage_break(e);
@@ -3405,19 +3452,18 @@ static int radius_build_grid(sgm_engine *e, const float *xyz, const float *disp,
     HIP_TRY(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     stage_break(e);
-    const uint32_t n_in = h_ctl[RAD_CTL_IN];
-    *n_in_out = n_in;
-    *n_out = h_ctl[RAD_CTL_OUT];
-    *cap_out = 0;
+    const uint32_t n_in = g->n_in = h_ctl[RAD_CTL_IN];
+    g->n_out = h_ctl[RAD_CTL_OUT];
     if (n_in == 0) return SGM_OK;
     // 2. the table: the smallest power of two of at least twice the points in range (debug: of at least the points themselves)
     const uint64_t want = (e->debug & SGM_DBG_RADIUS_TIGHT_TABLE) ? (uint64_t)n_in : 2 * (uint64_t)n_in;
     uint32_t cap = 1;
     while (cap < want) cap <<= 1;   // (n_in < 2^24: at most 2^25)
-    *cap_out = cap;
+    g->cap = cap, g->mask = cap - 1;
     if ((rc = e->rad_tab.ensure((size_t)cap * sizeof(RadSlot))) || (rc = e->rad_sorted.ensure((size_t)n_in * 16))) return rc;
     RadSlot *tab = (RadSlot *)e->rad_tab.p;
-    float4 *sorted = (float4 *)e->rad_sorted.p;
+    float4 *sorted = g->sorted = (float4 *)e->rad_sorted.p;
+    g->tab = tab;
     if ((rc = stage_begin(e, names[1]))) return rc;
     hipLaunchKernelGGL(k_radius_clear, dim3((cap + 255) / 256), dim3(256), 0, st, tab, cap);
     KCHECK();
@@ -3439,12 +3485,14 @@ static int radius_build_grid(sgm_engine *e, const float *xyz, const float *disp,
     return stage_end(e, 1);
 }
 
-// step 7 of both: the kept points through the ordered compaction; *total and the call's control words come back (blocks)
-static int radius_compact_kept(sgm_engine *e, const char *stage, const uint8_t *keep, const float *xyz, const uint8_t *colors, int64_t n,
-                               void *d_out_points, void *d_out_colors, void *d_out_index, uint32_t *total, uint32_t h_ctl[RAD_CTL_WORDS])
+// step 7 of both: the kept points through the ordered compaction; *total comes back with the call's control words (blocks), and
+// a set RAD_CTL_ERR is the error of `who` (cloud_no_slot)
+static int radius_compact_kept(sgm_engine *e, const char *who, const char *stage, const CloudGrid &g, const uint8_t *keep, const float *xyz,
+                               const uint8_t *colors, int64_t n, void *d_out_points, void *d_out_colors, void *d_out_index, uint32_t *total)
 {
-    const int m = (int)((n + 255) / 256);
+    const int m = g.m;
     int rc;
+    uint32_t h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0};
     uint32_t *cnt = (uint32_t *)e->ccount.p;
     hipStream_t st = e->stream;
     if ((rc = stage_begin(e, stage))) return rc;
@@ -3459,7 +3507,7 @@ static int radius_compact_kept(sgm_engine *e, const char *stage, const uint8_t *
     HIP_TRY(hipMemcpyAsync(h_ctl, e->rad_ctl.p, RAD_CTL_WORDS * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(total, cnt + m, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    return SGM_OK;
+    return h_ctl[RAD_CTL_ERR] ? cloud_no_slot(who, g) : SGM_OK;
 }
 
 int sgm_radius_outlier_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int64_t n, float radius,
@@ -3479,44 +3527,39 @@ int sgm_radius_outlier_device(sgm_engine *e, const void *d_xyz, const void *d_di
         (!d_out_keep && (rc = e->rad_keep.ensure((size_t)n))))
         return rc;
     if (e->profile) stage_reset(e);   // the stage record is the call's from here on
-    const float v = radius * 1.03125f;
-    const RadGrid G{1.0f / v, radius * radius, origin[0], origin[1], origin[2]};
     const float *xyz = (const float *)d_xyz, *disp = (const float *)d_disp_f32;
     const uint8_t *colors = (const uint8_t *)(d_out_colors ? d_colors_rgb : nullptr);
     uint32_t *counts = (uint32_t *)d_out_counts;
-    uint2 *slot_rank = (uint2 *)e->rad_pt.p;
     uint8_t *keep = (uint8_t *)(d_out_keep ? d_out_keep : e->rad_keep.p);
     hipStream_t st = e->stream;
     static const char *const names[5] = {"radius_count", "radius_clear", "radius_insert", "radius_starts", "radius_sort"};
-    uint32_t n_in = 0, n_out = 0, cap = 0;
-    if ((rc = radius_build_grid(e, xyz, disp, n, G, keep, counts, names, &n_in, &n_out, &cap))) return rc;
-    if (n_in == 0) {   // nobody has a neighbour
+    CloudGrid g;
+    if ((rc = radius_build_grid(e, xyz, disp, n, radius, origin, keep, counts, names, &g))) return rc;
+    if (g.n_in == 0) {   // nobody has a neighbour
         if (d_out_keep) HIP_TRY(hipMemsetAsync(d_out_keep, 0, (size_t)n, st));
         if (counts) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n * 4, st));
         HIP_TRY(hipStreamSynchronize(st));
         *n_kept = 0;
-        if (n_out_of_range) *n_out_of_range = (int64_t)n_out;
+        if (n_out_of_range) *n_out_of_range = (int64_t)g.n_out;
         return SGM_OK;
     }
-    const RadSlot *tab = (const RadSlot *)e->rad_tab.p;
-    const float4 *sorted = (const float4 *)e->rad_sorted.p;
     // 6. the counts
     if ((rc = stage_begin(e, "radius_query"))) return rc;
     if (e->debug & SGM_DBG_RADIUS_SOURCE_ORDER)
-        hipLaunchKernelGGL(k_radius_query<false>, dim3(m), dim3(256), 0, st, sorted, n_in, xyz, (const uint2 *)slot_rank, n, G,
-                           tab, cap - 1, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
+        hipLaunchKernelGGL(k_radius_query<false>, dim3(m), dim3(256), 0, st, (const float4 *)g.sorted, g.n_in, xyz, (const uint2 *)g.slot_rank, n,
+                           g.G, g.tab, g.mask, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
     else
-        hipLaunchKernelGGL(k_radius_query<true>, dim3((n_in + 255) / 256), dim3(256), 0, st, sorted, n_in, xyz,
-                           (const uint2 *)slot_rank, n, G, tab, cap - 1, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
+        hipLaunchKernelGGL(k_radius_query<true>, dim3((g.n_in + 255) / 256), dim3(256), 0, st, (const float4 *)g.sorted, g.n_in, xyz,
+                           (const uint2 *)g.slot_rank, n, g.G, g.tab, g.mask, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
     KCHECK();
     if ((rc = stage_end(e, 1))) return rc;
     // 7. the kept points through the ordered compaction
-    uint32_t total = 0, h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0};
-    if ((rc = radius_compact_kept(e, "radius_compact", keep, xyz, colors, n, d_out_points, d_out_colors, d_out_index, &total, h_ctl))) return rc;
-    if (h_ctl[RAD_CTL_ERR])
-        return set_err(SGM_ERR_HIP, "sgm_radius_outlier: a point found no slot in a table of %u slots for %u points", cap, n_in);
+    uint32_t total = 0;
+    if ((rc = radius_compact_kept(e, "sgm_radius_outlier", "radius_compact", g, keep, xyz, colors, n, d_out_points, d_out_colors, d_out_index,
+                                  &total)))
+        return rc;
     *n_kept = (int64_t)total;
-    if (n_out_of_range) *n_out_of_range = (int64_t)n_out;
+    if (n_out_of_range) *n_out_of_range = (int64_t)g.n_out;
     return SGM_OK;
 }
 
@@ -3530,32 +3573,14 @@ int sgm_radius_outlier(sgm_engine *e, const float *xyz, const float *disp, const
         if (n_out_of_range) *n_out_of_range = 0;
         return SGM_OK;
     }
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = e->xyz.ensure((size_t)n * 12)) || (disp && (rc = e->f32.ensure((size_t)n * 4))) || (rc = e->rad_keep.ensure((size_t)n)) ||
-        (out_counts && (rc = e->rad_cnt.ensure((size_t)n * 4))) || (out_points && (rc = e->cpts.ensure((size_t)n * 12))) ||
-        (out_index && (rc = e->rad_idx.ensure((size_t)n * 4))))
-        return rc;
-    if (out_colors && ((rc = e->crgb_in.ensure((size_t)n * 3)) || (rc = e->crgb.ensure((size_t)n * 3)))) return rc;
-    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, e->stream));
-    if (disp) HIP_TRY(hipMemcpyAsync(e->f32.p, disp, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    if (out_colors) HIP_TRY(hipMemcpyAsync(e->crgb_in.p, colors_rgb, (size_t)n * 3, hipMemcpyHostToDevice, e->stream));
     int64_t nk = 0, noor = 0;
-    if ((rc = sgm_radius_outlier_device(e, e->xyz.p, disp ? e->f32.p : nullptr, out_colors ? e->crgb_in.p : nullptr, n, radius, origin,
-                                        nb_points, max_count, e->rad_keep.p, out_counts ? e->rad_cnt.p : nullptr,
-                                        out_points ? e->cpts.p : nullptr, out_colors ? e->crgb.p : nullptr,
-                                        out_index ? e->rad_idx.p : nullptr, &nk, &noor))) {
-        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
+    const HostOut keep{out_keep, &e->rad_keep, 1, nullptr}, cnt{out_counts, &e->rad_cnt, 4, nullptr}, pts{out_points, &e->cpts, 12, &nk},
+        rgb{out_colors, &e->crgb, 3, &nk}, idx{out_index, &e->rad_idx, 4, &nk};
+    if (int rc = cloud_host_call(e, xyz, disp, out_colors ? colors_rgb : nullptr, n, {keep, cnt, pts, rgb, idx}, [&](void *d_disp, void *d_colors) {
+            return sgm_radius_outlier_device(e, e->xyz.p, d_disp, d_colors, n, radius, origin, nb_points, max_count, keep.d(), cnt.d(), pts.d(),
+                                             rgb.d(), idx.d(), &nk, &noor);
+        }))
         return rc;
-    }
-    if (out_keep) HIP_TRY(hipMemcpyAsync(out_keep, e->rad_keep.p, (size_t)n, hipMemcpyDeviceToHost, e->stream));
-    if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, e->rad_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-    if (nk > 0) {
-        if (out_points) HIP_TRY(hipMemcpyAsync(out_points, e->cpts.p, (size_t)nk * 12, hipMemcpyDeviceToHost, e->stream));
-        if (out_colors) HIP_TRY(hipMemcpyAsync(out_colors, e->crgb.p, (size_t)nk * 3, hipMemcpyDeviceToHost, e->stream));
-        if (out_index) HIP_TRY(hipMemcpyAsync(out_index, e->rad_idx.p, (size_t)nk * 4, hipMemcpyDeviceToHost, e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
     *n_kept = nk;
     if (n_out_of_range) *n_out_of_range = noor;
     return SGM_OK;
@@ -3565,20 +3590,14 @@ int sgm_radius_outlier(sgm_engine *e, const float *xyz, const float *disp, const
 static int stat_check_args(const sgm_engine *e, const void *xyz, const void *colors, int64_t n, int k, float ratio, float r, const float *origin,
                            const void *out_colors, const int64_t *n_kept)
 {
-    if (!e || !xyz || !n_kept) return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: null pointer");
-    if (n < 0) return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: n=%lld points", (long long)n);
-    if (k < 1 || k > STAT_MAX_K) return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: nb_neighbors %d outside 1 .. %d", k, STAT_MAX_K);
-    if (!std::isfinite(ratio) || !(ratio >= 0.0f))
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: std_ratio %g is not finite and >= 0", (double)ratio);
-    const float r2 = r * r, v = r * 1.03125f;
-    if (!std::isfinite(r) || !(r > 0.0f) || !std::isnormal(r2) || !std::isfinite(1.0f / v) || !std::isfinite(524288.0f / r))
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: max_radius %g is not finite and positive with a finite normal square", (double)r);
-    if (!origin || !std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: the origin is null or not finite");
-    if (out_colors && !colors) return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: out_colors requested without colors");
-    if (n > RAD_MAX_POINTS)
-        return set_err(SGM_ERR_UNSUPPORTED, "sgm_statistical_outlier: %lld points, more than 2^24 - 1 (a source index shares a record with its point)", (long long)n);
-    return SGM_OK;
+    return cloud_check_args("sgm_statistical_outlier", !e || !xyz || !n_kept, n, "max_radius", r, 524288.0f, origin, [&](int after) -> int {
+        if (after == 0 && (k < 1 || k > STAT_MAX_K))
+            return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: nb_neighbors %d outside 1 .. %d", k, STAT_MAX_K);
+        if (after == 0 && (!std::isfinite(ratio) || !(ratio >= 0.0f)))
+            return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: std_ratio %g is not finite and >= 0", (double)ratio);
+        if (after == 2 && out_colors && !colors) return set_err(SGM_ERR_INVALID_ARG, "sgm_statistical_outlier: out_colors requested without colors");
+        return SGM_OK;
+    });
 }
 
 // step 8 of the definition: T from m, A, B in binary64, every operation on its own (the build has -ffp-contract=off)
@@ -3616,18 +3635,18 @@ int sgm_statistical_outlier_device(sgm_engine *e, const void *d_xyz, const void 
         (rc = e->ccount.ensure((size_t)(m + 1) * 4)) || (!d_out_keep && (rc = e->rad_keep.ensure((size_t)n))))
         return rc;
     if (e->profile) stage_reset(e);   // the stage record is the call's from here on
-    const float v = max_radius * 1.03125f, qscale = 524288.0f / max_radius;
-    const RadGrid G{1.0f / v, max_radius * max_radius, origin[0], origin[1], origin[2]};
+    const float qscale = 524288.0f / max_radius;
     const float *xyz = (const float *)d_xyz, *disp = (const float *)d_disp_f32;
     const uint8_t *colors = (const uint8_t *)(d_out_colors ? d_colors_rgb : nullptr);
     float *mean = (float *)d_out_mean;
-    uint2 *pt = (uint2 *)e->rad_pt.p;
     unsigned long long *sums = (unsigned long long *)e->stat_sums.p;
     uint8_t *keep = (uint8_t *)(d_out_keep ? d_out_keep : e->rad_keep.p);
     hipStream_t st = e->stream;
     static const char *const names[5] = {"stat_count", "stat_clear", "stat_insert", "stat_starts", "stat_sort"};
-    uint32_t n_in = 0, n_out = 0, cap = 0;
-    if ((rc = radius_build_grid(e, xyz, disp, n, G, keep, nullptr, names, &n_in, &n_out, &cap))) return rc;
+    CloudGrid g;
+    if ((rc = radius_build_grid(e, xyz, disp, n, max_radius, origin, keep, nullptr, names, &g))) return rc;
+    const uint32_t n_in = g.n_in, n_out = g.n_out;
+    uint2 *pt = g.slot_rank;
     if (n_in == 0) {   // nobody has a neighbour
         if (d_out_keep) HIP_TRY(hipMemsetAsync(d_out_keep, 0, (size_t)n, st));
         if (mean) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)mean, (int)0xBF800000u, (size_t)n, st));   // -1.0f
@@ -3639,8 +3658,6 @@ int sgm_statistical_outlier_device(sgm_engine *e, const void *d_xyz, const void 
         }
         return SGM_OK;
     }
-    const RadSlot *tab = (const RadSlot *)e->rad_tab.p;
-    const float4 *sorted = (const float4 *)e->rad_sorted.p;
     // 6. per point the k nearest, their mean distance and q: the list of a lane has the smallest capacity that holds k
     HIP_TRY(hipMemsetAsync(sums, 0, STAT_SUM_WORDS * 8, st));
     stage_break(e);
@@ -3648,7 +3665,7 @@ int sgm_statistical_outlier_device(sgm_engine *e, const void *d_xyz, const void 
     const dim3 qgrid((n_in + 255) / 256);
     const uint32_t k = (uint32_t)nb_neighbors;
 #define SGM_STAT_QUERY(CAP) \
-    hipLaunchKernelGGL(k_stat_query<CAP>, qgrid, dim3(256), 0, st, sorted, n_in, G, tab, cap - 1, k, qscale, (uint32_t *)pt, mean)
+    hipLaunchKernelGGL(k_stat_query<CAP>, qgrid, dim3(256), 0, st, (const float4 *)g.sorted, n_in, g.G, g.tab, g.mask, k, qscale, (uint32_t *)pt, mean)
     if (e->debug & SGM_DBG_STAT_WIDE_LIST) SGM_STAT_QUERY(64);
     else if (k <= 8) SGM_STAT_QUERY(8);
     else if (k <= 16) SGM_STAT_QUERY(16);
@@ -3672,10 +3689,10 @@ int sgm_statistical_outlier_device(sgm_engine *e, const void *d_xyz, const void 
     hipLaunchKernelGGL(k_stat_keep, dim3(m), dim3(256), 0, st, (const uint2 *)pt, n, T, keep, mean);
     KCHECK();
     if ((rc = stage_end(e, 1))) return rc;
-    uint32_t total = 0, h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0};
-    if ((rc = radius_compact_kept(e, "stat_compact", keep, xyz, colors, n, d_out_points, d_out_colors, d_out_index, &total, h_ctl))) return rc;
-    if (h_ctl[RAD_CTL_ERR])
-        return set_err(SGM_ERR_HIP, "sgm_statistical_outlier: a point found no slot in a table of %u slots for %u points", cap, n_in);
+    uint32_t total = 0;
+    if ((rc = radius_compact_kept(e, "sgm_statistical_outlier", "stat_compact", g, keep, xyz, colors, n, d_out_points, d_out_colors, d_out_index,
+                                  &total)))
+        return rc;
     *n_kept = (int64_t)total;
     if (out_stats) {
         const uint64_t s[8] = {n_in, n_out, h_sums[STAT_SUM_M], n_in - h_sums[STAT_SUM_M], h_sums[STAT_SUM_A], h_sums[STAT_SUM_B], T, 0};
@@ -3694,33 +3711,15 @@ int sgm_statistical_outlier(sgm_engine *e, const float *xyz, const float *disp, 
         if (out_stats) std::fill(out_stats, out_stats + 8, (uint64_t)0);
         return SGM_OK;
     }
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = e->xyz.ensure((size_t)n * 12)) || (disp && (rc = e->f32.ensure((size_t)n * 4))) || (rc = e->rad_keep.ensure((size_t)n)) ||
-        (out_mean && (rc = e->stat_mean.ensure((size_t)n * 4))) || (out_points && (rc = e->cpts.ensure((size_t)n * 12))) ||
-        (out_index && (rc = e->rad_idx.ensure((size_t)n * 4))))
-        return rc;
-    if (out_colors && ((rc = e->crgb_in.ensure((size_t)n * 3)) || (rc = e->crgb.ensure((size_t)n * 3)))) return rc;
-    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, e->stream));
-    if (disp) HIP_TRY(hipMemcpyAsync(e->f32.p, disp, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    if (out_colors) HIP_TRY(hipMemcpyAsync(e->crgb_in.p, colors_rgb, (size_t)n * 3, hipMemcpyHostToDevice, e->stream));
     int64_t nk = 0;
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if ((rc = sgm_statistical_outlier_device(e, e->xyz.p, disp ? e->f32.p : nullptr, out_colors ? e->crgb_in.p : nullptr, n, nb_neighbors,
-                                             std_ratio, max_radius, origin, e->rad_keep.p, out_mean ? e->stat_mean.p : nullptr,
-                                             out_points ? e->cpts.p : nullptr, out_colors ? e->crgb.p : nullptr,
-                                             out_index ? e->rad_idx.p : nullptr, &nk, stats))) {
-        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
+    const HostOut keep{out_keep, &e->rad_keep, 1, nullptr}, mean{out_mean, &e->stat_mean, 4, nullptr}, pts{out_points, &e->cpts, 12, &nk},
+        rgb{out_colors, &e->crgb, 3, &nk}, idx{out_index, &e->rad_idx, 4, &nk};
+    if (int rc = cloud_host_call(e, xyz, disp, out_colors ? colors_rgb : nullptr, n, {keep, mean, pts, rgb, idx}, [&](void *d_disp, void *d_colors) {
+            return sgm_statistical_outlier_device(e, e->xyz.p, d_disp, d_colors, n, nb_neighbors, std_ratio, max_radius, origin, keep.d(), mean.d(),
+                                                  pts.d(), rgb.d(), idx.d(), &nk, stats);
+        }))
         return rc;
-    }
-    if (out_keep) HIP_TRY(hipMemcpyAsync(out_keep, e->rad_keep.p, (size_t)n, hipMemcpyDeviceToHost, e->stream));
-    if (out_mean) HIP_TRY(hipMemcpyAsync(out_mean, e->stat_mean.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-    if (nk > 0) {
-        if (out_points) HIP_TRY(hipMemcpyAsync(out_points, e->cpts.p, (size_t)nk * 12, hipMemcpyDeviceToHost, e->stream));
-        if (out_colors) HIP_TRY(hipMemcpyAsync(out_colors, e->crgb.p, (size_t)nk * 3, hipMemcpyDeviceToHost, e->stream));
-        if (out_index) HIP_TRY(hipMemcpyAsync(out_index, e->rad_idx.p, (size_t)nk * 4, hipMemcpyDeviceToHost, e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
     *n_kept = nk;
     if (out_stats) std::copy(stats, stats + 8, out_stats);
     return SGM_OK;
@@ -3730,21 +3729,15 @@ int sgm_statistical_outlier(sgm_engine *e, const float *xyz, const float *disp, 
 static int cov_check_args(const sgm_engine *e, const void *xyz, int64_t n, float r, int k, const float *origin, const float *viewpoint,
                           int orient)
 {
-    if (!e || !xyz) return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: null pointer");
-    if (n < 0) return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: n=%lld points", (long long)n);
-    const float r2 = r * r, v = r * 1.03125f;
-    if (!std::isfinite(r) || !(r > 0.0f) || !std::isnormal(r2) || !std::isfinite(1.0f / v) || !std::isfinite(32768.0f / r))
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: radius %g is not finite and positive with a finite normal square", (double)r);
-    if (k < COV_MIN_K || (int64_t)k > RAD_MAX_POINTS)
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: min_neighbors %d outside %d .. 2^24 - 1", k, COV_MIN_K);
-    if (!origin || !std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: the origin is null or not finite");
-    if (!viewpoint || !std::isfinite(viewpoint[0]) || !std::isfinite(viewpoint[1]) || !std::isfinite(viewpoint[2]))
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: the viewpoint is null or not finite");
-    if (orient != 0 && orient != 1) return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: orient %d is neither 0 nor 1", orient);
-    if (n > RAD_MAX_POINTS)
-        return set_err(SGM_ERR_UNSUPPORTED, "sgm_covariance_normals: %lld points, more than 2^24 - 1 (a source index shares a record with its point)", (long long)n);
-    return SGM_OK;
+    return cloud_check_args("sgm_covariance_normals", !e || !xyz, n, "radius", r, 32768.0f, origin, [&](int after) -> int {
+        if (after == 1 && (k < COV_MIN_K || (int64_t)k > RAD_MAX_POINTS))
+            return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: min_neighbors %d outside %d .. 2^24 - 1", k, COV_MIN_K);
+        if (after == 2 && (!viewpoint || !std::isfinite(viewpoint[0]) || !std::isfinite(viewpoint[1]) || !std::isfinite(viewpoint[2])))
+            return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: the viewpoint is null or not finite");
+        if (after == 2 && orient != 0 && orient != 1)
+            return set_err(SGM_ERR_INVALID_ARG, "sgm_covariance_normals: orient %d is neither 0 nor 1", orient);
+        return SGM_OK;
+    });
 }
 
 int sgm_covariance_normals_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, int64_t n, float radius, int min_neighbors,
@@ -3763,8 +3756,6 @@ int sgm_covariance_normals_device(sgm_engine *e, const void *d_xyz, const void *
         (rc = e->rad_keep.ensure((size_t)n)))
         return rc;
     if (e->profile) stage_reset(e);   // the stage record is the call's from here on
-    const float v = radius * 1.03125f;
-    const RadGrid G{1.0f / v, radius * radius, origin[0], origin[1], origin[2]};
     const CovView V{32768.0f / radius, viewpoint[0], viewpoint[1], viewpoint[2], (uint32_t)min_neighbors, (uint32_t)orient};
     const float *xyz = (const float *)d_xyz, *disp = (const float *)d_disp_f32;
     float *normals = (float *)d_out_normals, *curv = (float *)d_out_curvature;
@@ -3772,9 +3763,10 @@ int sgm_covariance_normals_device(sgm_engine *e, const void *d_xyz, const void *
     uint32_t *ctl = (uint32_t *)e->cov_ctl.p;
     hipStream_t st = e->stream;
     static const char *const names[5] = {"cov_count", "cov_clear", "cov_insert", "cov_starts", "cov_sort"};
-    uint32_t n_in = 0, n_out = 0, cap = 0;
+    CloudGrid g;
     // (the keep bytes k_radius_sort zeroes for the points in no cell are nobody's here: they go to the engine's own)
-    if ((rc = radius_build_grid(e, xyz, disp, n, G, (uint8_t *)e->rad_keep.p, counts, names, &n_in, &n_out, &cap))) return rc;
+    if ((rc = radius_build_grid(e, xyz, disp, n, radius, origin, (uint8_t *)e->rad_keep.p, counts, names, &g))) return rc;
+    const uint32_t n_in = g.n_in, n_out = g.n_out;
     if (n_in == 0) {   // nobody has a neighbour
         if (normals) HIP_TRY(hipMemsetAsync(normals, 0, (size_t)n * 12, st));
         if (curv) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)curv, (int)0xBF800000u, (size_t)n, st));   // -1.0f
@@ -3788,18 +3780,17 @@ int sgm_covariance_normals_device(sgm_engine *e, const void *d_xyz, const void *
     }
     const bool separate = (e->debug & SGM_DBG_COV_SEPARATE_SOLVE) != 0, select = (e->debug & SGM_DBG_COV_SELECT_ACCUM) != 0;
     if (separate && (rc = e->cov_mom.ensure((size_t)n_in * COV_WORDS * 8))) return rc;
-    const RadSlot *tab = (const RadSlot *)e->rad_tab.p;
-    const float4 *sorted = (const float4 *)e->rad_sorted.p;
+    const float4 *sorted = g.sorted;
     long long *staged = (long long *)(separate ? e->cov_mom.p : nullptr);
     // 6. per point the moments of its neighbours and (fused) the normal; the points in no cell get their zeros and -1 first
     HIP_TRY(hipMemsetAsync(ctl, 0, COV_CTL_WORDS * 4, st));
     stage_break(e);
     if ((rc = stage_begin(e, "cov_query"))) return rc;
     const bool fill = n_in < (uint64_t)n && (normals || curv);
-    if (fill) hipLaunchKernelGGL(k_cov_fill, dim3(m), dim3(256), 0, st, (const uint2 *)e->rad_pt.p, n, normals, curv);
+    if (fill) hipLaunchKernelGGL(k_cov_fill, dim3(m), dim3(256), 0, st, (const uint2 *)g.slot_rank, n, normals, curv);
     const dim3 qgrid((n_in + 255) / 256);
 #define SGM_COV_QUERY(SEP, SEL) \
-    hipLaunchKernelGGL((k_cov_query<SEP, SEL>), qgrid, dim3(256), 0, st, sorted, n_in, G, tab, cap - 1, V, staged, normals, curv, counts, ctl)
+    hipLaunchKernelGGL((k_cov_query<SEP, SEL>), qgrid, dim3(256), 0, st, sorted, n_in, g.G, g.tab, g.mask, V, staged, normals, curv, counts, ctl)
     if (separate && select) SGM_COV_QUERY(true, true);
     else if (separate) SGM_COV_QUERY(true, false);
     else if (select) SGM_COV_QUERY(false, true);
@@ -3818,8 +3809,7 @@ int sgm_covariance_normals_device(sgm_engine *e, const void *d_xyz, const void *
     HIP_TRY(hipMemcpyAsync(h_ctl, e->rad_ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(h_cov, ctl, sizeof(h_cov), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (h_ctl[RAD_CTL_ERR])
-        return set_err(SGM_ERR_HIP, "sgm_covariance_normals: a point found no slot in a table of %u slots for %u points", cap, n_in);
+    if (h_ctl[RAD_CTL_ERR]) return cloud_no_slot("sgm_covariance_normals", g);
     const uint64_t s[4] = {n_in, n_out, h_cov[COV_CTL_NORMAL], h_cov[COV_CTL_DEGENERATE]};
     std::copy(s, s + 4, out_stats);
     return SGM_OK;
@@ -3834,25 +3824,13 @@ int sgm_covariance_normals(sgm_engine *e, const float *xyz, const float *disp, i
         if (out_stats) std::fill(out_stats, out_stats + 4, (uint64_t)0);
         return SGM_OK;
     }
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = e->xyz.ensure((size_t)n * 12)) || (disp && (rc = e->f32.ensure((size_t)n * 4))) ||
-        (out_normals && (rc = e->cov_nrm.ensure((size_t)n * 12))) || (out_curvature && (rc = e->cov_curv.ensure((size_t)n * 4))) ||
-        (out_counts && (rc = e->rad_cnt.ensure((size_t)n * 4))))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, e->stream));
-    if (disp) HIP_TRY(hipMemcpyAsync(e->f32.p, disp, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
     uint64_t stats[4] = {0, 0, 0, 0};   // (always asked for: the host entry reports a full table whatever the caller wants)
-    if ((rc = sgm_covariance_normals_device(e, e->xyz.p, disp ? e->f32.p : nullptr, n, radius, min_neighbors, origin, viewpoint, orient,
-                                            out_normals ? e->cov_nrm.p : nullptr, out_curvature ? e->cov_curv.p : nullptr,
-                                            out_counts ? e->rad_cnt.p : nullptr, stats))) {
-        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
+    const HostOut nrm{out_normals, &e->cov_nrm, 12, nullptr}, curv{out_curvature, &e->cov_curv, 4, nullptr}, cnt{out_counts, &e->rad_cnt, 4, nullptr};
+    if (int rc = cloud_host_call(e, xyz, disp, nullptr, n, {nrm, curv, cnt}, [&](void *d_disp, void *) {
+            return sgm_covariance_normals_device(e, e->xyz.p, d_disp, n, radius, min_neighbors, origin, viewpoint, orient, nrm.d(), curv.d(), cnt.d(),
+                                                 stats);
+        }))
         return rc;
-    }
-    if (out_normals) HIP_TRY(hipMemcpyAsync(out_normals, e->cov_nrm.p, (size_t)n * 12, hipMemcpyDeviceToHost, e->stream));
-    if (out_curvature) HIP_TRY(hipMemcpyAsync(out_curvature, e->cov_curv.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-    if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, e->rad_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
     if (out_stats) std::copy(stats, stats + 4, out_stats);
     return SGM_OK;
 }
@@ -3860,17 +3838,11 @@ int sgm_covariance_normals(sgm_engine *e, const float *xyz, const float *disp, i
 // ---- density clustering of the point cloud (include/sgm_hip_dbscan.h, kernels_dbscan.h) -------------------------------------------
 static int dbscan_check_args(const sgm_engine *e, const void *xyz, int64_t n, float r, int k, const float *origin, const int64_t *n_clusters)
 {
-    if (!e || !xyz || !n_clusters) return set_err(SGM_ERR_INVALID_ARG, "sgm_cluster_dbscan: null pointer");
-    if (n < 0) return set_err(SGM_ERR_INVALID_ARG, "sgm_cluster_dbscan: n=%lld points", (long long)n);
-    const float r2 = r * r, v = r * 1.03125f;
-    if (!std::isfinite(r) || !(r > 0.0f) || !std::isnormal(r2) || !std::isfinite(1.0f / v))
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_cluster_dbscan: eps %g is not finite and positive with a finite normal square", (double)r);
-    if (k < 1 || (int64_t)k > RAD_MAX_POINTS) return set_err(SGM_ERR_INVALID_ARG, "sgm_cluster_dbscan: min_points %d outside 1 .. 2^24 - 1", k);
-    if (!origin || !std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
-        return set_err(SGM_ERR_INVALID_ARG, "sgm_cluster_dbscan: the origin is null or not finite");
-    if (n > RAD_MAX_POINTS)
-        return set_err(SGM_ERR_UNSUPPORTED, "sgm_cluster_dbscan: %lld points, more than 2^24 - 1 (a source index shares a record with its point)", (long long)n);
-    return SGM_OK;
+    return cloud_check_args("sgm_cluster_dbscan", !e || !xyz || !n_clusters, n, "eps", r, 0.0f, origin, [&](int after) -> int {
+        if (after == 1 && (k < 1 || (int64_t)k > RAD_MAX_POINTS))
+            return set_err(SGM_ERR_INVALID_ARG, "sgm_cluster_dbscan: min_points %d outside 1 .. 2^24 - 1", k);
+        return SGM_OK;
+    });
 }
 
 int sgm_cluster_dbscan_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, int64_t n, float eps, int min_points,
@@ -3891,16 +3863,15 @@ int sgm_cluster_dbscan_device(sgm_engine *e, const void *d_xyz, const void *d_di
         (rc = e->db_parent.ensure((size_t)n * 4)) || (rc = e->db_near.ensure((size_t)n * 4)) || (rc = e->db_rank.ensure((size_t)n * 4)))
         return rc;
     if (e->profile) stage_reset(e);   // the stage record is the call's from here on
-    const float v = eps * 1.03125f;
-    const RadGrid G{1.0f / v, eps * eps, origin[0], origin[1], origin[2]};
     const float *xyz = (const float *)d_xyz, *disp = (const float *)d_disp_f32;
     uint8_t *core = (uint8_t *)(d_out_core ? d_out_core : e->rad_keep.p);
     int *labels = (int *)d_out_labels;
     uint32_t *sizes = (uint32_t *)d_out_sizes;
     hipStream_t st = e->stream;
     static const char *const names[5] = {"dbscan_count", "dbscan_clear", "dbscan_insert", "dbscan_starts", "dbscan_sort"};
-    uint32_t n_in = 0, n_out = 0, cap = 0;
-    if ((rc = radius_build_grid(e, xyz, disp, n, G, core, nullptr, names, &n_in, &n_out, &cap))) return rc;
+    CloudGrid g;
+    if ((rc = radius_build_grid(e, xyz, disp, n, eps, origin, core, nullptr, names, &g))) return rc;
+    const uint32_t n_in = g.n_in, n_out = g.n_out;
     if (n_in == 0) {   // nobody has a neighbour: everything is noise
         if (labels) HIP_TRY(hipMemsetAsync(labels, 0xFF, (size_t)n * 4, st));   // -1
         if (d_out_core) HIP_TRY(hipMemsetAsync(d_out_core, 0, (size_t)n, st));
@@ -3912,9 +3883,8 @@ int sgm_cluster_dbscan_device(sgm_engine *e, const void *d_xyz, const void *d_di
         }
         return SGM_OK;
     }
-    const RadSlot *tab = (const RadSlot *)e->rad_tab.p;
-    float4 *sorted = (float4 *)e->rad_sorted.p;
-    const uint2 *slot_rank = (const uint2 *)e->rad_pt.p;
+    float4 *sorted = g.sorted;
+    const uint2 *slot_rank = g.slot_rank;
     int *parent = (int *)e->db_parent.p;
     uint32_t *nearest = (uint32_t *)e->db_near.p, *rank = (uint32_t *)e->db_rank.p, *ctl = (uint32_t *)e->db_ctl.p, *cnt = (uint32_t *)e->ccount.p;
     const bool gather = (e->debug & SGM_DBG_DBSCAN_GATHER_CORE) != 0;
@@ -3924,7 +3894,7 @@ int sgm_cluster_dbscan_device(sgm_engine *e, const void *d_xyz, const void *d_di
     HIP_TRY(hipMemsetAsync(ctl, 0, DB_CTL_WORDS * 4, st));
     stage_break(e);
     if ((rc = stage_begin(e, "dbscan_core"))) return rc;
-    hipLaunchKernelGGL(k_radius_query<true>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, xyz, slot_rank, n, G, tab, cap - 1,
+    hipLaunchKernelGGL(k_radius_query<true>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, xyz, slot_rank, n, g.G, g.tab, g.mask,
                        (uint32_t)min_points, (uint32_t)min_points, core, (uint32_t *)nullptr);
     if (gather) hipLaunchKernelGGL(k_dbscan_mark<false>, qgrid, dim3(256), 0, st, sorted, n_in, (const uint8_t *)core, parent, nearest);
     else hipLaunchKernelGGL(k_dbscan_mark<true>, qgrid, dim3(256), 0, st, sorted, n_in, (const uint8_t *)core, parent, nearest);
@@ -3932,8 +3902,8 @@ int sgm_cluster_dbscan_device(sgm_engine *e, const void *d_xyz, const void *d_di
     if ((rc = stage_end(e, 2))) return rc;
     // 6, 7. the links between core points and each other point's nearest core point
     if ((rc = stage_begin(e, "dbscan_link"))) return rc;
-    if (gather) hipLaunchKernelGGL(k_dbscan_link<true>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, G, tab, cap - 1, (const uint8_t *)core, parent, nearest);
-    else hipLaunchKernelGGL(k_dbscan_link<false>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, G, tab, cap - 1, (const uint8_t *)core, parent, nearest);
+    if (gather) hipLaunchKernelGGL(k_dbscan_link<true>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, g.G, g.tab, g.mask, (const uint8_t *)core, parent, nearest);
+    else hipLaunchKernelGGL(k_dbscan_link<false>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, g.G, g.tab, g.mask, (const uint8_t *)core, parent, nearest);
     KCHECK();
     if ((rc = stage_end(e, 1))) return rc;
     // 9. the roots in source order are the clusters in the order of their numbers
@@ -3954,8 +3924,7 @@ int sgm_cluster_dbscan_device(sgm_engine *e, const void *d_xyz, const void *d_di
     HIP_TRY(hipMemcpyAsync(h_db, ctl, sizeof(h_db), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&total, cnt + m, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (h_ctl[RAD_CTL_ERR])
-        return set_err(SGM_ERR_HIP, "sgm_cluster_dbscan: a point found no slot in a table of %u slots for %u points", cap, n_in);
+    if (h_ctl[RAD_CTL_ERR]) return cloud_no_slot("sgm_cluster_dbscan", g);
     *n_clusters = (int64_t)total;
     if (out_stats) {
         const uint64_t s[6] = {n_in, n_out, h_db[DB_CTL_CORE], h_db[DB_CTL_BORDER], h_db[DB_CTL_NOISE], total};
@@ -3973,24 +3942,13 @@ int sgm_cluster_dbscan(sgm_engine *e, const float *xyz, const float *disp, int64
         if (out_stats) std::fill(out_stats, out_stats + 6, (uint64_t)0);
         return SGM_OK;
     }
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = e->xyz.ensure((size_t)n * 12)) || (disp && (rc = e->f32.ensure((size_t)n * 4))) || (rc = e->rad_keep.ensure((size_t)n)) ||
-        (out_labels && (rc = e->db_lab.ensure((size_t)n * 4))) || (out_sizes && (rc = e->db_sizes.ensure((size_t)n * 4))))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, e->stream));
-    if (disp) HIP_TRY(hipMemcpyAsync(e->f32.p, disp, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
     int64_t nc = 0;
     uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
-    if ((rc = sgm_cluster_dbscan_device(e, e->xyz.p, disp ? e->f32.p : nullptr, n, eps, min_points, origin, out_labels ? e->db_lab.p : nullptr,
-                                        e->rad_keep.p, out_sizes ? e->db_sizes.p : nullptr, stats, &nc))) {
-        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
+    const HostOut lab{out_labels, &e->db_lab, 4, nullptr}, core{out_core, &e->rad_keep, 1, nullptr}, sizes{out_sizes, &e->db_sizes, 4, &nc};
+    if (int rc = cloud_host_call(e, xyz, disp, nullptr, n, {lab, core, sizes}, [&](void *d_disp, void *) {
+            return sgm_cluster_dbscan_device(e, e->xyz.p, d_disp, n, eps, min_points, origin, lab.d(), core.d(), sizes.d(), stats, &nc);
+        }))
         return rc;
-    }
-    if (out_labels) HIP_TRY(hipMemcpyAsync(out_labels, e->db_lab.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-    if (out_core) HIP_TRY(hipMemcpyAsync(out_core, e->rad_keep.p, (size_t)n, hipMemcpyDeviceToHost, e->stream));
-    if (out_sizes && nc > 0) HIP_TRY(hipMemcpyAsync(out_sizes, e->db_sizes.p, (size_t)nc * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
     *n_clusters = nc;
     if (out_stats) std::copy(stats, stats + 6, out_stats);
     return SGM_OK;

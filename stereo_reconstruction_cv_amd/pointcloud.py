@@ -144,6 +144,26 @@ def _outlier_cloud(who, points_3D, colors, disparity_map, confidence, min_confid
     return pts, disp, colors
 
 
+def _search_radius(who, name, radius, origin, extra_scales=(), numbers=None):
+    """what the searches on the grid of cells accept as their radius (`name` is the caller's word for it) and origin, checked
+    in the engine's float32 arithmetic: (np.float32 r, float32 origin[3]).  extra_scales: the s whose s / r must stay finite as
+    well; numbers: what the 'must be numbers' message names, where that is more than these two"""
+    with np.errstate(all="ignore"):
+        try:
+            r = np.float32(radius)
+            org = np.asarray(origin, np.float32)
+        except (TypeError, ValueError):
+            raise _cv.error(f"{who}: {numbers or name + ' and origin'} must be numbers") from None
+        r2 = r * r
+        if (r.shape != () or not np.isfinite(r) or not r > 0 or not np.isfinite(r2) or r2 < np.finfo(np.float32).tiny
+                or not np.isfinite(np.float32(1.0) / (r * np.float32(1.03125)))
+                or not all(np.isfinite(np.float32(s) / r) for s in extra_scales)):
+            raise _cv.error(f"{who}: {name}={radius!r} is not a finite positive float32 with a finite normal square")
+    if org.shape != (3,) or not np.isfinite(org).all():
+        raise _cv.error(f"{who}: origin={origin!r} is not three finite numbers")
+    return r, org
+
+
 def remove_radius_outlier(points_3D, colors, disparity_map, nb_points, radius, origin=(0, 0, 0), max_count=None, confidence=None,
                           min_confidence=0, return_mask=False, return_counts=False, return_index=False):
     """Radius outlier removal on the GPU: keeps the points that have at least nb_points OTHER points within radius, in source
@@ -160,18 +180,7 @@ def remove_radius_outlier(points_3D, colors, disparity_map, nb_points, radius, o
     source index of each kept point."""
     who = "remove_radius_outlier"
     pts, disp, colors = _outlier_cloud(who, points_3D, colors, disparity_map, confidence, min_confidence)
-    with np.errstate(all="ignore"):
-        try:
-            r = np.float32(radius)
-            org = np.asarray(origin, np.float32)
-        except (TypeError, ValueError):
-            raise _cv.error(f"{who}: radius and origin must be numbers") from None
-        r2 = r * r
-        if (r.shape != () or not np.isfinite(r) or not r > 0 or not np.isfinite(r2) or r2 < np.finfo(np.float32).tiny
-                or not np.isfinite(np.float32(1.0) / (r * np.float32(1.03125)))):
-            raise _cv.error(f"{who}: radius={radius!r} is not a finite positive float32 with a finite normal square")
-    if org.shape != (3,) or not np.isfinite(org).all():
-        raise _cv.error(f"{who}: origin={origin!r} is not three finite numbers")
+    r, org = _search_radius(who, "radius", radius, origin)
     if isinstance(nb_points, bool) or not isinstance(nb_points, (int, np.integer)) or not 1 <= int(nb_points) <= 2 ** 31 - 1:
         raise _cv.error(f"{who}: nb_points={nb_points!r} is not an integer >= 1")
     if max_count is not None and (isinstance(max_count, bool) or not isinstance(max_count, (int, np.integer))
@@ -231,17 +240,7 @@ def remove_statistical_outlier(points_3D, colors, disparity_map, nb_neighbors, s
             raise _cv.error(f"{who}: std_ratio={std_ratio!r} is not a number") from None
         if isinstance(std_ratio, bool) or ratio.shape != () or not np.isfinite(ratio) or not ratio >= 0:
             raise _cv.error(f"{who}: std_ratio={std_ratio!r} is not a finite float32 >= 0")
-        try:
-            r = np.float32(max_radius)
-            org = np.asarray(origin, np.float32)
-        except (TypeError, ValueError):
-            raise _cv.error(f"{who}: max_radius and origin must be numbers") from None
-        r2 = r * r
-        if (r.shape != () or not np.isfinite(r) or not r > 0 or not np.isfinite(r2) or r2 < np.finfo(np.float32).tiny
-                or not np.isfinite(np.float32(1.0) / (r * np.float32(1.03125))) or not np.isfinite(np.float32(524288.0) / r)):
-            raise _cv.error(f"{who}: max_radius={max_radius!r} is not a finite positive float32 with a finite normal square")
-    if org.shape != (3,) or not np.isfinite(org).all():
-        raise _cv.error(f"{who}: origin={origin!r} is not three finite numbers")
+    r, org = _search_radius(who, "max_radius", max_radius, origin, (524288.0,))
     n = pts.size // 3
     if n > RADIUS_MAX_POINTS:
         raise _cv.error(f"{who}: {n} points, more than {RADIUS_MAX_POINTS} (include/sgm_hip_statistical.h)")
@@ -304,19 +303,13 @@ def estimate_normals_radius(points_3D, disparity_map, radius, min_neighbors=3, o
         pts, disp, _ = _outlier_cloud(who, points_3D, None, disparity_map, confidence, min_confidence)
         shape = pts.shape[:-1]
         n = pts.size // 3
-    with np.errstate(all="ignore"):
-        try:
-            r = np.float32(radius)
-            org = np.asarray(origin, np.float32)
+    numbers = "radius, origin and viewpoint"
+    try:
+        with np.errstate(all="ignore"):
             view = np.asarray(viewpoint, np.float32)
-        except (TypeError, ValueError):
-            raise _cv.error(f"{who}: radius, origin and viewpoint must be numbers") from None
-        r2 = r * r
-        if (r.shape != () or not np.isfinite(r) or not r > 0 or not np.isfinite(r2) or r2 < np.finfo(np.float32).tiny
-                or not np.isfinite(np.float32(1.0) / (r * np.float32(1.03125))) or not np.isfinite(np.float32(32768.0) / r)):
-            raise _cv.error(f"{who}: radius={radius!r} is not a finite positive float32 with a finite normal square")
-    if org.shape != (3,) or not np.isfinite(org).all():
-        raise _cv.error(f"{who}: origin={origin!r} is not three finite numbers")
+    except (TypeError, ValueError):
+        raise _cv.error(f"{who}: {numbers} must be numbers") from None
+    r, org = _search_radius(who, "radius", radius, origin, (32768.0,), numbers)
     if view.shape != (3,) or not np.isfinite(view).all():
         raise _cv.error(f"{who}: viewpoint={viewpoint!r} is not three finite numbers")
     if (isinstance(min_neighbors, bool) or not isinstance(min_neighbors, (int, np.integer))
@@ -426,18 +419,7 @@ def cluster_dbscan(points_3D, disparity_map, eps, min_points, origin=(0, 0, 0), 
         pts, disp, _ = _outlier_cloud(who, points_3D, None, disparity_map, confidence, min_confidence)
         shape = pts.shape[:-1]
         n = pts.size // 3
-    with np.errstate(all="ignore"):
-        try:
-            r = np.float32(eps)
-            org = np.asarray(origin, np.float32)
-        except (TypeError, ValueError):
-            raise _cv.error(f"{who}: eps and origin must be numbers") from None
-        r2 = r * r
-        if (r.shape != () or not np.isfinite(r) or not r > 0 or not np.isfinite(r2) or r2 < np.finfo(np.float32).tiny
-                or not np.isfinite(np.float32(1.0) / (r * np.float32(1.03125)))):
-            raise _cv.error(f"{who}: eps={eps!r} is not a finite positive float32 with a finite normal square")
-    if org.shape != (3,) or not np.isfinite(org).all():
-        raise _cv.error(f"{who}: origin={origin!r} is not three finite numbers")
+    r, org = _search_radius(who, "eps", eps, origin)
     if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= int(min_points) <= RADIUS_MAX_POINTS:
         raise _cv.error(f"{who}: min_points={min_points!r} is not an integer in 1 .. {RADIUS_MAX_POINTS}")
     if n > RADIUS_MAX_POINTS:

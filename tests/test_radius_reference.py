@@ -298,3 +298,18 @@ def test_remove_radius_outlier_argument_errors_come_before_any_engine(no_engine)
     # an empty list needs no engine either
     out = rro(np.zeros((0, 3), np.float32), None, None, 4, 0.1, return_mask=True, return_counts=True, return_index=True)
     assert out[0].shape == (0, 3) and out[1] is None and [a.shape for a in out[2:]] == [(0,)] * 3
+
+
+def test_the_outlier_searches_keep_their_registers_on_the_shared_walk():
+    """resource remarks of the build: k_radius_query and k_stat_query, whose loop over the 27 cells is rad_walk with their own
+    state in a predicate and a visitor, without scratch memory and at no fewer waves per SIMD than with the loop written out in
+    each (8 for both orders of k_radius_query; 8, 8, 5, 4 for the lists of 8, 16, 32 and 64 words of k_stat_query)"""
+    txt = open(os.path.join(ROOT, "stereo_reconstruction_cv_amd", "csrc", "resource_usage.txt")).read()
+    blocks = re.findall(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+)", txt, flags=re.S)
+    mine = {n: (int(s), int(o)) for n, s, o in blocks if "k_radius_query" in n or "k_stat_query" in n}
+    floor = {"k_radius_queryILb1E": 8, "k_radius_queryILb0E": 8, "k_stat_queryILi8E": 8, "k_stat_queryILi16E": 8, "k_stat_queryILi32E": 5,
+             "k_stat_queryILi64E": 4}
+    assert len(mine) == len(floor), sorted(mine)
+    for key, waves in floor.items():
+        (scratch, occupancy), = [v for n, v in mine.items() if key in n]
+        assert scratch == 0 and occupancy >= waves, (key, scratch, occupancy)
