@@ -59,7 +59,7 @@ extern "C" {
                              * triangulation of sgm_hip_mesh.h; its vertex normals and the normal image of sgm_hip_normals.h; the
                              * radius outlier removal of sgm_hip_radius.h; the statistical outlier removal of
                              * sgm_hip_statistical.h; the covariance normals of sgm_hip_covariance.h; the density clustering of
-                             * sgm_hip_dbscan.h */
+                             * sgm_hip_dbscan.h; the plane segmentation of sgm_hip_plane.h */
 
 typedef enum {
     SGM_OK = 0,
@@ -330,4 +330,6 @@ int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_r
 #include "sgm_hip_covariance.h"
 /* density clustering of the cloud: core points, their connected components and the border points, on the same grid of cells */
 #include "sgm_hip_dbscan.h"
+/* plane segmentation of the cloud: seeded hypotheses scored on every valid point, the best one refitted from integer moments */
+#include "sgm_hip_plane.h"
 #endif

@@ -9,7 +9,7 @@ from .stereo import (CV_32F, STEREO_COST_BT, STEREO_COST_CENSUS, STEREO_SGBM_MOD
                      INTER_LINEAR, BORDER_CONSTANT, DisparityWLSFilter, createDisparityWLSFilter, wls_weights,
                      lrcConfidence)
 from .pipeline import compute_disparity_map, reconstruct_3D, rectify_pair, run_disparity, valid_point_mask
-from .pointcloud import (cluster_dbscan, largest_clusters, estimate_normals, estimate_normals_radius, mask_by_confidence, read_ply, read_point_cloud, read_triangle_mesh, remove_radius_outlier,
+from .pointcloud import (cluster_dbscan, largest_clusters, segment_plane, plane_inliers, estimate_normals, estimate_normals_radius, mask_by_confidence, read_ply, read_point_cloud, read_triangle_mesh, remove_radius_outlier,
                          remove_statistical_outlier, triangulate_points,
                          triangulate_points_with_normals, valid_points, voxel_down_sample, write_ply, write_point_cloud,
                          write_triangle_mesh)
@@ -27,5 +27,5 @@ __all__ = [
     "voxel_down_sample", "triangulate_points", "write_triangle_mesh", "read_triangle_mesh",
     "estimate_normals", "triangulate_points_with_normals", "write_ply", "read_ply",
     "remove_radius_outlier", "remove_statistical_outlier", "estimate_normals_radius",
-    "cluster_dbscan", "largest_clusters",
+    "cluster_dbscan", "largest_clusters", "segment_plane", "plane_inliers",
 ]

@@ -29,6 +29,7 @@ SGM_DBG_RADIUS_TIGHT_TABLE, SGM_DBG_RADIUS_SOURCE_ORDER = 1 << 24, 1 << 25   # c
 SGM_DBG_STAT_WIDE_LIST = 1 << 26   # csrc/sgm_debug.h: the A/B bit of sgm_statistical_outlier (the 64-word list at every nb_neighbors)
 SGM_DBG_COV_SEPARATE_SOLVE, SGM_DBG_COV_SELECT_ACCUM = 1 << 27, 1 << 28   # csrc/sgm_debug.h: the two A/B bits of sgm_covariance_normals
 SGM_DBG_DBSCAN_GATHER_CORE = 1 << 29   # csrc/sgm_debug.h: the A/B bit of sgm_cluster_dbscan (the core bit gathered by source index)
+SGM_DBG_PLANE_OTHER_COUNT = 1 << 30   # csrc/sgm_debug.h: the A/B bit of sgm_segment_plane (step 5 by the form that is not the default)
 SGM_MAX_STAGES = 32
 
 # every symbol include/sgm_hip.h declares (checked by tests/test_abi.py)
@@ -71,6 +72,12 @@ DBSCAN_EXPORTS = ("sgm_cluster_dbscan", "sgm_cluster_dbscan_device")
 # the stage record of one sgm_cluster_dbscan call with SGM_OPT_PROFILE
 DBSCAN_STAGES = ("dbscan_count", "dbscan_clear", "dbscan_insert", "dbscan_starts", "dbscan_sort", "dbscan_core", "dbscan_link",
                  "dbscan_number", "dbscan_label")
+# include/sgm_hip_plane.h (likewise): plane segmentation of the point cloud
+PLANE_EXPORTS = ("sgm_segment_plane", "sgm_segment_plane_device", "sgm_plane_inliers", "sgm_plane_inliers_device")
+# the stage record of one sgm_segment_plane call with SGM_OPT_PROFILE (plane_moments and plane_solve only with refine = 1;
+# sgm_plane_inliers has the last two)
+PLANE_STAGES = ("plane_valid", "plane_sample", "plane_count", "plane_best", "plane_moments", "plane_solve", "plane_classify",
+                "plane_compact")
 
 
 class SgmParams(C.Structure):
@@ -173,6 +180,10 @@ def load():
     L.sgm_covariance_normals_device.argtypes = [vp, vp, vp, C.c_int64, C.c_float, i32, vp, vp, i32, vp, vp, vp, vp]
     L.sgm_cluster_dbscan.argtypes = [vp, vp, vp, C.c_int64, C.c_float, i32, vp, vp, vp, vp, vp, vp]
     L.sgm_cluster_dbscan_device.argtypes = [vp, vp, vp, C.c_int64, C.c_float, i32, vp, vp, vp, vp, vp, vp]
+    L.sgm_segment_plane.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float, i32, C.c_uint32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sgm_segment_plane_device.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float, i32, C.c_uint32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sgm_plane_inliers.argtypes = [vp, vp, vp, vp, C.c_int64, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.sgm_plane_inliers_device.argtypes = [vp, vp, vp, vp, C.c_int64, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp]
     L.sgm_synchronize.argtypes = [vp]
     L.sgm_get_stage_times.argtypes = [vp, C.POINTER(SgmStageTimes)]
     L.sgm_algorithmic_bytes.argtypes = [pp, i32, i32, i32]
@@ -197,7 +208,7 @@ def load():
     L.sgm_debug_wta_raw_bytes.restype = C.c_longlong
     L.sgm_debug_wta_select_n.argtypes = [i32, i32, vp, i32, vp]
     L.sgm_debug_wta_select_n.restype = i32
-    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS + VOXEL_EXPORTS + MESH_EXPORTS + NORMALS_EXPORTS + RADIUS_EXPORTS + STATISTICAL_EXPORTS + COVARIANCE_EXPORTS + DBSCAN_EXPORTS:
+    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS + VOXEL_EXPORTS + MESH_EXPORTS + NORMALS_EXPORTS + RADIUS_EXPORTS + STATISTICAL_EXPORTS + COVARIANCE_EXPORTS + DBSCAN_EXPORTS + PLANE_EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("sgm_abi_version", "sgm_device_count"):
             fn.restype = i32

@@ -67,12 +67,12 @@ __device__ __forceinline__ double cov_pick(double a, double b, double c, long lo
     return __longlong_as_double((__double_as_longlong(a) & ma) | (__double_as_longlong(b) & mb) | (__double_as_longlong(c) & mc));
 }
 
-// steps 7 to 10 for a point with c >= k neighbours.  false: degenerate (the caller writes zeros and -1)
-__device__ __forceinline__ bool cov_solve(long long s0, long long s1, long long s2, long long s00, long long s01, long long s02,
-                                          long long s11, long long s12, long long s22, uint32_t c, float x, float y, float z,
-                                          const CovView &V, float nrm[3], float &kappa)
+// steps 7 to 9 up to the normalisation, for m terms: the unit normal in binary64 (n0, n1, n2), the diagonal after the sweeps
+// (l0, l1, l2) and its smallest entry.  false: degenerate.  (kernels_plane.h refits a plane with this.)
+__device__ __forceinline__ bool cov_normal(long long s0, long long s1, long long s2, long long s00, long long s01, long long s02,
+                                           long long s11, long long s12, long long s22, double m, double &n0, double &n1, double &n2,
+                                           double &l0, double &l1, double &l2, double &lmin)
 {
-    const double m = (double)(c + 1u);
     const double d0 = (double)s0, d1 = (double)s1, d2 = (double)s2;
     double a00 = (double)s00 - (d0 * d0) / m, a01 = (double)s01 - (d0 * d1) / m, a02 = (double)s02 - (d0 * d2) / m;
     double a11 = (double)s11 - (d1 * d1) / m, a12 = (double)s12 - (d1 * d2) / m, a22 = (double)s22 - (d2 * d2) / m;
@@ -89,17 +89,27 @@ __device__ __forceinline__ bool cov_solve(long long s0, long long s1, long long 
     // column i* of V, i* the first smallest diagonal entry.  The column is picked by masks on the bit patterns: written as selects
     // the compiler turns the choice into a load from a nine-word table in scratch memory.
     const bool pick1 = a11 < a00, pick2 = a22 < (pick1 ? a11 : a00);
-    const double lmin = pick2 ? a22 : (pick1 ? a11 : a00);
+    lmin = pick2 ? a22 : (pick1 ? a11 : a00);
     const long long m2 = pick2 ? -1ll : 0ll, m1 = pick1 && !pick2 ? -1ll : 0ll, m0 = ~(m1 | m2);
-    double n0 = cov_pick(v00, v01, v02, m0, m1, m2), n1 = cov_pick(v10, v11, v12, m0, m1, m2), n2 = cov_pick(v20, v21, v22, m0, m1, m2);
+    n0 = cov_pick(v00, v01, v02, m0, m1, m2), n1 = cov_pick(v10, v11, v12, m0, m1, m2), n2 = cov_pick(v20, v21, v22, m0, m1, m2);
     const double len = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
     n0 = n0 / len, n1 = n1 / len, n2 = n2 / len;
+    l0 = fmax(a00, 0.0), l1 = fmax(a11, 0.0), l2 = fmax(a22, 0.0);
+    return true;
+}
+
+// steps 7 to 10 for a point with c >= k neighbours.  false: degenerate (the caller writes zeros and -1)
+__device__ __forceinline__ bool cov_solve(long long s0, long long s1, long long s2, long long s00, long long s01, long long s02,
+                                          long long s11, long long s12, long long s22, uint32_t c, float x, float y, float z,
+                                          const CovView &V, float nrm[3], float &kappa)
+{
+    double n0, n1, n2, l0, l1, l2, lmin;
+    if (!cov_normal(s0, s1, s2, s00, s01, s02, s11, s12, s22, (double)(c + 1u), n0, n1, n2, l0, l1, l2, lmin)) return false;
     if (V.orient) {
         const double w0 = (double)x - (double)V.wx, w1 = (double)y - (double)V.wy, w2 = (double)z - (double)V.wz;
         if ((n0 * w0 + n1 * w1) + n2 * w2 > 0.0) n0 = -n0, n1 = -n1, n2 = -n2;
     }
     nrm[0] = (float)n0, nrm[1] = (float)n1, nrm[2] = (float)n2;
-    const double l0 = fmax(a00, 0.0), l1 = fmax(a11, 0.0), l2 = fmax(a22, 0.0);
     const double lsum = (l0 + l1) + l2;
     kappa = lsum == 0.0 ? 0.0f : (float)(fmax(lmin, 0.0) / lsum);
     return true;

@@ -49,7 +49,9 @@ enum {
     SGM_DBG_COV_SEPARATE_SOLVE = 1 << 27,   /* steps 7 to 10 in a kernel of their own (k_cov_solve) over ten staged words per point instead of at the end of k_cov_query's lane */
     SGM_DBG_COV_SELECT_ACCUM = 1 << 28,     /* k_cov_query adds zeros for a candidate that is no neighbour instead of branching over the accumulation */
     /* sgm_cluster_dbscan* (tools/dbscan_times.py); SGM_DBG_RADIUS_TIGHT_TABLE acts on its table and SGM_DBG_RADIUS_SOURCE_ORDER on nothing of it; the same bits under all */
-    SGM_DBG_DBSCAN_GATHER_CORE = 1 << 29    /* k_dbscan_link gathers core[source index] per candidate instead of reading the core bit k_dbscan_mark put into the sorted record */
+    SGM_DBG_DBSCAN_GATHER_CORE = 1 << 29,   /* k_dbscan_link gathers core[source index] per candidate instead of reading the core bit k_dbscan_mark put into the sorted record */
+    /* sgm_segment_plane* (tools/plane_times.py); the same bits under both */
+    SGM_DBG_PLANE_OTHER_COUNT = 1 << 30     /* step 5 by the form that is not the default (kernels_plane.h: PLANE_DEFAULT_MFMA): k_plane_count_mfma where k_plane_count_valu is, and the other way round */
 };
 
 /* Plan readout: what normalise + make_plan decide for one compute of a frame of H x W pixels on an engine with these

@@ -35,6 +35,7 @@
 #include "kernels_statistical.h"
 #include "kernels_covariance.h"
 #include "kernels_dbscan.h"
+#include "kernels_plane.h"
 #include "kernels_mesh.h"
 #include "kernels_normals.h"
 
@@ -273,6 +274,7 @@ struct Plan {
     BUF(stat_mean) BUF(stat_sums)                /* sgm_statistical_outlier, beside the radius search's buffers it reuses: the host entry's staged means (float32 [n]) and the call's 64-bit sums m, A, B (kernels_statistical.h); sgm_trim releases the first by name */ \
     BUF(cov_nrm) BUF(cov_curv) BUF(cov_mom) BUF(cov_ctl) /* sgm_covariance_normals, beside the radius search's buffers it reuses: the host entry's staged normals (float32 [n][3]) and curvatures (float32 [n]), the staged moments where the solve is a kernel of its own (int64 [points in range][10]) and the call's two counts (kernels_covariance.h); sgm_trim releases the first three by name */ \
     BUF(db_parent) BUF(db_near) BUF(db_rank) BUF(db_ctl) BUF(db_lab) BUF(db_sizes) /* sgm_cluster_dbscan, beside the radius search's buffers it reuses: per point the union-find link (int32 [n]), the nearest core point (uint32 [n]) and the root's rank (uint32 [n]), the call's three counts, and the host entry's staged labels (int32 [n]) and sizes (uint32 [n]; kernels_dbscan.h); sgm_trim releases all but the counts by name */ \
+    BUF(pl_pts) BUF(pl_hyp) BUF(pl_cnt) BUF(pl_ctl) BUF(pl_inl) BUF(pl_dist) /* sgm_segment_plane, sgm_plane_inliers: the valid points in source order (float4 [n]), the hypotheses (float4 [K]) and their counts (uint32 [K]), the call's control block, and the host entries' staged inlier bytes (uint8 [n]) and distances (float32 [n]; kernels_plane.h); the byte the compaction selects by is rad_keep, the staged rows are cpts, crgb and rad_idx; sgm_trim releases all but the control block by name */ \
     BUF(mesh_code) BUF(mesh_num) BUF(mesh_fcnt) BUF(mesh_vcnt) BUF(mesh_faces) /* sgm_mesh_grid: a code byte per quad (uint8 [H][W]), the pixel -> vertex number map (uint32 [H][W]), the blocks' numbers of faces and of vertices (uint32 [blocks + 1] each), the host entry's staged faces (kernels_mesh.h); sgm_trim releases the first two and the last by name */ \
     BUF(mesh_nrm)                                /* sgm_normals_grid, sgm_mesh_grid_normals: the host entries' staged normals (float32 [H][W][3]; kernels_normals.h); sgm_trim releases it by name */ \
     BUF(headroom)                                /* uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r */ \
@@ -2053,8 +2055,8 @@ int sgm_trim(sgm_engine *e)
         for (HostBuf &b : slot) b.release();
     for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f, &e->vox_tab, &e->vox_slot, &e->mesh_code, &e->mesh_num, &e->mesh_faces, &e->mesh_nrm,
                       &e->rad_tab, &e->rad_sorted, &e->rad_pt, &e->rad_keep, &e->rad_cnt, &e->rad_idx, &e->stat_mean, &e->cov_nrm, &e->cov_curv, &e->cov_mom,
-                      &e->db_parent, &e->db_near, &e->db_rank, &e->db_lab, &e->db_sizes})
-        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps, the staged normals, the radius search's table, records and staging, the staged means of the statistical one and the staged normals, curvatures and moments of the covariance normals and the links, ranks and staging of the clustering come back on the next call
+                      &e->db_parent, &e->db_near, &e->db_rank, &e->db_lab, &e->db_sizes, &e->pl_pts, &e->pl_hyp, &e->pl_cnt, &e->pl_inl, &e->pl_dist})
+        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps, the staged normals, the radius search's table, records and staging, the staged means of the statistical one and the staged normals, curvatures and moments of the covariance normals, the links, ranks and staging of the clustering and the valid list, hypotheses, counts and staging of the plane segmentation come back on the next call
     return check_chain(e);
 }
 
@@ -3952,6 +3954,223 @@ int sgm_cluster_dbscan(sgm_engine *e, const float *xyz, const float *disp, int64
     *n_clusters = nc;
     if (out_stats) std::copy(stats, stats + 6, out_stats);
     return SGM_OK;
+}
+
+// ---- plane segmentation of the point cloud (include/sgm_hip_plane.h, kernels_plane.h) ---------------------------------------------
+// What both pairs of entries refuse, under the entry's name.  fit: the entry has num_iterations and refine; otherwise a model.
+static int plane_check_args(const char *who, const sgm_engine *e, const void *xyz, const void *colors, const void *out_colors, int64_t n,
+                            float t, bool fit, int K, int refine, int select, const float *model, const int64_t *n_inliers)
+{
+    if (!e || !xyz || !n_inliers) return set_err(SGM_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (n < 0) return set_err(SGM_ERR_INVALID_ARG, "%s: n=%lld points", who, (long long)n);
+    if (!std::isfinite(t) || !(t > 0.0f) || !std::isnormal(t) || !std::isfinite(32.0f / t))
+        return set_err(SGM_ERR_INVALID_ARG, "%s: distance_threshold %g is not finite, positive and normal with a finite 32 / t", who, (double)t);
+    if (fit) {
+        if (K < 1 || K > PLANE_MAX_K) return set_err(SGM_ERR_INVALID_ARG, "%s: num_iterations %d outside 1 .. 65536", who, K);
+        if (refine != 0 && refine != 1) return set_err(SGM_ERR_INVALID_ARG, "%s: refine %d is neither 0 nor 1", who, refine);
+    } else {
+        if (!model) return set_err(SGM_ERR_INVALID_ARG, "%s: null pointer", who);
+        const float len2 = (model[0] * model[0] + model[1] * model[1]) + model[2] * model[2];
+        if (!std::isfinite(model[0]) || !std::isfinite(model[1]) || !std::isfinite(model[2]) || !std::isfinite(model[3]) ||
+            !(std::fabs(len2 - 1.0f) <= 0.0009765625f))
+            return set_err(SGM_ERR_INVALID_ARG, "%s: the model is not four finite numbers with a unit normal (squared length %g)", who, (double)len2);
+    }
+    if (select != 0 && select != 1) return set_err(SGM_ERR_INVALID_ARG, "%s: select %d is neither 0 nor 1", who, select);
+    if (out_colors && !colors) return set_err(SGM_ERR_INVALID_ARG, "%s: out_colors requested without colors", who);
+    if (n > RAD_MAX_POINTS) return set_err(SGM_ERR_UNSUPPORTED, "%s: %lld points, more than 2^24 - 1", who, (long long)n);
+    return SGM_OK;
+}
+
+// Both device entries.  K >= 1: the whole definition; K < 0: step 8 alone with the caller's model.  Blocks once, at the end.
+static int plane_run(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors, int64_t n, float t, int K, uint32_t seed,
+                     int refine, int select, const float *model, void *d_out_inlier, void *d_out_distance, void *d_out_points,
+                     void *d_out_colors, void *d_out_index, float *out_model, uint64_t *out_stats, int64_t *n_inliers, int64_t *n_selected)
+{
+    HIP_TRY(hipSetDevice(e->device));
+    const int m = (int)((n + 255) / 256);
+    const bool fit = K >= 1;
+    int rc;
+    if ((rc = e->pl_ctl.ensure(sizeof(PlaneCtl))) || (rc = e->ccount.ensure((size_t)(m + 1) * 4)) || (rc = e->rad_keep.ensure((size_t)n)) ||
+        (fit && ((rc = e->pl_pts.ensure((size_t)n * 16)) || (rc = e->pl_hyp.ensure((size_t)K * 16)) || (rc = e->pl_cnt.ensure((size_t)K * 4)))))
+        return rc;
+    if (e->profile) stage_reset(e);   // the stage record is the call's from here on
+    hipStream_t st = e->stream;
+    PlaneCtl *ctl = (PlaneCtl *)e->pl_ctl.p;
+    uint32_t *cnt = (uint32_t *)e->ccount.p;
+    uint8_t *keep = (uint8_t *)e->rad_keep.p;
+    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(PlaneCtl), st));
+    stage_break(e);
+    if (fit) {
+        float4 *vpts = (float4 *)e->pl_pts.p, *hyp = (float4 *)e->pl_hyp.p;
+        uint32_t *hcnt = (uint32_t *)e->pl_cnt.p;
+        const float qscale = 32.0f / t;
+        HIP_TRY(hipMemsetAsync(hcnt, 0, (size_t)K * 4, st));
+        // 1. the valid points in source order, and their number m in the control block
+        if ((rc = stage_begin(e, "plane_valid"))) return rc;
+        hipLaunchKernelGGL(k_plane_valid_count, dim3(m), dim3(256), 0, st, xyz, disp, n, cnt);
+        hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
+        hipLaunchKernelGGL(k_plane_valid_scatter, dim3(m), dim3(256), 0, st, xyz, disp, n, (const uint32_t *)cnt, m, vpts, ctl);
+        KCHECK();
+        if ((rc = stage_end(e, 3))) return rc;
+        // 3, 4. the hypotheses
+        if ((rc = stage_begin(e, "plane_sample"))) return rc;
+        hipLaunchKernelGGL(k_plane_sample, dim3((K + 255) / 256), dim3(256), 0, st, (const float4 *)vpts, (uint32_t)K, seed, hyp, ctl);
+        KCHECK();
+        if ((rc = stage_end(e, 1))) return rc;
+        // 5. every hypothesis on every valid point: a tile of 64 hypotheses per blockIdx.y, the chunks of points strided over blockIdx.x
+        const int tiles = (K + PLANE_TILE - 1) / PLANE_TILE;
+        const int chunks = (int)((n + PLANE_CHUNK - 1) / PLANE_CHUNK);
+        const dim3 cgrid(std::max(1, std::min(chunks, PLANE_COUNT_BLOCKS / tiles)), tiles);
+        const bool mfma = ((e->debug & SGM_DBG_PLANE_OTHER_COUNT) != 0) != PLANE_DEFAULT_MFMA;
+        if ((rc = stage_begin(e, "plane_count"))) return rc;
+        if (mfma)
+            hipLaunchKernelGGL(k_plane_count_mfma, cgrid, dim3(256), 0, st, (const float4 *)vpts, (const PlaneCtl *)ctl, (const float4 *)hyp,
+                               (uint32_t)K, t, hcnt);
+        else
+            hipLaunchKernelGGL(k_plane_count_valu, cgrid, dim3(256), 0, st, (const float4 *)vpts, (const PlaneCtl *)ctl, (const float4 *)hyp,
+                               (uint32_t)K, t, hcnt);
+        KCHECK();
+        if ((rc = stage_end(e, 1))) return rc;
+        // 6. the best
+        if ((rc = stage_begin(e, "plane_best"))) return rc;
+        hipLaunchKernelGGL(k_plane_best, dim3(1), dim3(1024), 0, st, (const uint32_t *)hcnt, (uint32_t)K, seed, (const float4 *)hyp,
+                           (const float4 *)vpts, ctl);
+        KCHECK();
+        if ((rc = stage_end(e, 1))) return rc;
+        // 7. the refit
+        if (refine) {
+            if ((rc = stage_begin(e, "plane_moments"))) return rc;
+            hipLaunchKernelGGL(k_plane_moments, dim3(std::min(m, PLANE_MOMENT_BLOCKS)), dim3(256), 0, st, (const float4 *)vpts, ctl, t, qscale);
+            KCHECK();
+            if ((rc = stage_end(e, 1))) return rc;
+            if ((rc = stage_begin(e, "plane_solve"))) return rc;
+            hipLaunchKernelGGL(k_plane_solve, dim3(1), dim3(64), 0, st, ctl, qscale);
+            KCHECK();
+            if ((rc = stage_end(e, 1))) return rc;
+        }
+    }
+    // 8. the classification and the selected points through the ordered compaction
+    const float4 given = fit ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(model[0], model[1], model[2], model[3]);
+    if ((rc = stage_begin(e, "plane_classify"))) return rc;
+    hipLaunchKernelGGL(k_plane_classify, dim3(m), dim3(256), 0, st, xyz, disp, n, given, (const PlaneCtl *)(fit ? ctl : nullptr), t, select,
+                       (uint8_t *)d_out_inlier, (float *)d_out_distance, keep, &ctl->n_inliers);
+    KCHECK();
+    if ((rc = stage_end(e, 1))) return rc;
+    if ((rc = stage_begin(e, "plane_compact"))) return rc;
+    hipLaunchKernelGGL(k_radius_keep_count, dim3(m), dim3(256), 0, st, (const uint8_t *)keep, n, cnt);
+    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
+    const bool rows = d_out_points || d_out_colors || d_out_index;
+    if (rows)
+        hipLaunchKernelGGL(k_radius_scatter, dim3(m), dim3(256), 0, st, (const uint8_t *)keep, xyz, colors, n, (const uint32_t *)cnt,
+                           (float *)d_out_points, (uint8_t *)d_out_colors, (uint32_t *)d_out_index);
+    KCHECK();
+    if ((rc = stage_end(e, rows ? 3 : 2))) return rc;
+    PlaneCtl h;
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&total, cnt + m, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_inliers = (int64_t)h.n_inliers;
+    if (n_selected) *n_selected = (int64_t)total;
+    if (out_model) std::copy(h.model, h.model + 4, out_model);
+    if (out_stats) {
+        const uint64_t s[8] = {h.m, h.degenerate, h.kbest, h.cbest, h.m_r, h.n_oor, h.refined, h.found};
+        std::copy(s, s + 8, out_stats);
+    }
+    return SGM_OK;
+}
+
+static void plane_nothing(float *out_model, uint64_t *out_stats, int64_t *n_inliers, int64_t *n_selected)
+{
+    *n_inliers = 0;
+    if (n_selected) *n_selected = 0;
+    if (out_model) std::fill(out_model, out_model + 4, 0.0f);
+    if (out_stats) std::fill(out_stats, out_stats + 8, (uint64_t)0);
+}
+
+int sgm_segment_plane_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int64_t n,
+                             float distance_threshold, int num_iterations, uint32_t seed, int refine, int select, void *d_out_inlier,
+                             void *d_out_distance, void *d_out_points, void *d_out_colors, void *d_out_index, float out_model[4],
+                             uint64_t out_stats[8], int64_t *n_inliers, int64_t *n_selected)
+{
+    if (int rc = plane_check_args("sgm_segment_plane", e, d_xyz, d_colors_rgb, d_out_colors, n, distance_threshold, true, num_iterations,
+                                  refine, select, nullptr, n_inliers))
+        return rc;
+    if (n == 0) return plane_nothing(out_model, out_stats, n_inliers, n_selected), SGM_OK;
+    return plane_run(e, (const float *)d_xyz, (const float *)d_disp_f32, (const uint8_t *)(d_out_colors ? d_colors_rgb : nullptr), n,
+                     distance_threshold, num_iterations, seed, refine, select, nullptr, d_out_inlier, d_out_distance, d_out_points, d_out_colors,
+                     d_out_index, out_model, out_stats, n_inliers, n_selected);
+}
+
+int sgm_plane_inliers_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int64_t n,
+                             const float model[4], float distance_threshold, int select, void *d_out_inlier, void *d_out_distance,
+                             void *d_out_points, void *d_out_colors, void *d_out_index, int64_t *n_inliers, int64_t *n_selected)
+{
+    if (int rc = plane_check_args("sgm_plane_inliers", e, d_xyz, d_colors_rgb, d_out_colors, n, distance_threshold, false, 0, 0, select, model,
+                                  n_inliers))
+        return rc;
+    if (n == 0) return plane_nothing(nullptr, nullptr, n_inliers, n_selected), SGM_OK;
+    return plane_run(e, (const float *)d_xyz, (const float *)d_disp_f32, (const uint8_t *)(d_out_colors ? d_colors_rgb : nullptr), n,
+                     distance_threshold, -1, 0u, 0, select, model, d_out_inlier, d_out_distance, d_out_points, d_out_colors, d_out_index, nullptr,
+                     nullptr, n_inliers, n_selected);
+}
+
+// the host entries of both: the staging, the device entry `run`, the results
+extern "C++" {   // (a template: this part of the file has C linkage)
+template <class Run>
+static int plane_host_call(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int64_t n, uint8_t *out_inlier,
+                           float *out_distance, float *out_points, uint8_t *out_colors, uint32_t *out_index, int64_t *n_inliers,
+                           int64_t *n_selected, Run run)
+{
+    int64_t ni = 0, ns = 0;
+    const HostOut inl{out_inlier, &e->pl_inl, 1, nullptr}, dist{out_distance, &e->pl_dist, 4, nullptr}, pts{out_points, &e->cpts, 12, &ns},
+        rgb{out_colors, &e->crgb, 3, &ns}, idx{out_index, &e->rad_idx, 4, &ns};
+    if (int rc = cloud_host_call(e, xyz, disp, out_colors ? colors_rgb : nullptr, n, {inl, dist, pts, rgb, idx}, [&](void *d_disp, void *d_colors) {
+            return run(d_disp, d_colors, inl.d(), dist.d(), pts.d(), rgb.d(), idx.d(), &ni, &ns);
+        }))
+        return rc;
+    *n_inliers = ni;
+    if (n_selected) *n_selected = ns;
+    return SGM_OK;
+}
+}  // extern "C++"
+
+int sgm_segment_plane(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int64_t n, float distance_threshold,
+                      int num_iterations, uint32_t seed, int refine, int select, uint8_t *out_inlier, float *out_distance, float *out_points,
+                      uint8_t *out_colors, uint32_t *out_index, float out_model[4], uint64_t out_stats[8], int64_t *n_inliers,
+                      int64_t *n_selected)
+{
+    if (int rc = plane_check_args("sgm_segment_plane", e, xyz, colors_rgb, out_colors, n, distance_threshold, true, num_iterations, refine,
+                                  select, nullptr, n_inliers))
+        return rc;
+    if (n == 0) return plane_nothing(out_model, out_stats, n_inliers, n_selected), SGM_OK;
+    float model[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (int rc = plane_host_call(e, xyz, disp, colors_rgb, n, out_inlier, out_distance, out_points, out_colors, out_index, n_inliers, n_selected,
+                                 [&](void *d_disp, void *d_colors, void *d_inl, void *d_dist, void *d_pts, void *d_rgb, void *d_idx, int64_t *ni,
+                                     int64_t *ns) {
+                                     return sgm_segment_plane_device(e, e->xyz.p, d_disp, d_colors, n, distance_threshold, num_iterations, seed,
+                                                                     refine, select, d_inl, d_dist, d_pts, d_rgb, d_idx, model, stats, ni, ns);
+                                 }))
+        return rc;
+    if (out_model) std::copy(model, model + 4, out_model);
+    if (out_stats) std::copy(stats, stats + 8, out_stats);
+    return SGM_OK;
+}
+
+int sgm_plane_inliers(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int64_t n, const float model[4],
+                      float distance_threshold, int select, uint8_t *out_inlier, float *out_distance, float *out_points, uint8_t *out_colors,
+                      uint32_t *out_index, int64_t *n_inliers, int64_t *n_selected)
+{
+    if (int rc = plane_check_args("sgm_plane_inliers", e, xyz, colors_rgb, out_colors, n, distance_threshold, false, 0, 0, select, model, n_inliers))
+        return rc;
+    if (n == 0) return plane_nothing(nullptr, nullptr, n_inliers, n_selected), SGM_OK;
+    return plane_host_call(e, xyz, disp, colors_rgb, n, out_inlier, out_distance, out_points, out_colors, out_index, n_inliers, n_selected,
+                           [&](void *d_disp, void *d_colors, void *d_inl, void *d_dist, void *d_pts, void *d_rgb, void *d_idx, int64_t *ni,
+                               int64_t *ns) {
+                               return sgm_plane_inliers_device(e, e->xyz.p, d_disp, d_colors, n, model, distance_threshold, select, d_inl, d_dist,
+                                                               d_pts, d_rgb, d_idx, ni, ns);
+                           });
 }
 
 // ---- triangle mesh from the organised cloud (include/sgm_hip_mesh.h, kernels_mesh.h) and its normals (include/sgm_hip_normals.h,

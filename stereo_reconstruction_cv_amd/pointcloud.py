@@ -22,6 +22,10 @@
     cluster_dbscan(points_3D, disparity_map, eps, min_points, ...)         the cloud split into the objects it holds: a cluster number
                  per point or -1 for noise, on the GPU (include/sgm_hip_dbscan.h; NOT Open3D's cluster_dbscan), and
     largest_clusters(labels, sizes, count, min_size)                       the mask of the largest of them, usable as a confidence map
+    segment_plane(points_3D, colors, disparity_map, distance_threshold, ...)   the dominant plane of the cloud (floor, table, wall)
+                 and the mask of the points on it, or with invert=True off it, on the GPU (include/sgm_hip_plane.h; NOT Open3D's
+                 segment_plane), and
+    plane_inliers(points_3D, colors, disparity_map, plane_model, distance_threshold, ...)   a model found once applied to other clouds
     write_ply(path, points, colors, normals, triangles) / read_ply(path)   one PLY writer for a cloud or a mesh, with or without normals
 
 The compaction runs on the GPU (ordered, so the result equals numpy's `points_3D[mask]`); the
@@ -488,6 +492,190 @@ def largest_clusters(labels, sizes, count=1, min_size=1):
     chosen = np.zeros(sz.size + 1, np.uint8)
     chosen[order] = 1
     return chosen[np.where(lab >= 0, lab, sz.size)]
+
+
+PLANE_STATS = ("valid", "degenerate", "best", "best_count", "refit_points", "out_of_refit_range", "refined", "found")
+PLANE_MAX_ITERATIONS = 65536
+
+
+def _plane_threshold(who, distance_threshold):
+    """the distance threshold as the engine's float32, checked as step 2 of include/sgm_hip_plane.h checks it"""
+    with np.errstate(all="ignore"):
+        try:
+            t = np.float32(distance_threshold)
+        except (TypeError, ValueError):
+            raise _cv.error(f"{who}: distance_threshold must be a number") from None
+        if (t.shape != () or not np.isfinite(t) or not t > 0 or t < np.finfo(np.float32).tiny
+                or not np.isfinite(np.float32(32.0) / t)):
+            raise _cv.error(f"{who}: distance_threshold={distance_threshold!r} is not a finite positive normal float32 with a finite 32 / t")
+    return t
+
+
+def _plane_call(who, points_3D, colors, disparity_map, confidence, min_confidence, select, flags, host, device):
+    """what segment_plane and plane_inliers share behind their argument checks: the cloud on the host or on the device, the call
+    (host(engine, pts, disp, colors) or device(engine, pts, disp, colors, n, outputs...)), and the optional results in their order.
+    Returns (head, mask, points, colors, index, distances): head is what the call returns in front of the per-point results."""
+    return_points, return_index, return_distances = flags
+    on_device = _cv._is_torch(points_3D)
+    if on_device:
+        import torch
+        pts, disp = _device_cloud(who, points_3D, disparity_map, confidence, min_confidence)
+        if colors is not None and (not _cv._is_torch(colors) or colors.device != pts.device or colors.dtype != torch.uint8
+                                   or tuple(colors.shape) != tuple(pts.shape)):
+            raise _cv.error(f"{who}: with a tensor points_3D colors must be a uint8 tensor of its shape on the same GPU")
+        colors = None if colors is None else colors.contiguous()
+        shape, n = tuple(pts.shape[:-1]), pts.numel() // 3
+    else:
+        pts, disp, colors = _outlier_cloud(who, points_3D, colors, disparity_map, confidence, min_confidence)
+        shape, n = pts.shape[:-1], pts.size // 3
+    if n > RADIUS_MAX_POINTS:
+        raise _cv.error(f"{who}: {n} points, more than {RADIUS_MAX_POINTS} (include/sgm_hip_plane.h)")
+    want_index = return_index or bool(select)      # (the inverted mask is made from the selected indices)
+    if on_device:
+        dev = pts.device
+        inl = torch.zeros(shape, dtype=torch.uint8, device=dev)
+        dist = torch.full(shape, float("nan"), dtype=torch.float32, device=dev) if return_distances else None
+        p = torch.empty((n, 3), dtype=torch.float32, device=dev) if return_points else None
+        c = torch.empty((n, 3), dtype=torch.uint8, device=dev) if return_points and colors is not None else None
+        idx = torch.empty(n, dtype=torch.int32, device=dev) if want_index else None      # (the bits of uint32 indices < 2^24)
+        head, ns = None, 0
+        if n:
+            e = _cv.get_engine(_cv._DEFAULT, dev.index)
+            torch.cuda.synchronize(dev)      # the inputs were made on torch's stream, the call runs on the engine's
+            ptr = lambda t: None if t is None else t.data_ptr()
+            head, ns = device(e, pts.data_ptr(), ptr(disp), ptr(colors), n, inl.data_ptr(), ptr(dist), ptr(p), ptr(c), ptr(idx))
+        p, c, idx = (None if a is None else a[:ns].clone() for a in (p, c, idx))
+        mask = inl
+        if select:
+            mask = torch.zeros(n, dtype=torch.uint8, device=dev)
+            mask[idx.to(torch.int64)] = 1
+            mask = mask.reshape(shape)
+    else:
+        head = None
+        inl, dist = np.zeros(shape, np.uint8), (np.full(shape, np.nan, np.float32) if return_distances else None)
+        p = np.zeros((0, 3), np.float32) if return_points else None
+        c = np.zeros((0, 3), np.uint8) if return_points and colors is not None else None
+        idx = np.zeros(0, np.uint32) if want_index else None
+        if n:      # (an empty cloud needs no engine)
+            head, inl, dist, p, c, idx = host(_cv.get_engine(_cv._DEFAULT), pts, disp, colors, want_index)
+            inl = inl.reshape(shape)
+            dist = None if dist is None else dist.reshape(shape)
+        mask = inl
+        if select:
+            mask = np.zeros(n, np.uint8)
+            mask[idx] = 1
+            mask = mask.reshape(shape)
+    return head, mask, p, c, idx if return_index else None, dist
+
+
+def _plane_results(first, mask, p, c, idx, dist, stats, flags):
+    return_points, return_index, return_distances = flags
+    out = first + (mask,)
+    if return_points:
+        out += (p, c)
+    if return_index:
+        out += (idx,)
+    if return_distances:
+        out += (dist,)
+    if stats is not None:
+        out += (stats,)
+    return out if len(out) > 1 else out[0]
+
+
+def segment_plane(points_3D, colors, disparity_map, distance_threshold, ransac_n=3, num_iterations=1000, seed=0, refine=True,
+                  invert=False, confidence=None, min_confidence=0, return_points=False, return_index=False, return_distances=False,
+                  return_stats=False):
+    """Plane segmentation of the cloud, on the GPU: the dominant plane (floor, table, wall) as plane_model = (a, b, c, d) with
+    a x + b y + c z + d = 0 and (a, b, c) a unit normal, and the mask of the points within distance_threshold of it.  num_iterations
+    hypotheses, each through three valid points drawn by a counter-based hash of seed, are ALL scored on EVERY valid point; the one
+    with the most inliers wins (ties: the lowest index); with refine its inliers are refitted by the covariance of integer moments
+    (offsets from one of its points quantised to distance_threshold / 32, out to +-16384 thresholds); the cloud is classified with
+    the refitted model; the normal points to the side of the origin, where the camera is, so the signed distances are heights
+    above a floor.  The definition is include/sgm_hip_plane.h, our own, and the result is the same bits on every run: it is NOT
+    Open3D's segment_plane -- no random state, no probability-based early stop, no ransac_n other than 3 -- and with fewer than
+    three valid points or inliers no plane is found: the model is (0, 0, 0, 0) and the mask empty.
+    points_3D (H, W, 3) with disparity_map (H, W) -- a point takes part iff X, Y, Z are finite and its disparity > 0, and with a
+    confidence map also confidence >= min_confidence, as in valid_points -- or an (N, 3) list with disparity_map=None (every
+    finite point takes part); numpy arrays, or HIP tensors (float32, on the GPU), which stay on the device.  colors: uint8 of the
+    shape of points_3D, or None.
+    Returns (plane_model float32 (4), mask[, points, colors][, index][, distances][, stats]): mask uint8 of the shape of
+    disparity_map (of (N,) for a list), 1 on the inliers -- with invert=True on the valid points that are NOT inliers --, usable as
+    the `confidence` of valid_points, cluster_dbscan and the other cloud calls with min_confidence=1; points float32 (M, 3),
+    colors uint8 (M, 3) or None and index uint32 (int32 for tensors) (M,): the masked points in source order; distances float32 of
+    the mask's shape, the signed distance of every valid point and NaN elsewhere; stats a dict: valid, degenerate (hypotheses),
+    best, best_count, refit_points, out_of_refit_range, refined, found.
+
+    The chain this exists for -- the objects standing on a floor:
+
+        model, off_floor = segment_plane(points_3D, None, disparity_map, 0.02, invert=True)
+        labels, sizes = cluster_dbscan(points_3D, disparity_map, eps, min_points, confidence=off_floor, min_confidence=1, return_sizes=True)
+        objects = largest_clusters(labels, sizes, count=5)
+        points, colors = valid_points(points_3D, colors, disparity_map, confidence=objects, min_confidence=1)
+
+    In short segment_plane(..., invert=True) -> cluster_dbscan(confidence=mask) -> largest_clusters -> valid_points.  Repeated calls
+    with the previous inverted mask as confidence peel plane after plane.  plane_inliers applies a model found once to other clouds.
+    """
+    who = "segment_plane"
+    if isinstance(ransac_n, bool) or not isinstance(ransac_n, (int, np.integer)) or int(ransac_n) != 3:
+        raise _cv.error(f"{who}: ransac_n={ransac_n!r}: only 3 is offered (include/sgm_hip_plane.h)")
+    t = _plane_threshold(who, distance_threshold)
+    if (isinstance(num_iterations, bool) or not isinstance(num_iterations, (int, np.integer))
+            or not 1 <= int(num_iterations) <= PLANE_MAX_ITERATIONS):
+        raise _cv.error(f"{who}: num_iterations={num_iterations!r} is not an integer in 1 .. {PLANE_MAX_ITERATIONS}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) <= 2 ** 32 - 1:
+        raise _cv.error(f"{who}: seed={seed!r} is not an integer in 0 .. 2^32 - 1")
+    K, seed, refine, select = int(num_iterations), int(seed), bool(refine), int(bool(invert))
+    flags = (bool(return_points), bool(return_index), bool(return_distances))
+
+    def host(e, pts, disp, col, want_index):
+        model, inl, dist, p, c, idx, st, _ = e.segment_plane_host(pts, disp, col, float(t), K, seed, refine, select, flags[2], flags[0],
+                                                                  want_index)
+        return (model, st), inl, dist, p, c, idx
+
+    def device(e, d_xyz, d_disp, d_col, n, d_inl, d_dist, d_p, d_c, d_idx):
+        model, st, _, ns = e.segment_plane_device(d_xyz, d_disp, d_col, n, float(t), K, seed, refine, select, d_inl, d_dist, d_p, d_c, d_idx)
+        return (model, st), ns
+
+    head, mask, p, c, idx, dist = _plane_call(who, points_3D, colors, disparity_map, confidence, min_confidence, select, flags, host, device)
+    model, st = head if head is not None else (np.zeros(4, np.float32), np.zeros(8, np.uint64))
+    stats = dict(zip(PLANE_STATS, (int(x) for x in st))) if return_stats else None
+    return _plane_results((model,), mask, p, c, idx, dist, stats, flags)
+
+
+def plane_inliers(points_3D, colors, disparity_map, plane_model, distance_threshold, invert=False, confidence=None, min_confidence=0,
+                  return_points=False, return_index=False, return_distances=False):
+    """The classification of segment_plane alone, on the GPU, with the caller's plane_model (a, b, c, d) -- a fixed rig fits its floor
+    once and applies it to every frame: the mask of the valid points with |a x + b y + c z + d| <= distance_threshold, the sum as
+    three binary32 fused multiply-adds from d (include/sgm_hip_plane.h, step 8; NOT Open3D's select_by_index on its own inliers).
+    plane_model: four finite numbers whose (a, b, c) has a squared length within 2^-10 of 1 in float32.  The cloud, colors,
+    confidence, invert and the return_ flags are segment_plane's.
+    Returns mask, or with any of the return_ flags a tuple (mask[, points, colors][, index][, distances])."""
+    who = "plane_inliers"
+    with np.errstate(all="ignore"):
+        try:
+            model = np.asarray(plane_model.cpu() if _cv._is_torch(plane_model) else plane_model, np.float32)
+        except (TypeError, ValueError):
+            raise _cv.error(f"{who}: plane_model must be four numbers") from None
+        ok = model.shape == (4,) and np.isfinite(model).all()
+        if ok:
+            len2 = (model[0] * model[0] + model[1] * model[1]) + model[2] * model[2]
+            ok = bool(np.abs(len2 - np.float32(1)) <= np.float32(2.0 ** -10))
+    if not ok:
+        raise _cv.error(f"{who}: plane_model={plane_model!r} is not four finite numbers with a unit normal")
+    t = _plane_threshold(who, distance_threshold)
+    select = int(bool(invert))
+    flags = (bool(return_points), bool(return_index), bool(return_distances))
+
+    def host(e, pts, disp, col, want_index):
+        inl, dist, p, c, idx, _ = e.plane_inliers_host(pts, disp, col, model, float(t), select, flags[2], flags[0], want_index)
+        return None, inl, dist, p, c, idx
+
+    def device(e, d_xyz, d_disp, d_col, n, d_inl, d_dist, d_p, d_c, d_idx):
+        _, ns = e.plane_inliers_device(d_xyz, d_disp, d_col, n, model, float(t), select, d_inl, d_dist, d_p, d_c, d_idx)
+        return None, ns
+
+    _, mask, p, c, idx, dist = _plane_call(who, points_3D, colors, disparity_map, confidence, min_confidence, select, flags, host, device)
+    return _plane_results((), mask, p, c, idx, dist, None, flags)
 
 
 MESH_MAX_PIXELS = 1 << 26

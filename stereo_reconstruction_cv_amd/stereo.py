@@ -404,6 +404,80 @@ class Engine:
                                                  d_labels, d_core, d_sizes, stats.ctypes.data, C.byref(nc)))
         return int(nc.value), stats
 
+    # -- plane segmentation of the point cloud (include/sgm_hip_plane.h) --
+    @staticmethod
+    def _plane_host_args(xyz, disp, colors, return_distances, return_points, return_index):
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = xyz.shape[0]
+        disp = None if disp is None else np.ascontiguousarray(disp, np.float32).reshape(-1)
+        colors = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        inl = np.zeros(n, np.uint8)
+        dist = np.full(n, np.nan, np.float32) if return_distances else None
+        pts = np.empty((n, 3), np.float32) if return_points else None
+        rgb = np.empty((n, 3), np.uint8) if return_points and colors is not None else None
+        idx = np.empty(n, np.uint32) if return_index else None
+        return xyz, n, disp, colors, inl, dist, pts, rgb, idx
+
+    def segment_plane_host(self, xyz: np.ndarray, disp: np.ndarray | None, colors: np.ndarray | None, distance_threshold: float,
+                           num_iterations: int = 1000, seed: int = 0, refine: bool = True, select: int = 0,
+                           return_distances: bool = False, return_points: bool = True, return_index: bool = False):
+        """sgm_segment_plane: float32 points (n, 3) or (H, W, 3), float32 disparities (n) or (H, W) or None, uint8 colours of the
+        points' shape or None.  Returns (model float32 (4), inlier uint8 (n), distances float32 (n) or None, points float32 (M, 3)
+        or None, colors uint8 (M, 3) or None, index uint32 (M) or None, stats uint64 (8), n_inliers): the M selected points --
+        the inliers (select 0) or the valid points off the plane (select 1) -- in source order; stats is valid points, degenerate
+        hypotheses, k*, its count, inliers in refit range, inliers out of it, refined, found."""
+        xyz, n, disp, colors, inl, dist, pts, rgb, idx = self._plane_host_args(xyz, disp, colors, return_distances, return_points,
+                                                                               return_index)
+        model, stats = np.zeros(4, np.float32), np.zeros(8, np.uint64)
+        ni, ns = C.c_int64(0), C.c_int64(0)
+        at = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.sgm_segment_plane(self._h, xyz.ctypes.data, at(disp), at(colors), n, float(distance_threshold), int(num_iterations),
+                                         int(seed), int(bool(refine)), int(select), inl.ctypes.data, at(dist), at(pts), at(rgb), at(idx),
+                                         model.ctypes.data, stats.ctypes.data, C.byref(ni), C.byref(ns)))
+        cut = lambda a: None if a is None else a[:ns.value].copy()
+        return model, inl, dist, cut(pts), cut(rgb), cut(idx), stats, int(ni.value)
+
+    def segment_plane_device(self, d_xyz: int, d_dispf: int | None, d_colors: int | None, n: int, distance_threshold: float,
+                             num_iterations: int = 1000, seed: int = 0, refine: bool = True, select: int = 0,
+                             d_inlier: int | None = None, d_distance: int | None = None, d_points: int | None = None,
+                             d_out_colors: int | None = None, d_index: int | None = None):
+        """sgm_segment_plane_device: device addresses; d_inlier (uint8) and d_distance (float32) have n entries, d_points,
+        d_out_colors and d_index (uint32) room for n rows, and the selected points go to their front in source order.  Returns
+        (model float32 (4), stats uint64 (8), n_inliers, n_selected) after synchronising the engine's stream, once."""
+        model, stats = np.zeros(4, np.float32), np.zeros(8, np.uint64)
+        ni, ns = C.c_int64(0), C.c_int64(0)
+        _check(self._L.sgm_segment_plane_device(self._h, d_xyz, d_dispf, d_colors, int(n), float(distance_threshold), int(num_iterations),
+                                                int(seed), int(bool(refine)), int(select), d_inlier, d_distance, d_points, d_out_colors,
+                                                d_index, model.ctypes.data, stats.ctypes.data, C.byref(ni), C.byref(ns)))
+        return model, stats, int(ni.value), int(ns.value)
+
+    def plane_inliers_host(self, xyz: np.ndarray, disp: np.ndarray | None, colors: np.ndarray | None, plane_model,
+                           distance_threshold: float, select: int = 0, return_distances: bool = False, return_points: bool = True,
+                           return_index: bool = False):
+        """sgm_plane_inliers: step 8 of sgm_segment_plane on the caller's model (a, b, c, d).  Returns (inlier uint8 (n), distances
+        float32 (n) or None, points float32 (M, 3) or None, colors uint8 (M, 3) or None, index uint32 (M) or None, n_inliers)."""
+        xyz, n, disp, colors, inl, dist, pts, rgb, idx = self._plane_host_args(xyz, disp, colors, return_distances, return_points,
+                                                                               return_index)
+        model = np.ascontiguousarray(plane_model, np.float32).reshape(4)
+        ni, ns = C.c_int64(0), C.c_int64(0)
+        at = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.sgm_plane_inliers(self._h, xyz.ctypes.data, at(disp), at(colors), n, model.ctypes.data, float(distance_threshold),
+                                         int(select), inl.ctypes.data, at(dist), at(pts), at(rgb), at(idx), C.byref(ni), C.byref(ns)))
+        cut = lambda a: None if a is None else a[:ns.value].copy()
+        return inl, dist, cut(pts), cut(rgb), cut(idx), int(ni.value)
+
+    def plane_inliers_device(self, d_xyz: int, d_dispf: int | None, d_colors: int | None, n: int, plane_model, distance_threshold: float,
+                             select: int = 0, d_inlier: int | None = None, d_distance: int | None = None, d_points: int | None = None,
+                             d_out_colors: int | None = None, d_index: int | None = None):
+        """sgm_plane_inliers_device: device addresses as in segment_plane_device.  Returns (n_inliers, n_selected) after
+        synchronising the engine's stream."""
+        model = np.ascontiguousarray(plane_model, np.float32).reshape(4)
+        ni, ns = C.c_int64(0), C.c_int64(0)
+        _check(self._L.sgm_plane_inliers_device(self._h, d_xyz, d_dispf, d_colors, int(n), model.ctypes.data, float(distance_threshold),
+                                                int(select), d_inlier, d_distance, d_points, d_out_colors, d_index, C.byref(ni),
+                                                C.byref(ns)))
+        return int(ni.value), int(ns.value)
+
     # -- triangle mesh from the organised cloud (include/sgm_hip_mesh.h) --
     def mesh_grid_host(self, xyz: np.ndarray, disp: np.ndarray, colors: np.ndarray | None, max_diff: float = 1.0):
         """sgm_mesh_grid: float32 points (H, W, 3), float32 disparities (H, W), uint8 colours (H, W, 3) or None.  Returns
