@@ -16,6 +16,12 @@
 //                preFilterCap 63, 3 * (255 + 63) = 954 once the byte-valued prefilter wraps), added in registers
 //                before it enters the ring: nothing downstream of it differs from gray.
 //   k_vsum     : vertical running box sum of hsum rows -> block cost C (no +P2 bias).
+//   k_pix      : byte pipeline (default): the per-pixel cost as one byte per (x, d); one wave per (row, column chunk),
+//                lanes span the disparities.  No window state: the chunk's segment of the six right-image planes is
+//                staged in LDS widened to 16 bits, in two copies one element apart, and a block of four columns takes
+//                its windows as aligned LDS reads -- the vector ALU does the Birchfield-Tomasi arithmetic and nothing
+//                else.
+//   k_box_u8   : the whole box filter from those bytes -> block cost C.
 #pragma once
 #include "sgm_device.h"
 
@@ -319,79 +325,142 @@ __global__ __launch_bounds__(64) void k_hsum(Geom g, const uint2 *__restrict__ l
 // box filter becomes one kernel that reads it back (k_box_u8).  HBM traffic of the cost stage:
 // 0.5 V written + ~0.55 V read + V written, against 3.1 V of k_hsum + k_vsum_ring.
 
-// pix(x, y, d) = BT(gradient channel) + (BT(raw channel) >> 2), one wave per (row, chunk of XL
-// columns), lanes span the disparities, sliding right-feature windows as in k_hsum.
+// pix(x, y, d) = BT(gradient channel) + (BT(raw channel) >> 2), one wave per (row, chunk of XL <= PIX_XL
+// columns), lanes span the disparities.
+//
+// The right-feature windows come ready-made from LDS; the loop keeps no window state.  Lane l holds the disparities
+// 2 NP l .. 2 NP l + 2 NP - 1 as NP packed pairs of 16-bit halves.  In the mirrored planes the byte of (column j,
+// disparity index d) is element (j1 - j) + d of the chunk's segment, so the window of column j + 1 is the window of
+// column j moved down by ONE element.  The segment of each of the six planes is staged WIDENED to 16-bit elements, in
+// two copies: copy 0 holds element e at index PIX_MARGIN + pad + e, copy 1 holds it one index further on.  Then
+//   - the window of column j is NP dwords at an even element index of copy 0 when (j - j0) is even, and the SAME
+//     address of copy 1 when it is odd;
+//   - pad = (4 - ((j1 - j0) & 3)) & 3 makes the window of the chunk's first column start at an element index that is a
+//     multiple of 4 in every lane with NP >= 2 (the lane stride is 2 NP elements): the NP dwords are 8-byte aligned
+//     ds_read_b64 (a _b64 LDS access off its natural alignment is replayed at 64 cycles: DESIGN.md 4.5), and stay so
+//     because a block of four columns moves the per-lane base by four elements = 8 bytes.  NP = 1 reads dwords;
+//   - a block of four columns j .. j + 3, (j - j0) % 4 == 0, reads per plane and copy the NP dwords B at column j's
+//     window and the dword A in front of them: columns j, j + 1 take B of copy 0, copy 1; columns j + 2, j + 3 take
+//     (A, B[0 .. NP - 2]) of copy 0, copy 1.  Every register is used as it arrives: no shifts, no byte merges.
+// PIX_MARGIN elements in front of the segment keep A inside the copy for the chunk's last (partial) block, whose
+// absent columns are read and not used.  Copy and plane strides are compile-time constants and multiples of 16 bytes
+// from the 16-byte-aligned dynamic base; the kernel has no static LDS.
+constexpr int PIX_XL = 128;    // most columns per chunk (the engine's COST_XL)
+constexpr int PIX_MARGIN = 4;  // elements in front of the segment; >= 3 (A of copy 1 in a block that starts at column j1), a multiple of 4
+// elements per copy: margin + pad (<= 3, and (j1 - j0) + pad <= PIX_XL) + the lanes' 128 NP + one for copy 1's shift, in 16-byte units
+template <int NP> constexpr int pix_copy_elems() { return (PIX_MARGIN + PIX_XL + 128 * NP + 1 + 7) & ~7; }
+template <int NP> constexpr int pix_lds_bytes() { return 12 * 2 * pix_copy_elems<NP>(); }
+
 template <int NP>
 __global__ __launch_bounds__(64) void k_pix(Geom g, const uint2 *__restrict__ lrec, const uint8_t *__restrict__ rplanes,
-                                            uint8_t *__restrict__ pix, int XL, int nchunks, int lrec_bytes, int seg_len,
+                                            uint8_t *__restrict__ pix, int XL, int nchunks,
                                             int y_base /* the launch covers rows y_base .. y_base + gridDim.x / nchunks - 1 */)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint8_t *seg = smem + lrec_bytes;  // (the first lrec_bytes are unused since the left records are read by scalar loads)
+    constexpr int CSB = 2 * pix_copy_elems<NP>();  // bytes per copy; plane c, copy k starts at (2 c + k) * CSB
     const int lane = threadIdx.x;
     const int unit = blockIdx.x;
     const int yr = __builtin_amdgcn_readfirstlane(unit / nchunks), ck = unit - yr * nchunks;  // (uniform: see uniform_rsrc)
     const int y = y_base + yr;
     const int W1 = g.W1, W = g.W;
-    const int j0 = ck * XL, j1 = min(j0 + XL, W1) - 1;
+    const int j0 = ck * XL, j1 = __builtin_amdgcn_readfirstlane(min(j0 + XL, W1) - 1);  // (uniform, and seen to be: the tail's tests are scalar)
     const bool active = 2 * NP * lane < g.D;
+    const int e0 = PIX_MARGIN + ((4 - ((j1 - j0) & 3)) & 3);  // index of the segment's element 0 in copy 0
     {
+        // Staging: element s of the segment is position base_j1 + s of row y of each plane, zero outside the image.  The
+        // loads go through one buffer descriptor per plane that covers exactly the row, so a position outside it reads
+        // zero, and no load hangs on a test: the NIT / 2 * 6 loads of a trip are in flight together, two round trips to
+        // memory per chunk (plain loads behind a test per position made three dependent ones per 64 elements, eighteen
+        // at NP = 2).  NIT covers the longest segment; what it stages past a shorter one lies inside the copy
+        // (static_assert) and is read by no lane.
+        constexpr int NIT = (PIX_XL - 1 + 128 * NP + 63) / 64;
+        static_assert(NIT % 2 == 0 && PIX_MARGIN + 3 + 64 * NIT + 1 <= pix_copy_elems<NP>(), "staging stays inside a copy");
         const int base_j1 = W - 1 - (j1 + g.minX1) + g.minD;  // mirrored position of (column j1, disparity index 0)
-        const int len = (j1 - j0) + 128 * NP;
         const int64_t psz = (int64_t)g.H * W;
-        for (int s = lane; s < len; s += 64) {
-            const int pos = base_j1 + s;
-            const bool ok = pos >= 0 && pos < W;
+        __amdgpu_buffer_rsrc_t rrow[6];
 #pragma unroll
-            for (int c = 0; c < 6; c++)
-                seg[c * seg_len + s] = ok ? rplanes[c * psz + (int64_t)y * W + pos] : (uint8_t)0;
+        for (int c = 0; c < 6; c++) rrow[c] = uniform_rsrc(rplanes, c * psz + (int64_t)y * W, W);
+        int pos = base_j1 + lane;
+        uint16_t *d = (uint16_t *)smem + e0 + lane;
+        int trips = 2;  // (two trips, and the count hidden: unrolled, the whole would be a longer block than the column loop)
+        asm volatile("" : "+s"(trips));
+#pragma unroll 1
+        for (int half = 0; half < trips; half++) {
+            uint16_t v[NIT / 2][6];
+#pragma unroll
+            for (int it = 0; it < NIT / 2; it++) {
+                const int p = pos + 64 * it;
+                const int voff = p >= 0 && p < W ? p : W;  // (W: past the descriptor's range, whatever the offset arithmetic does with a negative one)
+#pragma unroll
+                for (int c = 0; c < 6; c++) v[it][c] = __builtin_amdgcn_raw_buffer_load_b8(rrow[c], voff, 0, 0);
+            }
+#pragma unroll
+            for (int it = 0; it < NIT / 2; it++)
+#pragma unroll
+                for (int c = 0; c < 6; c++) {
+                    d[(2 * c) * (CSB / 2) + 64 * it] = v[it][c];
+                    d[(2 * c + 1) * (CSB / 2) + 64 * it + 1] = v[it][c];
+                }
+            pos += 64 * (NIT / 2);
+            d += 64 * (NIT / 2);
         }
     }
     __syncthreads();
-    uint32_t w[6][NP];
-    {
-        const int off = (j1 - j0) + 2 * NP * lane;
-#pragma unroll
-        for (int c = 0; c < 6; c++)
-#pragma unroll
-            for (int i = 0; i < NP; i++)
-                w[c][i] = (uint32_t)seg[c * seg_len + off + 2 * i] | ((uint32_t)seg[c * seg_len + off + 2 * i + 1] << 16);
-    }
     // this row of the output; lanes past D store nowhere (offset beyond the descriptor)
     const int row_bytes = W1 * g.D;
     const __amdgpu_buffer_rsrc_t orow = uniform_rsrc(pix, (int64_t)y * row_bytes, row_bytes);
     const int voff = active ? 2 * NP * lane : row_bytes;
     // The left pixel's record is the same for every lane: it is read with SCALAR loads straight from `lrec` and its six
     // bytes are splat into packed pairs on the scalar unit -- these launches run several waves per SIMD, so scalar
-    // work rides beside the other waves' vector instructions, and the kernel is bound by the vector ALU (round 3:
-    // 58 -> 47 vector instructions per column at NP = 2; the six v_perm splats of a VGPR-held record and the LDS tap
-    // address additions -- now immediates on a per-iteration base -- were a fifth of them).
+    // work rides beside the other waves' vector instructions (round 3: 58 -> 47 vector instructions per column at NP = 2;
+    // the six v_perm splats of a VGPR-held record were a tenth of them; with the windows read from LDS it is 33.5).
     // (constant address space: k_features wrote the records before this launch; hipcc uses scalar loads only there -- through
     // the global pointer the buffer stores below count as possible writers and the loads stay vector loads)
     typedef const __attribute__((address_space(4))) v2u32 *crec_ptr;  // (a plain vector type: HIP's uint2 class has no constructor from that address space)
     // (wave-uniform address; v_readfirstlane on both halves, or the 64-bit row arithmetic keeps it in VGPRs: see uniform_rsrc)
     const uint64_t la = (uint64_t)(uintptr_t)(lrec + ((int64_t)y * W + (j0 + g.minX1)));
-    const uint32_t la_lo = __builtin_amdgcn_readfirstlane((uint32_t)la), la_hi = __builtin_amdgcn_readfirstlane((uint32_t)(la >> 32));
+    uint32_t la_v0 = (uint32_t)la, la_v1 = (uint32_t)(la >> 32);
+    asm volatile("" : "+v"(la_v0), "+v"(la_v1));  // (where hipcc does the row arithmetic on the scalar unit it would drop the two reads below)
+    const uint32_t la_lo = __builtin_amdgcn_readfirstlane(la_v0), la_hi = __builtin_amdgcn_readfirstlane(la_v1);
     const crec_ptr lrow = (crec_ptr)(uintptr_t)(((uint64_t)la_hi << 32) | la_lo);  // (uint32_t first: the builtin returns int)
     auto splat = [](uint32_t v) __attribute__((always_inline)) { return v | (v << 16); };
     int so = j0 * g.D;
-    // one column: shift the six windows by the new bytes nw[] (not for the chunk's first column), cost, store
-    auto column = [&](const v2u32 rec, bool shift, const uint32_t (&nw)[6]) __attribute__((always_inline)) {
-        if (shift) {
+    // the reads of one block of four columns: per plane c and copy k, [0] is the dword A in front of the first column's
+    // window and [1 .. NP] are the window's dwords B
+    struct Win {
+        uint32_t r[6][2][NP + 1];
+    };
+    auto read_block = [&](int lo /* this lane's A of plane 0, copy 0 */) __attribute__((always_inline)) {
+        Win q;
 #pragma unroll
-            for (int c = 0; c < 6; c++) {
+        for (int c = 0; c < 6; c++)
 #pragma unroll
-                for (int i = NP - 1; i >= 1; i--) w[c][i] = __builtin_amdgcn_alignbit(w[c][i], w[c][i - 1], 16);
-                w[c][0] = (w[c][0] << 16) | nw[c];
+            for (int k = 0; k < 2; k++) {
+                const uint8_t *p = smem + lo + (2 * c + k) * CSB;
+                q.r[c][k][0] = *(const uint32_t *)p;
+                if constexpr (NP == 1) {
+                    q.r[c][k][1] = *(const uint32_t *)(p + 4);
+                } else {
+#pragma unroll
+                    for (int h = 0; h < NP / 2; h++) {
+                        const v2u32 b = *(const v2u32 *)(p + 4 + 8 * h);  // 8-byte aligned: see the pad
+                        q.r[c][k][1 + 2 * h] = b.x;
+                        q.r[c][k][2 + 2 * h] = b.y;
+                    }
+                }
             }
-        }
+        return q;
+    };
+    // column u (0 .. 3) of a block: the windows are registers of the block's reads; cost, store
+    auto column = [&](const v2u32 rec, const Win &q, const int u) __attribute__((always_inline)) {
+        const int k = u & 1, f = 1 - (u >> 1);
         const uint32_t U = splat(rec.x & 0xffu), U0 = splat((rec.x >> 8) & 0xffu), U1 = splat((rec.x >> 16) & 0xffu);
         const uint32_t R = splat(rec.y & 0xffu), R0 = splat((rec.y >> 8) & 0xffu), R1 = splat((rec.y >> 16) & 0xffu);
         uint32_t pv[NP];
 #pragma unroll
         for (int i = 0; i < NP; i++) {
-            const uint32_t a = bt_pair(U, U0, U1, w[0][i], w[1][i], w[2][i]);
-            const uint32_t b = bt_pair(R, R0, R1, w[3][i], w[4][i], w[5][i]);
+            const uint32_t a = bt_pair(U, U0, U1, q.r[0][k][f + i], q.r[1][k][f + i], q.r[2][k][f + i]);
+            const uint32_t b = bt_pair(R, R0, R1, q.r[3][k][f + i], q.r[4][k][f + i], q.r[5][k][f + i]);
             pv[i] = pk_add(a, pk_shr_u(b, 2));
         }
         // low byte of every int16 half: 2*NP bytes per lane, ascending d
@@ -407,37 +476,27 @@ __global__ __launch_bounds__(64) void k_pix(Geom g, const uint2 *__restrict__ lr
         }
         so += g.D;
     };
-    const uint32_t none[6] = {0, 0, 0, 0, 0, 0};
-    column(lrow[0], false, none);
-    int j = j0 + 1;
-    // per-lane LDS address of the six planes' new byte for column j + 3 (the last of a block of four); the bytes of
-    // columns j .. j + 3 are then at immediate offsets 3 .. 0
-    int tp[6];
-#pragma unroll
-    for (int c = 0; c < 6; c++) tp[c] = c * seg_len + 2 * NP * lane + (j1 - j0) - (j - j0) - 3;
-    // four columns per iteration: their 24 window bytes are read first (one counted wait instead of a
-    // full lgkmcnt(0) drain per column), then the four columns are computed from registers
+    int j = j0;
+    // per-lane LDS address of A for the block that starts at column j: plane 0, copy 0, the dword in front of the window
+    // of column j; the other planes and copies are immediate offsets, and a block moves it down by four elements
+    int lo = 2 * (e0 + (j1 - j0) + 2 * NP * lane) - 4;
+    // four columns per iteration: the block's windows are read first (one counted wait instead of a full lgkmcnt(0)
+    // drain per column), then the four columns are computed from those registers
     for (; j + 3 <= j1; j += 4) {
-        uint32_t nb[4][6];
         v2u32 rec[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) rec[u] = lrow[j - j0 + u];
+        const Win q = read_block(lo);
+        lo -= 8;
 #pragma unroll
-        for (int u = 0; u < 4; u++)
-#pragma unroll
-            for (int c = 0; c < 6; c++) nb[u][c] = seg[tp[c] + (3 - u)];
-#pragma unroll
-        for (int c = 0; c < 6; c++) tp[c] -= 4;
-#pragma unroll
-        for (int u = 0; u < 4; u++) column(rec[u], true, nb[u]);
+        for (int u = 0; u < 4; u++) column(rec[u], q, u);
     }
-    for (; j <= j1; j++) {
-        uint32_t nb[6];
-#pragma unroll
-        for (int c = 0; c < 6; c++) nb[c] = seg[tp[c] + 3];
-#pragma unroll
-        for (int c = 0; c < 6; c++) tp[c] -= 1;
-        column(lrow[j - j0], true, nb);
+    // the last one to three columns: the same reads (absent columns' registers come from the margin, unused)
+    if (j <= j1) {
+        const Win q = read_block(lo);
+        column(lrow[j - j0], q, 0);
+        if (j + 1 <= j1) column(lrow[j - j0 + 1], q, 1);
+        if (j + 2 <= j1) column(lrow[j - j0 + 2], q, 2);
     }
 }
 

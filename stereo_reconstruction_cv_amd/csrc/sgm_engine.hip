@@ -982,14 +982,13 @@ static void launch_pix(const Geom &g, const uint2 *lrec, const uint8_t *rpl, uin
         hipLaunchKernelGGL(k_pix_px, dim3((g.W1 + 255) / 256, g.H), dim3(256), (size_t)6 * (256 + g.D), st, g, lrec, rpl, px);
         return;
     }
-    const int nchunks = cost_chunks(g), nj = COST_XL + 2;
-    const int lrec_b = ((nj * 8) + 15) & ~15;
-    const int seg_l = (nj + 128 * g.NP + 15) & ~15;
-    const size_t lds = (size_t)lrec_b + 6 * (size_t)seg_l;
+    // LDS: the six planes' segments widened to 16 bits, two copies each (kernels_cost.h: 6.2 / 9.2 / 15.2 KiB at NP = 1 / 2 / 4)
+    static_assert(COST_XL <= PIX_XL, "k_pix sizes its LDS copies for chunks of at most PIX_XL columns");
+    const int nchunks = cost_chunks(g);
     dim3 grid((unsigned)((int64_t)g.H * nchunks)), block(64);
-    if (g.NP == 1) hipLaunchKernelGGL(k_pix<1>, grid, block, lds, st, g, lrec, rpl, px, COST_XL, nchunks, lrec_b, seg_l, 0);
-    else if (g.NP == 2) hipLaunchKernelGGL(k_pix<2>, grid, block, lds, st, g, lrec, rpl, px, COST_XL, nchunks, lrec_b, seg_l, 0);
-    else hipLaunchKernelGGL(k_pix<4>, grid, block, lds, st, g, lrec, rpl, px, COST_XL, nchunks, lrec_b, seg_l, 0);
+    if (g.NP == 1) hipLaunchKernelGGL(k_pix<1>, grid, block, (size_t)pix_lds_bytes<1>(), st, g, lrec, rpl, px, COST_XL, nchunks, 0);
+    else if (g.NP == 2) hipLaunchKernelGGL(k_pix<2>, grid, block, (size_t)pix_lds_bytes<2>(), st, g, lrec, rpl, px, COST_XL, nchunks, 0);
+    else hipLaunchKernelGGL(k_pix<4>, grid, block, (size_t)pix_lds_bytes<4>(), st, g, lrec, rpl, px, COST_XL, nchunks, 0);
 }
 
 // census: Hamming distances of the descriptors as bytes, where launch_pix puts its bytes.  D <= 32: one thread per pixel
