@@ -59,7 +59,8 @@ extern "C" {
                              * triangulation of sgm_hip_mesh.h; its vertex normals and the normal image of sgm_hip_normals.h; the
                              * radius outlier removal of sgm_hip_radius.h; the statistical outlier removal of
                              * sgm_hip_statistical.h; the covariance normals of sgm_hip_covariance.h; the density clustering of
-                             * sgm_hip_dbscan.h; the plane segmentation of sgm_hip_plane.h */
+                             * sgm_hip_dbscan.h; the plane segmentation of sgm_hip_plane.h; the rigid registration of
+                             * sgm_hip_icp.h */
 
 typedef enum {
     SGM_OK = 0,
@@ -332,4 +333,6 @@ int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_r
 #include "sgm_hip_dbscan.h"
 /* plane segmentation of the cloud: seeded hypotheses scored on every valid point, the best one refitted from integer moments */
 #include "sgm_hip_plane.h"
+/* rigid registration of two clouds: iterated closest points on the target's grid of cells, the sums in one fixed tree */
+#include "sgm_hip_icp.h"
 #endif

@@ -78,6 +78,11 @@ PLANE_EXPORTS = ("sgm_segment_plane", "sgm_segment_plane_device", "sgm_plane_inl
 # sgm_plane_inliers has the last two)
 PLANE_STAGES = ("plane_valid", "plane_sample", "plane_count", "plane_best", "plane_moments", "plane_solve", "plane_classify",
                 "plane_compact")
+# include/sgm_hip_icp.h (likewise): rigid registration of two point clouds
+ICP_EXPORTS = ("sgm_register_icp", "sgm_register_icp_device", "sgm_evaluate_registration", "sgm_evaluate_registration_device",
+               "sgm_transform_points", "sgm_transform_points_device", "sgm_icp_solve")
+# the stage record of one sgm_register_icp call with SGM_OPT_PROFILE: the target's grid, then the last evaluation
+ICP_STAGES = ("icp_count", "icp_clear", "icp_insert", "icp_starts", "icp_sort", "icp_correspond", "icp_terms", "icp_reduce")
 
 
 class SgmParams(C.Structure):
@@ -184,6 +189,14 @@ def load():
     L.sgm_segment_plane_device.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float, i32, C.c_uint32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.sgm_plane_inliers.argtypes = [vp, vp, vp, vp, C.c_int64, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp]
     L.sgm_plane_inliers_device.argtypes = [vp, vp, vp, vp, C.c_int64, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp]
+    f64, dp = C.c_double, C.POINTER(C.c_double)
+    L.sgm_register_icp.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_float, vp, vp, i32, i32, f64, f64, vp, dp, dp, vp, vp, vp, vp]
+    L.sgm_register_icp_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_float, vp, vp, i32, i32, f64, f64, vp, dp, dp, vp, vp, vp, vp]
+    L.sgm_evaluate_registration.argtypes = [vp, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_float, vp, vp, dp, dp, vp, vp, vp]
+    L.sgm_evaluate_registration_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_float, vp, vp, dp, dp, vp, vp, vp]
+    L.sgm_transform_points.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp]
+    L.sgm_transform_points_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp]
+    L.sgm_icp_solve.argtypes = [vp, i32, vp, vp, C.POINTER(i32)]
     L.sgm_synchronize.argtypes = [vp]
     L.sgm_get_stage_times.argtypes = [vp, C.POINTER(SgmStageTimes)]
     L.sgm_algorithmic_bytes.argtypes = [pp, i32, i32, i32]
@@ -208,7 +221,7 @@ def load():
     L.sgm_debug_wta_raw_bytes.restype = C.c_longlong
     L.sgm_debug_wta_select_n.argtypes = [i32, i32, vp, i32, vp]
     L.sgm_debug_wta_select_n.restype = i32
-    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS + VOXEL_EXPORTS + MESH_EXPORTS + NORMALS_EXPORTS + RADIUS_EXPORTS + STATISTICAL_EXPORTS + COVARIANCE_EXPORTS + DBSCAN_EXPORTS + PLANE_EXPORTS:
+    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS + VOXEL_EXPORTS + MESH_EXPORTS + NORMALS_EXPORTS + RADIUS_EXPORTS + STATISTICAL_EXPORTS + COVARIANCE_EXPORTS + DBSCAN_EXPORTS + PLANE_EXPORTS + ICP_EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("sgm_abi_version", "sgm_device_count"):
             fn.restype = i32

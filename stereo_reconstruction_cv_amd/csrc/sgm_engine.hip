@@ -36,6 +36,7 @@
 #include "kernels_covariance.h"
 #include "kernels_dbscan.h"
 #include "kernels_plane.h"
+#include "kernels_icp.h"
 #include "kernels_mesh.h"
 #include "kernels_normals.h"
 
@@ -275,6 +276,7 @@ struct Plan {
     BUF(cov_nrm) BUF(cov_curv) BUF(cov_mom) BUF(cov_ctl) /* sgm_covariance_normals, beside the radius search's buffers it reuses: the host entry's staged normals (float32 [n][3]) and curvatures (float32 [n]), the staged moments where the solve is a kernel of its own (int64 [points in range][10]) and the call's two counts (kernels_covariance.h); sgm_trim releases the first three by name */ \
     BUF(db_parent) BUF(db_near) BUF(db_rank) BUF(db_ctl) BUF(db_lab) BUF(db_sizes) /* sgm_cluster_dbscan, beside the radius search's buffers it reuses: per point the union-find link (int32 [n]), the nearest core point (uint32 [n]) and the root's rank (uint32 [n]), the call's three counts, and the host entry's staged labels (int32 [n]) and sizes (uint32 [n]; kernels_dbscan.h); sgm_trim releases all but the counts by name */ \
     BUF(pl_pts) BUF(pl_hyp) BUF(pl_cnt) BUF(pl_ctl) BUF(pl_inl) BUF(pl_dist) /* sgm_segment_plane, sgm_plane_inliers: the valid points in source order (float4 [n]), the hypotheses (float4 [K]) and their counts (uint32 [K]), the call's control block, and the host entries' staged inlier bytes (uint8 [n]) and distances (float32 [n]; kernels_plane.h); the byte the compaction selects by is rad_keep, the staged rows are cpts, crgb and rad_idx; sgm_trim releases all but the control block by name */ \
+    BUF(icp_corr) BUF(icp_d2) BUF(icp_part) BUF(icp_ctl) BUF(icp_txyz) BUF(icp_tdisp) BUF(icp_tnrm) /* sgm_register_icp, sgm_evaluate_registration, sgm_transform_points, beside the radius search's buffers they reuse for the target's grid: per source point the correspondence (int32 [ns]) and its squared distance (float32 [ns]), the blocks' partial sums (double [blocks of 256][28]), the result record and the counts of one evaluation, and the host entries' staged target points, disparities and normals (kernels_icp.h); the staged source is xyz and f32; sgm_trim releases all but the record by name */ \
     BUF(mesh_code) BUF(mesh_num) BUF(mesh_fcnt) BUF(mesh_vcnt) BUF(mesh_faces) /* sgm_mesh_grid: a code byte per quad (uint8 [H][W]), the pixel -> vertex number map (uint32 [H][W]), the blocks' numbers of faces and of vertices (uint32 [blocks + 1] each), the host entry's staged faces (kernels_mesh.h); sgm_trim releases the first two and the last by name */ \
     BUF(mesh_nrm)                                /* sgm_normals_grid, sgm_mesh_grid_normals: the host entries' staged normals (float32 [H][W][3]; kernels_normals.h); sgm_trim releases it by name */ \
     BUF(headroom)                                /* uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r */ \
@@ -349,6 +351,7 @@ struct sgm_engine {
     hipStream_t copy_in = nullptr, copy_out = nullptr;
     hipEvent_t ev_group = nullptr;
     HostBuf pin_left, pin_right, pin_disp;
+    HostBuf pin_icp;                      // sgm_register_icp: the 232-byte result record and the three counts of one evaluation
     hipEvent_t ev_done = nullptr;
 
     // shape of the last compute
@@ -1952,6 +1955,7 @@ void sgm_destroy(sgm_engine *e)
     e->pin_left.release();
     e->pin_right.release();
     e->pin_disp.release();
+    e->pin_icp.release();
     if (e->ev_done) (void)hipEventDestroy(e->ev_done);
     if (e->peer) sgm_destroy(e->peer);
     if (e->peer2) sgm_destroy(e->peer2);
@@ -2050,12 +2054,14 @@ int sgm_trim(sgm_engine *e)
     e->pin_left.release();
     e->pin_right.release();
     e->pin_disp.release();
+    e->pin_icp.release();
     for (auto &slot : e->pin_io)
         for (HostBuf &b : slot) b.release();
     for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f, &e->vox_tab, &e->vox_slot, &e->mesh_code, &e->mesh_num, &e->mesh_faces, &e->mesh_nrm,
                       &e->rad_tab, &e->rad_sorted, &e->rad_pt, &e->rad_keep, &e->rad_cnt, &e->rad_idx, &e->stat_mean, &e->cov_nrm, &e->cov_curv, &e->cov_mom,
-                      &e->db_parent, &e->db_near, &e->db_rank, &e->db_lab, &e->db_sizes, &e->pl_pts, &e->pl_hyp, &e->pl_cnt, &e->pl_inl, &e->pl_dist})
-        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps, the staged normals, the radius search's table, records and staging, the staged means of the statistical one and the staged normals, curvatures and moments of the covariance normals, the links, ranks and staging of the clustering and the valid list, hypotheses, counts and staging of the plane segmentation come back on the next call
+                      &e->db_parent, &e->db_near, &e->db_rank, &e->db_lab, &e->db_sizes, &e->pl_pts, &e->pl_hyp, &e->pl_cnt, &e->pl_inl, &e->pl_dist,
+                      &e->icp_corr, &e->icp_d2, &e->icp_part, &e->icp_txyz, &e->icp_tdisp, &e->icp_tnrm})
+        (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps, the staged normals, the radius search's table, records and staging, the staged means of the statistical one and the staged normals, curvatures and moments of the covariance normals, the links, ranks and staging of the clustering and the valid list, hypotheses, counts and staging of the plane segmentation and the correspondences, partial sums and staged target of the registration come back on the next call
     return check_chain(e);
 }
 
@@ -4170,6 +4176,356 @@ int sgm_plane_inliers(sgm_engine *e, const float *xyz, const float *disp, const 
                                return sgm_plane_inliers_device(e, e->xyz.p, d_disp, d_colors, n, model, distance_threshold, select, d_inl, d_dist,
                                                                d_pts, d_rgb, d_idx, ni, ns);
                            });
+}
+
+// ---- rigid registration of two point clouds (include/sgm_hip_icp.h, kernels_icp.h) ------------------------------------------------
+// step 6 of the definition: LDL^T without pivoting, host, binary64, fixed order (the build has -ffp-contract=off).  false: degenerate.
+static bool icp_solve6(const double s[ICP_SUMS], double x[6])
+{
+    double A[6][6], L[6][6], D[6], v[6], y[6];
+    for (int r = 0, k = 0; r < 6; r++)
+        for (int q = r; q < 6; q++, k++) A[r][q] = A[q][r] = s[k];
+    for (int j = 0; j < 6; j++) {
+        for (int k = 0; k < j; k++) v[k] = L[j][k] * D[k];
+        double dj = A[j][j];
+        for (int k = 0; k < j; k++) dj = dj - L[j][k] * v[k];
+        if (!(std::isfinite(dj) && dj > 0.0)) return false;
+        D[j] = dj;
+        for (int i = j + 1; i < 6; i++) {
+            double t = A[i][j];
+            for (int k = 0; k < j; k++) t = t - L[i][k] * v[k];
+            L[i][j] = t / dj;
+        }
+    }
+    for (int i = 0; i < 6; i++) {
+        y[i] = s[21 + i];
+        for (int k = 0; k < i; k++) y[i] = y[i] - L[i][k] * y[k];
+    }
+    for (int i = 0; i < 6; i++) y[i] = y[i] / D[i];
+    for (int i = 5; i >= 0; i--) {
+        x[i] = y[i];
+        for (int k = i + 1; k < 6; k++) x[i] = x[i] - L[k][i] * x[k];
+    }
+    for (int i = 0; i < 6; i++)
+        if (!std::isfinite(x[i])) return false;
+    return true;
+}
+
+// step 7: the quaternion (1, x0 / 2, x1 / 2, x2 / 2) as a rotation with the division by its squared norm written out, then dT * T
+static void icp_update(const double x[6], const double Tin[16], double Tout[16])
+{
+    const double qx = x[0] * 0.5, qy = x[1] * 0.5, qz = x[2] * 0.5;
+    const double xx = qx * qx, yy = qy * qy, zz = qz * qz;
+    const double nn = ((1.0 + xx) + yy) + zz;
+    const double dT[3][4] = {{(((1.0 + xx) - yy) - zz) / nn, (2.0 * (qx * qy - qz)) / nn, (2.0 * (qx * qz + qy)) / nn, x[3]},
+                             {(2.0 * (qx * qy + qz)) / nn, (((1.0 - xx) + yy) - zz) / nn, (2.0 * (qy * qz - qx)) / nn, x[4]},
+                             {(2.0 * (qx * qz - qy)) / nn, (2.0 * (qy * qz + qx)) / nn, (((1.0 - xx) - yy) + zz) / nn, x[5]}};
+    double out[16];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 4; j++)
+            out[4 * i + j] = ((dT[i][0] * Tin[j] + dT[i][1] * Tin[4 + j]) + dT[i][2] * Tin[8 + j]) + dT[i][3] * Tin[12 + j];
+    out[12] = out[13] = out[14] = 0.0, out[15] = 1.0;
+    std::copy(out, out + 16, Tout);
+}
+
+int sgm_icp_solve(const double sums[28], int estimation, double T_in[16], double T_out[16], int *status)
+{
+    if (!sums || !T_in || !T_out || !status) return set_err(SGM_ERR_INVALID_ARG, "sgm_icp_solve: null pointer");
+    if (estimation != 0 && estimation != 1) return set_err(SGM_ERR_INVALID_ARG, "sgm_icp_solve: estimation %d is neither 0 nor 1", estimation);
+    double x[6];
+    if (!icp_solve6(sums, x)) {
+        if (T_out != T_in) std::copy(T_in, T_in + 16, T_out);
+        *status = 3;
+        return SGM_OK;
+    }
+    icp_update(x, T_in, T_out);
+    *status = 0;
+    return SGM_OK;
+}
+
+static int icp_check_T(const char *who, const double *T)
+{
+    for (int k = 0; k < 16; k++)
+        if (!std::isfinite(T[k])) return set_err(SGM_ERR_INVALID_ARG, "%s: the transformation has an entry that is not finite", who);
+    if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0)
+        return set_err(SGM_ERR_INVALID_ARG, "%s: the last row of the transformation is not (0, 0, 0, 1)", who);
+    return SGM_OK;
+}
+
+// What the registration entries refuse, under the entry's name, before anything touches the device
+static int icp_check_args(const char *who, const sgm_engine *e, const void *xyz_s, int64_t ns, const void *xyz_t, int64_t nt, float r,
+                          const float *origin, const double *T, int estimation, const void *normals_t, int max_iteration, double rel_fitness,
+                          double rel_rmse)
+{
+    if (!e || !T || (ns > 0 && !xyz_s) || (nt > 0 && !xyz_t)) return set_err(SGM_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (ns < 0 || nt < 0) return set_err(SGM_ERR_INVALID_ARG, "%s: ns=%lld, nt=%lld points", who, (long long)ns, (long long)nt);
+    const float r2 = r * r, v = r * 1.03125f;
+    if (!std::isfinite(r) || !(r > 0.0f) || !std::isnormal(r2) || !std::isfinite(1.0f / v))
+        return set_err(SGM_ERR_INVALID_ARG, "%s: max_correspondence_distance %g is not finite and positive with a finite normal square", who, (double)r);
+    if (!origin || !std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+        return set_err(SGM_ERR_INVALID_ARG, "%s: the origin is null or not finite", who);
+    if (int rc = icp_check_T(who, T)) return rc;
+    if (estimation != 0 && estimation != 1) return set_err(SGM_ERR_INVALID_ARG, "%s: estimation %d is neither 0 nor 1", who, estimation);
+    if (estimation == 1 && !normals_t) return set_err(SGM_ERR_INVALID_ARG, "%s: point-to-plane needs the target's normals", who);
+    if (max_iteration < 0 || max_iteration > ICP_MAX_ITERATION)
+        return set_err(SGM_ERR_INVALID_ARG, "%s: max_iteration %d outside 0 .. %d", who, max_iteration, ICP_MAX_ITERATION);
+    if (!(rel_fitness >= 0.0) || !(rel_rmse >= 0.0))
+        return set_err(SGM_ERR_INVALID_ARG, "%s: relative_fitness %g or relative_rmse %g is negative or not a number", who, rel_fitness, rel_rmse);
+    if (ns > RAD_MAX_POINTS || nt > RAD_MAX_POINTS)
+        return set_err(SGM_ERR_UNSUPPORTED, "%s: %lld and %lld points, more than 2^24 - 1", who, (long long)ns, (long long)nt);
+    return SGM_OK;
+}
+
+// All four registration entries behind their checks.  Blocks once for the target grid's size and once per evaluation.
+static int icp_run(sgm_engine *e, const char *who, const float *xyz_s, const float *disp_s, int64_t ns, const float *xyz_t, const float *disp_t,
+                   const float *nrm_t, int64_t nt, float r, const float origin[3], const double T0[16], int estimation, int max_iteration,
+                   double rel_fitness, double rel_rmse, double *out_T, double *out_fitness, double *out_rmse, void *d_out_corr, void *d_out_d2,
+                   double *out_history, uint64_t *out_stats)
+{
+    double T[16];
+    std::copy(T0, T0 + 16, T);
+    std::vector<double> hist;
+    uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 2};
+    double fitness = 0.0, rmse = 0.0;
+    if (ns == 0) {
+        hist = {0.0, 0.0};
+    } else {
+        HIP_TRY(hipSetDevice(e->device));
+        const int mblocks = (int)((ns + 255) / 256);
+        int64_t npad = 1;
+        while (npad < ns) npad <<= 1;
+        uint32_t npow = 1;
+        while (npow < (uint32_t)mblocks) npow <<= 1;
+        const size_t pin_bytes = sizeof(IcpResult) + sizeof(IcpCtl) + RAD_CTL_WORDS * 4;
+        int rc;
+        if ((rc = e->rad_ctl.ensure(RAD_CTL_WORDS * 4)) || (rc = e->icp_ctl.ensure(sizeof(IcpResult) + sizeof(IcpCtl))) ||
+            (rc = e->icp_part.ensure((size_t)mblocks * ICP_SUMS * 8)) || (rc = e->pin_icp.ensure(pin_bytes)) ||
+            (nt > 0 && ((rc = e->rad_pt.ensure((size_t)nt * 8)) || (rc = e->rad_keep.ensure((size_t)nt)))) ||
+            (!d_out_corr && (rc = e->icp_corr.ensure((size_t)ns * 4))) || (!d_out_d2 && (rc = e->icp_d2.ensure((size_t)ns * 4))))
+            return rc;
+        if (e->profile) stage_reset(e);   // the stage record is the call's from here on
+        hipStream_t st = e->stream;
+        IcpResult *d_res = (IcpResult *)e->icp_ctl.p;
+        IcpCtl *d_ctl = (IcpCtl *)((char *)e->icp_ctl.p + sizeof(IcpResult));
+        const IcpResult *h_res = (const IcpResult *)e->pin_icp.p;
+        const IcpCtl *h_ctl = (const IcpCtl *)((const char *)e->pin_icp.p + sizeof(IcpResult));
+        const uint32_t *h_rad = (const uint32_t *)((const char *)e->pin_icp.p + sizeof(IcpResult) + sizeof(IcpCtl));
+        int32_t *corr = (int32_t *)(d_out_corr ? d_out_corr : e->icp_corr.p);
+        float *d2 = (float *)(d_out_d2 ? d_out_d2 : e->icp_d2.p);
+        double *part = (double *)e->icp_part.p;
+        // 1. the target's grid: radius_build_grid, unchanged, under stage names of this call
+        static const char *const names[5] = {"icp_count", "icp_clear", "icp_insert", "icp_starts", "icp_sort"};
+        CloudGrid g{RadGrid{1.0f / (r * 1.03125f), r * r, origin[0], origin[1], origin[2]}, 0, 0, 0, 0, nullptr, nullptr, nullptr, 0};
+        if (nt > 0) {
+            if ((rc = radius_build_grid(e, xyz_t, disp_t, nt, r, origin, (uint8_t *)e->rad_keep.p, nullptr, names, &g))) return rc;
+        } else {
+            HIP_TRY(hipMemsetAsync(e->rad_ctl.p, 0, RAD_CTL_WORDS * 4, st));
+        }
+        const int grid_stages = e->nstages, grid_events = e->nevents;
+        // 2 to 5. one evaluation under T: the counts zeroed, the three kernels, the record and the counts read back, one wait
+        auto evaluate = [&]() -> int {
+            IcpM M;
+            for (int k = 0; k < 12; k++) M.m[k] = (float)T[k];
+            if (e->profile) e->nstages = grid_stages, e->nevents = grid_events;   // the record keeps the grid's stages and the last evaluation's
+            HIP_TRY(hipMemsetAsync(d_ctl, 0, sizeof(IcpCtl), st));
+            stage_break(e);
+            int rc2;
+            if ((rc2 = stage_begin(e, "icp_correspond"))) return rc2;
+            hipLaunchKernelGGL(k_icp_correspond, dim3(mblocks), dim3(256), 0, st, xyz_s, disp_s, ns, M, (const float4 *)g.sorted, g.tab, g.mask,
+                               g.G, corr, d2, d_ctl);
+            KCHECK();
+            if ((rc2 = stage_end(e, 1))) return rc2;
+            if ((rc2 = stage_begin(e, "icp_terms"))) return rc2;
+            hipLaunchKernelGGL(k_icp_terms, dim3(mblocks), dim3(256), 0, st, xyz_s, ns, npad, M, xyz_t, nrm_t, estimation, (const int32_t *)corr,
+                               (const float *)d2, part, d_ctl);
+            KCHECK();
+            if ((rc2 = stage_end(e, 1))) return rc2;
+            if ((rc2 = stage_begin(e, "icp_reduce"))) return rc2;
+            hipLaunchKernelGGL(k_icp_reduce, dim3(1), dim3(ICP_REDUCE_CHUNK), 0, st, (const double *)part, (uint32_t)mblocks, npow,
+                               (const IcpCtl *)d_ctl, d_res);
+            KCHECK();
+            if ((rc2 = stage_end(e, 1))) return rc2;
+            // ONE copy: the 232-byte record and, adjacent to it in icp_ctl, the evaluation's 16 bytes of counts
+            HIP_TRY(hipMemcpyAsync(e->pin_icp.p, d_res, sizeof(IcpResult) + sizeof(IcpCtl), hipMemcpyDeviceToHost, st));
+            if (hist.empty())   // the grid's control words once, in the first wait: only k_radius_insert sets RAD_CTL_ERR, no walk does
+                HIP_TRY(hipMemcpyAsync((char *)e->pin_icp.p + sizeof(IcpResult) + sizeof(IcpCtl), e->rad_ctl.p, RAD_CTL_WORDS * 4,
+                                       hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (hist.empty() && h_rad[RAD_CTL_ERR]) return cloud_no_slot(who, g);
+            const uint32_t nc = h_res->n_corr, ms = h_ctl->m_s;
+            fitness = ms ? (double)nc / (double)ms : 0.0;
+            rmse = nc ? std::sqrt(h_res->sums[27] / (double)nc) : 0.0;
+            hist.push_back(fitness), hist.push_back(rmse);
+            return SGM_OK;
+        };
+        if ((rc = evaluate())) return rc;
+        int iterations = 0, status;
+        for (;;) {
+            if (h_res->n_corr < 6u) { status = 2; break; }
+            if (iterations == max_iteration) { status = 1; break; }
+            double x[6];
+            if (!icp_solve6(h_res->sums, x)) { status = 3; break; }
+            icp_update(x, T, T);
+            const double f0 = fitness, r0 = rmse;
+            if ((rc = evaluate())) return rc;
+            iterations++;
+            if (std::fabs(fitness - f0) < rel_fitness && std::fabs(rmse - r0) < rel_rmse) { status = 0; break; }
+        }
+        const uint64_t s[8] = {h_ctl->m_s, g.n_in, g.n_out, (uint64_t)iterations, h_res->n_corr, h_ctl->unplaced, h_ctl->unusable, (uint64_t)status};
+        std::copy(s, s + 8, stats);
+    }
+    if (out_T) std::copy(T, T + 16, out_T);
+    if (out_fitness) *out_fitness = fitness;
+    if (out_rmse) *out_rmse = rmse;
+    if (out_history) std::copy(hist.begin(), hist.end(), out_history);
+    if (out_stats) std::copy(stats, stats + 8, out_stats);
+    return SGM_OK;
+}
+
+int sgm_register_icp_device(sgm_engine *e, const void *d_xyz_s, const void *d_disp_s, int64_t ns, const void *d_xyz_t, const void *d_disp_t,
+                            const void *d_normals_t, int64_t nt, float max_correspondence_distance, const float origin[3],
+                            const double T0[16], int estimation, int max_iteration, double relative_fitness, double relative_rmse,
+                            double out_T[16], double *out_fitness, double *out_rmse, void *d_out_corr, void *d_out_d2,
+                            double *out_history, uint64_t out_stats[8])
+{
+    const char *who = "sgm_register_icp";
+    if (int rc = icp_check_args(who, e, d_xyz_s, ns, d_xyz_t, nt, max_correspondence_distance, origin, T0, estimation, d_normals_t, max_iteration,
+                                relative_fitness, relative_rmse))
+        return rc;
+    return icp_run(e, who, (const float *)d_xyz_s, (const float *)d_disp_s, ns, (const float *)d_xyz_t, (const float *)d_disp_t,
+                   (const float *)d_normals_t, nt, max_correspondence_distance, origin, T0, estimation, max_iteration, relative_fitness,
+                   relative_rmse, out_T, out_fitness, out_rmse, d_out_corr, d_out_d2, out_history, out_stats);
+}
+
+int sgm_evaluate_registration_device(sgm_engine *e, const void *d_xyz_s, const void *d_disp_s, int64_t ns, const void *d_xyz_t,
+                                     const void *d_disp_t, int64_t nt, float max_correspondence_distance, const float origin[3],
+                                     const double T[16], double *out_fitness, double *out_rmse, void *d_out_corr, void *d_out_d2,
+                                     uint64_t out_stats[8])
+{
+    const char *who = "sgm_evaluate_registration";
+    if (int rc = icp_check_args(who, e, d_xyz_s, ns, d_xyz_t, nt, max_correspondence_distance, origin, T, 0, nullptr, 0, 0.0, 0.0)) return rc;
+    return icp_run(e, who, (const float *)d_xyz_s, (const float *)d_disp_s, ns, (const float *)d_xyz_t, (const float *)d_disp_t, nullptr, nt,
+                   max_correspondence_distance, origin, T, 0, 0, 0.0, 0.0, nullptr, out_fitness, out_rmse, d_out_corr, d_out_d2, nullptr, out_stats);
+}
+
+// the host entries of both: the two clouds up (the source to xyz and f32, the target to icp_txyz, icp_tdisp, icp_tnrm), the device
+// entry `run` on them with the engine's own corr and d2, those two down
+extern "C++" {   // (a template: this part of the file has C linkage)
+template <class Run>
+static int icp_host_call(sgm_engine *e, const float *xyz_s, const float *disp_s, int64_t ns, const float *xyz_t, const float *disp_t,
+                         const float *normals_t, int64_t nt, int32_t *out_corr, float *out_d2, Run run)
+{
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    hipStream_t st = e->stream;
+    if ((ns > 0 && (rc = e->xyz.ensure((size_t)ns * 12))) || (ns > 0 && disp_s && (rc = e->f32.ensure((size_t)ns * 4))) ||
+        (nt > 0 && (rc = e->icp_txyz.ensure((size_t)nt * 12))) || (nt > 0 && disp_t && (rc = e->icp_tdisp.ensure((size_t)nt * 4))) ||
+        (nt > 0 && normals_t && (rc = e->icp_tnrm.ensure((size_t)nt * 12))))
+        return rc;
+    if (ns > 0) HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz_s, (size_t)ns * 12, hipMemcpyHostToDevice, st));
+    if (ns > 0 && disp_s) HIP_TRY(hipMemcpyAsync(e->f32.p, disp_s, (size_t)ns * 4, hipMemcpyHostToDevice, st));
+    if (nt > 0) HIP_TRY(hipMemcpyAsync(e->icp_txyz.p, xyz_t, (size_t)nt * 12, hipMemcpyHostToDevice, st));
+    if (nt > 0 && disp_t) HIP_TRY(hipMemcpyAsync(e->icp_tdisp.p, disp_t, (size_t)nt * 4, hipMemcpyHostToDevice, st));
+    if (nt > 0 && normals_t) HIP_TRY(hipMemcpyAsync(e->icp_tnrm.p, normals_t, (size_t)nt * 12, hipMemcpyHostToDevice, st));
+    rc = run(ns > 0 ? e->xyz.p : nullptr, ns > 0 && disp_s ? e->f32.p : nullptr, nt > 0 ? e->icp_txyz.p : nullptr,
+             nt > 0 && disp_t ? e->icp_tdisp.p : nullptr, nt > 0 && normals_t ? e->icp_tnrm.p : nullptr);   // (no target: no pair ever reads a normal)
+    if (rc) {
+        (void)hipStreamSynchronize(st);   // (the caller's memory is the source of nothing when the call returns)
+        return rc;
+    }
+    if (ns > 0 && out_corr) HIP_TRY(hipMemcpyAsync(out_corr, e->icp_corr.p, (size_t)ns * 4, hipMemcpyDeviceToHost, st));
+    if (ns > 0 && out_d2) HIP_TRY(hipMemcpyAsync(out_d2, e->icp_d2.p, (size_t)ns * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return SGM_OK;
+}
+}  // extern "C++"
+
+int sgm_register_icp(sgm_engine *e, const float *xyz_s, const float *disp_s, int64_t ns, const float *xyz_t, const float *disp_t,
+                     const float *normals_t, int64_t nt, float max_correspondence_distance, const float origin[3], const double T0[16],
+                     int estimation, int max_iteration, double relative_fitness, double relative_rmse, double out_T[16],
+                     double *out_fitness, double *out_rmse, int32_t *out_corr, float *out_d2, double *out_history, uint64_t out_stats[8])
+{
+    const char *who = "sgm_register_icp";
+    if (int rc = icp_check_args(who, e, xyz_s, ns, xyz_t, nt, max_correspondence_distance, origin, T0, estimation, normals_t, max_iteration,
+                                relative_fitness, relative_rmse))
+        return rc;
+    if (ns == 0)   // nothing runs and nothing is staged
+        return icp_run(e, who, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nt, max_correspondence_distance, origin, T0, estimation,
+                       max_iteration, relative_fitness, relative_rmse, out_T, out_fitness, out_rmse, nullptr, nullptr, out_history, out_stats);
+    return icp_host_call(e, xyz_s, disp_s, ns, xyz_t, disp_t, normals_t, nt, out_corr, out_d2,
+                         [&](void *d_s, void *d_ds, void *d_t, void *d_dt, void *d_n) {
+                             return icp_run(e, who, (const float *)d_s, (const float *)d_ds, ns, (const float *)d_t, (const float *)d_dt,
+                                            (const float *)d_n, nt, max_correspondence_distance, origin, T0, estimation, max_iteration,
+                                            relative_fitness, relative_rmse, out_T, out_fitness, out_rmse, nullptr, nullptr, out_history,
+                                            out_stats);
+                         });
+}
+
+int sgm_evaluate_registration(sgm_engine *e, const float *xyz_s, const float *disp_s, int64_t ns, const float *xyz_t, const float *disp_t,
+                              int64_t nt, float max_correspondence_distance, const float origin[3], const double T[16],
+                              double *out_fitness, double *out_rmse, int32_t *out_corr, float *out_d2, uint64_t out_stats[8])
+{
+    const char *who = "sgm_evaluate_registration";
+    if (int rc = icp_check_args(who, e, xyz_s, ns, xyz_t, nt, max_correspondence_distance, origin, T, 0, nullptr, 0, 0.0, 0.0)) return rc;
+    if (ns == 0)   // nothing runs and nothing is staged
+        return icp_run(e, who, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nt, max_correspondence_distance, origin, T, 0, 0, 0.0, 0.0,
+                       nullptr, out_fitness, out_rmse, nullptr, nullptr, nullptr, out_stats);
+    return icp_host_call(e, xyz_s, disp_s, ns, xyz_t, disp_t, nullptr, nt, out_corr, out_d2,
+                         [&](void *d_s, void *d_ds, void *d_t, void *d_dt, void *) {
+                             return icp_run(e, who, (const float *)d_s, (const float *)d_ds, ns, (const float *)d_t, (const float *)d_dt, nullptr,
+                                            nt, max_correspondence_distance, origin, T, 0, 0, 0.0, 0.0, nullptr, out_fitness, out_rmse, nullptr,
+                                            nullptr, nullptr, out_stats);
+                         });
+}
+
+static int icp_transform_check(const sgm_engine *e, const void *xyz, const void *normals, int64_t n, const double *T, const void *out_xyz,
+                               const void *out_normals)
+{
+    const char *who = "sgm_transform_points";
+    if (!e || !T || (n > 0 && !xyz)) return set_err(SGM_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (n < 0) return set_err(SGM_ERR_INVALID_ARG, "%s: n=%lld points", who, (long long)n);
+    if ((normals == nullptr) != (out_normals == nullptr))
+        return set_err(SGM_ERR_INVALID_ARG, "%s: normals and out_normals are not both null or both given", who);
+    if (!out_xyz && !out_normals) return set_err(SGM_ERR_INVALID_ARG, "%s: no output", who);
+    if (int rc = icp_check_T(who, T)) return rc;
+    if (n > RAD_MAX_POINTS) return set_err(SGM_ERR_UNSUPPORTED, "%s: %lld points, more than 2^24 - 1", who, (long long)n);
+    return SGM_OK;
+}
+
+int sgm_transform_points_device(sgm_engine *e, const void *d_xyz, const void *d_normals, int64_t n, const double T[16], void *d_out_xyz,
+                                void *d_out_normals)
+{
+    if (int rc = icp_transform_check(e, d_xyz, d_normals, n, T, d_out_xyz, d_out_normals)) return rc;
+    if (n == 0) return SGM_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    IcpM M;
+    for (int k = 0; k < 12; k++) M.m[k] = (float)T[k];
+    hipLaunchKernelGGL(k_icp_transform, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, (const float *)d_xyz, (const float *)d_normals,
+                       n, M, (float *)d_out_xyz, (float *)d_out_normals);
+    KCHECK();
+    return SGM_OK;
+}
+
+int sgm_transform_points(sgm_engine *e, const float *xyz, const float *normals, int64_t n, const double T[16], float *out_xyz,
+                         float *out_normals)
+{
+    if (int rc = icp_transform_check(e, xyz, normals, n, T, out_xyz, out_normals)) return rc;
+    if (n == 0) return SGM_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    hipStream_t st = e->stream;
+    if ((rc = e->xyz.ensure((size_t)n * 12)) || (normals && (rc = e->icp_tnrm.ensure((size_t)n * 12)))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, st));
+    if (normals) HIP_TRY(hipMemcpyAsync(e->icp_tnrm.p, normals, (size_t)n * 12, hipMemcpyHostToDevice, st));
+    if ((rc = sgm_transform_points_device(e, e->xyz.p, normals ? e->icp_tnrm.p : nullptr, n, T, out_xyz ? e->xyz.p : nullptr,
+                                          normals ? e->icp_tnrm.p : nullptr))) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if (out_xyz) HIP_TRY(hipMemcpyAsync(out_xyz, e->xyz.p, (size_t)n * 12, hipMemcpyDeviceToHost, st));
+    if (out_normals) HIP_TRY(hipMemcpyAsync(out_normals, e->icp_tnrm.p, (size_t)n * 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return SGM_OK;
 }
 
 // ---- triangle mesh from the organised cloud (include/sgm_hip_mesh.h, kernels_mesh.h) and its normals (include/sgm_hip_normals.h,

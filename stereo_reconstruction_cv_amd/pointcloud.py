@@ -26,6 +26,10 @@
                  and the mask of the points on it, or with invert=True off it, on the GPU (include/sgm_hip_plane.h; NOT Open3D's
                  segment_plane), and
     plane_inliers(points_3D, colors, disparity_map, plane_model, distance_threshold, ...)   a model found once applied to other clouds
+    registration_icp(source, target, max_correspondence_distance, ...)     the rigid motion that lays one cloud on another, by
+                 iterated closest points on the GPU (include/sgm_hip_icp.h; NOT Open3D's registration_icp), with
+    evaluate_registration(source, target, max_correspondence_distance, transformation)   its correspondence pass alone, and
+    transform_points(points, transformation, normals)                      the motion applied, so that the two can be merged
     write_ply(path, points, colors, normals, triangles) / read_ply(path)   one PLY writer for a cloud or a mesh, with or without normals
 
 The compaction runs on the GPU (ordered, so the result equals numpy's `points_3D[mask]`); the
@@ -676,6 +680,237 @@ def plane_inliers(points_3D, colors, disparity_map, plane_model, distance_thresh
 
     _, mask, p, c, idx, dist = _plane_call(who, points_3D, colors, disparity_map, confidence, min_confidence, select, flags, host, device)
     return _plane_results((), mask, p, c, idx, dist, None, flags)
+
+
+ICP_STATS = ("valid_source", "target_in_range", "target_out_of_range", "iterations", "correspondences", "unplaced", "unusable_normals",
+             "status")
+ICP_STATUS = ("converged", "max_iteration", "too_few", "degenerate")
+ICP_ESTIMATIONS = ("point_to_point", "point_to_plane")
+ICP_MAX_ITERATION = 1000
+
+
+def _icp_matrix(who, name, T):
+    """a rigid transformation as float64 (4, 4), checked as include/sgm_hip_icp.h checks it; None is the identity"""
+    if T is None:
+        return np.eye(4, dtype=np.float64)
+    try:
+        M = np.asarray(T.cpu() if _cv._is_torch(T) else T, np.float64)
+    except (TypeError, ValueError):
+        raise _cv.error(f"{who}: {name} must be a 4 x 4 matrix of numbers") from None
+    if M.shape != (4, 4) or not np.isfinite(M).all() or M[3].tolist() != [0.0, 0.0, 0.0, 1.0]:
+        raise _cv.error(f"{who}: {name} is not a finite 4 x 4 matrix with the last row (0, 0, 0, 1)")
+    return np.ascontiguousarray(M)
+
+
+def _icp_clouds(who, source, target, source_disparity, target_disparity, target_normals):
+    """the two clouds of a registration call, both numpy arrays or both HIP tensors on one GPU, checked:
+    (on_device, source, source disparities, target, target disparities, target normals)"""
+    on_device = _cv._is_torch(source)
+    if on_device != _cv._is_torch(target):
+        raise _cv.error(f"{who}: source and target must both be numpy arrays or both be tensors")
+    if on_device:
+        import torch
+        s, ds = _device_cloud(who + " (source)", source, source_disparity, None, 0)
+        t, dt = _device_cloud(who + " (target)", target, target_disparity, None, 0)
+        if s.device != t.device:
+            raise _cv.error(f"{who}: source and target must be on the same GPU")
+        nrm = target_normals
+        if nrm is not None:
+            if not _cv._is_torch(nrm) or nrm.device != t.device or nrm.dtype != torch.float32 or tuple(nrm.shape) != tuple(t.shape):
+                raise _cv.error(f"{who}: target_normals must be a float32 tensor of the target's shape on the same GPU")
+            nrm = nrm.contiguous()
+        ns, nt = s.numel() // 3, t.numel() // 3
+    else:
+        s, ds, _ = _outlier_cloud(who + " (source)", source, None, source_disparity, None, 0)
+        t, dt, _ = _outlier_cloud(who + " (target)", target, None, target_disparity, None, 0)
+        nrm = target_normals
+        if nrm is not None:
+            nrm = np.asarray(nrm)
+            if nrm.dtype != np.float32 or nrm.shape != t.shape:
+                raise _cv.error(f"{who}: target_normals must be float32 and have the shape of target")
+        for name, d in (("source_disparity", ds), ("target_disparity", dt)):
+            if d is not None and d.dtype != np.float32:
+                raise _cv.error(f"{who}: {name} must be float32 (in pixels), not {d.dtype}")
+        ns, nt = s.size // 3, t.size // 3
+    if max(ns, nt) > RADIUS_MAX_POINTS:
+        raise _cv.error(f"{who}: {max(ns, nt)} points, more than {RADIUS_MAX_POINTS} (include/sgm_hip_icp.h)")
+    return on_device, s, ds, t, dt, nrm, ns, nt
+
+
+def _icp_call(who, source, target, r, T0, estimation, target_normals, source_disparity, target_disparity, max_iteration, rel_f, rel_r,
+              origin, evaluate):
+    """registration_icp and evaluate_registration behind their argument checks: (T, fitness, rmse, corr, d2, history, stats)"""
+    r, org = _search_radius(who, "max_correspondence_distance", r, origin)
+    on_device, s, ds, t, dt, nrm, ns, nt = _icp_clouds(who, source, target, source_disparity, target_disparity, target_normals)
+    if estimation == 1 and nrm is None:
+        raise _cv.error(f"{who}: point_to_plane needs target_normals (estimate_normals_radius on the target)")
+    shape = tuple(s.shape[:-1])
+    if ns == 0:      # nothing to send to the device
+        st = np.zeros(8, np.uint64)
+        st[7] = 2
+        corr, d2 = np.full(shape, -1, np.int32), np.full(shape, np.nan, np.float32)
+        if on_device:
+            import torch
+            corr, d2 = torch.from_numpy(corr).to(s.device), torch.from_numpy(d2).to(s.device)
+        return T0, 0.0, 0.0, corr, d2, np.zeros((1, 2), np.float64), st
+    if on_device:
+        import torch
+        dev = s.device
+        corr = torch.full(shape, -1, dtype=torch.int32, device=dev)
+        d2 = torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+        e = _cv.get_engine(_cv._DEFAULT, dev.index)
+        torch.cuda.synchronize(dev)      # the inputs were made on torch's stream, the call runs on the engine's
+        ptr = lambda a: None if a is None else a.data_ptr()
+        if evaluate:
+            fit, rmse, st = e.evaluate_registration_device(s.data_ptr(), ptr(ds), ns, t.data_ptr(), ptr(dt), nt, float(r), org, T0,
+                                                           corr.data_ptr(), d2.data_ptr())
+            T, hist = T0, np.array([[fit, rmse]], np.float64)
+        else:
+            T, fit, rmse, hist, st = e.register_icp_device(s.data_ptr(), ptr(ds), ns, t.data_ptr(), ptr(dt), ptr(nrm), nt, float(r), org, T0,
+                                                           estimation, max_iteration, rel_f, rel_r, corr.data_ptr(), d2.data_ptr())
+        return T, fit, rmse, corr, d2, hist, st
+    e = _cv.get_engine(_cv._DEFAULT)
+    if evaluate:
+        fit, rmse, corr, d2, st = e.evaluate_registration_host(s, ds, t, dt, float(r), org, T0)
+        T, hist = T0, np.array([[fit, rmse]], np.float64)
+    else:
+        T, fit, rmse, corr, d2, hist, st = e.register_icp_host(s, ds, t, dt, nrm, float(r), org, T0, estimation, max_iteration, rel_f, rel_r)
+    return T, fit, rmse, corr.reshape(shape), d2.reshape(shape), hist, st
+
+
+def registration_icp(source, target, max_correspondence_distance, init=None, estimation="point_to_plane", target_normals=None,
+                     source_disparity=None, target_disparity=None, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6,
+                     origin=(0, 0, 0), return_correspondences=False, return_history=False, return_stats=False):
+    """Rigid registration of two clouds by iterated closest points, on the GPU: the 4 x 4 transformation that lays `source` on
+    `target`, the share of the valid source points that find a target point within max_correspondence_distance (fitness) and the
+    root mean square distance of those pairs (inlier_rmse).  Each iteration transforms the source by the current estimate in
+    float32, gives every source point its nearest target point within the distance on the target's grid of cells (ties in the float32
+    squared distance: the lowest target index), sums the 6 x 6 Gauss-Newton system of the pairs in one fixed pairwise tree in
+    float64, solves it on the host by LDL^T and updates the estimate by a quaternion.  estimation: "point_to_plane" (needs
+    target_normals; a pair whose normal is not about unit length counts but does not vote) or "point_to_point".  It stops when
+    fitness and rmse both change by less than relative_fitness and relative_rmse, after max_iteration (0 .. 1000) iterations, with
+    fewer than 6 pairs, or on a system that is not positive definite (a single plane under point_to_plane).
+    The definition is include/sgm_hip_icp.h, our own, and the result is the same bits on every run: it is NOT Open3D's
+    registration_icp -- the correspondence tie rule; the range rule (target points and transformed source points whose cell index,
+    cells of edge max_correspondence_distance * 1.03125 anchored at origin, leaves -2^16 .. 2^16 - 1 take no part); point_to_point
+    by the same Gauss-Newton step, not Umeyama's closed form; a quaternion update, not Euler angles; tree-ordered sums; and the two
+    thresholds are absolute differences.
+    source, target: XYZ images (H, W, 3) with their source_disparity / target_disparity (H, W) -- a point takes part iff X, Y, Z are
+    finite and its disparity > 0 -- or (N, 3) lists with no disparity (every finite point takes part); numpy arrays, or HIP tensors
+    (float32, on one GPU), which stay on the device.  target_normals: float32 of target's shape.  init: the first estimate (None:
+    the identity).
+    Returns (transformation float64 (4, 4), fitness, inlier_rmse[, correspondences, distances2][, history][, stats]):
+    correspondences int32 of the source's point shape, the target index or -1; distances2 float32, the squared distance or NaN;
+    history float64 (evaluations, 2), fitness and rmse of every evaluation from the one under init on; stats a dict: valid_source,
+    target_in_range, target_out_of_range, iterations, correspondences, unplaced, unusable_normals, status ("converged",
+    "max_iteration", "too_few", "degenerate").
+
+    The chain this exists for -- two clouds merged into one:
+
+        s, _ = voxel_down_sample(source_xyz, None, source_disp, voxel)
+        t, _ = voxel_down_sample(target_xyz, None, target_disp, voxel)
+        n = estimate_normals_radius(t, None, 2 * voxel)
+        T, fitness, rmse = registration_icp(s, t, 2 * voxel, target_normals=n)
+        merged = np.concatenate([transform_points(s, T), t])
+        write_ply(path, merged)
+
+    In short voxel_down_sample -> estimate_normals_radius (target) -> registration_icp -> transform_points -> concatenate -> write_ply.
+    """
+    who = "registration_icp"
+    if estimation not in ICP_ESTIMATIONS:
+        raise _cv.error(f"{who}: estimation={estimation!r} is not one of {ICP_ESTIMATIONS}")
+    est = ICP_ESTIMATIONS.index(estimation)
+    if isinstance(max_iteration, bool) or not isinstance(max_iteration, (int, np.integer)) or not 0 <= int(max_iteration) <= ICP_MAX_ITERATION:
+        raise _cv.error(f"{who}: max_iteration={max_iteration!r} is not an integer in 0 .. {ICP_MAX_ITERATION}")
+    rel = []
+    for name, v in (("relative_fitness", relative_fitness), ("relative_rmse", relative_rmse)):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise _cv.error(f"{who}: {name} must be a number") from None
+        if isinstance(v, bool) or not f >= 0:
+            raise _cv.error(f"{who}: {name}={v!r} is not a number >= 0")
+        rel.append(f)
+    T0 = _icp_matrix(who, "init", init)
+    T, fit, rmse, corr, d2, hist, st = _icp_call(who, source, target, max_correspondence_distance, T0, est, target_normals, source_disparity,
+                                                 target_disparity, int(max_iteration), rel[0], rel[1], origin, False)
+    out = (T, fit, rmse)
+    if return_correspondences:
+        out += (corr, d2)
+    if return_history:
+        out += (hist,)
+    if return_stats:
+        d = dict(zip(ICP_STATS, (int(x) for x in st)))
+        d["status"] = ICP_STATUS[d["status"]]
+        out += (d,)
+    return out
+
+
+def evaluate_registration(source, target, max_correspondence_distance, transformation=None, source_disparity=None, target_disparity=None,
+                          origin=(0, 0, 0), return_correspondences=False, return_stats=False):
+    """The correspondence pass of registration_icp alone under the caller's transformation (None: the identity), on the GPU: fitness
+    and inlier_rmse of include/sgm_hip_icp.h, as registration_icp with max_iteration=0 reports them (NOT Open3D's
+    evaluate_registration: the tie rule, the range rule and the tree-ordered sum of that header).  The clouds, origin and the
+    optional results are registration_icp's.
+    Returns (fitness, inlier_rmse[, correspondences, distances2][, stats])."""
+    who = "evaluate_registration"
+    T0 = _icp_matrix(who, "transformation", transformation)
+    _, fit, rmse, corr, d2, _, st = _icp_call(who, source, target, max_correspondence_distance, T0, 0, None, source_disparity,
+                                              target_disparity, 0, 0.0, 0.0, origin, True)
+    out = (fit, rmse)
+    if return_correspondences:
+        out += (corr, d2)
+    if return_stats:
+        d = dict(zip(ICP_STATS, (int(x) for x in st)))
+        d["status"] = ICP_STATUS[d["status"]]
+        out += (d,)
+    return out
+
+
+def transform_points(points, transformation, normals=None):
+    """The points under a rigid transformation, on the GPU, in the arithmetic registration_icp itself uses (include/sgm_hip_icp.h,
+    step 2: the matrix rounded to float32, three fused multiply-adds per coordinate from the translation), so that a registered
+    cloud can be merged with its target; normals, if given, by the rotation part only.  points, normals: float32 (..., 3), numpy
+    arrays or HIP tensors, which stay on the device; rows that are not finite stay not finite.
+    Returns points, or (points, normals) with normals."""
+    who = "transform_points"
+    T = _icp_matrix(who, "transformation", transformation)
+    if transformation is None:
+        raise _cv.error(f"{who}: transformation is not a finite 4 x 4 matrix with the last row (0, 0, 0, 1)")
+    if _cv._is_torch(points):
+        import torch
+        p = points
+        if not p.is_cuda or p.dtype != torch.float32 or p.dim() < 1 or p.shape[-1] != 3:
+            raise _cv.error(f"{who}: a tensor points must be float32 (..., 3) and on the GPU")
+        nrm = normals
+        if nrm is not None and (not _cv._is_torch(nrm) or nrm.device != p.device or nrm.dtype != torch.float32
+                                or tuple(nrm.shape) != tuple(p.shape)):
+            raise _cv.error(f"{who}: normals must be a float32 tensor of the points' shape on the same GPU")
+        p = p.contiguous()
+        nrm = None if nrm is None else nrm.contiguous()
+        out, out_n = torch.empty_like(p), None if nrm is None else torch.empty_like(nrm)
+        if p.numel():
+            e = _cv.get_engine(_cv._DEFAULT, p.device.index)
+            torch.cuda.synchronize(p.device)
+            e.transform_points_device(p.data_ptr(), None if nrm is None else nrm.data_ptr(), p.numel() // 3, T, out.data_ptr(),
+                                      None if out_n is None else out_n.data_ptr())
+            e.synchronize()
+    else:
+        p = np.asarray(points)
+        if p.dtype != np.float32 or p.ndim < 1 or p.shape[-1] != 3:
+            raise _cv.error(f"{who}: points must be float32 (..., 3), not {p.dtype} {p.shape}")
+        nrm = normals
+        if nrm is not None:
+            nrm = np.asarray(nrm)
+            if nrm.dtype != np.float32 or nrm.shape != p.shape:
+                raise _cv.error(f"{who}: normals must be float32 and have the shape of points")
+        if p.size // 3 > RADIUS_MAX_POINTS:
+            raise _cv.error(f"{who}: {p.size // 3} points, more than {RADIUS_MAX_POINTS} (include/sgm_hip_icp.h)")
+        if p.size == 0:
+            out, out_n = p.copy(), None if nrm is None else nrm.copy()
+        else:
+            out, out_n = _cv.get_engine(_cv._DEFAULT).transform_points_host(p, T, nrm)
+    return out if normals is None else (out, out_n)
 
 
 MESH_MAX_PIXELS = 1 << 26

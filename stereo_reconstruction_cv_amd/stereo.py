@@ -478,6 +478,103 @@ class Engine:
                                                 C.byref(ns)))
         return int(ni.value), int(ns.value)
 
+    # -- rigid registration of two point clouds (include/sgm_hip_icp.h) --
+    @staticmethod
+    def _icp_small(max_iteration):
+        """the small host results of a registration call: (T, fitness, rmse, history pre-filled with NaN, stats)"""
+        return (np.zeros(16, np.float64), C.c_double(0.0), C.c_double(0.0), np.full((int(max_iteration) + 1, 2), np.nan, np.float64),
+                np.zeros(8, np.uint64))
+
+    def register_icp_host(self, source: np.ndarray, source_disp: np.ndarray | None, target: np.ndarray, target_disp: np.ndarray | None,
+                          target_normals: np.ndarray | None, max_correspondence_distance: float, origin=(0.0, 0.0, 0.0), init=None,
+                          estimation: int = 1, max_iteration: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6):
+        """sgm_register_icp: float32 points (n, 3) or (H, W, 3) and float32 disparities (n) or (H, W) or None for both clouds, float32
+        normals of the target's shape or None.  Returns (T float64 (4, 4), fitness, rmse, corr int32 (ns), d2 float32 (ns), history
+        float64 (evaluations, 2), stats uint64 (8)): stats is valid source points, target points in range, valid target points out
+        of range, iterations, correspondences, unplaced, unusable normals, status."""
+        src = np.ascontiguousarray(source, np.float32).reshape(-1, 3)
+        tgt = np.ascontiguousarray(target, np.float32).reshape(-1, 3)
+        ns, nt = src.shape[0], tgt.shape[0]
+        ds = None if source_disp is None else np.ascontiguousarray(source_disp, np.float32).reshape(-1)
+        dt = None if target_disp is None else np.ascontiguousarray(target_disp, np.float32).reshape(-1)
+        nrm = None if target_normals is None else np.ascontiguousarray(target_normals, np.float32).reshape(-1, 3)
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        T0 = np.ascontiguousarray(np.eye(4) if init is None else init, np.float64).reshape(16)
+        T, fit, rmse, hist, stats = self._icp_small(max_iteration)
+        corr, d2 = np.full(ns, -1, np.int32), np.full(ns, np.nan, np.float32)
+        at = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.sgm_register_icp(self._h, src.ctypes.data, at(ds), ns, tgt.ctypes.data, at(dt), at(nrm), nt,
+                                        float(max_correspondence_distance), org.ctypes.data, T0.ctypes.data, int(estimation),
+                                        int(max_iteration), float(relative_fitness), float(relative_rmse), T.ctypes.data, C.byref(fit),
+                                        C.byref(rmse), corr.ctypes.data, d2.ctypes.data, hist.ctypes.data, stats.ctypes.data))
+        return T.reshape(4, 4), fit.value, rmse.value, corr, d2, hist[:int(stats[3]) + 1].copy(), stats
+
+    def register_icp_device(self, d_source: int, d_source_disp: int | None, ns: int, d_target: int, d_target_disp: int | None,
+                            d_target_normals: int | None, nt: int, max_correspondence_distance: float, origin=(0.0, 0.0, 0.0), init=None,
+                            estimation: int = 1, max_iteration: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6,
+                            d_corr: int | None = None, d_d2: int | None = None):
+        """sgm_register_icp_device: device addresses; d_corr (int32) and d_d2 (float32) have ns entries.  Returns (T float64 (4, 4),
+        fitness, rmse, history float64 (evaluations, 2), stats uint64 (8)); synchronises the engine's stream once for the target's
+        grid and once per evaluation."""
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        T0 = np.ascontiguousarray(np.eye(4) if init is None else init, np.float64).reshape(16)
+        T, fit, rmse, hist, stats = self._icp_small(max_iteration)
+        _check(self._L.sgm_register_icp_device(self._h, d_source, d_source_disp, int(ns), d_target, d_target_disp, d_target_normals, int(nt),
+                                               float(max_correspondence_distance), org.ctypes.data, T0.ctypes.data, int(estimation),
+                                               int(max_iteration), float(relative_fitness), float(relative_rmse), T.ctypes.data,
+                                               C.byref(fit), C.byref(rmse), d_corr, d_d2, hist.ctypes.data, stats.ctypes.data))
+        return T.reshape(4, 4), fit.value, rmse.value, hist[:int(stats[3]) + 1].copy(), stats
+
+    def evaluate_registration_host(self, source: np.ndarray, source_disp: np.ndarray | None, target: np.ndarray,
+                                   target_disp: np.ndarray | None, max_correspondence_distance: float, origin=(0.0, 0.0, 0.0),
+                                   transformation=None):
+        """sgm_evaluate_registration: the correspondence pass alone under `transformation` (None: the identity).  Returns (fitness,
+        rmse, corr int32 (ns), d2 float32 (ns), stats uint64 (8))."""
+        src = np.ascontiguousarray(source, np.float32).reshape(-1, 3)
+        tgt = np.ascontiguousarray(target, np.float32).reshape(-1, 3)
+        ns, nt = src.shape[0], tgt.shape[0]
+        ds = None if source_disp is None else np.ascontiguousarray(source_disp, np.float32).reshape(-1)
+        dt = None if target_disp is None else np.ascontiguousarray(target_disp, np.float32).reshape(-1)
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        T = np.ascontiguousarray(np.eye(4) if transformation is None else transformation, np.float64).reshape(16)
+        fit, rmse, stats = C.c_double(0.0), C.c_double(0.0), np.zeros(8, np.uint64)
+        corr, d2 = np.full(ns, -1, np.int32), np.full(ns, np.nan, np.float32)
+        at = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.sgm_evaluate_registration(self._h, src.ctypes.data, at(ds), ns, tgt.ctypes.data, at(dt), nt,
+                                                 float(max_correspondence_distance), org.ctypes.data, T.ctypes.data, C.byref(fit),
+                                                 C.byref(rmse), corr.ctypes.data, d2.ctypes.data, stats.ctypes.data))
+        return fit.value, rmse.value, corr, d2, stats
+
+    def evaluate_registration_device(self, d_source: int, d_source_disp: int | None, ns: int, d_target: int, d_target_disp: int | None,
+                                     nt: int, max_correspondence_distance: float, origin=(0.0, 0.0, 0.0), transformation=None,
+                                     d_corr: int | None = None, d_d2: int | None = None):
+        """sgm_evaluate_registration_device: device addresses as in register_icp_device.  Returns (fitness, rmse, stats uint64 (8))."""
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        T = np.ascontiguousarray(np.eye(4) if transformation is None else transformation, np.float64).reshape(16)
+        fit, rmse, stats = C.c_double(0.0), C.c_double(0.0), np.zeros(8, np.uint64)
+        _check(self._L.sgm_evaluate_registration_device(self._h, d_source, d_source_disp, int(ns), d_target, d_target_disp, int(nt),
+                                                        float(max_correspondence_distance), org.ctypes.data, T.ctypes.data, C.byref(fit),
+                                                        C.byref(rmse), d_corr, d_d2, stats.ctypes.data))
+        return fit.value, rmse.value, stats
+
+    def transform_points_host(self, xyz: np.ndarray, transformation, normals: np.ndarray | None = None):
+        """sgm_transform_points: float32 points of any shape (..., 3) under the float64 4 x 4 transformation, the normals by its
+        rotation part.  Returns (points, normals or None) of the inputs' shapes."""
+        pts = np.ascontiguousarray(xyz, np.float32)
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32)
+        T = np.ascontiguousarray(transformation, np.float64).reshape(16)
+        out, out_n = np.empty_like(pts), None if nrm is None else np.empty_like(nrm)
+        at = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.sgm_transform_points(self._h, pts.ctypes.data, at(nrm), pts.size // 3, T.ctypes.data, out.ctypes.data, at(out_n)))
+        return out, out_n
+
+    def transform_points_device(self, d_xyz: int, d_normals: int | None, n: int, transformation, d_out_xyz: int | None,
+                                d_out_normals: int | None = None):
+        """sgm_transform_points_device: device addresses (the outputs may be the inputs); enqueued on the engine's stream, which
+        synchronize() waits for."""
+        T = np.ascontiguousarray(transformation, np.float64).reshape(16)
+        _check(self._L.sgm_transform_points_device(self._h, d_xyz, d_normals, int(n), T.ctypes.data, d_out_xyz, d_out_normals))
+
     # -- triangle mesh from the organised cloud (include/sgm_hip_mesh.h) --
     def mesh_grid_host(self, xyz: np.ndarray, disp: np.ndarray, colors: np.ndarray | None, max_diff: float = 1.0):
         """sgm_mesh_grid: float32 points (H, W, 3), float32 disparities (H, W), uint8 colours (H, W, 3) or None.  Returns
