@@ -1242,6 +1242,12 @@ static int run_stage(sgm_engine *e, const char *name, hipStream_t on, F &&enqueu
     KCHECK();
     return stage_end(e, n, on);
 }
+// ... on the engine's own stream
+template <class F>
+static int run_stage(sgm_engine *e, const char *name, F &&enqueue)
+{
+    return run_stage(e, name, e->stream, enqueue);
+}
 
 // the auxiliary streams and their events, created on first use
 static int ensure_aux(sgm_engine *e, bool second)
@@ -1708,21 +1714,21 @@ static int run_reproject(sgm_engine *e, const float *d_disp, int H, int W, const
 static int run_float_xyz(sgm_engine *e, const int16_t *di, int H, int W, const double Q[16], void *d_disp_f32, void *d_xyz_f32)
 {
     const int64_t n = (int64_t)H * W;
-    int rc;
     if (!d_disp_f32 && !d_xyz_f32) return SGM_OK;
     if (d_xyz_f32) {
         if (!Q) return set_err(SGM_ERR_INVALID_ARG, "Q is null");
         QMat q;
         memcpy(q.q, Q, sizeof(q.q));
-        if ((rc = stage_begin(e, "float_xyz"))) return rc;
-        hipLaunchKernelGGL(k_float_xyz, dim3((W + 255) / 256, H), dim3(256), 0, e->stream, di, H, W, q,
-                           (float *)d_disp_f32, (float *)d_xyz_f32);
-        KCHECK();
-        return stage_end(e, 1);
+        return run_stage(e, "float_xyz", [&] {
+            hipLaunchKernelGGL(k_float_xyz, dim3((W + 255) / 256, H), dim3(256), 0, e->stream, di, H, W, q,
+                               (float *)d_disp_f32, (float *)d_xyz_f32);
+            return 1;
+        });
     }
-    if ((rc = stage_begin(e, "to_float"))) return rc;
-    if ((rc = run_to_float(e, di, n, (float *)d_disp_f32))) return rc;
-    return stage_end(e, 1);
+    return run_stage(e, "to_float", [&] {
+        const int rc = run_to_float(e, di, n, (float *)d_disp_f32);
+        return rc ? rc : 1;
+    });
 }
 
 // ---- exported C ABI -------------------------------------------------------------------------------
@@ -2435,11 +2441,12 @@ static int run_group(sgm_engine *e, sgm_engine *const *eng, int n, const Plan &p
                     (uint32_t *)e->chain_err.p, nbands};
         HIP_TRY(hipMemsetAsync(e->chain_ctl.p, 0, ctl_bytes, e->stream));
         stage_break(e);
-        if ((rc = stage_begin(e, pass == 0 ? "chain_dn" : "chain_up"))) return rc;
         const int cm = pass == 0 ? SWEEP_FIRST : (pl.wta_split ? SWEEP_REDUCE : SWEEP_ACCUM);
-        if ((rc = launch_chain(g, a, fr, cm, chain_window(g, R, nbands, n, e->chain_wgs), e->stream, pl.axis))) return rc;
-        KCHECK();
-        if ((rc = stage_end(e, 1))) return rc;
+        rc = run_stage(e, pass == 0 ? "chain_dn" : "chain_up", [&] {
+            const int err = launch_chain(g, a, fr, cm, chain_window(g, R, nbands, n, e->chain_wgs), e->stream, pl.axis);
+            return err ? err : 1;
+        });
+        if (rc) return rc;
     }
     HIP_TRY(hipEventRecord(e->ev_group, e->stream));
     // ---- the rest of every pair on its own stream (memory-bound kernels of different pairs side by side)
@@ -2863,44 +2870,64 @@ int sgm_compact_points_device_async(sgm_engine *e, const void *d_xyz, const void
     return SGM_OK;
 }
 
-// One output of a point-list call's host entry: `host` (null: not asked for) gets rows of `row` bytes from the engine's `dev`,
-// which is made to hold n of them -- as many as *rows says once the device entry has run, or n with rows null
+// One input of an add-on's host entry: `bytes` from `host` go up to the engine's `dev`.  A null host or no bytes: not staged.
+struct HostIn {
+    const void *host;
+    DevBuf *dev;
+    size_t bytes;
+    void *d() const { return host && bytes ? dev->p : nullptr; }   // what the device entry gets (after the buffers have been made)
+};
+// One output: `host` (null: not asked for) gets rows of `row` bytes from the engine's `dev`, which is made to hold cap of them
+// (cap < 0: the call's n) -- as many as *rows says once the device entry has run, or all of them with rows null
 struct HostOut {
     void *host;
     DevBuf *dev;
     size_t row;
     const int64_t *rows;
-    void *d() const { return host ? dev->p : nullptr; }   // what the device entry gets (after the buffers have been made)
+    int64_t cap = -1;
+    void *d() const { return host ? dev->p : nullptr; }
 };
 
-// What the host entries of the point-list calls share: the buffers, the cloud up (xyz to e->xyz; disp, colors: to e->f32, e->crgb_in,
-// or null), run(d_disp, d_colors) -- the device entry on these --, then the outputs down and one synchronise.
-extern "C++" {   // (a template: this part of the file has C linkage)
+// What the host entries of the add-ons share: every buffer made, the inputs up, run() -- the device entry on in.d() and out.d() --,
+// then the outputs down and one synchronise.  n: the rows an output holds unless it says otherwise.
+extern "C++" {   // (templates: this part of the file has C linkage)
 template <class Run>
-static int cloud_host_call(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors, int64_t n,
-                           std::initializer_list<HostOut> outs, Run run)
+static int host_call(sgm_engine *e, int64_t n, std::initializer_list<HostIn> ins, std::initializer_list<HostOut> outs, Run run)
 {
     HIP_TRY(hipSetDevice(e->device));
     int rc;
-    if ((rc = e->xyz.ensure((size_t)n * 12)) || (disp && (rc = e->f32.ensure((size_t)n * 4))) || (colors && (rc = e->crgb_in.ensure((size_t)n * 3))))
-        return rc;
+    for (const HostIn &i : ins)
+        if (i.host && i.bytes && (rc = i.dev->ensure(i.bytes))) return rc;
     for (const HostOut &o : outs)
-        if (o.host && (rc = o.dev->ensure((size_t)n * o.row))) return rc;
-    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, e->stream));
-    if (disp) HIP_TRY(hipMemcpyAsync(e->f32.p, disp, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    if (colors) HIP_TRY(hipMemcpyAsync(e->crgb_in.p, colors, (size_t)n * 3, hipMemcpyHostToDevice, e->stream));
-    if ((rc = run(disp ? e->f32.p : nullptr, colors ? e->crgb_in.p : nullptr))) {
+        if (o.host && (rc = o.dev->ensure((size_t)(o.cap < 0 ? n : o.cap) * o.row))) return rc;
+    for (const HostIn &i : ins)
+        if (i.host && i.bytes) HIP_TRY(hipMemcpyAsync(i.dev->p, i.host, i.bytes, hipMemcpyHostToDevice, e->stream));
+    if ((rc = run())) {
         (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
         return rc;
     }
     for (const HostOut &o : outs) {
-        const int64_t rows = o.rows ? *o.rows : n;
+        const int64_t rows = o.rows ? *o.rows : (o.cap < 0 ? n : o.cap);
         if (o.host && rows > 0) HIP_TRY(hipMemcpyAsync(o.host, o.dev->p, (size_t)rows * o.row, hipMemcpyDeviceToHost, e->stream));
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     return SGM_OK;
 }
+// the point-list form: the cloud up (xyz to e->xyz; disp, colors: to e->f32, e->crgb_in, or null), run(d_disp, d_colors)
+template <class Run>
+static int cloud_host_call(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors, int64_t n,
+                           std::initializer_list<HostOut> outs, Run run)
+{
+    const HostIn pts{xyz, &e->xyz, (size_t)n * 12}, dsp{disp, &e->f32, (size_t)n * 4}, rgb{colors, &e->crgb_in, (size_t)n * 3};
+    return host_call(e, n, {pts, dsp, rgb}, outs, [&] { return run(dsp.d(), rgb.d()); });
+}
 }  // extern "C++"
+
+// the statistics of a call into the caller's table (null: not asked for)
+static void put_stats(uint64_t *out, std::initializer_list<uint64_t> s)
+{
+    if (out) std::copy(s.begin(), s.end(), out);
+}
 
 int sgm_compact_points(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int64_t n,
                        float *out_points, uint8_t *out_colors, int64_t *n_valid)
@@ -3049,34 +3076,37 @@ static int run_wls_batch(sgm_engine *e, int n, const void *const *d_disp, const 
     const dim3 px((unsigned)((npx + 255) / 256), n);
     int rc;
     stage_break(e);   // (the host entry's copies lie between the chunks)
-    if ((rc = stage_begin(e, "wls_init"))) return rc;
-    hipLaunchKernelGGL(k_wls_init, px, dim3(256), 0, e->stream, disps, confs, invalid, npx, u, v);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    rc = run_stage(e, "wls_init", [&] {
+        hipLaunchKernelGGL(k_wls_init, px, dim3(256), 0, e->stream, disps, confs, invalid, npx, u, v);
+        return 1;
+    });
+    if (rc) return rc;
     const int T = 3;
     for (int it = 1; it <= T; it++) {
         const float lam = (float)(1.5 * lambda * (double)(1 << (2 * (T - it))) / (double)((1 << (2 * T)) - 1));
         if (W > 1) {   // (a line of one element is the identity)
             const dim3 grid((H + WLS_T - 1) / WLS_T, n);
-            if ((rc = stage_begin(e, "wls_rows"))) return rc;
-            if (cn == 3) launch_wls_rows<3>(rshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
-            else launch_wls_rows<1>(rshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
-            KCHECK();
-            if ((rc = stage_end(e, 1))) return rc;
+            rc = run_stage(e, "wls_rows", [&] {
+                if (cn == 3) launch_wls_rows<3>(rshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
+                else launch_wls_rows<1>(rshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
+                return 1;
+            });
+            if (rc) return rc;
         }
         if (H > 1) {
             const dim3 grid((W + WLS_T - 1) / WLS_T, n);
-            if ((rc = stage_begin(e, "wls_cols"))) return rc;
-            if (cn == 3) launch_wls_cols<3>(cshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
-            else launch_wls_cols<1>(cshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
-            KCHECK();
-            if ((rc = stage_end(e, 1))) return rc;
+            rc = run_stage(e, "wls_cols", [&] {
+                if (cn == 3) launch_wls_cols<3>(cshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
+                else launch_wls_cols<1>(cshape, grid, e->stream, u, v, c, guides, t, lam, H, W);
+                return 1;
+            });
+            if (rc) return rc;
         }
     }
-    if ((rc = stage_begin(e, "wls_final"))) return rc;
-    hipLaunchKernelGGL(k_wls_final, px, dim3(256), 0, e->stream, (const float *)u, (const float *)v, invalid, npx, outs, outfs);
-    KCHECK();
-    return stage_end(e, 1);
+    return run_stage(e, "wls_final", [&] {
+        hipLaunchKernelGGL(k_wls_final, px, dim3(256), 0, e->stream, (const float *)u, (const float *)v, invalid, npx, outs, outfs);
+        return 1;
+    });
 }
 
 int sgm_wls_filter_batch_device(sgm_engine *e, int N, const void *const *d_disp_i16, const void *const *d_guide_u8, int cn,
@@ -3196,16 +3226,17 @@ static int run_lrc_batch(sgm_engine *e, int n, const void *const *d_left, const 
     uint8_t *fac = (uint8_t *)e->lrc_f.p;
     int rc;
     stage_break(e);
-    if ((rc = stage_begin(e, "lrc_factor"))) return rc;
-    hipLaunchKernelGGL(k_lrc_factor, dim3((W + LRC_TW - 1) / LRC_TW, (H + LRC_TH - 1) / LRC_TH, 2 * n), dim3(LRC_THREADS),
-                       lrc_lds_bytes(radius), e->stream, lefts, rights, invalid, radius, (int64_t)var_max, H, W, fac);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
-    if ((rc = stage_begin(e, "lrc_match"))) return rc;
-    hipLaunchKernelGGL(k_lrc_match, dim3((W + 255) / 256, H, n), dim3(256), 0, e->stream, lefts, rights, bases, invalid, thresh, H, W,
-                       (const uint8_t *)fac, cls, crs);
-    KCHECK();
-    return stage_end(e, 1);
+    rc = run_stage(e, "lrc_factor", [&] {
+        hipLaunchKernelGGL(k_lrc_factor, dim3((W + LRC_TW - 1) / LRC_TW, (H + LRC_TH - 1) / LRC_TH, 2 * n), dim3(LRC_THREADS),
+                           lrc_lds_bytes(radius), e->stream, lefts, rights, invalid, radius, (int64_t)var_max, H, W, fac);
+        return 1;
+    });
+    if (rc) return rc;
+    return run_stage(e, "lrc_match", [&] {
+        hipLaunchKernelGGL(k_lrc_match, dim3((W + 255) / 256, H, n), dim3(256), 0, e->stream, lefts, rights, bases, invalid, thresh, H, W,
+                           (const uint8_t *)fac, cls, crs);
+        return 1;
+    });
 }
 
 int sgm_lrc_confidence_batch_device(sgm_engine *e, int N, const void *const *d_lefts, const void *const *d_rights,
@@ -3287,16 +3318,19 @@ static int voxel_check_args(const sgm_engine *e, const void *xyz, const void *co
     return SGM_OK;
 }
 
+// the result of a call that found no point in range, for the two calls that report a count and the points out of range
+static void cloud_nothing(int64_t *n_result, int64_t *n_out_of_range, int64_t n_out)
+{
+    *n_result = 0;
+    if (n_out_of_range) *n_out_of_range = n_out;
+}
+
 int sgm_voxel_downsample_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int64_t n,
                                 float voxel_size, const float origin[3], int min_points, void *d_out_points, void *d_out_colors,
                                 void *d_out_counts, int64_t *n_voxels, int64_t *n_out_of_range)
 {
     if (int rc = voxel_check_args(e, d_xyz, d_colors_rgb, n, voxel_size, origin, min_points, d_out_points, d_out_colors, n_voxels)) return rc;
-    if (n == 0) {
-        *n_voxels = 0;
-        if (n_out_of_range) *n_out_of_range = 0;
-        return SGM_OK;
-    }
+    if (n == 0) return cloud_nothing(n_voxels, n_out_of_range, 0), SGM_OK;
     HIP_TRY(hipSetDevice(e->device));
     const int m = (int)((n + 255) / 256);
     int rc;
@@ -3311,45 +3345,43 @@ int sgm_voxel_downsample_device(sgm_engine *e, const void *d_xyz, const void *d_
     // 1. how many points arrive: the table is sized from them, and a cloud with none is done here
     HIP_TRY(hipMemsetAsync(ctl, 0, VOX_CTL_WORDS * 4, st));
     stage_break(e);
-    if ((rc = stage_begin(e, "voxel_count"))) return rc;
-    hipLaunchKernelGGL(k_voxel_count, dim3(std::min(m, VOX_COUNT_BLOCKS)), dim3(256), 0, st, xyz, disp, n, G, ctl);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    rc = run_stage(e, "voxel_count", [&] {
+        hipLaunchKernelGGL(k_voxel_count, dim3(std::min(m, VOX_COUNT_BLOCKS)), dim3(256), 0, st, xyz, disp, n, G, ctl);
+        return 1;
+    });
+    if (rc) return rc;
     uint32_t h_ctl[VOX_CTL_WORDS] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     stage_break(e);
     const uint32_t n_in = h_ctl[VOX_CTL_IN];
+    if (n_in == 0) return cloud_nothing(n_voxels, n_out_of_range, (int64_t)h_ctl[VOX_CTL_OUT]), SGM_OK;
     if (n_out_of_range) *n_out_of_range = (int64_t)h_ctl[VOX_CTL_OUT];
-    if (n_in == 0) {
-        *n_voxels = 0;
-        return SGM_OK;
-    }
     // 2. the table: the smallest power of two of at least twice the points in range (debug: of at least the points themselves)
     const uint64_t want = (e->debug & SGM_DBG_VOXEL_TIGHT_TABLE) ? (uint64_t)n_in : 2 * (uint64_t)n_in;
     uint32_t cap = 1;
     while (cap < want) cap <<= 1;   // (n_in < 2^24: at most 2^25)
     if ((rc = e->vox_tab.ensure((size_t)cap * sizeof(VoxSlot)))) return rc;
     VoxSlot *tab = (VoxSlot *)e->vox_tab.p;
-    if ((rc = stage_begin(e, "voxel_clear"))) return rc;
-    hipLaunchKernelGGL(k_voxel_clear, dim3((cap + 255) / 256), dim3(256), 0, st, tab, cap);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    if ((rc = run_stage(e, "voxel_clear", [&] { hipLaunchKernelGGL(k_voxel_clear, dim3((cap + 255) / 256), dim3(256), 0, st, tab, cap); return 1; })))
+        return rc;
     // 3. insert and accumulate
-    if ((rc = stage_begin(e, "voxel_insert"))) return rc;
-    const bool pre = VOX_PRE_DEFAULT != !!(e->debug & SGM_DBG_VOXEL_OTHER_REDUCTION);
-    if (pre) hipLaunchKernelGGL(k_voxel_insert<true>, dim3(m), dim3(256), 0, st, xyz, disp, colors, n, G, tab, cap - 1, slot_of, ctl);
-    else hipLaunchKernelGGL(k_voxel_insert<false>, dim3(m), dim3(256), 0, st, xyz, disp, colors, n, G, tab, cap - 1, slot_of, ctl);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    rc = run_stage(e, "voxel_insert", [&] {
+        const bool pre = VOX_PRE_DEFAULT != !!(e->debug & SGM_DBG_VOXEL_OTHER_REDUCTION);
+        if (pre) hipLaunchKernelGGL(k_voxel_insert<true>, dim3(m), dim3(256), 0, st, xyz, disp, colors, n, G, tab, cap - 1, slot_of, ctl);
+        else hipLaunchKernelGGL(k_voxel_insert<false>, dim3(m), dim3(256), 0, st, xyz, disp, colors, n, G, tab, cap - 1, slot_of, ctl);
+        return 1;
+    });
+    if (rc) return rc;
     // 4. the heads of the kept voxels through the ordered compaction; the scatter computes the rows
-    if ((rc = stage_begin(e, "voxel_heads"))) return rc;
-    hipLaunchKernelGGL(k_voxel_head_count, dim3(m), dim3(256), 0, st, (const uint32_t *)slot_of, (const VoxSlot *)tab, n, (uint32_t)min_points, cnt);
-    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
-    hipLaunchKernelGGL(k_voxel_scatter, dim3(m), dim3(256), 0, st, (const uint32_t *)slot_of, (const VoxSlot *)tab, n, (uint32_t)min_points,
-                       (const uint32_t *)cnt, G, (float *)d_out_points, (uint8_t *)d_out_colors, (uint32_t *)d_out_counts);
-    KCHECK();
-    if ((rc = stage_end(e, 3))) return rc;
+    rc = run_stage(e, "voxel_heads", [&] {
+        hipLaunchKernelGGL(k_voxel_head_count, dim3(m), dim3(256), 0, st, (const uint32_t *)slot_of, (const VoxSlot *)tab, n, (uint32_t)min_points, cnt);
+        hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
+        hipLaunchKernelGGL(k_voxel_scatter, dim3(m), dim3(256), 0, st, (const uint32_t *)slot_of, (const VoxSlot *)tab, n, (uint32_t)min_points,
+                           (const uint32_t *)cnt, G, (float *)d_out_points, (uint8_t *)d_out_colors, (uint32_t *)d_out_counts);
+        return 3;
+    });
+    if (rc) return rc;
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&total, cnt + m, 4, hipMemcpyDeviceToHost, st));
@@ -3365,11 +3397,7 @@ int sgm_voxel_downsample(sgm_engine *e, const float *xyz, const float *disp, con
                          int64_t *n_voxels, int64_t *n_out_of_range)
 {
     if (int rc = voxel_check_args(e, xyz, colors_rgb, n, voxel_size, origin, min_points, out_points, out_colors, n_voxels)) return rc;
-    if (n == 0) {
-        *n_voxels = 0;
-        if (n_out_of_range) *n_out_of_range = 0;
-        return SGM_OK;
-    }
+    if (n == 0) return cloud_nothing(n_voxels, n_out_of_range, 0), SGM_OK;
     int64_t nv = 0, noor = 0;
     const HostOut pts{out_points, &e->cpts, 12, &nv}, rgb{out_colors, &e->crgb, 3, &nv}, cnt{out_counts, &e->vox_cnt, 4, &nv};
     if (int rc = cloud_host_call(e, xyz, disp, out_colors ? colors_rgb : nullptr, n, {pts, rgb, cnt}, [&](void *d_disp, void *d_colors) {
@@ -3451,10 +3479,11 @@ static int radius_build_grid(sgm_engine *e, const float *xyz, const float *disp,
     // 1. how many points arrive: the table and the sorted records are sized from them, and a cloud with none is done here
     HIP_TRY(hipMemsetAsync(ctl, 0, RAD_CTL_WORDS * 4, st));
     stage_break(e);
-    if ((rc = stage_begin(e, names[0]))) return rc;
-    hipLaunchKernelGGL(k_radius_count, dim3(std::min(m, RAD_COUNT_BLOCKS)), dim3(256), 0, st, xyz, disp, n, G, ctl);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    rc = run_stage(e, names[0], [&] {
+        hipLaunchKernelGGL(k_radius_count, dim3(std::min(m, RAD_COUNT_BLOCKS)), dim3(256), 0, st, xyz, disp, n, G, ctl);
+        return 1;
+    });
+    if (rc) return rc;
     uint32_t h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h_ctl, ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -3471,29 +3500,43 @@ static int radius_build_grid(sgm_engine *e, const float *xyz, const float *disp,
     RadSlot *tab = (RadSlot *)e->rad_tab.p;
     float4 *sorted = g->sorted = (float4 *)e->rad_sorted.p;
     g->tab = tab;
-    if ((rc = stage_begin(e, names[1]))) return rc;
-    hipLaunchKernelGGL(k_radius_clear, dim3((cap + 255) / 256), dim3(256), 0, st, tab, cap);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    if ((rc = run_stage(e, names[1], [&] { hipLaunchKernelGGL(k_radius_clear, dim3((cap + 255) / 256), dim3(256), 0, st, tab, cap); return 1; })))
+        return rc;
     // 3. insert: each point's cell and its rank there
-    if ((rc = stage_begin(e, names[2]))) return rc;
-    hipLaunchKernelGGL(k_radius_insert, dim3(m), dim3(256), 0, st, xyz, disp, n, G, tab, cap - 1, slot_rank, ctl);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    rc = run_stage(e, names[2], [&] {
+        hipLaunchKernelGGL(k_radius_insert, dim3(m), dim3(256), 0, st, xyz, disp, n, G, tab, cap - 1, slot_rank, ctl);
+        return 1;
+    });
+    if (rc) return rc;
     // 4. where each cell's run begins
-    if ((rc = stage_begin(e, names[3]))) return rc;
-    hipLaunchKernelGGL(k_radius_starts, dim3((cap + RAD_STARTS_PER_BLOCK - 1) / RAD_STARTS_PER_BLOCK), dim3(256), 0, st, tab, cap, ctl);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    rc = run_stage(e, names[3], [&] {
+        hipLaunchKernelGGL(k_radius_starts, dim3((cap + RAD_STARTS_PER_BLOCK - 1) / RAD_STARTS_PER_BLOCK), dim3(256), 0, st, tab, cap, ctl);
+        return 1;
+    });
+    if (rc) return rc;
     // 5. the records sorted by cell; the points in no cell get their zeros
-    if ((rc = stage_begin(e, names[4]))) return rc;
-    hipLaunchKernelGGL(k_radius_sort, dim3(m), dim3(256), 0, st, xyz, n, (const RadSlot *)tab, (const uint2 *)slot_rank, sorted, keep, counts);
-    KCHECK();
-    return stage_end(e, 1);
+    return run_stage(e, names[4], [&] {
+        hipLaunchKernelGGL(k_radius_sort, dim3(m), dim3(256), 0, st, xyz, n, (const RadSlot *)tab, (const uint2 *)slot_rank, sorted, keep, counts);
+        return 1;
+    });
 }
 
 // step 7 of both: the kept points through the ordered compaction; *total comes back with the call's control words (blocks), and
 // a set RAD_CTL_ERR is the error of `who` (cloud_no_slot)
+// The ordered compaction of the points with a set keep byte: the blocks' counts, their scan (the total behind them in ccount) and,
+// when an output of rows is asked for, the scatter.  Returns the launches, for the caller's stage.
+static int launch_keep_compaction(sgm_engine *e, int m, const uint8_t *keep, const float *xyz, const uint8_t *colors, int64_t n,
+                                  void *d_out_points, void *d_out_colors, void *d_out_index)
+{
+    uint32_t *cnt = (uint32_t *)e->ccount.p;
+    hipLaunchKernelGGL(k_radius_keep_count, dim3(m), dim3(256), 0, e->stream, keep, n, cnt);
+    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, e->stream, cnt, m);
+    if (!d_out_points && !d_out_colors && !d_out_index) return 2;
+    hipLaunchKernelGGL(k_radius_scatter, dim3(m), dim3(256), 0, e->stream, keep, xyz, colors, n, (const uint32_t *)cnt, (float *)d_out_points,
+                       (uint8_t *)d_out_colors, (uint32_t *)d_out_index);
+    return 3;
+}
+
 static int radius_compact_kept(sgm_engine *e, const char *who, const char *stage, const CloudGrid &g, const uint8_t *keep, const float *xyz,
                                const uint8_t *colors, int64_t n, void *d_out_points, void *d_out_colors, void *d_out_index, uint32_t *total)
 {
@@ -3502,15 +3545,8 @@ static int radius_compact_kept(sgm_engine *e, const char *who, const char *stage
     uint32_t h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0};
     uint32_t *cnt = (uint32_t *)e->ccount.p;
     hipStream_t st = e->stream;
-    if ((rc = stage_begin(e, stage))) return rc;
-    hipLaunchKernelGGL(k_radius_keep_count, dim3(m), dim3(256), 0, st, keep, n, cnt);
-    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
-    const bool rows = d_out_points || d_out_colors || d_out_index;
-    if (rows)
-        hipLaunchKernelGGL(k_radius_scatter, dim3(m), dim3(256), 0, st, keep, xyz, colors, n, (const uint32_t *)cnt,
-                           (float *)d_out_points, (uint8_t *)d_out_colors, (uint32_t *)d_out_index);
-    KCHECK();
-    if ((rc = stage_end(e, rows ? 3 : 2))) return rc;
+    if ((rc = run_stage(e, stage, [&] { return launch_keep_compaction(e, m, keep, xyz, colors, n, d_out_points, d_out_colors, d_out_index); })))
+        return rc;
     HIP_TRY(hipMemcpyAsync(h_ctl, e->rad_ctl.p, RAD_CTL_WORDS * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(total, cnt + m, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -3522,11 +3558,7 @@ int sgm_radius_outlier_device(sgm_engine *e, const void *d_xyz, const void *d_di
                               void *d_out_points, void *d_out_colors, void *d_out_index, int64_t *n_kept, int64_t *n_out_of_range)
 {
     if (int rc = radius_check_args(e, d_xyz, d_colors_rgb, n, radius, origin, nb_points, max_count, d_out_colors, n_kept)) return rc;
-    if (n == 0) {
-        *n_kept = 0;
-        if (n_out_of_range) *n_out_of_range = 0;
-        return SGM_OK;
-    }
+    if (n == 0) return cloud_nothing(n_kept, n_out_of_range, 0), SGM_OK;
     HIP_TRY(hipSetDevice(e->device));
     const int m = (int)((n + 255) / 256);
     int rc;
@@ -3546,20 +3578,19 @@ int sgm_radius_outlier_device(sgm_engine *e, const void *d_xyz, const void *d_di
         if (d_out_keep) HIP_TRY(hipMemsetAsync(d_out_keep, 0, (size_t)n, st));
         if (counts) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n * 4, st));
         HIP_TRY(hipStreamSynchronize(st));
-        *n_kept = 0;
-        if (n_out_of_range) *n_out_of_range = (int64_t)g.n_out;
-        return SGM_OK;
+        return cloud_nothing(n_kept, n_out_of_range, (int64_t)g.n_out), SGM_OK;
     }
     // 6. the counts
-    if ((rc = stage_begin(e, "radius_query"))) return rc;
-    if (e->debug & SGM_DBG_RADIUS_SOURCE_ORDER)
-        hipLaunchKernelGGL(k_radius_query<false>, dim3(m), dim3(256), 0, st, (const float4 *)g.sorted, g.n_in, xyz, (const uint2 *)g.slot_rank, n,
-                           g.G, g.tab, g.mask, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
-    else
-        hipLaunchKernelGGL(k_radius_query<true>, dim3((g.n_in + 255) / 256), dim3(256), 0, st, (const float4 *)g.sorted, g.n_in, xyz,
-                           (const uint2 *)g.slot_rank, n, g.G, g.tab, g.mask, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    rc = run_stage(e, "radius_query", [&] {
+        if (e->debug & SGM_DBG_RADIUS_SOURCE_ORDER)
+            hipLaunchKernelGGL(k_radius_query<false>, dim3(m), dim3(256), 0, st, (const float4 *)g.sorted, g.n_in, xyz, (const uint2 *)g.slot_rank,
+                               n, g.G, g.tab, g.mask, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
+        else
+            hipLaunchKernelGGL(k_radius_query<true>, dim3((g.n_in + 255) / 256), dim3(256), 0, st, (const float4 *)g.sorted, g.n_in, xyz,
+                               (const uint2 *)g.slot_rank, n, g.G, g.tab, g.mask, (uint32_t)nb_points, (uint32_t)max_count, keep, counts);
+        return 1;
+    });
+    if (rc) return rc;
     // 7. the kept points through the ordered compaction
     uint32_t total = 0;
     if ((rc = radius_compact_kept(e, "sgm_radius_outlier", "radius_compact", g, keep, xyz, colors, n, d_out_points, d_out_colors, d_out_index,
@@ -3575,11 +3606,7 @@ int sgm_radius_outlier(sgm_engine *e, const float *xyz, const float *disp, const
                        uint8_t *out_colors, uint32_t *out_index, int64_t *n_kept, int64_t *n_out_of_range)
 {
     if (int rc = radius_check_args(e, xyz, colors_rgb, n, radius, origin, nb_points, max_count, out_colors, n_kept)) return rc;
-    if (n == 0) {
-        *n_kept = 0;
-        if (n_out_of_range) *n_out_of_range = 0;
-        return SGM_OK;
-    }
+    if (n == 0) return cloud_nothing(n_kept, n_out_of_range, 0), SGM_OK;
     int64_t nk = 0, noor = 0;
     const HostOut keep{out_keep, &e->rad_keep, 1, nullptr}, cnt{out_counts, &e->rad_cnt, 4, nullptr}, pts{out_points, &e->cpts, 12, &nk},
         rgb{out_colors, &e->crgb, 3, &nk}, idx{out_index, &e->rad_idx, 4, &nk};
@@ -3624,17 +3651,19 @@ static uint32_t stat_threshold(uint64_t m, uint64_t A, uint64_t B, float ratio)
     return thr >= 4294967295.0 ? 4294967294u : (uint32_t)thr;
 }
 
+static void stat_nothing(int64_t *n_kept, uint64_t *out_stats, uint64_t n_out)
+{
+    *n_kept = 0;
+    put_stats(out_stats, {0, n_out, 0, 0, 0, 0, 0, 0});
+}
+
 int sgm_statistical_outlier_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int64_t n,
                                    int nb_neighbors, float std_ratio, float max_radius, const float origin[3], void *d_out_keep,
                                    void *d_out_mean, void *d_out_points, void *d_out_colors, void *d_out_index, int64_t *n_kept,
                                    uint64_t *out_stats)
 {
     if (int rc = stat_check_args(e, d_xyz, d_colors_rgb, n, nb_neighbors, std_ratio, max_radius, origin, d_out_colors, n_kept)) return rc;
-    if (n == 0) {
-        *n_kept = 0;
-        if (out_stats) std::fill(out_stats, out_stats + 8, (uint64_t)0);
-        return SGM_OK;
-    }
+    if (n == 0) return stat_nothing(n_kept, out_stats, 0), SGM_OK;
     HIP_TRY(hipSetDevice(e->device));
     const int m = (int)((n + 255) / 256);
     int rc;
@@ -3658,53 +3687,45 @@ int sgm_statistical_outlier_device(sgm_engine *e, const void *d_xyz, const void 
         if (d_out_keep) HIP_TRY(hipMemsetAsync(d_out_keep, 0, (size_t)n, st));
         if (mean) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)mean, (int)0xBF800000u, (size_t)n, st));   // -1.0f
         HIP_TRY(hipStreamSynchronize(st));
-        *n_kept = 0;
-        if (out_stats) {
-            std::fill(out_stats, out_stats + 8, (uint64_t)0);
-            out_stats[1] = n_out;
-        }
-        return SGM_OK;
+        return stat_nothing(n_kept, out_stats, n_out), SGM_OK;
     }
     // 6. per point the k nearest, their mean distance and q: the list of a lane has the smallest capacity that holds k
     HIP_TRY(hipMemsetAsync(sums, 0, STAT_SUM_WORDS * 8, st));
     stage_break(e);
-    if ((rc = stage_begin(e, "stat_query"))) return rc;
-    const dim3 qgrid((n_in + 255) / 256);
-    const uint32_t k = (uint32_t)nb_neighbors;
+    rc = run_stage(e, "stat_query", [&] {
+        const dim3 qgrid((n_in + 255) / 256);
+        const uint32_t k = (uint32_t)nb_neighbors;
 #define SGM_STAT_QUERY(CAP) \
     hipLaunchKernelGGL(k_stat_query<CAP>, qgrid, dim3(256), 0, st, (const float4 *)g.sorted, n_in, g.G, g.tab, g.mask, k, qscale, (uint32_t *)pt, mean)
-    if (e->debug & SGM_DBG_STAT_WIDE_LIST) SGM_STAT_QUERY(64);
-    else if (k <= 8) SGM_STAT_QUERY(8);
-    else if (k <= 16) SGM_STAT_QUERY(16);
-    else if (k <= 32) SGM_STAT_QUERY(32);
-    else SGM_STAT_QUERY(64);
+        if (e->debug & SGM_DBG_STAT_WIDE_LIST) SGM_STAT_QUERY(64);
+        else if (k <= 8) SGM_STAT_QUERY(8);
+        else if (k <= 16) SGM_STAT_QUERY(16);
+        else if (k <= 32) SGM_STAT_QUERY(32);
+        else SGM_STAT_QUERY(64);
 #undef SGM_STAT_QUERY
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+        return 1;
+    });
+    if (rc) return rc;
     // 7. m, A, B over the dense points; the host forms T from them
-    if ((rc = stage_begin(e, "stat_reduce"))) return rc;
-    hipLaunchKernelGGL(k_stat_reduce, dim3(std::min(m, RAD_COUNT_BLOCKS)), dim3(256), 0, st, (const uint2 *)pt, n, sums);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    rc = run_stage(e, "stat_reduce", [&] {
+        hipLaunchKernelGGL(k_stat_reduce, dim3(std::min(m, RAD_COUNT_BLOCKS)), dim3(256), 0, st, (const uint2 *)pt, n, sums);
+        return 1;
+    });
+    if (rc) return rc;
     unsigned long long h_sums[STAT_SUM_WORDS] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h_sums, sums, sizeof(h_sums), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     stage_break(e);
     const uint32_t T = stat_threshold(h_sums[STAT_SUM_M], h_sums[STAT_SUM_A], h_sums[STAT_SUM_B], std_ratio);
     // 8. keep, then the kept points through the ordered compaction
-    if ((rc = stage_begin(e, "stat_keep"))) return rc;
-    hipLaunchKernelGGL(k_stat_keep, dim3(m), dim3(256), 0, st, (const uint2 *)pt, n, T, keep, mean);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    if ((rc = run_stage(e, "stat_keep", [&] { hipLaunchKernelGGL(k_stat_keep, dim3(m), dim3(256), 0, st, (const uint2 *)pt, n, T, keep, mean); return 1; })))
+        return rc;
     uint32_t total = 0;
     if ((rc = radius_compact_kept(e, "sgm_statistical_outlier", "stat_compact", g, keep, xyz, colors, n, d_out_points, d_out_colors, d_out_index,
                                   &total)))
         return rc;
     *n_kept = (int64_t)total;
-    if (out_stats) {
-        const uint64_t s[8] = {n_in, n_out, h_sums[STAT_SUM_M], n_in - h_sums[STAT_SUM_M], h_sums[STAT_SUM_A], h_sums[STAT_SUM_B], T, 0};
-        std::copy(s, s + 8, out_stats);
-    }
+    put_stats(out_stats, {n_in, n_out, h_sums[STAT_SUM_M], n_in - h_sums[STAT_SUM_M], h_sums[STAT_SUM_A], h_sums[STAT_SUM_B], T, 0});
     return SGM_OK;
 }
 
@@ -3713,11 +3734,7 @@ int sgm_statistical_outlier(sgm_engine *e, const float *xyz, const float *disp, 
                             uint8_t *out_colors, uint32_t *out_index, int64_t *n_kept, uint64_t *out_stats)
 {
     if (int rc = stat_check_args(e, xyz, colors_rgb, n, nb_neighbors, std_ratio, max_radius, origin, out_colors, n_kept)) return rc;
-    if (n == 0) {
-        *n_kept = 0;
-        if (out_stats) std::fill(out_stats, out_stats + 8, (uint64_t)0);
-        return SGM_OK;
-    }
+    if (n == 0) return stat_nothing(n_kept, out_stats, 0), SGM_OK;
     int64_t nk = 0;
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const HostOut keep{out_keep, &e->rad_keep, 1, nullptr}, mean{out_mean, &e->stat_mean, 4, nullptr}, pts{out_points, &e->cpts, 12, &nk},
@@ -3747,15 +3764,14 @@ static int cov_check_args(const sgm_engine *e, const void *xyz, int64_t n, float
     });
 }
 
+static void cov_nothing(uint64_t *out_stats, uint64_t n_out) { put_stats(out_stats, {0, n_out, 0, 0}); }
+
 int sgm_covariance_normals_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, int64_t n, float radius, int min_neighbors,
                                   const float origin[3], const float viewpoint[3], int orient, void *d_out_normals,
                                   void *d_out_curvature, void *d_out_counts, uint64_t *out_stats)
 {
     if (int rc = cov_check_args(e, d_xyz, n, radius, min_neighbors, origin, viewpoint, orient)) return rc;
-    if (n == 0) {
-        if (out_stats) std::fill(out_stats, out_stats + 4, (uint64_t)0);
-        return SGM_OK;
-    }
+    if (n == 0) return cov_nothing(out_stats, 0), SGM_OK;
     HIP_TRY(hipSetDevice(e->device));
     const int m = (int)((n + 255) / 256);
     int rc;
@@ -3778,12 +3794,8 @@ int sgm_covariance_normals_device(sgm_engine *e, const void *d_xyz, const void *
         if (normals) HIP_TRY(hipMemsetAsync(normals, 0, (size_t)n * 12, st));
         if (curv) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)curv, (int)0xBF800000u, (size_t)n, st));   // -1.0f
         if (counts) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n * 4, st));
-        if (out_stats) {
-            HIP_TRY(hipStreamSynchronize(st));
-            std::fill(out_stats, out_stats + 4, (uint64_t)0);
-            out_stats[1] = n_out;
-        }
-        return SGM_OK;
+        if (out_stats) HIP_TRY(hipStreamSynchronize(st));
+        return cov_nothing(out_stats, n_out), SGM_OK;
     }
     const bool separate = (e->debug & SGM_DBG_COV_SEPARATE_SOLVE) != 0, select = (e->debug & SGM_DBG_COV_SELECT_ACCUM) != 0;
     if (separate && (rc = e->cov_mom.ensure((size_t)n_in * COV_WORDS * 8))) return rc;
@@ -3792,24 +3804,26 @@ int sgm_covariance_normals_device(sgm_engine *e, const void *d_xyz, const void *
     // 6. per point the moments of its neighbours and (fused) the normal; the points in no cell get their zeros and -1 first
     HIP_TRY(hipMemsetAsync(ctl, 0, COV_CTL_WORDS * 4, st));
     stage_break(e);
-    if ((rc = stage_begin(e, "cov_query"))) return rc;
-    const bool fill = n_in < (uint64_t)n && (normals || curv);
-    if (fill) hipLaunchKernelGGL(k_cov_fill, dim3(m), dim3(256), 0, st, (const uint2 *)g.slot_rank, n, normals, curv);
     const dim3 qgrid((n_in + 255) / 256);
+    rc = run_stage(e, "cov_query", [&] {
+        const bool fill = n_in < (uint64_t)n && (normals || curv);
+        if (fill) hipLaunchKernelGGL(k_cov_fill, dim3(m), dim3(256), 0, st, (const uint2 *)g.slot_rank, n, normals, curv);
 #define SGM_COV_QUERY(SEP, SEL) \
     hipLaunchKernelGGL((k_cov_query<SEP, SEL>), qgrid, dim3(256), 0, st, sorted, n_in, g.G, g.tab, g.mask, V, staged, normals, curv, counts, ctl)
-    if (separate && select) SGM_COV_QUERY(true, true);
-    else if (separate) SGM_COV_QUERY(true, false);
-    else if (select) SGM_COV_QUERY(false, true);
-    else SGM_COV_QUERY(false, false);
+        if (separate && select) SGM_COV_QUERY(true, true);
+        else if (separate) SGM_COV_QUERY(true, false);
+        else if (select) SGM_COV_QUERY(false, true);
+        else SGM_COV_QUERY(false, false);
 #undef SGM_COV_QUERY
-    KCHECK();
-    if ((rc = stage_end(e, fill ? 2 : 1))) return rc;
+        return fill ? 2 : 1;
+    });
+    if (rc) return rc;
     if (separate) {   // 7. the solve as a kernel of its own
-        if ((rc = stage_begin(e, "cov_solve"))) return rc;
-        hipLaunchKernelGGL(k_cov_solve, qgrid, dim3(256), 0, st, sorted, n_in, V, (const long long *)staged, normals, curv, counts, ctl);
-        KCHECK();
-        if ((rc = stage_end(e, 1))) return rc;
+        rc = run_stage(e, "cov_solve", [&] {
+            hipLaunchKernelGGL(k_cov_solve, qgrid, dim3(256), 0, st, sorted, n_in, V, (const long long *)staged, normals, curv, counts, ctl);
+            return 1;
+        });
+        if (rc) return rc;
     }
     if (!out_stats) return SGM_OK;
     uint32_t h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0}, h_cov[COV_CTL_WORDS] = {0, 0, 0, 0};
@@ -3817,8 +3831,7 @@ int sgm_covariance_normals_device(sgm_engine *e, const void *d_xyz, const void *
     HIP_TRY(hipMemcpyAsync(h_cov, ctl, sizeof(h_cov), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (h_ctl[RAD_CTL_ERR]) return cloud_no_slot("sgm_covariance_normals", g);
-    const uint64_t s[4] = {n_in, n_out, h_cov[COV_CTL_NORMAL], h_cov[COV_CTL_DEGENERATE]};
-    std::copy(s, s + 4, out_stats);
+    put_stats(out_stats, {n_in, n_out, h_cov[COV_CTL_NORMAL], h_cov[COV_CTL_DEGENERATE]});
     return SGM_OK;
 }
 
@@ -3827,10 +3840,7 @@ int sgm_covariance_normals(sgm_engine *e, const float *xyz, const float *disp, i
                            uint32_t *out_counts, uint64_t *out_stats)
 {
     if (int rc = cov_check_args(e, xyz, n, radius, min_neighbors, origin, viewpoint, orient)) return rc;
-    if (n == 0) {
-        if (out_stats) std::fill(out_stats, out_stats + 4, (uint64_t)0);
-        return SGM_OK;
-    }
+    if (n == 0) return cov_nothing(out_stats, 0), SGM_OK;
     uint64_t stats[4] = {0, 0, 0, 0};   // (always asked for: the host entry reports a full table whatever the caller wants)
     const HostOut nrm{out_normals, &e->cov_nrm, 12, nullptr}, curv{out_curvature, &e->cov_curv, 4, nullptr}, cnt{out_counts, &e->rad_cnt, 4, nullptr};
     if (int rc = cloud_host_call(e, xyz, disp, nullptr, n, {nrm, curv, cnt}, [&](void *d_disp, void *) {
@@ -3852,16 +3862,18 @@ static int dbscan_check_args(const sgm_engine *e, const void *xyz, int64_t n, fl
     });
 }
 
+static void dbscan_nothing(int64_t *n_clusters, uint64_t *out_stats, uint64_t n_out)
+{
+    *n_clusters = 0;
+    put_stats(out_stats, {0, n_out, 0, 0, 0, 0});
+}
+
 int sgm_cluster_dbscan_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, int64_t n, float eps, int min_points,
                               const float origin[3], void *d_out_labels, void *d_out_core, void *d_out_sizes, uint64_t *out_stats,
                               int64_t *n_clusters)
 {
     if (int rc = dbscan_check_args(e, d_xyz, n, eps, min_points, origin, n_clusters)) return rc;
-    if (n == 0) {
-        *n_clusters = 0;
-        if (out_stats) std::fill(out_stats, out_stats + 6, (uint64_t)0);
-        return SGM_OK;
-    }
+    if (n == 0) return dbscan_nothing(n_clusters, out_stats, 0), SGM_OK;
     HIP_TRY(hipSetDevice(e->device));
     const int m = (int)((n + 255) / 256);
     int rc;
@@ -3883,12 +3895,7 @@ int sgm_cluster_dbscan_device(sgm_engine *e, const void *d_xyz, const void *d_di
         if (labels) HIP_TRY(hipMemsetAsync(labels, 0xFF, (size_t)n * 4, st));   // -1
         if (d_out_core) HIP_TRY(hipMemsetAsync(d_out_core, 0, (size_t)n, st));
         HIP_TRY(hipStreamSynchronize(st));
-        *n_clusters = 0;
-        if (out_stats) {
-            std::fill(out_stats, out_stats + 6, (uint64_t)0);
-            out_stats[1] = n_out;
-        }
-        return SGM_OK;
+        return dbscan_nothing(n_clusters, out_stats, n_out), SGM_OK;
     }
     float4 *sorted = g.sorted;
     const uint2 *slot_rank = g.slot_rank;
@@ -3900,32 +3907,36 @@ int sgm_cluster_dbscan_device(sgm_engine *e, const void *d_xyz, const void *d_di
     // links set to identity
     HIP_TRY(hipMemsetAsync(ctl, 0, DB_CTL_WORDS * 4, st));
     stage_break(e);
-    if ((rc = stage_begin(e, "dbscan_core"))) return rc;
-    hipLaunchKernelGGL(k_radius_query<true>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, xyz, slot_rank, n, g.G, g.tab, g.mask,
-                       (uint32_t)min_points, (uint32_t)min_points, core, (uint32_t *)nullptr);
-    if (gather) hipLaunchKernelGGL(k_dbscan_mark<false>, qgrid, dim3(256), 0, st, sorted, n_in, (const uint8_t *)core, parent, nearest);
-    else hipLaunchKernelGGL(k_dbscan_mark<true>, qgrid, dim3(256), 0, st, sorted, n_in, (const uint8_t *)core, parent, nearest);
-    KCHECK();
-    if ((rc = stage_end(e, 2))) return rc;
+    rc = run_stage(e, "dbscan_core", [&] {
+        hipLaunchKernelGGL(k_radius_query<true>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, xyz, slot_rank, n, g.G, g.tab, g.mask,
+                           (uint32_t)min_points, (uint32_t)min_points, core, (uint32_t *)nullptr);
+        if (gather) hipLaunchKernelGGL(k_dbscan_mark<false>, qgrid, dim3(256), 0, st, sorted, n_in, (const uint8_t *)core, parent, nearest);
+        else hipLaunchKernelGGL(k_dbscan_mark<true>, qgrid, dim3(256), 0, st, sorted, n_in, (const uint8_t *)core, parent, nearest);
+        return 2;
+    });
+    if (rc) return rc;
     // 6, 7. the links between core points and each other point's nearest core point
-    if ((rc = stage_begin(e, "dbscan_link"))) return rc;
-    if (gather) hipLaunchKernelGGL(k_dbscan_link<true>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, g.G, g.tab, g.mask, (const uint8_t *)core, parent, nearest);
-    else hipLaunchKernelGGL(k_dbscan_link<false>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, g.G, g.tab, g.mask, (const uint8_t *)core, parent, nearest);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    rc = run_stage(e, "dbscan_link", [&] {
+        if (gather) hipLaunchKernelGGL(k_dbscan_link<true>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, g.G, g.tab, g.mask, (const uint8_t *)core, parent, nearest);
+        else hipLaunchKernelGGL(k_dbscan_link<false>, qgrid, dim3(256), 0, st, (const float4 *)sorted, n_in, g.G, g.tab, g.mask, (const uint8_t *)core, parent, nearest);
+        return 1;
+    });
+    if (rc) return rc;
     // 9. the roots in source order are the clusters in the order of their numbers
-    if ((rc = stage_begin(e, "dbscan_number"))) return rc;
-    hipLaunchKernelGGL(k_dbscan_roots, dim3(m), dim3(256), 0, st, (const uint8_t *)core, (const int *)parent, n, cnt);
-    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
-    hipLaunchKernelGGL(k_dbscan_rank, dim3(m), dim3(256), 0, st, (const uint8_t *)core, (const int *)parent, n, (const uint32_t *)cnt, m, rank, sizes);
-    KCHECK();
-    if ((rc = stage_end(e, 3))) return rc;
+    rc = run_stage(e, "dbscan_number", [&] {
+        hipLaunchKernelGGL(k_dbscan_roots, dim3(m), dim3(256), 0, st, (const uint8_t *)core, (const int *)parent, n, cnt);
+        hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
+        hipLaunchKernelGGL(k_dbscan_rank, dim3(m), dim3(256), 0, st, (const uint8_t *)core, (const int *)parent, n, (const uint32_t *)cnt, m, rank, sizes);
+        return 3;
+    });
+    if (rc) return rc;
     // 8, 10. labels, sizes, statistics
-    if ((rc = stage_begin(e, "dbscan_label"))) return rc;
-    hipLaunchKernelGGL(k_dbscan_label, dim3(m), dim3(256), 0, st, slot_rank, (const uint8_t *)core, parent, (const uint32_t *)nearest,
-                       (const uint32_t *)rank, n, labels, sizes, ctl);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    rc = run_stage(e, "dbscan_label", [&] {
+        hipLaunchKernelGGL(k_dbscan_label, dim3(m), dim3(256), 0, st, slot_rank, (const uint8_t *)core, parent, (const uint32_t *)nearest,
+                           (const uint32_t *)rank, n, labels, sizes, ctl);
+        return 1;
+    });
+    if (rc) return rc;
     uint32_t h_ctl[RAD_CTL_WORDS] = {0, 0, 0, 0}, h_db[DB_CTL_WORDS] = {0, 0, 0, 0}, total = 0;
     HIP_TRY(hipMemcpyAsync(h_ctl, e->rad_ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(h_db, ctl, sizeof(h_db), hipMemcpyDeviceToHost, st));
@@ -3933,10 +3944,7 @@ int sgm_cluster_dbscan_device(sgm_engine *e, const void *d_xyz, const void *d_di
     HIP_TRY(hipStreamSynchronize(st));
     if (h_ctl[RAD_CTL_ERR]) return cloud_no_slot("sgm_cluster_dbscan", g);
     *n_clusters = (int64_t)total;
-    if (out_stats) {
-        const uint64_t s[6] = {n_in, n_out, h_db[DB_CTL_CORE], h_db[DB_CTL_BORDER], h_db[DB_CTL_NOISE], total};
-        std::copy(s, s + 6, out_stats);
-    }
+    put_stats(out_stats, {n_in, n_out, h_db[DB_CTL_CORE], h_db[DB_CTL_BORDER], h_db[DB_CTL_NOISE], total});
     return SGM_OK;
 }
 
@@ -3944,11 +3952,7 @@ int sgm_cluster_dbscan(sgm_engine *e, const float *xyz, const float *disp, int64
                        int32_t *out_labels, uint8_t *out_core, uint32_t *out_sizes, uint64_t *out_stats, int64_t *n_clusters)
 {
     if (int rc = dbscan_check_args(e, xyz, n, eps, min_points, origin, n_clusters)) return rc;
-    if (n == 0) {
-        *n_clusters = 0;
-        if (out_stats) std::fill(out_stats, out_stats + 6, (uint64_t)0);
-        return SGM_OK;
-    }
+    if (n == 0) return dbscan_nothing(n_clusters, out_stats, 0), SGM_OK;
     int64_t nc = 0;
     uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
     const HostOut lab{out_labels, &e->db_lab, 4, nullptr}, core{out_core, &e->rad_keep, 1, nullptr}, sizes{out_sizes, &e->db_sizes, 4, &nc};
@@ -4011,65 +4015,61 @@ static int plane_run(sgm_engine *e, const float *xyz, const float *disp, const u
         const float qscale = 32.0f / t;
         HIP_TRY(hipMemsetAsync(hcnt, 0, (size_t)K * 4, st));
         // 1. the valid points in source order, and their number m in the control block
-        if ((rc = stage_begin(e, "plane_valid"))) return rc;
-        hipLaunchKernelGGL(k_plane_valid_count, dim3(m), dim3(256), 0, st, xyz, disp, n, cnt);
-        hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
-        hipLaunchKernelGGL(k_plane_valid_scatter, dim3(m), dim3(256), 0, st, xyz, disp, n, (const uint32_t *)cnt, m, vpts, ctl);
-        KCHECK();
-        if ((rc = stage_end(e, 3))) return rc;
+        rc = run_stage(e, "plane_valid", [&] {
+            hipLaunchKernelGGL(k_plane_valid_count, dim3(m), dim3(256), 0, st, xyz, disp, n, cnt);
+            hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
+            hipLaunchKernelGGL(k_plane_valid_scatter, dim3(m), dim3(256), 0, st, xyz, disp, n, (const uint32_t *)cnt, m, vpts, ctl);
+            return 3;
+        });
+        if (rc) return rc;
         // 3, 4. the hypotheses
-        if ((rc = stage_begin(e, "plane_sample"))) return rc;
-        hipLaunchKernelGGL(k_plane_sample, dim3((K + 255) / 256), dim3(256), 0, st, (const float4 *)vpts, (uint32_t)K, seed, hyp, ctl);
-        KCHECK();
-        if ((rc = stage_end(e, 1))) return rc;
+        rc = run_stage(e, "plane_sample", [&] {
+            hipLaunchKernelGGL(k_plane_sample, dim3((K + 255) / 256), dim3(256), 0, st, (const float4 *)vpts, (uint32_t)K, seed, hyp, ctl);
+            return 1;
+        });
+        if (rc) return rc;
         // 5. every hypothesis on every valid point: a tile of 64 hypotheses per blockIdx.y, the chunks of points strided over blockIdx.x
         const int tiles = (K + PLANE_TILE - 1) / PLANE_TILE;
         const int chunks = (int)((n + PLANE_CHUNK - 1) / PLANE_CHUNK);
         const dim3 cgrid(std::max(1, std::min(chunks, PLANE_COUNT_BLOCKS / tiles)), tiles);
         const bool mfma = ((e->debug & SGM_DBG_PLANE_OTHER_COUNT) != 0) != PLANE_DEFAULT_MFMA;
-        if ((rc = stage_begin(e, "plane_count"))) return rc;
-        if (mfma)
-            hipLaunchKernelGGL(k_plane_count_mfma, cgrid, dim3(256), 0, st, (const float4 *)vpts, (const PlaneCtl *)ctl, (const float4 *)hyp,
-                               (uint32_t)K, t, hcnt);
-        else
-            hipLaunchKernelGGL(k_plane_count_valu, cgrid, dim3(256), 0, st, (const float4 *)vpts, (const PlaneCtl *)ctl, (const float4 *)hyp,
-                               (uint32_t)K, t, hcnt);
-        KCHECK();
-        if ((rc = stage_end(e, 1))) return rc;
+        rc = run_stage(e, "plane_count", [&] {
+            if (mfma)
+                hipLaunchKernelGGL(k_plane_count_mfma, cgrid, dim3(256), 0, st, (const float4 *)vpts, (const PlaneCtl *)ctl, (const float4 *)hyp,
+                                   (uint32_t)K, t, hcnt);
+            else
+                hipLaunchKernelGGL(k_plane_count_valu, cgrid, dim3(256), 0, st, (const float4 *)vpts, (const PlaneCtl *)ctl, (const float4 *)hyp,
+                                   (uint32_t)K, t, hcnt);
+            return 1;
+        });
+        if (rc) return rc;
         // 6. the best
-        if ((rc = stage_begin(e, "plane_best"))) return rc;
-        hipLaunchKernelGGL(k_plane_best, dim3(1), dim3(1024), 0, st, (const uint32_t *)hcnt, (uint32_t)K, seed, (const float4 *)hyp,
-                           (const float4 *)vpts, ctl);
-        KCHECK();
-        if ((rc = stage_end(e, 1))) return rc;
+        rc = run_stage(e, "plane_best", [&] {
+            hipLaunchKernelGGL(k_plane_best, dim3(1), dim3(1024), 0, st, (const uint32_t *)hcnt, (uint32_t)K, seed, (const float4 *)hyp,
+                               (const float4 *)vpts, ctl);
+            return 1;
+        });
+        if (rc) return rc;
         // 7. the refit
         if (refine) {
-            if ((rc = stage_begin(e, "plane_moments"))) return rc;
-            hipLaunchKernelGGL(k_plane_moments, dim3(std::min(m, PLANE_MOMENT_BLOCKS)), dim3(256), 0, st, (const float4 *)vpts, ctl, t, qscale);
-            KCHECK();
-            if ((rc = stage_end(e, 1))) return rc;
-            if ((rc = stage_begin(e, "plane_solve"))) return rc;
-            hipLaunchKernelGGL(k_plane_solve, dim3(1), dim3(64), 0, st, ctl, qscale);
-            KCHECK();
-            if ((rc = stage_end(e, 1))) return rc;
+            rc = run_stage(e, "plane_moments", [&] {
+                hipLaunchKernelGGL(k_plane_moments, dim3(std::min(m, PLANE_MOMENT_BLOCKS)), dim3(256), 0, st, (const float4 *)vpts, ctl, t, qscale);
+                return 1;
+            });
+            if (rc) return rc;
+            if ((rc = run_stage(e, "plane_solve", [&] { hipLaunchKernelGGL(k_plane_solve, dim3(1), dim3(64), 0, st, ctl, qscale); return 1; }))) return rc;
         }
     }
     // 8. the classification and the selected points through the ordered compaction
     const float4 given = fit ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(model[0], model[1], model[2], model[3]);
-    if ((rc = stage_begin(e, "plane_classify"))) return rc;
-    hipLaunchKernelGGL(k_plane_classify, dim3(m), dim3(256), 0, st, xyz, disp, n, given, (const PlaneCtl *)(fit ? ctl : nullptr), t, select,
-                       (uint8_t *)d_out_inlier, (float *)d_out_distance, keep, &ctl->n_inliers);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
-    if ((rc = stage_begin(e, "plane_compact"))) return rc;
-    hipLaunchKernelGGL(k_radius_keep_count, dim3(m), dim3(256), 0, st, (const uint8_t *)keep, n, cnt);
-    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, cnt, m);
-    const bool rows = d_out_points || d_out_colors || d_out_index;
-    if (rows)
-        hipLaunchKernelGGL(k_radius_scatter, dim3(m), dim3(256), 0, st, (const uint8_t *)keep, xyz, colors, n, (const uint32_t *)cnt,
-                           (float *)d_out_points, (uint8_t *)d_out_colors, (uint32_t *)d_out_index);
-    KCHECK();
-    if ((rc = stage_end(e, rows ? 3 : 2))) return rc;
+    rc = run_stage(e, "plane_classify", [&] {
+        hipLaunchKernelGGL(k_plane_classify, dim3(m), dim3(256), 0, st, xyz, disp, n, given, (const PlaneCtl *)(fit ? ctl : nullptr), t, select,
+                           (uint8_t *)d_out_inlier, (float *)d_out_distance, keep, &ctl->n_inliers);
+        return 1;
+    });
+    if (rc) return rc;
+    if ((rc = run_stage(e, "plane_compact", [&] { return launch_keep_compaction(e, m, keep, xyz, colors, n, d_out_points, d_out_colors, d_out_index); })))
+        return rc;
     PlaneCtl h;
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&h, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -4078,10 +4078,7 @@ static int plane_run(sgm_engine *e, const float *xyz, const float *disp, const u
     *n_inliers = (int64_t)h.n_inliers;
     if (n_selected) *n_selected = (int64_t)total;
     if (out_model) std::copy(h.model, h.model + 4, out_model);
-    if (out_stats) {
-        const uint64_t s[8] = {h.m, h.degenerate, h.kbest, h.cbest, h.m_r, h.n_oor, h.refined, h.found};
-        std::copy(s, s + 8, out_stats);
-    }
+    put_stats(out_stats, {h.m, h.degenerate, h.kbest, h.cbest, h.m_r, h.n_oor, h.refined, h.found});
     return SGM_OK;
 }
 
@@ -4090,7 +4087,7 @@ static void plane_nothing(float *out_model, uint64_t *out_stats, int64_t *n_inli
     *n_inliers = 0;
     if (n_selected) *n_selected = 0;
     if (out_model) std::fill(out_model, out_model + 4, 0.0f);
-    if (out_stats) std::fill(out_stats, out_stats + 8, (uint64_t)0);
+    put_stats(out_stats, {0, 0, 0, 0, 0, 0, 0, 0});
 }
 
 int sgm_segment_plane_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int64_t n,
@@ -4330,21 +4327,24 @@ static int icp_run(sgm_engine *e, const char *who, const float *xyz_s, const flo
             HIP_TRY(hipMemsetAsync(d_ctl, 0, sizeof(IcpCtl), st));
             stage_break(e);
             int rc2;
-            if ((rc2 = stage_begin(e, "icp_correspond"))) return rc2;
-            hipLaunchKernelGGL(k_icp_correspond, dim3(mblocks), dim3(256), 0, st, xyz_s, disp_s, ns, M, (const float4 *)g.sorted, g.tab, g.mask,
-                               g.G, corr, d2, d_ctl);
-            KCHECK();
-            if ((rc2 = stage_end(e, 1))) return rc2;
-            if ((rc2 = stage_begin(e, "icp_terms"))) return rc2;
-            hipLaunchKernelGGL(k_icp_terms, dim3(mblocks), dim3(256), 0, st, xyz_s, ns, npad, M, xyz_t, nrm_t, estimation, (const int32_t *)corr,
-                               (const float *)d2, part, d_ctl);
-            KCHECK();
-            if ((rc2 = stage_end(e, 1))) return rc2;
-            if ((rc2 = stage_begin(e, "icp_reduce"))) return rc2;
-            hipLaunchKernelGGL(k_icp_reduce, dim3(1), dim3(ICP_REDUCE_CHUNK), 0, st, (const double *)part, (uint32_t)mblocks, npow,
-                               (const IcpCtl *)d_ctl, d_res);
-            KCHECK();
-            if ((rc2 = stage_end(e, 1))) return rc2;
+            rc2 = run_stage(e, "icp_correspond", [&] {
+                hipLaunchKernelGGL(k_icp_correspond, dim3(mblocks), dim3(256), 0, st, xyz_s, disp_s, ns, M, (const float4 *)g.sorted, g.tab, g.mask,
+                                   g.G, corr, d2, d_ctl);
+                return 1;
+            });
+            if (rc2) return rc2;
+            rc2 = run_stage(e, "icp_terms", [&] {
+                hipLaunchKernelGGL(k_icp_terms, dim3(mblocks), dim3(256), 0, st, xyz_s, ns, npad, M, xyz_t, nrm_t, estimation, (const int32_t *)corr,
+                                   (const float *)d2, part, d_ctl);
+                return 1;
+            });
+            if (rc2) return rc2;
+            rc2 = run_stage(e, "icp_reduce", [&] {
+                hipLaunchKernelGGL(k_icp_reduce, dim3(1), dim3(ICP_REDUCE_CHUNK), 0, st, (const double *)part, (uint32_t)mblocks, npow,
+                                   (const IcpCtl *)d_ctl, d_res);
+                return 1;
+            });
+            if (rc2) return rc2;
             // ONE copy: the 232-byte record and, adjacent to it in icp_ctl, the evaluation's 16 bytes of counts
             HIP_TRY(hipMemcpyAsync(e->pin_icp.p, d_res, sizeof(IcpResult) + sizeof(IcpCtl), hipMemcpyDeviceToHost, st));
             if (hist.empty())   // the grid's control words once, in the first wait: only k_radius_insert sets RAD_CTL_ERR, no walk does
@@ -4371,8 +4371,7 @@ static int icp_run(sgm_engine *e, const char *who, const float *xyz_s, const flo
             iterations++;
             if (std::fabs(fitness - f0) < rel_fitness && std::fabs(rmse - r0) < rel_rmse) { status = 0; break; }
         }
-        const uint64_t s[8] = {h_ctl->m_s, g.n_in, g.n_out, (uint64_t)iterations, h_res->n_corr, h_ctl->unplaced, h_ctl->unusable, (uint64_t)status};
-        std::copy(s, s + 8, stats);
+        put_stats(stats, {h_ctl->m_s, g.n_in, g.n_out, (uint64_t)iterations, h_res->n_corr, h_ctl->unplaced, h_ctl->unusable, (uint64_t)status});
     }
     if (out_T) std::copy(T, T + 16, out_T);
     if (out_fitness) *out_fitness = fitness;
@@ -4408,37 +4407,25 @@ int sgm_evaluate_registration_device(sgm_engine *e, const void *d_xyz_s, const v
                    max_correspondence_distance, origin, T, 0, 0, 0.0, 0.0, nullptr, out_fitness, out_rmse, d_out_corr, d_out_d2, nullptr, out_stats);
 }
 
-// the host entries of both: the two clouds up (the source to xyz and f32, the target to icp_txyz, icp_tdisp, icp_tnrm), the device
-// entry `run` on them with the engine's own corr and d2, those two down
-extern "C++" {   // (a template: this part of the file has C linkage)
-template <class Run>
-static int icp_host_call(sgm_engine *e, const float *xyz_s, const float *disp_s, int64_t ns, const float *xyz_t, const float *disp_t,
-                         const float *normals_t, int64_t nt, int32_t *out_corr, float *out_d2, Run run)
+// The host entries of both: the two clouds up (the source to xyz and f32, the target to icp_txyz, icp_tdisp, icp_tnrm), icp_run on
+// them, corr and d2 down.  An empty cloud is not staged (no target: no pair ever reads a normal); with no source nothing runs.
+static int icp_run_host(sgm_engine *e, const char *who, const float *xyz_s, const float *disp_s, int64_t ns, const float *xyz_t,
+                        const float *disp_t, const float *normals_t, int64_t nt, float r, const float origin[3], const double T0[16],
+                        int estimation, int max_iteration, double rel_fitness, double rel_rmse, double *out_T, double *out_fitness,
+                        double *out_rmse, int32_t *out_corr, float *out_d2, double *out_history, uint64_t *out_stats)
 {
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    hipStream_t st = e->stream;
-    if ((ns > 0 && (rc = e->xyz.ensure((size_t)ns * 12))) || (ns > 0 && disp_s && (rc = e->f32.ensure((size_t)ns * 4))) ||
-        (nt > 0 && (rc = e->icp_txyz.ensure((size_t)nt * 12))) || (nt > 0 && disp_t && (rc = e->icp_tdisp.ensure((size_t)nt * 4))) ||
-        (nt > 0 && normals_t && (rc = e->icp_tnrm.ensure((size_t)nt * 12))))
-        return rc;
-    if (ns > 0) HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz_s, (size_t)ns * 12, hipMemcpyHostToDevice, st));
-    if (ns > 0 && disp_s) HIP_TRY(hipMemcpyAsync(e->f32.p, disp_s, (size_t)ns * 4, hipMemcpyHostToDevice, st));
-    if (nt > 0) HIP_TRY(hipMemcpyAsync(e->icp_txyz.p, xyz_t, (size_t)nt * 12, hipMemcpyHostToDevice, st));
-    if (nt > 0 && disp_t) HIP_TRY(hipMemcpyAsync(e->icp_tdisp.p, disp_t, (size_t)nt * 4, hipMemcpyHostToDevice, st));
-    if (nt > 0 && normals_t) HIP_TRY(hipMemcpyAsync(e->icp_tnrm.p, normals_t, (size_t)nt * 12, hipMemcpyHostToDevice, st));
-    rc = run(ns > 0 ? e->xyz.p : nullptr, ns > 0 && disp_s ? e->f32.p : nullptr, nt > 0 ? e->icp_txyz.p : nullptr,
-             nt > 0 && disp_t ? e->icp_tdisp.p : nullptr, nt > 0 && normals_t ? e->icp_tnrm.p : nullptr);   // (no target: no pair ever reads a normal)
-    if (rc) {
-        (void)hipStreamSynchronize(st);   // (the caller's memory is the source of nothing when the call returns)
-        return rc;
-    }
-    if (ns > 0 && out_corr) HIP_TRY(hipMemcpyAsync(out_corr, e->icp_corr.p, (size_t)ns * 4, hipMemcpyDeviceToHost, st));
-    if (ns > 0 && out_d2) HIP_TRY(hipMemcpyAsync(out_d2, e->icp_d2.p, (size_t)ns * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return SGM_OK;
+    if (ns == 0)
+        return icp_run(e, who, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nt, r, origin, T0, estimation, max_iteration, rel_fitness,
+                       rel_rmse, out_T, out_fitness, out_rmse, nullptr, nullptr, out_history, out_stats);
+    const HostIn s{xyz_s, &e->xyz, (size_t)ns * 12}, ds{disp_s, &e->f32, (size_t)ns * 4}, t{xyz_t, &e->icp_txyz, (size_t)nt * 12},
+        dt{disp_t, &e->icp_tdisp, (size_t)nt * 4}, nrm{normals_t, &e->icp_tnrm, (size_t)nt * 12};
+    const HostOut corr{out_corr, &e->icp_corr, 4, nullptr}, d2{out_d2, &e->icp_d2, 4, nullptr};
+    return host_call(e, ns, {s, ds, t, dt, nrm}, {corr, d2}, [&] {
+        return icp_run(e, who, (const float *)s.d(), (const float *)ds.d(), ns, (const float *)t.d(), (const float *)dt.d(),
+                       (const float *)nrm.d(), nt, r, origin, T0, estimation, max_iteration, rel_fitness, rel_rmse, out_T, out_fitness, out_rmse,
+                       corr.d(), d2.d(), out_history, out_stats);
+    });
 }
-}  // extern "C++"
 
 int sgm_register_icp(sgm_engine *e, const float *xyz_s, const float *disp_s, int64_t ns, const float *xyz_t, const float *disp_t,
                      const float *normals_t, int64_t nt, float max_correspondence_distance, const float origin[3], const double T0[16],
@@ -4449,16 +4436,8 @@ int sgm_register_icp(sgm_engine *e, const float *xyz_s, const float *disp_s, int
     if (int rc = icp_check_args(who, e, xyz_s, ns, xyz_t, nt, max_correspondence_distance, origin, T0, estimation, normals_t, max_iteration,
                                 relative_fitness, relative_rmse))
         return rc;
-    if (ns == 0)   // nothing runs and nothing is staged
-        return icp_run(e, who, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nt, max_correspondence_distance, origin, T0, estimation,
-                       max_iteration, relative_fitness, relative_rmse, out_T, out_fitness, out_rmse, nullptr, nullptr, out_history, out_stats);
-    return icp_host_call(e, xyz_s, disp_s, ns, xyz_t, disp_t, normals_t, nt, out_corr, out_d2,
-                         [&](void *d_s, void *d_ds, void *d_t, void *d_dt, void *d_n) {
-                             return icp_run(e, who, (const float *)d_s, (const float *)d_ds, ns, (const float *)d_t, (const float *)d_dt,
-                                            (const float *)d_n, nt, max_correspondence_distance, origin, T0, estimation, max_iteration,
-                                            relative_fitness, relative_rmse, out_T, out_fitness, out_rmse, nullptr, nullptr, out_history,
-                                            out_stats);
-                         });
+    return icp_run_host(e, who, xyz_s, disp_s, ns, xyz_t, disp_t, normals_t, nt, max_correspondence_distance, origin, T0, estimation,
+                        max_iteration, relative_fitness, relative_rmse, out_T, out_fitness, out_rmse, out_corr, out_d2, out_history, out_stats);
 }
 
 int sgm_evaluate_registration(sgm_engine *e, const float *xyz_s, const float *disp_s, int64_t ns, const float *xyz_t, const float *disp_t,
@@ -4467,15 +4446,8 @@ int sgm_evaluate_registration(sgm_engine *e, const float *xyz_s, const float *di
 {
     const char *who = "sgm_evaluate_registration";
     if (int rc = icp_check_args(who, e, xyz_s, ns, xyz_t, nt, max_correspondence_distance, origin, T, 0, nullptr, 0, 0.0, 0.0)) return rc;
-    if (ns == 0)   // nothing runs and nothing is staged
-        return icp_run(e, who, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nt, max_correspondence_distance, origin, T, 0, 0, 0.0, 0.0,
-                       nullptr, out_fitness, out_rmse, nullptr, nullptr, nullptr, out_stats);
-    return icp_host_call(e, xyz_s, disp_s, ns, xyz_t, disp_t, nullptr, nt, out_corr, out_d2,
-                         [&](void *d_s, void *d_ds, void *d_t, void *d_dt, void *) {
-                             return icp_run(e, who, (const float *)d_s, (const float *)d_ds, ns, (const float *)d_t, (const float *)d_dt, nullptr,
-                                            nt, max_correspondence_distance, origin, T, 0, 0, 0.0, 0.0, nullptr, out_fitness, out_rmse, nullptr,
-                                            nullptr, nullptr, out_stats);
-                         });
+    return icp_run_host(e, who, xyz_s, disp_s, ns, xyz_t, disp_t, nullptr, nt, max_correspondence_distance, origin, T, 0, 0, 0.0, 0.0, nullptr,
+                        out_fitness, out_rmse, out_corr, out_d2, nullptr, out_stats);
 }
 
 static int icp_transform_check(const sgm_engine *e, const void *xyz, const void *normals, int64_t n, const double *T, const void *out_xyz,
@@ -4511,21 +4483,10 @@ int sgm_transform_points(sgm_engine *e, const float *xyz, const float *normals, 
 {
     if (int rc = icp_transform_check(e, xyz, normals, n, T, out_xyz, out_normals)) return rc;
     if (n == 0) return SGM_OK;
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    hipStream_t st = e->stream;
-    if ((rc = e->xyz.ensure((size_t)n * 12)) || (normals && (rc = e->icp_tnrm.ensure((size_t)n * 12)))) return rc;
-    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, st));
-    if (normals) HIP_TRY(hipMemcpyAsync(e->icp_tnrm.p, normals, (size_t)n * 12, hipMemcpyHostToDevice, st));
-    if ((rc = sgm_transform_points_device(e, e->xyz.p, normals ? e->icp_tnrm.p : nullptr, n, T, out_xyz ? e->xyz.p : nullptr,
-                                          normals ? e->icp_tnrm.p : nullptr))) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    if (out_xyz) HIP_TRY(hipMemcpyAsync(out_xyz, e->xyz.p, (size_t)n * 12, hipMemcpyDeviceToHost, st));
-    if (out_normals) HIP_TRY(hipMemcpyAsync(out_normals, e->icp_tnrm.p, (size_t)n * 12, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return SGM_OK;
+    // in place: an output comes down from the buffer its input went up to
+    const HostIn pts{xyz, &e->xyz, (size_t)n * 12}, nrm{normals, &e->icp_tnrm, (size_t)n * 12};
+    const HostOut opts{out_xyz, &e->xyz, 12, nullptr}, onrm{out_normals, &e->icp_tnrm, 12, nullptr};
+    return host_call(e, n, {pts, nrm}, {opts, onrm}, [&] { return sgm_transform_points_device(e, pts.d(), nrm.d(), n, T, opts.d(), onrm.d()); });
 }
 
 // ---- triangle mesh from the organised cloud (include/sgm_hip_mesh.h, kernels_mesh.h) and its normals (include/sgm_hip_normals.h,
@@ -4549,14 +4510,13 @@ static int mesh_stage_quads(sgm_engine *e, const float *xyz, const float *disp, 
     uint8_t *code = (uint8_t *)e->mesh_code.p;
     uint32_t *fcnt = (uint32_t *)e->mesh_fcnt.p;
     hipStream_t st = e->stream;
-    int rc;
-    if ((rc = stage_begin(e, "mesh_quads"))) return rc;
-    // (16-byte loads where every group of four pixels, and the four below it, starts on a 16-byte boundary)
-    const bool wide = W % 4 == 0 && (uintptr_t)xyz % 16 == 0 && (uintptr_t)disp % 16 == 0;
-    if (wide) hipLaunchKernelGGL(k_mesh_quads<true>, dim3(m), dim3(MESH_BLOCK / 4), 0, st, xyz, disp, H, W, max_diff, code, fcnt);
-    else hipLaunchKernelGGL(k_mesh_quads<false>, dim3(m), dim3(MESH_BLOCK / 4), 0, st, xyz, disp, H, W, max_diff, code, fcnt);
-    KCHECK();
-    return stage_end(e, 1);
+    return run_stage(e, "mesh_quads", [&] {
+        // (16-byte loads where every group of four pixels, and the four below it, starts on a 16-byte boundary)
+        const bool wide = W % 4 == 0 && (uintptr_t)xyz % 16 == 0 && (uintptr_t)disp % 16 == 0;
+        if (wide) hipLaunchKernelGGL(k_mesh_quads<true>, dim3(m), dim3(MESH_BLOCK / 4), 0, st, xyz, disp, H, W, max_diff, code, fcnt);
+        else hipLaunchKernelGGL(k_mesh_quads<false>, dim3(m), dim3(MESH_BLOCK / 4), 0, st, xyz, disp, H, W, max_diff, code, fcnt);
+        return 1;
+    });
 }
 
 // The mesh on the engine's stream from device pointers, for sgm_mesh_grid_device and sgm_mesh_grid_normals_device: with
@@ -4585,34 +4545,36 @@ static int mesh_run(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, co
     hipStream_t st = e->stream;
     // 1. every quad's code and the blocks' numbers of triangles; 2. from the codes, the blocks' numbers of vertices
     if ((rc = mesh_stage_quads(e, xyz, disp, H, W, max_diff, m))) return rc;
-    if ((rc = stage_begin(e, "mesh_used"))) return rc;
-    hipLaunchKernelGGL(k_mesh_used, dim3(m), dim3(MESH_BLOCK), 0, st, (const uint8_t *)code, H, W, vcnt);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    if ((rc = run_stage(e, "mesh_used", [&] { hipLaunchKernelGGL(k_mesh_used, dim3(m), dim3(MESH_BLOCK), 0, st, (const uint8_t *)code, H, W, vcnt); return 1; })))
+        return rc;
     // 3. both lists of counts become offsets, the totals behind them
-    if ((rc = stage_begin(e, "mesh_scan"))) return rc;
-    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, vcnt, m);
-    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, fcnt, m);
-    KCHECK();
-    if ((rc = stage_end(e, 2))) return rc;
+    rc = run_stage(e, "mesh_scan", [&] {
+        hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, vcnt, m);
+        hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, st, fcnt, m);
+        return 2;
+    });
+    if (rc) return rc;
     // 4. the vertices and each used pixel's number; 5. the faces, in those numbers
-    if ((rc = stage_begin(e, "mesh_vertices"))) return rc;
-    hipLaunchKernelGGL(k_mesh_vertices, dim3(m), dim3(MESH_BLOCK), 0, st, xyz, colors, (const uint8_t *)code, H, W, (const uint32_t *)vcnt,
-                       (float *)d_out_vertices, (uint8_t *)d_out_colors, number);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
-    if ((rc = stage_begin(e, "mesh_faces"))) return rc;
-    hipLaunchKernelGGL(k_mesh_faces, dim3(m), dim3(MESH_BLOCK), 0, st, (const uint8_t *)code, (const uint32_t *)number, H, W, (const uint32_t *)fcnt,
-                       (int32_t *)d_out_faces);
-    KCHECK();
-    if ((rc = stage_end(e, 1))) return rc;
+    rc = run_stage(e, "mesh_vertices", [&] {
+        hipLaunchKernelGGL(k_mesh_vertices, dim3(m), dim3(MESH_BLOCK), 0, st, xyz, colors, (const uint8_t *)code, H, W, (const uint32_t *)vcnt,
+                           (float *)d_out_vertices, (uint8_t *)d_out_colors, number);
+        return 1;
+    });
+    if (rc) return rc;
+    rc = run_stage(e, "mesh_faces", [&] {
+        hipLaunchKernelGGL(k_mesh_faces, dim3(m), dim3(MESH_BLOCK), 0, st, (const uint8_t *)code, (const uint32_t *)number, H, W,
+                           (const uint32_t *)fcnt, (int32_t *)d_out_faces);
+        return 1;
+    });
+    if (rc) return rc;
     // 6 - 9. the vertices' normals, to the rows step 4 numbered the pixels with
     if (d_out_normals) {
-        if ((rc = stage_begin(e, "mesh_normals"))) return rc;
-        hipLaunchKernelGGL(k_normals<true>, dim3(m), dim3(MESH_BLOCK), 0, st, xyz, (const uint8_t *)code, (const uint32_t *)number, H, W, orient,
-                           (float *)d_out_normals);
-        KCHECK();
-        if ((rc = stage_end(e, 1))) return rc;
+        rc = run_stage(e, "mesh_normals", [&] {
+            hipLaunchKernelGGL(k_normals<true>, dim3(m), dim3(MESH_BLOCK), 0, st, xyz, (const uint8_t *)code, (const uint32_t *)number, H, W, orient,
+                               (float *)d_out_normals);
+            return 1;
+        });
+        if (rc) return rc;
     }
     uint32_t nv = 0, nf = 0;
     HIP_TRY(hipMemcpyAsync(&nv, vcnt + m, 4, hipMemcpyDeviceToHost, st));
@@ -4624,38 +4586,21 @@ static int mesh_run(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, co
 }
 
 // The same from host pointers through the engine's staging buffers, for sgm_mesh_grid and sgm_mesh_grid_normals
-static int mesh_run_host(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int H, int W, float max_diff,
-                         int orient, float *out_vertices, uint8_t *out_colors, int32_t *out_faces, float *out_normals, int64_t *n_vertices,
-                         int64_t *n_faces)
+static int mesh_host_call(sgm_engine *e, const float *xyz, const float *disp, const uint8_t *colors_rgb, int H, int W, float max_diff,
+                          int orient, float *out_vertices, uint8_t *out_colors, int32_t *out_faces, float *out_normals, int64_t *n_vertices,
+                          int64_t *n_faces)
 {
-    if (H < 2 || W < 2) {
-        *n_vertices = 0;
-        *n_faces = 0;
-        return SGM_OK;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t n = (size_t)H * W, fmax = 2 * (size_t)(H - 1) * (W - 1);
-    int rc;
-    if ((rc = e->xyz.ensure(n * 12)) || (rc = e->f32.ensure(n * 4)) || (rc = e->cpts.ensure(n * 12)) || (rc = e->mesh_faces.ensure(fmax * 12)))
-        return rc;
-    if (out_colors && ((rc = e->crgb_in.ensure(n * 3)) || (rc = e->crgb.ensure(n * 3)))) return rc;
-    if (out_normals && (rc = e->mesh_nrm.ensure(n * 12))) return rc;
-    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, n * 12, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->f32.p, disp, n * 4, hipMemcpyHostToDevice, e->stream));
-    if (out_colors) HIP_TRY(hipMemcpyAsync(e->crgb_in.p, colors_rgb, n * 3, hipMemcpyHostToDevice, e->stream));
     int64_t nv = 0, nf = 0;
-    if ((rc = mesh_run(e, e->xyz.p, e->f32.p, out_colors ? e->crgb_in.p : nullptr, H, W, max_diff, orient, e->cpts.p,
-                       out_colors ? e->crgb.p : nullptr, e->mesh_faces.p, out_normals ? e->mesh_nrm.p : nullptr, &nv, &nf))) {
-        (void)hipStreamSynchronize(e->stream);   // (the caller's memory is the source of nothing when the call returns)
-        return rc;
+    if (H >= 2 && W >= 2) {   // (otherwise no quad)
+        const size_t n = (size_t)H * W;
+        const HostIn pts{xyz, &e->xyz, n * 12}, dsp{disp, &e->f32, n * 4}, rgb{out_colors ? colors_rgb : nullptr, &e->crgb_in, n * 3};
+        const HostOut vtx{out_vertices, &e->cpts, 12, &nv}, vrgb{out_colors, &e->crgb, 3, &nv}, nrm{out_normals, &e->mesh_nrm, 12, &nv},
+            faces{out_faces, &e->mesh_faces, 12, &nf, 2 * (int64_t)(H - 1) * (W - 1)};
+        if (int rc = host_call(e, (int64_t)n, {pts, dsp, rgb}, {vtx, vrgb, nrm, faces}, [&] {
+                return mesh_run(e, pts.d(), dsp.d(), rgb.d(), H, W, max_diff, orient, vtx.d(), vrgb.d(), faces.d(), nrm.d(), &nv, &nf);
+            }))
+            return rc;
     }
-    if (nv > 0) {
-        HIP_TRY(hipMemcpyAsync(out_vertices, e->cpts.p, (size_t)nv * 12, hipMemcpyDeviceToHost, e->stream));
-        if (out_colors) HIP_TRY(hipMemcpyAsync(out_colors, e->crgb.p, (size_t)nv * 3, hipMemcpyDeviceToHost, e->stream));
-        if (out_normals) HIP_TRY(hipMemcpyAsync(out_normals, e->mesh_nrm.p, (size_t)nv * 12, hipMemcpyDeviceToHost, e->stream));
-    }
-    if (nf > 0) HIP_TRY(hipMemcpyAsync(out_faces, e->mesh_faces.p, (size_t)nf * 12, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
     *n_vertices = nv;
     *n_faces = nf;
     return SGM_OK;
@@ -4676,7 +4621,7 @@ int sgm_mesh_grid(sgm_engine *e, const float *xyz, const float *disp, const uint
     if (int rc = mesh_check_args("sgm_mesh_grid", !e || !xyz || !disp || !out_vertices || !out_faces || !n_vertices || !n_faces, H, W, max_diff, 0,
                                  out_colors && !colors_rgb))
         return rc;
-    return mesh_run_host(e, xyz, disp, colors_rgb, H, W, max_diff, 0, out_vertices, out_colors, out_faces, nullptr, n_vertices, n_faces);
+    return mesh_host_call(e, xyz, disp, colors_rgb, H, W, max_diff, 0, out_vertices, out_colors, out_faces, nullptr, n_vertices, n_faces);
 }
 
 int sgm_mesh_grid_normals_device(sgm_engine *e, const void *d_xyz, const void *d_disp_f32, const void *d_colors_rgb, int H, int W,
@@ -4698,7 +4643,7 @@ int sgm_mesh_grid_normals(sgm_engine *e, const float *xyz, const float *disp, co
     if (int rc = mesh_check_args("sgm_mesh_grid_normals", !e || !xyz || !disp || !out_vertices || !out_faces || !out_normals || !n_vertices || !n_faces,
                                  H, W, max_diff, orient, out_colors && !colors_rgb))
         return rc;
-    return mesh_run_host(e, xyz, disp, colors_rgb, H, W, max_diff, orient, out_vertices, out_colors, out_faces, out_normals, n_vertices, n_faces);
+    return mesh_host_call(e, xyz, disp, colors_rgb, H, W, max_diff, orient, out_vertices, out_colors, out_faces, out_normals, n_vertices, n_faces);
 }
 
 // The normal image: the quads' codes, then one pass over the pixels.  Nothing is counted, so nothing waits.
@@ -4717,11 +4662,11 @@ int sgm_normals_grid_device(sgm_engine *e, const void *d_xyz, const void *d_disp
     int rc;
     if ((rc = e->mesh_code.ensure((size_t)n)) || (rc = e->mesh_fcnt.ensure((size_t)(m + 1) * 4))) return rc;
     if ((rc = mesh_stage_quads(e, (const float *)d_xyz, (const float *)d_disp_f32, H, W, max_diff, m))) return rc;
-    if ((rc = stage_begin(e, "normals_grid"))) return rc;
-    hipLaunchKernelGGL(k_normals<false>, dim3(m), dim3(MESH_BLOCK), 0, e->stream, (const float *)d_xyz, (const uint8_t *)e->mesh_code.p,
-                       (const uint32_t *)nullptr, H, W, orient, (float *)d_out_normals);
-    KCHECK();
-    return stage_end(e, 1);
+    return run_stage(e, "normals_grid", [&] {
+        hipLaunchKernelGGL(k_normals<false>, dim3(m), dim3(MESH_BLOCK), 0, e->stream, (const float *)d_xyz, (const uint8_t *)e->mesh_code.p,
+                           (const uint32_t *)nullptr, H, W, orient, (float *)d_out_normals);
+        return 1;
+    });
 }
 
 int sgm_normals_grid(sgm_engine *e, const float *xyz, const float *disp, int H, int W, float max_diff, int orient, float *out_normals)
@@ -4732,18 +4677,9 @@ int sgm_normals_grid(sgm_engine *e, const float *xyz, const float *disp, int H, 
         memset(out_normals, 0, n * 12);
         return SGM_OK;
     }
-    HIP_TRY(hipSetDevice(e->device));
-    int rc;
-    if ((rc = e->xyz.ensure(n * 12)) || (rc = e->f32.ensure(n * 4)) || (rc = e->mesh_nrm.ensure(n * 12))) return rc;
-    HIP_TRY(hipMemcpyAsync(e->xyz.p, xyz, n * 12, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->f32.p, disp, n * 4, hipMemcpyHostToDevice, e->stream));
-    if ((rc = sgm_normals_grid_device(e, e->xyz.p, e->f32.p, H, W, max_diff, orient, e->mesh_nrm.p))) {
-        (void)hipStreamSynchronize(e->stream);
-        return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out_normals, e->mesh_nrm.p, n * 12, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return SGM_OK;
+    const HostIn pts{xyz, &e->xyz, n * 12}, dsp{disp, &e->f32, n * 4};
+    const HostOut nrm{out_normals, &e->mesh_nrm, 12, nullptr};
+    return host_call(e, (int64_t)n, {pts, dsp}, {nrm}, [&] { return sgm_normals_grid_device(e, pts.d(), dsp.d(), H, W, max_diff, orient, nrm.d()); });
 }
 
 int sgm_filter_speckles(sgm_engine *e, int16_t *img, int H, int W, int newVal, int maxSpeckleSize, int maxDiff)

@@ -84,25 +84,7 @@ def voxel_down_sample(points_3D, colors, disparity_map, voxel_size, origin=(0, 0
     finite point counts).  colors: uint8 of the shape of points_3D, or None.
     Returns (points float32 (M, 3), colors uint8 (M, 3) or None[, counts uint32 (M)])."""
     who = "voxel_down_sample"
-    pts = np.asarray(points_3D)
-    if pts.dtype != np.float32:
-        raise _cv.error(f"{who}: points_3D must be float32, not {pts.dtype}")
-    if disparity_map is None:
-        if pts.ndim != 2 or pts.shape[1] != 3:
-            raise _cv.error(f"{who}: without a disparity_map points_3D must be an (N, 3) list")
-        if confidence is not None:
-            raise _cv.error(f"{who}: a confidence map needs a disparity_map")
-        disp = None
-    else:
-        disp = np.asarray(disparity_map)
-        if pts.ndim != 3 or pts.shape[2] != 3 or pts.shape[:2] != disp.shape:
-            raise _cv.error(f"{who}: points_3D must be (H, W, 3) and disparity_map (H, W)")
-        if confidence is not None:
-            disp = mask_by_confidence(disp, confidence, min_confidence)
-    if colors is not None:
-        colors = np.asarray(colors)
-        if colors.shape != pts.shape or colors.dtype != np.uint8:
-            raise _cv.error(f"{who}: colors must be uint8 and have the shape of points_3D")
+    pts, disp, colors = _outlier_cloud(who, points_3D, colors, disparity_map, confidence, min_confidence)
     with np.errstate(all="ignore"):
         try:
             v = np.float32(voxel_size)
@@ -113,8 +95,7 @@ def voxel_down_sample(points_3D, colors, disparity_map, voxel_size, origin=(0, 0
             raise _cv.error(f"{who}: voxel_size={voxel_size!r} is not a finite positive float32 with a finite reciprocal")
     if org.shape != (3,) or not np.isfinite(org).all():
         raise _cv.error(f"{who}: origin={origin!r} is not three finite numbers")
-    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= int(min_points) <= 2 ** 31 - 1:
-        raise _cv.error(f"{who}: min_points={min_points!r} is not an integer >= 1")
+    _int_arg(who, min_points, 1, 2 ** 31 - 1, f"min_points={min_points!r} is not an integer >= 1")
     if pts.size // 3 > VOXEL_MAX_POINTS:
         raise _cv.error(f"{who}: {pts.size // 3} points, more than {VOXEL_MAX_POINTS} (include/sgm_hip_voxel.h)")
     if pts.size == 0:      # nothing to send to the device
@@ -128,8 +109,14 @@ def voxel_down_sample(points_3D, colors, disparity_map, voxel_size, origin=(0, 0
 RADIUS_MAX_POINTS = (1 << 24) - 1
 
 
+def _int_arg(who, v, lo, hi, message):
+    """an argument that must be an integer (no bool) in lo .. hi, or the error `who: message`"""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise _cv.error(f"{who}: {message}")
+
+
 def _outlier_cloud(who, points_3D, colors, disparity_map, confidence, min_confidence):
-    """what the two outlier removals accept as a cloud: (points, disparities or None, colours or None), checked"""
+    """what the calls on arrays accept as a cloud: (points, disparities or None, colours or None), checked"""
     pts = np.asarray(points_3D)
     if pts.dtype != np.float32:
         raise _cv.error(f"{who}: points_3D must be float32, not {pts.dtype}")
@@ -189,11 +176,9 @@ def remove_radius_outlier(points_3D, colors, disparity_map, nb_points, radius, o
     who = "remove_radius_outlier"
     pts, disp, colors = _outlier_cloud(who, points_3D, colors, disparity_map, confidence, min_confidence)
     r, org = _search_radius(who, "radius", radius, origin)
-    if isinstance(nb_points, bool) or not isinstance(nb_points, (int, np.integer)) or not 1 <= int(nb_points) <= 2 ** 31 - 1:
-        raise _cv.error(f"{who}: nb_points={nb_points!r} is not an integer >= 1")
-    if max_count is not None and (isinstance(max_count, bool) or not isinstance(max_count, (int, np.integer))
-                                  or not int(nb_points) <= int(max_count) <= 2 ** 31 - 1):
-        raise _cv.error(f"{who}: max_count={max_count!r} is not an integer >= nb_points")
+    _int_arg(who, nb_points, 1, 2 ** 31 - 1, f"nb_points={nb_points!r} is not an integer >= 1")
+    if max_count is not None:
+        _int_arg(who, max_count, int(nb_points), 2 ** 31 - 1, f"max_count={max_count!r} is not an integer >= nb_points")
     n = pts.size // 3
     if n > RADIUS_MAX_POINTS:
         raise _cv.error(f"{who}: {n} points, more than {RADIUS_MAX_POINTS} (include/sgm_hip_radius.h)")
@@ -239,8 +224,7 @@ def remove_statistical_outlier(points_3D, colors, disparity_map, nb_neighbors, s
     out_of_range, dense, sparse, A, B, T."""
     who = "remove_statistical_outlier"
     pts, disp, colors = _outlier_cloud(who, points_3D, colors, disparity_map, confidence, min_confidence)
-    if isinstance(nb_neighbors, bool) or not isinstance(nb_neighbors, (int, np.integer)) or not 1 <= int(nb_neighbors) <= STATISTICAL_MAX_NEIGHBORS:
-        raise _cv.error(f"{who}: nb_neighbors={nb_neighbors!r} is not an integer in 1 .. {STATISTICAL_MAX_NEIGHBORS}")
+    _int_arg(who, nb_neighbors, 1, STATISTICAL_MAX_NEIGHBORS, f"nb_neighbors={nb_neighbors!r} is not an integer in 1 .. {STATISTICAL_MAX_NEIGHBORS}")
     with np.errstate(all="ignore"):
         try:
             ratio = np.float32(std_ratio)
@@ -302,15 +286,7 @@ def estimate_normals_radius(points_3D, disparity_map, radius, min_neighbors=3, o
         write_ply(path, centroids, colors, normals)
     """
     who = "estimate_normals_radius"
-    on_device = _cv._is_torch(points_3D)
-    if on_device:
-        pts, disp = _device_cloud(who, points_3D, disparity_map, confidence, min_confidence)
-        shape = tuple(pts.shape[:-1])
-        n = pts.numel() // 3
-    else:
-        pts, disp, _ = _outlier_cloud(who, points_3D, None, disparity_map, confidence, min_confidence)
-        shape = pts.shape[:-1]
-        n = pts.size // 3
+    on_device, pts, disp, _, shape, n = _host_or_device_cloud(who, points_3D, None, disparity_map, confidence, min_confidence)
     numbers = "radius, origin and viewpoint"
     try:
         with np.errstate(all="ignore"):
@@ -320,9 +296,8 @@ def estimate_normals_radius(points_3D, disparity_map, radius, min_neighbors=3, o
     r, org = _search_radius(who, "radius", radius, origin, (32768.0,), numbers)
     if view.shape != (3,) or not np.isfinite(view).all():
         raise _cv.error(f"{who}: viewpoint={viewpoint!r} is not three finite numbers")
-    if (isinstance(min_neighbors, bool) or not isinstance(min_neighbors, (int, np.integer))
-            or not COVARIANCE_MIN_NEIGHBORS <= int(min_neighbors) <= RADIUS_MAX_POINTS):
-        raise _cv.error(f"{who}: min_neighbors={min_neighbors!r} is not an integer in {COVARIANCE_MIN_NEIGHBORS} .. {RADIUS_MAX_POINTS}")
+    _int_arg(who, min_neighbors, COVARIANCE_MIN_NEIGHBORS, RADIUS_MAX_POINTS,
+             f"min_neighbors={min_neighbors!r} is not an integer in {COVARIANCE_MIN_NEIGHBORS} .. {RADIUS_MAX_POINTS}")
     if not isinstance(orient, (bool, np.bool_)):
         raise _cv.error(f"{who}: orient={orient!r} is not a bool")
     if n > RADIUS_MAX_POINTS:
@@ -384,6 +359,16 @@ def _device_cloud(who, points_3D, disparity_map, confidence, min_confidence):
     return pts.contiguous(), disp.contiguous()
 
 
+def _host_or_device_cloud(who, points_3D, colors, disparity_map, confidence, min_confidence):
+    """the cloud of a call that takes arrays or tensors, checked: (on_device, points, disparities or None, colours -- of a tensor
+    cloud as given --, the shape of the per-point results, n)"""
+    if _cv._is_torch(points_3D):
+        pts, disp = _device_cloud(who, points_3D, disparity_map, confidence, min_confidence)
+        return True, pts, disp, colors, tuple(pts.shape[:-1]), pts.numel() // 3
+    pts, disp, colors = _outlier_cloud(who, points_3D, colors, disparity_map, confidence, min_confidence)
+    return False, pts, disp, colors, pts.shape[:-1], pts.size // 3
+
+
 DBSCAN_STATS = ("in_range", "out_of_range", "core", "border", "noise", "clusters")
 
 
@@ -418,18 +403,9 @@ def cluster_dbscan(points_3D, disparity_map, eps, min_points, origin=(0, 0, 0), 
     valid_points(points_3D, colors, disparity_map, confidence=mask, min_confidence=1).
     """
     who = "cluster_dbscan"
-    on_device = _cv._is_torch(points_3D)
-    if on_device:
-        pts, disp = _device_cloud(who, points_3D, disparity_map, confidence, min_confidence)
-        shape = tuple(pts.shape[:-1])
-        n = pts.numel() // 3
-    else:
-        pts, disp, _ = _outlier_cloud(who, points_3D, None, disparity_map, confidence, min_confidence)
-        shape = pts.shape[:-1]
-        n = pts.size // 3
+    on_device, pts, disp, _, shape, n = _host_or_device_cloud(who, points_3D, None, disparity_map, confidence, min_confidence)
     r, org = _search_radius(who, "eps", eps, origin)
-    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= int(min_points) <= RADIUS_MAX_POINTS:
-        raise _cv.error(f"{who}: min_points={min_points!r} is not an integer in 1 .. {RADIUS_MAX_POINTS}")
+    _int_arg(who, min_points, 1, RADIUS_MAX_POINTS, f"min_points={min_points!r} is not an integer in 1 .. {RADIUS_MAX_POINTS}")
     if n > RADIUS_MAX_POINTS:
         raise _cv.error(f"{who}: {n} points, more than {RADIUS_MAX_POINTS} (include/sgm_hip_dbscan.h)")
     if on_device:
@@ -469,8 +445,8 @@ def largest_clusters(labels, sizes, count=1, min_size=1):
     outlier removals with min_confidence=1.  Plain numpy, or plain torch for tensors: no kernel."""
     who = "largest_clusters"
     for name, v in (("count", count), ("min_size", min_size)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < (0 if name == "count" else 1):
-            raise _cv.error(f"{who}: {name}={v!r} is not an integer >= {0 if name == 'count' else 1}")
+        lo = 0 if name == "count" else 1
+        _int_arg(who, v, lo, float("inf"), f"{name}={v!r} is not an integer >= {lo}")
     if _cv._is_torch(labels):
         import torch
         sz = sizes if _cv._is_torch(sizes) else torch.from_numpy(np.asarray(sizes).astype(np.int64))
@@ -520,18 +496,13 @@ def _plane_call(who, points_3D, colors, disparity_map, confidence, min_confidenc
     (host(engine, pts, disp, colors) or device(engine, pts, disp, colors, n, outputs...)), and the optional results in their order.
     Returns (head, mask, points, colors, index, distances): head is what the call returns in front of the per-point results."""
     return_points, return_index, return_distances = flags
-    on_device = _cv._is_torch(points_3D)
+    on_device, pts, disp, colors, shape, n = _host_or_device_cloud(who, points_3D, colors, disparity_map, confidence, min_confidence)
     if on_device:
         import torch
-        pts, disp = _device_cloud(who, points_3D, disparity_map, confidence, min_confidence)
         if colors is not None and (not _cv._is_torch(colors) or colors.device != pts.device or colors.dtype != torch.uint8
                                    or tuple(colors.shape) != tuple(pts.shape)):
             raise _cv.error(f"{who}: with a tensor points_3D colors must be a uint8 tensor of its shape on the same GPU")
         colors = None if colors is None else colors.contiguous()
-        shape, n = tuple(pts.shape[:-1]), pts.numel() // 3
-    else:
-        pts, disp, colors = _outlier_cloud(who, points_3D, colors, disparity_map, confidence, min_confidence)
-        shape, n = pts.shape[:-1], pts.size // 3
     if n > RADIUS_MAX_POINTS:
         raise _cv.error(f"{who}: {n} points, more than {RADIUS_MAX_POINTS} (include/sgm_hip_plane.h)")
     want_index = return_index or bool(select)      # (the inverted mask is made from the selected indices)
@@ -620,14 +591,10 @@ def segment_plane(points_3D, colors, disparity_map, distance_threshold, ransac_n
     with the previous inverted mask as confidence peel plane after plane.  plane_inliers applies a model found once to other clouds.
     """
     who = "segment_plane"
-    if isinstance(ransac_n, bool) or not isinstance(ransac_n, (int, np.integer)) or int(ransac_n) != 3:
-        raise _cv.error(f"{who}: ransac_n={ransac_n!r}: only 3 is offered (include/sgm_hip_plane.h)")
+    _int_arg(who, ransac_n, 3, 3, f"ransac_n={ransac_n!r}: only 3 is offered (include/sgm_hip_plane.h)")
     t = _plane_threshold(who, distance_threshold)
-    if (isinstance(num_iterations, bool) or not isinstance(num_iterations, (int, np.integer))
-            or not 1 <= int(num_iterations) <= PLANE_MAX_ITERATIONS):
-        raise _cv.error(f"{who}: num_iterations={num_iterations!r} is not an integer in 1 .. {PLANE_MAX_ITERATIONS}")
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) <= 2 ** 32 - 1:
-        raise _cv.error(f"{who}: seed={seed!r} is not an integer in 0 .. 2^32 - 1")
+    _int_arg(who, num_iterations, 1, PLANE_MAX_ITERATIONS, f"num_iterations={num_iterations!r} is not an integer in 1 .. {PLANE_MAX_ITERATIONS}")
+    _int_arg(who, seed, 0, 2 ** 32 - 1, f"seed={seed!r} is not an integer in 0 .. 2^32 - 1")
     K, seed, refine, select = int(num_iterations), int(seed), bool(refine), int(bool(invert))
     flags = (bool(return_points), bool(return_index), bool(return_distances))
 
@@ -820,8 +787,7 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
     if estimation not in ICP_ESTIMATIONS:
         raise _cv.error(f"{who}: estimation={estimation!r} is not one of {ICP_ESTIMATIONS}")
     est = ICP_ESTIMATIONS.index(estimation)
-    if isinstance(max_iteration, bool) or not isinstance(max_iteration, (int, np.integer)) or not 0 <= int(max_iteration) <= ICP_MAX_ITERATION:
-        raise _cv.error(f"{who}: max_iteration={max_iteration!r} is not an integer in 0 .. {ICP_MAX_ITERATION}")
+    _int_arg(who, max_iteration, 0, ICP_MAX_ITERATION, f"max_iteration={max_iteration!r} is not an integer in 0 .. {ICP_MAX_ITERATION}")
     rel = []
     for name, v in (("relative_fitness", relative_fitness), ("relative_rmse", relative_rmse)):
         try:

@@ -62,6 +62,23 @@ def _check(rc: int) -> None:
         raise error(f"sgm_hip error {rc}: {_lib.last_error()}")
 
 
+def _at(a):
+    """The address of an array for a C entry; None (a null pointer) for None."""
+    return None if a is None else a.ctypes.data
+
+
+def _vec3(v) -> np.ndarray:
+    return np.ascontiguousarray(v, np.float32).reshape(3)
+
+
+def _cloud_in(xyz, disp, colors):
+    """A point list as the C entries read it: (xyz float32 (n, 3), n, disp float32 (n) or None, colors uint8 (n, 3) or None)."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    disp = None if disp is None else np.ascontiguousarray(disp, np.float32).reshape(-1)
+    colors = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+    return xyz, xyz.shape[0], disp, colors
+
+
 class Engine:
     """Owns one sgm_engine handle (device buffers + stream) for a fixed parameter set."""
 
@@ -232,18 +249,14 @@ class Engine:
         """sgm_voxel_downsample: float32 points (n, 3) or (H, W, 3), float32 disparities (n) or (H, W) or None, uint8 colours of
         the points' shape or None.  Returns (points float32 (M, 3), colors uint8 (M, 3) or None, counts uint32 (M) or None,
         n_out_of_range), the voxels in the order of their first points."""
-        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        n = xyz.shape[0]
-        disp = None if disp is None else np.ascontiguousarray(disp, np.float32).reshape(-1)
-        colors = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        xyz, n, disp, colors = _cloud_in(xyz, disp, colors)
+        org = _vec3(origin)
         pts = np.empty((n, 3), np.float32)
         rgb = None if colors is None else np.empty((n, 3), np.uint8)
         cnt = np.empty(n, np.uint32) if return_counts else None
         nv, noor = C.c_int64(0), C.c_int64(0)
-        at = lambda a: None if a is None else a.ctypes.data
-        _check(self._L.sgm_voxel_downsample(self._h, xyz.ctypes.data, at(disp), at(colors), n, float(voxel_size), org.ctypes.data,
-                                            int(min_points), pts.ctypes.data, at(rgb), at(cnt), C.byref(nv), C.byref(noor)))
+        _check(self._L.sgm_voxel_downsample(self._h, xyz.ctypes.data, _at(disp), _at(colors), n, float(voxel_size), org.ctypes.data,
+                                            int(min_points), pts.ctypes.data, _at(rgb), _at(cnt), C.byref(nv), C.byref(noor)))
         m = nv.value
         return (pts[:m].copy(), None if rgb is None else rgb[:m].copy(), None if cnt is None else cnt[:m].copy(), int(noor.value))
 
@@ -251,7 +264,7 @@ class Engine:
                                 min_points: int, d_points: int, d_out_colors: int | None = None, d_out_counts: int | None = None):
         """sgm_voxel_downsample_device: device addresses, outputs with room for n rows; the rows go to the front of the outputs in
         the order of the voxels' first points.  Returns (n_voxels, n_out_of_range); synchronises the engine's stream."""
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        org = _vec3(origin)
         nv, noor = C.c_int64(0), C.c_int64(0)
         _check(self._L.sgm_voxel_downsample_device(self._h, d_xyz, d_dispf, d_colors, int(n), float(voxel_size), org.ctypes.data,
                                                    int(min_points), d_points, d_out_colors, d_out_counts, C.byref(nv), C.byref(noor)))
@@ -264,21 +277,17 @@ class Engine:
         """sgm_radius_outlier: float32 points (n, 3) or (H, W, 3), float32 disparities (n) or (H, W) or None, uint8 colours of the
         points' shape or None; max_count None means nb_points.  Returns (points float32 (M, 3), colors uint8 (M, 3) or None,
         keep uint8 (n), counts uint32 (n) or None, index uint32 (M) or None, n_out_of_range): the kept points in source order."""
-        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        n = xyz.shape[0]
-        disp = None if disp is None else np.ascontiguousarray(disp, np.float32).reshape(-1)
-        colors = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        xyz, n, disp, colors = _cloud_in(xyz, disp, colors)
+        org = _vec3(origin)
         keep = np.zeros(n, np.uint8)
         cnt = np.zeros(n, np.uint32) if return_counts else None
         pts = np.empty((n, 3), np.float32)
         rgb = None if colors is None else np.empty((n, 3), np.uint8)
         idx = np.empty(n, np.uint32) if return_index else None
         nk, noor = C.c_int64(0), C.c_int64(0)
-        at = lambda a: None if a is None else a.ctypes.data
-        _check(self._L.sgm_radius_outlier(self._h, xyz.ctypes.data, at(disp), at(colors), n, float(radius), org.ctypes.data,
+        _check(self._L.sgm_radius_outlier(self._h, xyz.ctypes.data, _at(disp), _at(colors), n, float(radius), org.ctypes.data,
                                           int(nb_points), int(nb_points if max_count is None else max_count), keep.ctypes.data,
-                                          at(cnt), pts.ctypes.data, at(rgb), at(idx), C.byref(nk), C.byref(noor)))
+                                          _at(cnt), pts.ctypes.data, _at(rgb), _at(idx), C.byref(nk), C.byref(noor)))
         m = nk.value
         return (pts[:m].copy(), None if rgb is None else rgb[:m].copy(), keep, cnt, None if idx is None else idx[:m].copy(),
                 int(noor.value))
@@ -290,7 +299,7 @@ class Engine:
         """sgm_radius_outlier_device: device addresses; d_keep (uint8) and d_counts (uint32) have n entries, d_points, d_out_colors
         and d_index (uint32) room for n rows, and the kept points go to their front in source order.  Returns (n_kept,
         n_out_of_range); synchronises the engine's stream."""
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        org = _vec3(origin)
         nk, noor = C.c_int64(0), C.c_int64(0)
         _check(self._L.sgm_radius_outlier_device(self._h, d_xyz, d_dispf, d_colors, int(n), float(radius), org.ctypes.data,
                                                  int(nb_points), int(nb_points if max_count is None else max_count), d_keep, d_counts,
@@ -305,21 +314,17 @@ class Engine:
         the points' shape or None.  Returns (points float32 (M, 3), colors uint8 (M, 3) or None, keep uint8 (n), mean float32 (n)
         or None, index uint32 (M) or None, stats uint64 (8)): the kept points in source order; stats is points in range, valid
         points out of range, dense, sparse, A, B, T, 0."""
-        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        n = xyz.shape[0]
-        disp = None if disp is None else np.ascontiguousarray(disp, np.float32).reshape(-1)
-        colors = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        xyz, n, disp, colors = _cloud_in(xyz, disp, colors)
+        org = _vec3(origin)
         keep = np.zeros(n, np.uint8)
         mean = np.full(n, -1, np.float32) if return_distances else None
         pts = np.empty((n, 3), np.float32)
         rgb = None if colors is None else np.empty((n, 3), np.uint8)
         idx = np.empty(n, np.uint32) if return_index else None
         nk, stats = C.c_int64(0), np.zeros(8, np.uint64)
-        at = lambda a: None if a is None else a.ctypes.data
-        _check(self._L.sgm_statistical_outlier(self._h, xyz.ctypes.data, at(disp), at(colors), n, int(nb_neighbors), float(std_ratio),
-                                               float(max_radius), org.ctypes.data, keep.ctypes.data, at(mean), pts.ctypes.data, at(rgb),
-                                               at(idx), C.byref(nk), stats.ctypes.data))
+        _check(self._L.sgm_statistical_outlier(self._h, xyz.ctypes.data, _at(disp), _at(colors), n, int(nb_neighbors), float(std_ratio),
+                                               float(max_radius), org.ctypes.data, keep.ctypes.data, _at(mean), pts.ctypes.data, _at(rgb),
+                                               _at(idx), C.byref(nk), stats.ctypes.data))
         m = nk.value
         return (pts[:m].copy(), None if rgb is None else rgb[:m].copy(), keep, mean, None if idx is None else idx[:m].copy(), stats)
 
@@ -330,7 +335,7 @@ class Engine:
         """sgm_statistical_outlier_device: device addresses; d_keep (uint8) and d_mean (float32) have n entries, d_points,
         d_out_colors and d_index (uint32) room for n rows, and the kept points go to their front in source order.  Returns
         (n_kept, stats uint64 (8)); synchronises the engine's stream."""
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        org = _vec3(origin)
         nk, stats = C.c_int64(0), np.zeros(8, np.uint64)
         _check(self._L.sgm_statistical_outlier_device(self._h, d_xyz, d_dispf, d_colors, int(n), int(nb_neighbors), float(std_ratio),
                                                       float(max_radius), org.ctypes.data, d_keep, d_mean, d_points, d_out_colors, d_index,
@@ -345,18 +350,15 @@ class Engine:
         float32 (n, 3), curvature float32 (n) or None, counts uint32 (n) or None, stats uint64 (4)), all at the source index: a
         point without a normal has (0, 0, 0) and -1; stats is points in range, valid points out of range, points with a normal,
         degenerate points."""
-        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        n = xyz.shape[0]
-        disp = None if disp is None else np.ascontiguousarray(disp, np.float32).reshape(-1)
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
-        view = np.ascontiguousarray(viewpoint, np.float32).reshape(3)
+        xyz, n, disp, _ = _cloud_in(xyz, disp, None)
+        org = _vec3(origin)
+        view = _vec3(viewpoint)
         nrm = np.zeros((n, 3), np.float32)
         curv = np.full(n, -1, np.float32) if return_curvature else None
         cnt = np.zeros(n, np.uint32) if return_counts else None
         stats = np.zeros(4, np.uint64)
-        at = lambda a: None if a is None else a.ctypes.data
-        _check(self._L.sgm_covariance_normals(self._h, xyz.ctypes.data, at(disp), n, float(radius), int(min_neighbors), org.ctypes.data,
-                                              view.ctypes.data, int(bool(orient)), nrm.ctypes.data, at(curv), at(cnt), stats.ctypes.data))
+        _check(self._L.sgm_covariance_normals(self._h, xyz.ctypes.data, _at(disp), n, float(radius), int(min_neighbors), org.ctypes.data,
+                                              view.ctypes.data, int(bool(orient)), nrm.ctypes.data, _at(curv), _at(cnt), stats.ctypes.data))
         return nrm, curv, cnt, stats
 
     def covariance_normals_device(self, d_xyz: int, d_dispf: int | None, n: int, radius: float, min_neighbors: int = 3,
@@ -365,8 +367,8 @@ class Engine:
         """sgm_covariance_normals_device: device addresses; d_normals (float32) has n rows of 3, d_curvature (float32) and d_counts
         (uint32) n entries.  Returns stats uint64 (4) after synchronising the engine's stream, or with return_stats=False None
         with the outputs complete once the stream has run (synchronize())."""
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
-        view = np.ascontiguousarray(viewpoint, np.float32).reshape(3)
+        org = _vec3(origin)
+        view = _vec3(viewpoint)
         stats = np.zeros(4, np.uint64) if return_stats else None
         _check(self._L.sgm_covariance_normals_device(self._h, d_xyz, d_dispf, int(n), float(radius), int(min_neighbors), org.ctypes.data,
                                                      view.ctypes.data, int(bool(orient)), d_normals, d_curvature, d_counts,
@@ -379,25 +381,22 @@ class Engine:
         """sgm_cluster_dbscan: float32 points (n, 3) or (H, W, 3), float32 disparities (n) or (H, W) or None.  Returns (labels int32
         (n): the cluster's number or -1, core uint8 (n) or None, sizes uint32 (clusters) or None, stats uint64 (6)), the first two at
         the source index; stats is points in range, valid points out of range, core, border, in-range noise, clusters."""
-        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        n = xyz.shape[0]
-        disp = None if disp is None else np.ascontiguousarray(disp, np.float32).reshape(-1)
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        xyz, n, disp, _ = _cloud_in(xyz, disp, None)
+        org = _vec3(origin)
         labels = np.full(n, -1, np.int32)
         core = np.zeros(n, np.uint8) if return_core else None
         sizes = np.zeros(n, np.uint32) if return_sizes else None
         stats = np.zeros(6, np.uint64)
         nc = C.c_int64(0)
-        at = lambda a: None if a is None else a.ctypes.data
-        _check(self._L.sgm_cluster_dbscan(self._h, xyz.ctypes.data, at(disp), n, float(eps), int(min_points), org.ctypes.data,
-                                          labels.ctypes.data, at(core), at(sizes), stats.ctypes.data, C.byref(nc)))
+        _check(self._L.sgm_cluster_dbscan(self._h, xyz.ctypes.data, _at(disp), n, float(eps), int(min_points), org.ctypes.data,
+                                          labels.ctypes.data, _at(core), _at(sizes), stats.ctypes.data, C.byref(nc)))
         return labels, core, None if sizes is None else sizes[:int(nc.value)].copy(), stats
 
     def cluster_dbscan_device(self, d_xyz: int, d_dispf: int | None, n: int, eps: float, min_points: int, origin=(0.0, 0.0, 0.0),
                               d_labels: int | None = None, d_core: int | None = None, d_sizes: int | None = None):
         """sgm_cluster_dbscan_device: device addresses; d_labels (int32) and d_core (uint8) have n entries, d_sizes (uint32) room for
         n of which the first `clusters` are written.  Returns (clusters, stats uint64 (6)) after synchronising the engine's stream."""
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        org = _vec3(origin)
         stats = np.zeros(6, np.uint64)
         nc = C.c_int64(0)
         _check(self._L.sgm_cluster_dbscan_device(self._h, d_xyz, d_dispf, int(n), float(eps), int(min_points), org.ctypes.data,
@@ -407,10 +406,7 @@ class Engine:
     # -- plane segmentation of the point cloud (include/sgm_hip_plane.h) --
     @staticmethod
     def _plane_host_args(xyz, disp, colors, return_distances, return_points, return_index):
-        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        n = xyz.shape[0]
-        disp = None if disp is None else np.ascontiguousarray(disp, np.float32).reshape(-1)
-        colors = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        xyz, n, disp, colors = _cloud_in(xyz, disp, colors)
         inl = np.zeros(n, np.uint8)
         dist = np.full(n, np.nan, np.float32) if return_distances else None
         pts = np.empty((n, 3), np.float32) if return_points else None
@@ -430,9 +426,8 @@ class Engine:
                                                                                return_index)
         model, stats = np.zeros(4, np.float32), np.zeros(8, np.uint64)
         ni, ns = C.c_int64(0), C.c_int64(0)
-        at = lambda a: None if a is None else a.ctypes.data
-        _check(self._L.sgm_segment_plane(self._h, xyz.ctypes.data, at(disp), at(colors), n, float(distance_threshold), int(num_iterations),
-                                         int(seed), int(bool(refine)), int(select), inl.ctypes.data, at(dist), at(pts), at(rgb), at(idx),
+        _check(self._L.sgm_segment_plane(self._h, xyz.ctypes.data, _at(disp), _at(colors), n, float(distance_threshold), int(num_iterations),
+                                         int(seed), int(bool(refine)), int(select), inl.ctypes.data, _at(dist), _at(pts), _at(rgb), _at(idx),
                                          model.ctypes.data, stats.ctypes.data, C.byref(ni), C.byref(ns)))
         cut = lambda a: None if a is None else a[:ns.value].copy()
         return model, inl, dist, cut(pts), cut(rgb), cut(idx), stats, int(ni.value)
@@ -460,9 +455,8 @@ class Engine:
                                                                                return_index)
         model = np.ascontiguousarray(plane_model, np.float32).reshape(4)
         ni, ns = C.c_int64(0), C.c_int64(0)
-        at = lambda a: None if a is None else a.ctypes.data
-        _check(self._L.sgm_plane_inliers(self._h, xyz.ctypes.data, at(disp), at(colors), n, model.ctypes.data, float(distance_threshold),
-                                         int(select), inl.ctypes.data, at(dist), at(pts), at(rgb), at(idx), C.byref(ni), C.byref(ns)))
+        _check(self._L.sgm_plane_inliers(self._h, xyz.ctypes.data, _at(disp), _at(colors), n, model.ctypes.data, float(distance_threshold),
+                                         int(select), inl.ctypes.data, _at(dist), _at(pts), _at(rgb), _at(idx), C.byref(ni), C.byref(ns)))
         cut = lambda a: None if a is None else a[:ns.value].copy()
         return inl, dist, cut(pts), cut(rgb), cut(idx), int(ni.value)
 
@@ -492,18 +486,14 @@ class Engine:
         normals of the target's shape or None.  Returns (T float64 (4, 4), fitness, rmse, corr int32 (ns), d2 float32 (ns), history
         float64 (evaluations, 2), stats uint64 (8)): stats is valid source points, target points in range, valid target points out
         of range, iterations, correspondences, unplaced, unusable normals, status."""
-        src = np.ascontiguousarray(source, np.float32).reshape(-1, 3)
-        tgt = np.ascontiguousarray(target, np.float32).reshape(-1, 3)
-        ns, nt = src.shape[0], tgt.shape[0]
-        ds = None if source_disp is None else np.ascontiguousarray(source_disp, np.float32).reshape(-1)
-        dt = None if target_disp is None else np.ascontiguousarray(target_disp, np.float32).reshape(-1)
+        src, ns, ds, _ = _cloud_in(source, source_disp, None)
+        tgt, nt, dt, _ = _cloud_in(target, target_disp, None)
         nrm = None if target_normals is None else np.ascontiguousarray(target_normals, np.float32).reshape(-1, 3)
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        org = _vec3(origin)
         T0 = np.ascontiguousarray(np.eye(4) if init is None else init, np.float64).reshape(16)
         T, fit, rmse, hist, stats = self._icp_small(max_iteration)
         corr, d2 = np.full(ns, -1, np.int32), np.full(ns, np.nan, np.float32)
-        at = lambda a: None if a is None else a.ctypes.data
-        _check(self._L.sgm_register_icp(self._h, src.ctypes.data, at(ds), ns, tgt.ctypes.data, at(dt), at(nrm), nt,
+        _check(self._L.sgm_register_icp(self._h, src.ctypes.data, _at(ds), ns, tgt.ctypes.data, _at(dt), _at(nrm), nt,
                                         float(max_correspondence_distance), org.ctypes.data, T0.ctypes.data, int(estimation),
                                         int(max_iteration), float(relative_fitness), float(relative_rmse), T.ctypes.data, C.byref(fit),
                                         C.byref(rmse), corr.ctypes.data, d2.ctypes.data, hist.ctypes.data, stats.ctypes.data))
@@ -516,7 +506,7 @@ class Engine:
         """sgm_register_icp_device: device addresses; d_corr (int32) and d_d2 (float32) have ns entries.  Returns (T float64 (4, 4),
         fitness, rmse, history float64 (evaluations, 2), stats uint64 (8)); synchronises the engine's stream once for the target's
         grid and once per evaluation."""
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        org = _vec3(origin)
         T0 = np.ascontiguousarray(np.eye(4) if init is None else init, np.float64).reshape(16)
         T, fit, rmse, hist, stats = self._icp_small(max_iteration)
         _check(self._L.sgm_register_icp_device(self._h, d_source, d_source_disp, int(ns), d_target, d_target_disp, d_target_normals, int(nt),
@@ -530,17 +520,13 @@ class Engine:
                                    transformation=None):
         """sgm_evaluate_registration: the correspondence pass alone under `transformation` (None: the identity).  Returns (fitness,
         rmse, corr int32 (ns), d2 float32 (ns), stats uint64 (8))."""
-        src = np.ascontiguousarray(source, np.float32).reshape(-1, 3)
-        tgt = np.ascontiguousarray(target, np.float32).reshape(-1, 3)
-        ns, nt = src.shape[0], tgt.shape[0]
-        ds = None if source_disp is None else np.ascontiguousarray(source_disp, np.float32).reshape(-1)
-        dt = None if target_disp is None else np.ascontiguousarray(target_disp, np.float32).reshape(-1)
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        src, ns, ds, _ = _cloud_in(source, source_disp, None)
+        tgt, nt, dt, _ = _cloud_in(target, target_disp, None)
+        org = _vec3(origin)
         T = np.ascontiguousarray(np.eye(4) if transformation is None else transformation, np.float64).reshape(16)
         fit, rmse, stats = C.c_double(0.0), C.c_double(0.0), np.zeros(8, np.uint64)
         corr, d2 = np.full(ns, -1, np.int32), np.full(ns, np.nan, np.float32)
-        at = lambda a: None if a is None else a.ctypes.data
-        _check(self._L.sgm_evaluate_registration(self._h, src.ctypes.data, at(ds), ns, tgt.ctypes.data, at(dt), nt,
+        _check(self._L.sgm_evaluate_registration(self._h, src.ctypes.data, _at(ds), ns, tgt.ctypes.data, _at(dt), nt,
                                                  float(max_correspondence_distance), org.ctypes.data, T.ctypes.data, C.byref(fit),
                                                  C.byref(rmse), corr.ctypes.data, d2.ctypes.data, stats.ctypes.data))
         return fit.value, rmse.value, corr, d2, stats
@@ -549,7 +535,7 @@ class Engine:
                                      nt: int, max_correspondence_distance: float, origin=(0.0, 0.0, 0.0), transformation=None,
                                      d_corr: int | None = None, d_d2: int | None = None):
         """sgm_evaluate_registration_device: device addresses as in register_icp_device.  Returns (fitness, rmse, stats uint64 (8))."""
-        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        org = _vec3(origin)
         T = np.ascontiguousarray(np.eye(4) if transformation is None else transformation, np.float64).reshape(16)
         fit, rmse, stats = C.c_double(0.0), C.c_double(0.0), np.zeros(8, np.uint64)
         _check(self._L.sgm_evaluate_registration_device(self._h, d_source, d_source_disp, int(ns), d_target, d_target_disp, int(nt),
@@ -564,8 +550,7 @@ class Engine:
         nrm = None if normals is None else np.ascontiguousarray(normals, np.float32)
         T = np.ascontiguousarray(transformation, np.float64).reshape(16)
         out, out_n = np.empty_like(pts), None if nrm is None else np.empty_like(nrm)
-        at = lambda a: None if a is None else a.ctypes.data
-        _check(self._L.sgm_transform_points(self._h, pts.ctypes.data, at(nrm), pts.size // 3, T.ctypes.data, out.ctypes.data, at(out_n)))
+        _check(self._L.sgm_transform_points(self._h, pts.ctypes.data, _at(nrm), pts.size // 3, T.ctypes.data, out.ctypes.data, _at(out_n)))
         return out, out_n
 
     def transform_points_device(self, d_xyz: int, d_normals: int | None, n: int, transformation, d_out_xyz: int | None,
@@ -588,9 +573,8 @@ class Engine:
         rgb = None if colors is None else np.empty((H * W, 3), np.uint8)
         faces = np.empty((2 * max(H - 1, 0) * max(W - 1, 0), 3), np.int32)
         nv, nf = C.c_int64(0), C.c_int64(0)
-        at = lambda a: None if a is None else a.ctypes.data
-        _check(self._L.sgm_mesh_grid(self._h, xyz.ctypes.data, disp.ctypes.data, at(colors), H, W, float(max_diff), vert.ctypes.data,
-                                     at(rgb), faces.ctypes.data, C.byref(nv), C.byref(nf)))
+        _check(self._L.sgm_mesh_grid(self._h, xyz.ctypes.data, disp.ctypes.data, _at(colors), H, W, float(max_diff), vert.ctypes.data,
+                                     _at(rgb), faces.ctypes.data, C.byref(nv), C.byref(nf)))
         return vert[:nv.value].copy(), None if rgb is None else rgb[:nv.value].copy(), faces[:nf.value].copy()
 
     def mesh_grid_device(self, d_xyz: int, d_dispf: int, d_colors: int | None, H: int, W: int, max_diff: float, d_vertices: int,
@@ -630,9 +614,8 @@ class Engine:
         rgb = None if colors is None else np.empty((H * W, 3), np.uint8)
         faces = np.empty((2 * max(H - 1, 0) * max(W - 1, 0), 3), np.int32)
         nv, nf = C.c_int64(0), C.c_int64(0)
-        at = lambda a: None if a is None else a.ctypes.data
-        _check(self._L.sgm_mesh_grid_normals(self._h, xyz.ctypes.data, disp.ctypes.data, at(colors), H, W, float(max_diff), int(orient),
-                                             vert.ctypes.data, at(rgb), faces.ctypes.data, nrm.ctypes.data, C.byref(nv), C.byref(nf)))
+        _check(self._L.sgm_mesh_grid_normals(self._h, xyz.ctypes.data, disp.ctypes.data, _at(colors), H, W, float(max_diff), int(orient),
+                                             vert.ctypes.data, _at(rgb), faces.ctypes.data, nrm.ctypes.data, C.byref(nv), C.byref(nf)))
         return vert[:nv.value].copy(), None if rgb is None else rgb[:nv.value].copy(), faces[:nf.value].copy(), nrm[:nv.value].copy()
 
     def mesh_grid_normals_device(self, d_xyz: int, d_dispf: int, d_colors: int | None, H: int, W: int, max_diff: float, orient: bool,
