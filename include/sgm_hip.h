@@ -60,7 +60,7 @@ extern "C" {
                              * radius outlier removal of sgm_hip_radius.h; the statistical outlier removal of
                              * sgm_hip_statistical.h; the covariance normals of sgm_hip_covariance.h; the density clustering of
                              * sgm_hip_dbscan.h; the plane segmentation of sgm_hip_plane.h; the rigid registration of
-                             * sgm_hip_icp.h */
+                             * sgm_hip_icp.h; the signed distance volume of sgm_hip_tsdf.h */
 
 typedef enum {
     SGM_OK = 0,
@@ -335,4 +335,6 @@ int64_t sgm_algorithmic_bytes(const sgm_params *params, int H, int W, int with_r
 #include "sgm_hip_plane.h"
 /* rigid registration of two clouds: iterated closest points on the target's grid of cells, the sums in one fixed tree */
 #include "sgm_hip_icp.h"
+/* many frames fused into one model: a truncated signed distance volume of integer sums, and its zero crossings as a point list */
+#include "sgm_hip_tsdf.h"
 #endif

@@ -12,7 +12,8 @@ from .pipeline import compute_disparity_map, reconstruct_3D, rectify_pair, run_d
 from .pointcloud import (cluster_dbscan, largest_clusters, segment_plane, plane_inliers, estimate_normals, estimate_normals_radius, mask_by_confidence, read_ply, read_point_cloud, read_triangle_mesh, remove_radius_outlier,
                          remove_statistical_outlier, triangulate_points,
                          triangulate_points_with_normals, valid_points, voxel_down_sample, write_ply, write_point_cloud,
-                         write_triangle_mesh, registration_icp, evaluate_registration, transform_points)
+                         write_triangle_mesh, registration_icp, evaluate_registration, transform_points,
+                         TSDFVolume, camera_from_Q, invert_rigid)
 from ._lib import SGM_OPT_CONFIDENCE, SGM_TAP_CONF, SGM_TAP_CONF_RAW
 from ._lib import SGM_OPT_RIGHT_VIEW, SGM_TAP_RIGHT, SGM_TAP_RIGHT_RAW
 
@@ -29,4 +30,5 @@ __all__ = [
     "remove_radius_outlier", "remove_statistical_outlier", "estimate_normals_radius",
     "cluster_dbscan", "largest_clusters", "segment_plane", "plane_inliers",
     "registration_icp", "evaluate_registration", "transform_points",
+    "TSDFVolume", "camera_from_Q", "invert_rigid",
 ]

@@ -83,6 +83,10 @@ ICP_EXPORTS = ("sgm_register_icp", "sgm_register_icp_device", "sgm_evaluate_regi
                "sgm_transform_points", "sgm_transform_points_device", "sgm_icp_solve")
 # the stage record of one sgm_register_icp call with SGM_OPT_PROFILE: the target's grid, then the last evaluation
 ICP_STAGES = ("icp_count", "icp_clear", "icp_insert", "icp_starts", "icp_sort", "icp_correspond", "icp_terms", "icp_reduce")
+# include/sgm_hip_tsdf.h (likewise): the truncated signed distance volume
+TSDF_EXPORTS = ("sgm_tsdf_integrate", "sgm_tsdf_integrate_device", "sgm_tsdf_extract_points", "sgm_tsdf_extract_points_device")
+# the stage records with SGM_OPT_PROFILE: tsdf_integrate of an integration; the other three of an extraction (tsdf_emit unless it only counts)
+TSDF_STAGES = ("tsdf_integrate", "tsdf_count", "tsdf_scan", "tsdf_emit")
 
 
 class SgmParams(C.Structure):
@@ -197,6 +201,10 @@ def load():
     L.sgm_transform_points.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp]
     L.sgm_transform_points_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp]
     L.sgm_icp_solve.argtypes = [vp, i32, vp, vp, C.POINTER(i32)]
+    L.sgm_tsdf_integrate.argtypes = [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, C.c_float, vp]
+    L.sgm_tsdf_integrate_device.argtypes = [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, C.c_float, vp]
+    L.sgm_tsdf_extract_points.argtypes = [vp, vp, C.c_float, vp, vp, vp, vp, i32, i64, vp, vp, C.POINTER(i64)]
+    L.sgm_tsdf_extract_points_device.argtypes = [vp, vp, C.c_float, vp, vp, vp, vp, i32, i64, vp, vp, C.POINTER(i64)]
     L.sgm_synchronize.argtypes = [vp]
     L.sgm_get_stage_times.argtypes = [vp, C.POINTER(SgmStageTimes)]
     L.sgm_algorithmic_bytes.argtypes = [pp, i32, i32, i32]
@@ -221,7 +229,7 @@ def load():
     L.sgm_debug_wta_raw_bytes.restype = C.c_longlong
     L.sgm_debug_wta_select_n.argtypes = [i32, i32, vp, i32, vp]
     L.sgm_debug_wta_select_n.restype = i32
-    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS + VOXEL_EXPORTS + MESH_EXPORTS + NORMALS_EXPORTS + RADIUS_EXPORTS + STATISTICAL_EXPORTS + COVARIANCE_EXPORTS + DBSCAN_EXPORTS + PLANE_EXPORTS + ICP_EXPORTS:
+    for name in EXPORTS + CONFIDENCE_EXPORTS + RIGHT_EXPORTS + WLS_EXPORTS + WLS_BATCH_EXPORTS + LRC_EXPORTS + VOXEL_EXPORTS + MESH_EXPORTS + NORMALS_EXPORTS + RADIUS_EXPORTS + STATISTICAL_EXPORTS + COVARIANCE_EXPORTS + DBSCAN_EXPORTS + PLANE_EXPORTS + ICP_EXPORTS + TSDF_EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("sgm_abi_version", "sgm_device_count"):
             fn.restype = i32

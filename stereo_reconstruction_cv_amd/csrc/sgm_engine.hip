@@ -37,6 +37,7 @@
 #include "kernels_dbscan.h"
 #include "kernels_plane.h"
 #include "kernels_icp.h"
+#include "kernels_tsdf.h"
 #include "kernels_mesh.h"
 #include "kernels_normals.h"
 
@@ -277,6 +278,7 @@ struct Plan {
     BUF(db_parent) BUF(db_near) BUF(db_rank) BUF(db_ctl) BUF(db_lab) BUF(db_sizes) /* sgm_cluster_dbscan, beside the radius search's buffers it reuses: per point the union-find link (int32 [n]), the nearest core point (uint32 [n]) and the root's rank (uint32 [n]), the call's three counts, and the host entry's staged labels (int32 [n]) and sizes (uint32 [n]; kernels_dbscan.h); sgm_trim releases all but the counts by name */ \
     BUF(pl_pts) BUF(pl_hyp) BUF(pl_cnt) BUF(pl_ctl) BUF(pl_inl) BUF(pl_dist) /* sgm_segment_plane, sgm_plane_inliers: the valid points in source order (float4 [n]), the hypotheses (float4 [K]) and their counts (uint32 [K]), the call's control block, and the host entries' staged inlier bytes (uint8 [n]) and distances (float32 [n]; kernels_plane.h); the byte the compaction selects by is rad_keep, the staged rows are cpts, crgb and rad_idx; sgm_trim releases all but the control block by name */ \
     BUF(icp_corr) BUF(icp_d2) BUF(icp_part) BUF(icp_ctl) BUF(icp_txyz) BUF(icp_tdisp) BUF(icp_tnrm) /* sgm_register_icp, sgm_evaluate_registration, sgm_transform_points, beside the radius search's buffers they reuse for the target's grid: per source point the correspondence (int32 [ns]) and its squared distance (float32 [ns]), the blocks' partial sums (double [blocks of 256][28]), the result record and the counts of one evaluation, and the host entries' staged target points, disparities and normals (kernels_icp.h); the staged source is xyz and f32; sgm_trim releases all but the record by name */ \
+    BUF(tsdf_sum) BUF(tsdf_w) BUF(tsdf_rgb) BUF(tsdf_cnt) BUF(tsdf_off) BUF(tsdf_ctl) /* sgm_tsdf_integrate, sgm_tsdf_extract_points: the host entries' staged planes (int32 [V], int32 [V], uint32 [3][V]), the extraction's counts per 1024 voxels (uint32 [blocks]) and their scanned offsets (uint64 [blocks + 1]), and the 256 copies of the eight counts of one integration (kernels_tsdf.h); the staged frame is xyz, f32 and crgb_in, the staged rows are cpts and crgb; sgm_trim releases all but the counts by name */ \
     BUF(mesh_code) BUF(mesh_num) BUF(mesh_fcnt) BUF(mesh_vcnt) BUF(mesh_faces) /* sgm_mesh_grid: a code byte per quad (uint8 [H][W]), the pixel -> vertex number map (uint32 [H][W]), the blocks' numbers of faces and of vertices (uint32 [blocks + 1] each), the host entry's staged faces (kernels_mesh.h); sgm_trim releases the first two and the last by name */ \
     BUF(mesh_nrm)                                /* sgm_normals_grid, sgm_mesh_grid_normals: the host entries' staged normals (float32 [H][W][3]; kernels_normals.h); sgm_trim releases it by name */ \
     BUF(headroom)                                /* uint32[2]: max C_true (incl. upstream's running-sum intermediate), max min_d L_r */ \
@@ -2066,7 +2068,8 @@ int sgm_trim(sgm_engine *e)
     for (DevBuf *b : {&e->wls_u, &e->wls_v, &e->wls_c, &e->lrc_f, &e->vox_tab, &e->vox_slot, &e->mesh_code, &e->mesh_num, &e->mesh_faces, &e->mesh_nrm,
                       &e->rad_tab, &e->rad_sorted, &e->rad_pt, &e->rad_keep, &e->rad_cnt, &e->rad_idx, &e->stat_mean, &e->cov_nrm, &e->cov_curv, &e->cov_mom,
                       &e->db_parent, &e->db_near, &e->db_rank, &e->db_lab, &e->db_sizes, &e->pl_pts, &e->pl_hyp, &e->pl_cnt, &e->pl_inl, &e->pl_dist,
-                      &e->icp_corr, &e->icp_d2, &e->icp_part, &e->icp_txyz, &e->icp_tdisp, &e->icp_tnrm})
+                      &e->icp_corr, &e->icp_d2, &e->icp_part, &e->icp_txyz, &e->icp_tdisp, &e->icp_tnrm,
+                      &e->tsdf_sum, &e->tsdf_w, &e->tsdf_rgb, &e->tsdf_cnt, &e->tsdf_off})
         (void)b->release();   // the filter's planes, the LR confidence's factors, the voxel table, the mesh's maps, the staged normals, the radius search's table, records and staging, the staged means of the statistical one and the staged normals, curvatures and moments of the covariance normals, the links, ranks and staging of the clustering and the valid list, hypotheses, counts and staging of the plane segmentation and the correspondences, partial sums and staged target of the registration come back on the next call
     return check_chain(e);
 }
@@ -4487,6 +4490,210 @@ int sgm_transform_points(sgm_engine *e, const float *xyz, const float *normals, 
     const HostIn pts{xyz, &e->xyz, (size_t)n * 12}, nrm{normals, &e->icp_tnrm, (size_t)n * 12};
     const HostOut opts{out_xyz, &e->xyz, 12, nullptr}, onrm{out_normals, &e->icp_tnrm, 12, nullptr};
     return host_call(e, n, {pts, nrm}, {opts, onrm}, [&] { return sgm_transform_points_device(e, pts.d(), nrm.d(), n, T, opts.d(), onrm.d()); });
+}
+
+// ---- the truncated signed distance volume (include/sgm_hip_tsdf.h, kernels_tsdf.h) -------------------------------------------------
+// What every entry of the header refuses about the volume, under the entry's name, before anything touches the device.  *V: nx ny nz.
+static int tsdf_check_volume(const char *who, const sgm_engine *e, const int32_t *dims, float vs, const float *origin, const void *sum,
+                             const void *weight, TsdfVol *vol, int64_t *V)
+{
+    if (!e || !dims || !origin || !sum || !weight) return set_err(SGM_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (!std::isfinite(vs) || !(vs > 0.0f)) return set_err(SGM_ERR_INVALID_ARG, "%s: voxel_size %g is not finite and positive", who, (double)vs);
+    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+        return set_err(SGM_ERR_INVALID_ARG, "%s: the origin is not finite", who);
+    for (int a = 0; a < 3; a++)
+        if (dims[a] < 1 || dims[a] > TSDF_MAX_DIM)
+            return set_err(SGM_ERR_UNSUPPORTED, "%s: dimension %d outside 1 .. %d", who, (int)dims[a], TSDF_MAX_DIM);
+    *V = (int64_t)dims[0] * dims[1] * dims[2];
+    if (*V > TSDF_MAX_VOXELS) return set_err(SGM_ERR_UNSUPPORTED, "%s: %lld voxels, more than 2^30", who, (long long)*V);
+    *vol = TsdfVol{dims[0], dims[1], dims[2], vs, origin[0], origin[1], origin[2]};
+    return SGM_OK;
+}
+
+// ... and about the frame of an integration
+static int tsdf_check_frame(const char *who, float tau, const void *rgb_sum, const void *xyz, const void *colors, int H, int W, const float *cam,
+                            int front, const double *extrinsic, float max_depth, TsdfFrame *fr)
+{
+    if (!xyz || !cam || !extrinsic) return set_err(SGM_ERR_INVALID_ARG, "%s: null pointer", who);
+    if ((rgb_sum == nullptr) != (colors == nullptr))
+        return set_err(SGM_ERR_INVALID_ARG, "%s: rgb_sum and colors are not both null or both given", who);
+    if (front != 1 && front != -1) return set_err(SGM_ERR_INVALID_ARG, "%s: front %d is neither +1 nor -1", who, front);
+    for (int k = 0; k < 4; k++)
+        if (!std::isfinite(cam[k])) return set_err(SGM_ERR_INVALID_ARG, "%s: the camera (fx, fy, cx, cy) has an entry that is not finite", who);
+    const float kappa = 32767.0f / tau;
+    if (!std::isfinite(tau) || !(tau > 0.0f) || !std::isfinite(kappa))
+        return set_err(SGM_ERR_INVALID_ARG, "%s: sdf_trunc %g is not finite and positive with a finite 32767 / sdf_trunc", who, (double)tau);
+    if (int rc = icp_check_T(who, extrinsic)) return rc;
+    if (!(max_depth > 0.0f)) return set_err(SGM_ERR_INVALID_ARG, "%s: max_depth %g is not > 0", who, (double)max_depth);
+    if (H < 1 || W < 1) return set_err(SGM_ERR_INVALID_ARG, "%s: a frame of %d x %d", who, H, W);
+    if ((int64_t)H * W > TSDF_MAX_PIXELS) return set_err(SGM_ERR_UNSUPPORTED, "%s: %d x %d pixels, more than 2^27", who, H, W);
+    for (int k = 0; k < 12; k++) fr->m[k] = (float)extrinsic[k];
+    fr->fx = cam[0], fr->fy = cam[1], fr->cx = cam[2], fr->cy = cam[3];
+    fr->front = (float)front, fr->max_depth = max_depth, fr->tau = tau, fr->kappa = kappa;
+    fr->H = H, fr->W = W;
+    return SGM_OK;
+}
+
+// the integration behind its checks: the stage, and the counts if they are asked for (the only wait)
+static int tsdf_integrate_run(sgm_engine *e, const TsdfVol &vol, int64_t V, const TsdfFrame &fr, void *d_sum, void *d_weight, void *d_rgb,
+                              const void *d_xyz, const void *d_disp, const void *d_colors, uint64_t *out_stats)
+{
+    HIP_TRY(hipSetDevice(e->device));
+    int rc;
+    constexpr size_t ctl_bytes = (size_t)TSDF_STAT_SLOTS * 64;
+    if (out_stats && (rc = e->tsdf_ctl.ensure(ctl_bytes))) return rc;
+    if (e->profile) stage_reset(e);   // the stage record is the call's from here on
+    hipStream_t st = e->stream;
+    unsigned long long *d_stats = out_stats ? (unsigned long long *)e->tsdf_ctl.p : nullptr;
+    if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, ctl_bytes, st));
+    const uint32_t xchunks = (uint32_t)((vol.nx + 63) / 64), rows = (uint32_t)vol.ny * (uint32_t)vol.nz;
+    const uint32_t blocks = xchunks * ((rows + 3u) / 4u);
+    const int64_t npix = (int64_t)fr.H * fr.W;
+    rc = run_stage(e, "tsdf_integrate", [&] {
+        if (!d_stats) {
+            hipLaunchKernelGGL(k_tsdf_integrate<false>, dim3(blocks), dim3(256), 0, st, vol, fr, xchunks, rows, V, (int32_t *)d_sum,
+                               (int32_t *)d_weight, (uint32_t *)d_rgb, (const float *)d_xyz, (const float *)d_disp, (const uint8_t *)d_colors,
+                               d_stats);
+            return 1;
+        }
+        hipLaunchKernelGGL(k_tsdf_integrate<true>, dim3(blocks), dim3(256), 0, st, vol, fr, xchunks, rows, V, (int32_t *)d_sum, (int32_t *)d_weight,
+                           (uint32_t *)d_rgb, (const float *)d_xyz, (const float *)d_disp, (const uint8_t *)d_colors, d_stats);
+        hipLaunchKernelGGL(k_tsdf_usable, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, (const float *)d_xyz, (const float *)d_disp,
+                           npix, fr.front, fr.max_depth, d_stats);
+        return 2;
+    });
+    if (rc) return rc;
+    if (out_stats) {
+        std::vector<uint64_t> h((size_t)TSDF_STAT_SLOTS * 8);      // the 256 copies of the record, added up here
+        HIP_TRY(hipMemcpyAsync(h.data(), d_stats, ctl_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::fill(out_stats, out_stats + 8, (uint64_t)0);
+        for (size_t k = 0; k < h.size(); k++) out_stats[k & 7] += h[k];
+    }
+    return SGM_OK;
+}
+
+int sgm_tsdf_integrate_device(sgm_engine *e, const int32_t dims[3], float voxel_size, float sdf_trunc, const float origin[3], void *d_sum,
+                              void *d_weight, void *d_rgb_sum, const void *d_xyz, const void *d_disp, const void *d_colors_rgb, int H, int W,
+                              const float cam[4], int front, const double extrinsic[16], float max_depth, uint64_t out_stats[8])
+{
+    const char *who = "sgm_tsdf_integrate_device";
+    TsdfVol vol;
+    TsdfFrame fr;
+    int64_t V = 0;
+    if (int rc = tsdf_check_volume(who, e, dims, voxel_size, origin, d_sum, d_weight, &vol, &V)) return rc;
+    if (int rc = tsdf_check_frame(who, sdf_trunc, d_rgb_sum, d_xyz, d_colors_rgb, H, W, cam, front, extrinsic, max_depth, &fr)) return rc;
+    return tsdf_integrate_run(e, vol, V, fr, d_sum, d_weight, d_rgb_sum, d_xyz, d_disp, d_colors_rgb, out_stats);
+}
+
+int sgm_tsdf_integrate(sgm_engine *e, const int32_t dims[3], float voxel_size, float sdf_trunc, const float origin[3], int32_t *sum,
+                       int32_t *weight, uint32_t *rgb_sum, const float *xyz, const float *disp, const uint8_t *colors_rgb, int H, int W,
+                       const float cam[4], int front, const double extrinsic[16], float max_depth, uint64_t out_stats[8])
+{
+    const char *who = "sgm_tsdf_integrate";
+    TsdfVol vol;
+    TsdfFrame fr;
+    int64_t V = 0;
+    if (int rc = tsdf_check_volume(who, e, dims, voxel_size, origin, sum, weight, &vol, &V)) return rc;
+    if (int rc = tsdf_check_frame(who, sdf_trunc, rgb_sum, xyz, colors_rgb, H, W, cam, front, extrinsic, max_depth, &fr)) return rc;
+    const size_t npix = (size_t)H * W;
+    // in place: a plane comes down from the buffer it went up to
+    const HostIn s{sum, &e->tsdf_sum, (size_t)V * 4}, w{weight, &e->tsdf_w, (size_t)V * 4}, c{rgb_sum, &e->tsdf_rgb, (size_t)V * 12},
+        pts{xyz, &e->xyz, npix * 12}, dsp{disp, &e->f32, npix * 4}, rgb{colors_rgb, &e->crgb_in, npix * 3};
+    const HostOut os{sum, &e->tsdf_sum, 4, nullptr}, ow{weight, &e->tsdf_w, 4, nullptr}, oc{rgb_sum, &e->tsdf_rgb, 12, nullptr};
+    uint64_t stats[8];
+    if (int rc = host_call(e, V, {s, w, c, pts, dsp, rgb}, {os, ow, oc}, [&] {
+            return tsdf_integrate_run(e, vol, V, fr, s.d(), w.d(), c.d(), pts.d(), dsp.d(), rgb.d(), out_stats ? stats : nullptr);
+        }))
+        return rc;
+    if (out_stats) std::copy(stats, stats + 8, out_stats);
+    return SGM_OK;
+}
+
+// What the extraction refuses beside the volume
+static int tsdf_check_extract(const char *who, const void *rgb_sum, int min_weight, int64_t capacity, const void *out_points, const void *out_colors,
+                              const int64_t *out_total)
+{
+    if (!out_total) return set_err(SGM_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (min_weight < 1) return set_err(SGM_ERR_INVALID_ARG, "%s: min_weight %d is not >= 1", who, min_weight);
+    if (capacity < 0) return set_err(SGM_ERR_INVALID_ARG, "%s: a capacity of %lld rows", who, (long long)capacity);
+    if (out_colors && !rgb_sum) return set_err(SGM_ERR_INVALID_ARG, "%s: out_colors requested without rgb_sum", who);
+    if (out_colors && !out_points) return set_err(SGM_ERR_INVALID_ARG, "%s: out_colors requested without out_points", who);
+    return SGM_OK;
+}
+
+// the extraction behind its checks: count, scan, emit (unless the call only counts), then ONE wait for the total
+static int tsdf_extract_run(sgm_engine *e, const TsdfVol &vol, int64_t V, const void *d_sum, const void *d_weight, const void *d_rgb,
+                            int min_weight, int64_t capacity, void *d_out_points, void *d_out_colors, int64_t *out_total)
+{
+    HIP_TRY(hipSetDevice(e->device));
+    const int m = (int)((V + TSDF_BLOCK_VOXELS - 1) / TSDF_BLOCK_VOXELS);
+    int rc;
+    if ((rc = e->tsdf_cnt.ensure((size_t)m * 4)) || (rc = e->tsdf_off.ensure((size_t)(m + 1) * 8))) return rc;
+    if (e->profile) stage_reset(e);   // the stage record is the call's from here on
+    hipStream_t st = e->stream;
+    uint32_t *cnt = (uint32_t *)e->tsdf_cnt.p;
+    unsigned long long *off = (unsigned long long *)e->tsdf_off.p;
+    rc = run_stage(e, "tsdf_count", [&] {
+        hipLaunchKernelGGL(k_tsdf_count, dim3(m), dim3(256), 0, st, vol, V, (const int32_t *)d_sum, (const int32_t *)d_weight, min_weight, cnt);
+        return 1;
+    });
+    if (rc) return rc;
+    rc = run_stage(e, "tsdf_scan", [&] {
+        hipLaunchKernelGGL(k_tsdf_scan, dim3(1), dim3(1024), 0, st, (const uint32_t *)cnt, m, off);
+        return 1;
+    });
+    if (rc) return rc;
+    if (d_out_points && capacity > 0) {
+        rc = run_stage(e, "tsdf_emit", [&] {
+            hipLaunchKernelGGL(k_tsdf_emit, dim3(m), dim3(256), 0, st, vol, V, (const int32_t *)d_sum, (const int32_t *)d_weight,
+                               (const uint32_t *)d_rgb, min_weight, (const unsigned long long *)off, capacity, (float *)d_out_points,
+                               (uint8_t *)d_out_colors);
+            return 1;
+        });
+        if (rc) return rc;
+    }
+    unsigned long long total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, off + m, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out_total = (int64_t)total;
+    return SGM_OK;
+}
+
+int sgm_tsdf_extract_points_device(sgm_engine *e, const int32_t dims[3], float voxel_size, const float origin[3], const void *d_sum,
+                                   const void *d_weight, const void *d_rgb_sum, int min_weight, int64_t capacity, void *d_out_points,
+                                   void *d_out_colors, int64_t *out_total)
+{
+    const char *who = "sgm_tsdf_extract_points_device";
+    TsdfVol vol;
+    int64_t V = 0;
+    if (int rc = tsdf_check_volume(who, e, dims, voxel_size, origin, d_sum, d_weight, &vol, &V)) return rc;
+    if (int rc = tsdf_check_extract(who, d_rgb_sum, min_weight, capacity, d_out_points, d_out_colors, out_total)) return rc;
+    return tsdf_extract_run(e, vol, V, d_sum, d_weight, d_rgb_sum, min_weight, capacity, d_out_points, d_out_colors, out_total);
+}
+
+int sgm_tsdf_extract_points(sgm_engine *e, const int32_t dims[3], float voxel_size, const float origin[3], const int32_t *sum,
+                            const int32_t *weight, const uint32_t *rgb_sum, int min_weight, int64_t capacity, float *out_points,
+                            uint8_t *out_colors, int64_t *out_total)
+{
+    const char *who = "sgm_tsdf_extract_points";
+    TsdfVol vol;
+    int64_t V = 0;
+    if (int rc = tsdf_check_volume(who, e, dims, voxel_size, origin, sum, weight, &vol, &V)) return rc;
+    if (int rc = tsdf_check_extract(who, rgb_sum, min_weight, capacity, out_points, out_colors, out_total)) return rc;
+    // the colour sums go up only if colours are asked for; the rows that come down are the written ones
+    const HostIn s{sum, &e->tsdf_sum, (size_t)V * 4}, w{weight, &e->tsdf_w, (size_t)V * 4}, c{out_colors ? rgb_sum : nullptr, &e->tsdf_rgb, (size_t)V * 12};
+    int64_t total = 0, rows = 0;
+    const HostOut pts{capacity > 0 ? out_points : nullptr, &e->cpts, 12, &rows, capacity},
+        rgb{capacity > 0 ? out_colors : nullptr, &e->crgb, 3, &rows, capacity};
+    if (int rc = host_call(e, V, {s, w, c}, {pts, rgb}, [&] {
+            const int rc2 = tsdf_extract_run(e, vol, V, s.d(), w.d(), c.d(), min_weight, capacity, pts.d(), rgb.d(), &total);
+            rows = std::min(total, capacity);
+            return rc2;
+        }))
+        return rc;
+    *out_total = total;
+    return SGM_OK;
 }
 
 // ---- triangle mesh from the organised cloud (include/sgm_hip_mesh.h, kernels_mesh.h) and its normals (include/sgm_hip_normals.h,

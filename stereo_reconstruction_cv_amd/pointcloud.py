@@ -30,6 +30,9 @@
                  iterated closest points on the GPU (include/sgm_hip_icp.h; NOT Open3D's registration_icp), with
     evaluate_registration(source, target, max_correspondence_distance, transformation)   its correspondence pass alone, and
     transform_points(points, transformation, normals)                      the motion applied, so that the two can be merged
+    TSDFVolume(voxel_size, sdf_trunc, dims, ...).integrate(...) / .extract_point_cloud()   many frames with their poses fused into
+                 one denoised surface: a dense signed distance volume of integer sums on the GPU (include/sgm_hip_tsdf.h; NOT
+                 Open3D's UniformTSDFVolume), with camera_from_Q(Q) and invert_rigid(T) for its camera and pose
     write_ply(path, points, colors, normals, triangles) / read_ply(path)   one PLY writer for a cloud or a mesh, with or without normals
 
 The compaction runs on the GPU (ordered, so the result equals numpy's `points_3D[mask]`); the
@@ -1190,3 +1193,235 @@ def read_ply(filename):
                 raise _cv.error("read_ply: the file is cut short or a face is no triangle")
             tri = np.array([[int(v) for v in r[1:]] for r in frows], np.int32).reshape(nf, 3)
         return pts, col, nrm, tri
+
+
+# ---- many frames fused into one model: the truncated signed distance volume (include/sgm_hip_tsdf.h) ------------------------------
+TSDF_STATS = ("updated", "unclamped", "no_depth", "occluded", "saturated", "outside", "usable_pixels")
+TSDF_MAX_DIM = 4096
+TSDF_MAX_VOXELS = 1 << 30
+TSDF_MAX_PIXELS = 1 << 27
+TSDF_MAX_WEIGHT = 65535
+
+
+def camera_from_Q(Q):
+    """The pinhole camera behind a reprojection matrix Q (cv2.stereoRectify's, the notebook's, synth.default_Q):
+    ((fx, fy, cx, cy), front) with fx = fy = Q[2, 3], cx = -Q[0, 3], cy = -Q[1, 3] and front = sign(Q[2, 3] * Q[3, 2]), the sign of
+    Z in front of the camera under reprojectImageTo3D with that Q (the notebook's Q gives -1).  Raises unless Q[0, 0] = Q[1, 1] = 1."""
+    try:
+        Q = np.asarray(Q.cpu() if _cv._is_torch(Q) else Q, np.float64)
+    except (TypeError, ValueError):
+        raise _cv.error("camera_from_Q: Q must be a 4 x 4 matrix of numbers") from None
+    if Q.shape != (4, 4) or not np.isfinite(Q).all():
+        raise _cv.error("camera_from_Q: Q must be a finite 4 x 4 matrix")
+    if Q[0, 0] != 1.0 or Q[1, 1] != 1.0:
+        raise _cv.error("camera_from_Q: Q[0, 0] and Q[1, 1] must be 1 (a Q of another scale is not a pinhole camera in pixels)")
+    s = Q[2, 3] * Q[3, 2]
+    if s == 0.0:
+        raise _cv.error("camera_from_Q: Q[2, 3] * Q[3, 2] is 0: no focal length or no baseline")
+    f = float(Q[2, 3])
+    return (f, f, float(-Q[0, 3]), float(-Q[1, 3])), (1 if s > 0 else -1)
+
+
+def invert_rigid(T):
+    """The inverse of a rigid transformation in float64: [R | t]^-1 = [R^T | -R^T t].  registration_icp(frame_k, frame_0)
+    gives camera k -> world (frame 0); TSDFVolume.integrate wants world -> camera: extrinsic = invert_rigid(T)."""
+    if T is None:
+        raise _cv.error("invert_rigid: T is None: a rigid transformation (4 x 4) is needed")
+    M = _icp_matrix("invert_rigid", "T", T)
+    out = np.eye(4, dtype=np.float64)
+    out[:3, :3] = M[:3, :3].T
+    out[:3, 3] = -(M[:3, :3].T @ M[:3, 3])
+    return out
+
+
+def _tsdf_positive(who, name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise _cv.error(f"{who}: {name} must be a number")
+    f = np.float32(v)
+    if not np.isfinite(f) or not f > 0:
+        raise _cv.error(f"{who}: {name} must be finite and positive in float32, not {v!r}")
+    return float(f)
+
+
+class TSDFVolume:
+    """A dense truncated signed distance volume that fuses many frames into one denoised surface, on the GPU
+    (include/sgm_hip_tsdf.h).  It stands where Open3D's UniformTSDFVolume / ScalableTSDFVolume stand in user code, but it is NOT
+    Open3D's integration: the depth is the Z of the XYZ image, the distance is taken along the camera's Z axis and quantised to
+    1 / 32767 of sdf_trunc, each voxel keeps an INTEGER sum and count (so the order of the frames does not matter, up to 65535
+    frames per voxel), and the extraction interpolates the zero crossing on every voxel edge in index order.
+
+    TSDFVolume(voxel_size, sdf_trunc, dims=(nx, ny, nz), origin=(0, 0, 0), color=True, device=None): the voxel (i, j, k) has its
+    centre at origin + (i + .5, j + .5, k + .5) * voxel_size, in the world frame.  The planes .sum, .weight (int32 (nz, ny, nx))
+    and .rgb_sum (uint32 (3, nz, ny, nx), None without color) are HIP tensors when `device` (a GPU index or True; the default
+    wherever a GPU is present), else numpy arrays; reset() zeroes them.
+
+    The chain, per frame k:  compute -> reprojectImageTo3D -> registration_icp(frame k, frame 0) -> vol.integrate(points_3D, colors,
+    disparity_map, camera_from_Q(Q)[0], extrinsic=invert_rigid(T));  once:  extract_point_cloud -> estimate_normals_radius ->
+    write_ply.
+    Not offered: a hashed or sparse volume, truncation scaled with depth, weights other than 1, normals from the gradient, a
+    marching-cubes mesh, ray casting, a batch of frames per call."""
+
+    def __init__(self, voxel_size, sdf_trunc, dims, origin=(0, 0, 0), color=True, device=None):
+        who = "TSDFVolume"
+        self.voxel_size = _tsdf_positive(who, "voxel_size", voxel_size)
+        self.sdf_trunc = _tsdf_positive(who, "sdf_trunc", sdf_trunc)
+        with np.errstate(all="ignore"):
+            kappa = np.float32(32767.0) / np.float32(self.sdf_trunc)
+        if not np.isfinite(kappa):
+            raise _cv.error(f"{who}: 32767 / sdf_trunc is not finite in float32")
+        try:
+            d = [v for v in dims]
+        except TypeError:
+            d = []
+        if len(d) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= TSDF_MAX_DIM for v in d):
+            raise _cv.error(f"{who}: dims must be three integers (nx, ny, nz) in 1 .. {TSDF_MAX_DIM}")
+        self.dims = tuple(int(v) for v in d)
+        nx, ny, nz = self.dims
+        if nx * ny * nz > TSDF_MAX_VOXELS:
+            raise _cv.error(f"{who}: {nx * ny * nz} voxels, more than 2^30")
+        try:
+            org = np.asarray(origin, np.float32).reshape(-1)
+        except (TypeError, ValueError):
+            org = np.zeros(0, np.float32)
+        if org.shape != (3,) or not np.isfinite(org).all():
+            raise _cv.error(f"{who}: origin must be three finite numbers")
+        self.origin = tuple(float(v) for v in org)
+        self.color = bool(color)
+        if device is None:      # the GPU wherever there is one; a library that does not load is an error, not a reason for numpy planes
+            device = _cv.get_device() if _cv._lib.load().sgm_device_count() > 0 else False
+        if device is True:
+            device = _cv.get_device()
+        self.device = None if device is False else int(device)
+        if self.device is None:
+            self.sum, self.weight = np.zeros((nz, ny, nx), np.int32), np.zeros((nz, ny, nx), np.int32)
+            self.rgb_sum = np.zeros((3, nz, ny, nx), np.uint32) if self.color else None
+        else:
+            import torch
+            dev = torch.device("cuda", self.device)
+            self.sum, self.weight = torch.zeros((nz, ny, nx), dtype=torch.int32, device=dev), torch.zeros((nz, ny, nx), dtype=torch.int32, device=dev)
+            # (torch has no uint32 arithmetic worth the name: the bytes are uint32, the tensor's dtype is int32)
+            self.rgb_sum = torch.zeros((3, nz, ny, nx), dtype=torch.int32, device=dev) if self.color else None
+
+    def reset(self):
+        """The empty volume: every plane zero."""
+        for p in (self.sum, self.weight, self.rgb_sum):
+            if p is not None:
+                p.fill_(0) if _cv._is_torch(p) else p.fill(0)
+
+    def _engine(self):
+        return _cv.get_engine(_cv._DEFAULT, self.device)
+
+    def integrate(self, points_3D, colors, disparity_map, intrinsic, extrinsic=None, front=None, max_depth=None, confidence=None,
+                  min_confidence=0, return_stats=False):
+        """One frame into the volume.  points_3D float32 (H, W, 3) -- reprojectImageTo3D's image --, colors uint8 (H, W, 3) (needed
+        iff the volume has colour; ignored otherwise), disparity_map float32 (H, W) or None: arrays or HIP tensors.  intrinsic:
+        (fx, fy, cx, cy) in pixels (camera_from_Q(Q)[0]).  extrinsic: world -> camera, 4 x 4 (None: the identity; invert_rigid of an
+        ICP result).  front: +1 or -1, the sign of Z in front of the camera; None takes the sign of the median Z of the valid
+        pixels.  max_depth: pixels farther than this (|Z|) are not used; None: no limit.  confidence masks the disparity as in every
+        other cloud call.  Returns None, or with return_stats the dict of TSDF_STATS."""
+        who = "TSDFVolume.integrate"
+        on_dev = _cv._is_torch(points_3D)
+        if disparity_map is None:
+            if confidence is not None:
+                raise _cv.error(f"{who}: a confidence map needs a disparity_map")
+            if on_dev:
+                import torch
+                if not points_3D.is_cuda or points_3D.dtype != torch.float32:
+                    raise _cv.error(f"{who}: a tensor points_3D must be float32 and on the GPU")
+                pts, disp = points_3D.contiguous(), None
+            else:
+                pts, disp = np.asarray(points_3D), None
+                if pts.dtype != np.float32:
+                    raise _cv.error(f"{who}: points_3D must be float32, not {pts.dtype}")
+            if pts.ndim != 3 or pts.shape[2] != 3:
+                raise _cv.error(f"{who}: points_3D must be (H, W, 3)")
+        elif on_dev:
+            pts, disp = _device_cloud(who, points_3D, disparity_map, confidence, min_confidence)
+        else:
+            pts, disp, _ = _outlier_cloud(who, points_3D, None, disparity_map, confidence, min_confidence)
+            if disp.dtype != np.float32:
+                raise _cv.error(f"{who}: disparity_map must be float32, not {disp.dtype}")
+        H, W = int(pts.shape[0]), int(pts.shape[1])
+        if H < 1 or W < 1 or H * W > TSDF_MAX_PIXELS:
+            raise _cv.error(f"{who}: a frame of {H} x {W} pixels (1 .. 2^27 are supported)")
+        col = None
+        if self.color:
+            if colors is None:
+                raise _cv.error(f"{who}: the volume has colour: colors must be uint8 (H, W, 3)")
+            if _cv._is_torch(colors):
+                import torch
+                if colors.dtype != torch.uint8 or tuple(colors.shape) != (H, W, 3):
+                    raise _cv.error(f"{who}: colors must be uint8 and have the shape of points_3D")
+                col = colors
+            else:
+                col = np.asarray(colors)
+                if col.dtype != np.uint8 or col.shape != (H, W, 3):
+                    raise _cv.error(f"{who}: colors must be uint8 and have the shape of points_3D")
+        try:
+            cam = np.asarray(intrinsic, np.float32).reshape(-1)
+        except (TypeError, ValueError):
+            cam = np.zeros(0, np.float32)
+        if cam.shape != (4,) or not np.isfinite(cam).all():
+            raise _cv.error(f"{who}: intrinsic must be four finite numbers (fx, fy, cx, cy)")
+        T = _icp_matrix(who, "extrinsic", extrinsic)
+        if max_depth is None:
+            max_depth = float("inf")
+        elif isinstance(max_depth, bool) or not isinstance(max_depth, (int, float, np.integer, np.floating)) or not np.float32(max_depth) > 0:
+            raise _cv.error(f"{who}: max_depth must be a number > 0 or None")
+        if front is None:
+            if on_dev:
+                import torch
+                ok = torch.isfinite(pts).all(dim=2) if disp is None else torch.isfinite(pts).all(dim=2) & (disp > 0)
+                z = pts[..., 2][ok]
+                front = -1 if z.numel() and float(z.median()) < 0 else 1
+            else:
+                ok = np.isfinite(pts).all(axis=2) if disp is None else np.isfinite(pts).all(axis=2) & (disp > 0)
+                z = pts[..., 2][ok]
+                front = -1 if z.size and float(np.median(z)) < 0 else 1
+        elif isinstance(front, bool) or front not in (1, -1):
+            raise _cv.error(f"{who}: front must be +1, -1 or None")
+        front = int(front)
+        e = self._engine()
+        if self.device is None:
+            to_np = lambda a: None if a is None else (a.cpu().numpy() if _cv._is_torch(a) else a)
+            st = e.tsdf_integrate_host(self.dims, self.voxel_size, self.sdf_trunc, self.origin, self.sum, self.weight, self.rgb_sum,
+                                       to_np(pts), to_np(disp), to_np(col), cam, front, T, max_depth, stats=return_stats)
+        else:
+            import torch
+            dev = self.sum.device
+            to_t = lambda a: None if a is None else (a.to(dev) if _cv._is_torch(a) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)).contiguous()
+            pts, disp, col = to_t(pts), to_t(disp), to_t(col)
+            ptr = lambda a: None if a is None else a.data_ptr()
+            torch.cuda.synchronize(dev)
+            st = e.tsdf_integrate_device(self.dims, self.voxel_size, self.sdf_trunc, self.origin, self.sum.data_ptr(), self.weight.data_ptr(),
+                                         ptr(self.rgb_sum), pts.data_ptr(), ptr(disp), ptr(col), H, W, cam, front, T, max_depth,
+                                         stats=return_stats)
+            e.synchronize()
+        return dict(zip(TSDF_STATS, (int(v) for v in st[:7]))) if return_stats else None
+
+    def extract_point_cloud(self, min_weight=1):
+        """The zero crossings of the averaged distance on the voxel edges between voxels that at least min_weight frames saw:
+        (points float32 (N, 3), colors uint8 (N, 3) or None), in voxel order, x, y, z edge of a voxel in that order; arrays or HIP
+        tensors as the planes are.  Counts first, then allocates."""
+        who = "TSDFVolume.extract_point_cloud"
+        _int_arg(who, min_weight, 1, (1 << 31) - 1, "min_weight must be an integer >= 1")
+        e = self._engine()
+        if self.device is None:
+            n = e.tsdf_extract_host(self.dims, self.voxel_size, self.origin, self.sum, self.weight, None, min_weight)
+            pts = np.empty((n, 3), np.float32)
+            col = np.empty((n, 3), np.uint8) if self.color else None
+            if n:
+                e.tsdf_extract_host(self.dims, self.voxel_size, self.origin, self.sum, self.weight, self.rgb_sum, min_weight, pts, col)
+            return pts, col
+        import torch
+        dev = self.sum.device
+        torch.cuda.synchronize(dev)
+        rgb = None if self.rgb_sum is None else self.rgb_sum.data_ptr()
+        n = e.tsdf_extract_device(self.dims, self.voxel_size, self.origin, self.sum.data_ptr(), self.weight.data_ptr(), None, min_weight)
+        pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        col = torch.empty((n, 3), dtype=torch.uint8, device=dev) if self.color else None
+        if n:
+            torch.cuda.synchronize(dev)
+            e.tsdf_extract_device(self.dims, self.voxel_size, self.origin, self.sum.data_ptr(), self.weight.data_ptr(), rgb, min_weight, n,
+                                  pts.data_ptr(), None if col is None else col.data_ptr())
+        return pts, col

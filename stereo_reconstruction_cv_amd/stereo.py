@@ -560,6 +560,59 @@ class Engine:
         T = np.ascontiguousarray(transformation, np.float64).reshape(16)
         _check(self._L.sgm_transform_points_device(self._h, d_xyz, d_normals, int(n), T.ctypes.data, d_out_xyz, d_out_normals))
 
+    # -- the truncated signed distance volume (include/sgm_hip_tsdf.h) --
+    def tsdf_integrate_host(self, dims, voxel_size, sdf_trunc, origin, sum_, weight, rgb_sum, xyz, disp, colors, cam, front, extrinsic,
+                            max_depth=float("inf"), stats=False):
+        """sgm_tsdf_integrate: one frame into the planes, IN PLACE (int32 (V) sum and weight, uint32 (3, V) rgb_sum or None, all
+        C-contiguous numpy arrays); xyz float32 (H, W, 3), disp float32 (H, W) or None, colors uint8 (H, W, 3) iff rgb_sum.
+        Returns the eight counts (uint64) with stats, else None."""
+        d = np.ascontiguousarray(dims, np.int32).reshape(3)
+        org, cam4 = _vec3(origin), np.ascontiguousarray(cam, np.float32).reshape(4)
+        T = np.ascontiguousarray(extrinsic, np.float64).reshape(16)
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        H, W = xyz.shape[:2]
+        disp = None if disp is None else np.ascontiguousarray(disp, np.float32)
+        colors = None if colors is None else np.ascontiguousarray(colors, np.uint8)
+        st = np.zeros(8, np.uint64) if stats else None
+        _check(self._L.sgm_tsdf_integrate(self._h, d.ctypes.data, float(voxel_size), float(sdf_trunc), org.ctypes.data, _at(sum_), _at(weight),
+                                          _at(rgb_sum), xyz.ctypes.data, _at(disp), _at(colors), H, W, cam4.ctypes.data, int(front),
+                                          T.ctypes.data, float(max_depth), _at(st)))
+        return st
+
+    def tsdf_integrate_device(self, dims, voxel_size, sdf_trunc, origin, d_sum: int, d_weight: int, d_rgb_sum: int | None, d_xyz: int,
+                              d_disp: int | None, d_colors: int | None, H: int, W: int, cam, front, extrinsic, max_depth=float("inf"),
+                              stats=False):
+        """sgm_tsdf_integrate_device: device addresses; enqueued on the engine's stream, which it waits for only with stats."""
+        d = np.ascontiguousarray(dims, np.int32).reshape(3)
+        org, cam4 = _vec3(origin), np.ascontiguousarray(cam, np.float32).reshape(4)
+        T = np.ascontiguousarray(extrinsic, np.float64).reshape(16)
+        st = np.zeros(8, np.uint64) if stats else None
+        _check(self._L.sgm_tsdf_integrate_device(self._h, d.ctypes.data, float(voxel_size), float(sdf_trunc), org.ctypes.data, d_sum, d_weight,
+                                                 d_rgb_sum, d_xyz, d_disp, d_colors, int(H), int(W), cam4.ctypes.data, int(front),
+                                                 T.ctypes.data, float(max_depth), _at(st)))
+        return st
+
+    def tsdf_extract_host(self, dims, voxel_size, origin, sum_, weight, rgb_sum, min_weight=1, out_points=None, out_colors=None):
+        """sgm_tsdf_extract_points: the number of crossings; rows go to out_points float32 (capacity, 3) and out_colors uint8
+        (capacity, 3) if given (min(total, capacity) of them; the others stay as they are)."""
+        d = np.ascontiguousarray(dims, np.int32).reshape(3)
+        org = _vec3(origin)
+        cap = 0 if out_points is None else out_points.shape[0]
+        total = C.c_int64(-1)
+        _check(self._L.sgm_tsdf_extract_points(self._h, d.ctypes.data, float(voxel_size), org.ctypes.data, _at(sum_), _at(weight), _at(rgb_sum),
+                                               int(min_weight), cap, _at(out_points), _at(out_colors), C.byref(total)))
+        return total.value
+
+    def tsdf_extract_device(self, dims, voxel_size, origin, d_sum: int, d_weight: int, d_rgb_sum: int | None, min_weight=1, capacity=0,
+                            d_out_points: int | None = None, d_out_colors: int | None = None):
+        """sgm_tsdf_extract_points_device: device addresses; blocks once, returns the number of crossings."""
+        d = np.ascontiguousarray(dims, np.int32).reshape(3)
+        org = _vec3(origin)
+        total = C.c_int64(-1)
+        _check(self._L.sgm_tsdf_extract_points_device(self._h, d.ctypes.data, float(voxel_size), org.ctypes.data, d_sum, d_weight, d_rgb_sum,
+                                                      int(min_weight), int(capacity), d_out_points, d_out_colors, C.byref(total)))
+        return total.value
+
     # -- triangle mesh from the organised cloud (include/sgm_hip_mesh.h) --
     def mesh_grid_host(self, xyz: np.ndarray, disp: np.ndarray, colors: np.ndarray | None, max_diff: float = 1.0):
         """sgm_mesh_grid: float32 points (H, W, 3), float32 disparities (H, W), uint8 colours (H, W, 3) or None.  Returns
