@@ -11,7 +11,8 @@ sized for the frame and must notice that the plan now wants more of them.
 
 Shared by tests/feature_walk_child.py (which takes the walks on the GPU) and tests/test_feature_walks.py (which regenerates
 them with the references alone and checks the conditions that keep them meaningful).  Everything is a function of (engine
-index, walk seed): a failing walk can be replayed from the step list its failure message prints."""
+index, walk seed): a failing walk can be replayed from the step list its failure message prints.  The point-cloud calls added
+later (covariance normals, clustering, planes, registration, the TSDF volume) are walked in tests/cloud_walk.py."""
 from __future__ import annotations
 
 import numpy as np

@@ -7,7 +7,8 @@ living engine, their maps through the taps or through the bind entries, and in f
 calls that share buffers with it (the edge-aware filter, the left-right confidence, the voxel grid, the two outlier filters,
 the mesh, the normals) -- once plain and once with every buffer poisoned in front of every call.  Everything is compared bit
 for bit with the references the feature tests use.  tests/test_feature_walks.py holds, without a GPU, the conditions under
-which a walk that passes means something.
+which a walk that passes means something.  The point-cloud calls added later are walked in tests/cloud_walk.py
+(tests/test_gpu_cloud_walk.py).
 
 A child that ends by a signal, by an abort or at its time limit has met a fault or a hang: nothing more is started on the
 card after it.  That test fails, and the walks behind it skip with its reason."""
